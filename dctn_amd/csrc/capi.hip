@@ -1,15 +1,52 @@
 // C-ABI entry points (include/dctn_amd.h): argument validation + dispatch to kernel families.
 #include "common.h"
 
+#include <stdio.h>
 #include <stdlib.h>
 
 #include <atomic>
 
-// The library's only mutable global: a diagnostic pointer to a string literal naming the kernel family of the last
-// successful call (process-wide, relaxed atomic, last writer wins: autograd runs backward on its own thread, so a
-// thread-local would hide the backward's kernels from the caller).  No entry point reads it to decide anything.
+// The library's process-wide state.  g_last_kernel, its only mutable global: a diagnostic pointer to a string literal
+// naming the kernel family of the last successful call (relaxed atomic, last writer wins: autograd runs backward on its
+// own thread, so a thread-local would hide the backward's kernels from the caller).  No entry point reads it to decide
+// anything.  dctn_dev(): the device's CU count and LDS per CU, set once on first use, which every plan and launch reads.
 static std::atomic<const char*> g_last_kernel{"none"};
 void dctn_set_last_kernel(const char* name) { g_last_kernel.store(name, std::memory_order_relaxed); }
+
+const DctnDev& dctn_dev() {
+  static const DctnDev d = [] {
+    DctnDev r{256, 160 * 1024};   // gfx950 (MI355X)
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) == hipSuccess) {
+      if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) r.cus = v;
+      if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) == hipSuccess && v >= 64 * 1024) r.lds = v;
+    }
+    // test hook: DCTN_DEVICE_LIMITS="cus,lds_bytes" runs the plans of a smaller device (a partitioned card) on this one;
+    // it only lowers the values, so no kernel asks for more than the card has
+    int cus = 0, lds = 0;
+    const char* lim = getenv("DCTN_DEVICE_LIMITS");
+    if (lim && sscanf(lim, "%d,%d", &cus, &lds) == 2) {
+      if (cus > 0 && cus < r.cus) r.cus = cus;
+      if (lds > 0 && lds < r.lds) r.lds = lds;
+    }
+    return r;
+  }();
+  return d;
+}
+
+int dctn_lds_wg_max() { return dctn_dev().lds / 16 * 15; }
+
+long long dctn_resident_wgs(size_t lds_bytes, int lo, int hi) {
+  long long per_cu = lds_bytes ? (long long)dctn_dev().lds / (long long)lds_bytes : hi;
+  if (per_cu < lo) per_cu = lo;
+  if (per_cu > hi) per_cu = hi;
+  return (long long)dctn_dev().cus * per_cu;
+}
+
+bool dctn_lds_optin(const void* fn, size_t bytes) {
+  return bytes <= (size_t)dctn_dev().lds &&
+         hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+}
 
 namespace {
 __global__ __launch_bounds__(256) void dctn_zero_k(unsigned* __restrict__ p, size_t words) {
@@ -54,6 +91,13 @@ extern "C" {
 int dctn_version(void) { return 500; }   // round 5: register-resident exact-f32 EPS family (eps_q2f32.hip), fused head both ways in float32
 
 const char* dctn_last_kernel(void) { return g_last_kernel.load(std::memory_order_relaxed); }
+
+int dctn_device_limits(int* cus, int* lds_bytes) {
+  if (!cus || !lds_bytes) return DCTN_ERR_NULL;
+  *cus = dctn_dev().cus;
+  *lds_bytes = dctn_dev().lds;
+  return DCTN_OK;
+}
 
 const char* dctn_strerror(int code) {
   switch (code) {

@@ -11,7 +11,15 @@ template <typename S> struct AccOf { typedef float type; };
 template <> struct AccOf<double> { typedef double type; };
 
 #define DCTN_WAVE 64
-#define DCTN_LDS_BUDGET (150 * 1024)  // bytes of the 160 KiB LDS a single workgroup may claim here
+
+// The device's geometry, asked once per process (capi.hip); gfx950 defaults when the runtime cannot say
+struct DctnDev { int cus; int lds; };   // CUs, LDS bytes per CU
+const DctnDev& dctn_dev();
+int dctn_lds_wg_max();   // LDS bytes one workgroup's plan may claim: 15/16 of a CU's (150 of 160 KiB on gfx950)
+// workgroups resident at once: cus * clamp(lds / lds_bytes, lo, hi); lds_bytes == 0 -> cus * hi
+long long dctn_resident_wgs(size_t lds_bytes, int lo, int hi);
+// the dynamic-LDS opt-in of a kernel: false when `bytes` exceeds a CU's LDS or the runtime refuses
+bool dctn_lds_optin(const void* fn, size_t bytes);
 
 #define DCTN_CHECK_LAUNCH()                                   \
   do {                                                        \

@@ -348,13 +348,11 @@ template <typename S, typename A>
 int fwd_launch(const void* x, void* out, SbsP& p, hipStream_t st) {
   const size_t per_col = ((size_t)2 * p.vmax + p.qc + p.Otot) * sizeof(A);
   p.cs = DCTN_WAVE;
-  while (p.cs > 1 && per_col * p.cs > DCTN_LDS_BUDGET) p.cs >>= 1;
+  while (p.cs > 1 && per_col * p.cs > dctn_lds_wg_max()) p.cs >>= 1;
   const size_t lds = per_col * p.cs;
-  if (lds > DCTN_LDS_BUDGET) return DCTN_ERR_UNSUPPORTED;
+  if (lds > dctn_lds_wg_max() || !dctn_lds_optin((const void*)convsbs_fwd_generic_k<S, A>, lds)) return DCTN_ERR_UNSUPPORTED;
   p.cst = p.cs;
   const unsigned grid = (unsigned)((p.Wn + p.cs - 1) / p.cs);
-  (void)hipFuncSetAttribute((const void*)convsbs_fwd_generic_k<S, A>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL((convsbs_fwd_generic_k<S, A>), dim3(grid), dim3(DCTN_WAVE), lds, st,
                      (const S*)x, (S*)out, p);
   DCTN_CHECK_LAUNCH();
@@ -400,17 +398,17 @@ int bwd_launch(const void* x, const void* dY, void* dX, void* const* dCores, voi
   for (int c = 0; c < p.n; ++c) p.core_off[c + 1] = p.core_off[c] + core_elems(p, c);
   const int need_dcore_lds = dCores != nullptr;
   const size_t acc_bytes = need_dcore_lds ? (size_t)p.core_off[p.n] * sizeof(A) : 0;
-  if (acc_bytes > DCTN_LDS_BUDGET / 2) return DCTN_ERR_UNSUPPORTED;
+  if (acc_bytes > dctn_lds_wg_max() / 2) return DCTN_ERR_UNSUPPORTED;
   const size_t per_col = ((size_t)3 * p.vmax + 2 * p.qc + p.Otot) * sizeof(A);
   p.cs = DCTN_WAVE;
-  while (p.cs > 1 && per_col * (p.cs + 1) + acc_bytes > DCTN_LDS_BUDGET) p.cs >>= 1;
+  while (p.cs > 1 && per_col * (p.cs + 1) + acc_bytes > dctn_lds_wg_max()) p.cs >>= 1;
   int waves = 1;  // several waves share one dCore accumulator when every wave has its 64 columns
   if (p.cs == DCTN_WAVE && acc_bytes >= 4096)  // small strings: more, smaller workgroups win
-    while (waves < 4 && per_col * (2 * waves * DCTN_WAVE + 1) + acc_bytes <= DCTN_LDS_BUDGET) waves *= 2;
+    while (waves < 4 && per_col * (2 * waves * DCTN_WAVE + 1) + acc_bytes <= dctn_lds_wg_max()) waves *= 2;
   const int csb = waves * p.cs;
   p.cst = csb + 1;
   const size_t lds = per_col * p.cst + acc_bytes;
-  if (lds > DCTN_LDS_BUDGET) return DCTN_ERR_UNSUPPORTED;
+  if (lds > dctn_lds_wg_max() || !dctn_lds_optin((const void*)convsbs_bwd_generic_k<S, A>, lds)) return DCTN_ERR_UNSUPPORTED;
   unsigned char* wsp = (unsigned char*)ws;
   A* states = (A*)wsp;
   wsp += align256((size_t)state_elems(p) * p.Wn * sizeof(A));
@@ -470,13 +468,8 @@ int bwd_launch(const void* x, const void* dY, void* dX, void* const* dCores, voi
   }
   const long long ngroups = (p.Wn + csb - 1) / csb;
   // persistent workgroups: as many as can be resident (LDS-limited), at most one per window group
-  long long per_cu = (long long)(160 * 1024) / (long long)(lds ? lds : 1);
-  if (per_cu < 1) per_cu = 1;
-  if (per_cu > 8) per_cu = 8;
-  long long grid = 256 * per_cu;
+  long long grid = dctn_resident_wgs(lds, 1, 8);
   if (grid > ngroups) grid = ngroups;
-  (void)hipFuncSetAttribute((const void*)convsbs_bwd_generic_k<S, A>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL((convsbs_bwd_generic_k<S, A>), dim3((unsigned)grid), dim3(DCTN_WAVE * waves), lds, st,
                      (const S*)x, (const S*)dY, states, gxw, p, dX != nullptr, need_dcore, ngroups);
   DCTN_CHECK_LAUNCH();

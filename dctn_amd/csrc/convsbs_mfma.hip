@@ -1406,17 +1406,14 @@ static int convsbs_fwd_mfma_one(const void* x, const int64_t xs[5], const void* 
     p.save = save;
   }
   const size_t lds = (size_t)off * sizeof(float);
-  if (lds > DCTN_LDS_BUDGET) return DCTN_ERR_UNSUPPORTED;
+  if (lds > dctn_lds_wg_max()) return DCTN_ERR_UNSUPPORTED;
   long long blocks = (p.ngroups + 3) / 4;
-  long long fwd_per_cu = lds > 0 ? (160 * 1024) / (long long)lds : 8;   // persistent: the core pack is paid once per workgroup
-  if (fwd_per_cu < 2) fwd_per_cu = 2;
-  if (fwd_per_cu > 8) fwd_per_cu = 8;
-  if (blocks > 256 * fwd_per_cu) blocks = 256 * fwd_per_cu;
+  const long long resident = dctn_resident_wgs(lds, 2, 8);   // persistent: the core pack is paid once per workgroup
+  if (blocks > resident) blocks = resident;
   const int chmode = p.C == 1 ? 1 : (p.C == 2 && p.q == 2) ? 2 : 0;
 #define SBS_LAUNCH_CH(RR, CHV)                                                                    \
   do {                                                                                            \
-    (void)hipFuncSetAttribute((const void*)convsbs_fwd_mfma_k<RR, CHV>,                           \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);              \
+    if (!dctn_lds_optin((const void*)convsbs_fwd_mfma_k<RR, CHV>, lds)) return DCTN_ERR_UNSUPPORTED; \
     hipLaunchKernelGGL((convsbs_fwd_mfma_k<RR, CHV>), dim3((unsigned)blocks), dim3(256), lds, st, \
                        (const float*)x, (float*)out, p);                                          \
   } while (0)
@@ -1502,7 +1499,7 @@ static int sbsm_for_slices(int n, const void* const* cores, const int* out_sizes
       }
       const SbsSlice sl{1, (int)obase, (int)otot, !first, l0 > 0, (int)(ring ? R0 * qc : qc), m >= 0 ? (int)ostr[m] : 1};
       const int rc = visit(coff, outs, bonds, sl);
-      if (rc != DCTN_OK) return rc;
+      if (rc != DCTN_OK) return rc == DCTN_ERR_UNSUPPORTED && !first ? DCTN_ERR_LAUNCH : rc;   // (earlier slices ran: no fall-through)
       first = false;
     }
     int c = n - 1;   // next combination of outputs (the last core runs fastest)
@@ -1611,20 +1608,17 @@ static int convsbs_bwd_mfma_one(const void* x, const int64_t xs[5], const void* 
     for (int c = 0; c < n; ++c) {
       q2.core_off[c + 1] = q2.core_off[c] + p.o[c] * p.bl[c] * p.br[c] * p.qc;
     }
-    if (lds2 <= DCTN_LDS_BUDGET) {
+    if (lds2 <= dctn_lds_wg_max()) {
       long long blocks = (p.ngroups + 3) / 4;
       // latency-bound sweeps: as many workgroups as the LDS plan lets a CU hold (the small-bond strings fit several;
       // 3 600 window groups then run in one round instead of two or four)
-      long long per_cu2 = (160 * 1024) / (long long)lds2;
-      if (per_cu2 < 1) per_cu2 = 1;
-      if (per_cu2 > 8) per_cu2 = 8;
-      if (blocks > 256 * per_cu2) blocks = 256 * per_cu2;
+      const long long resident = dctn_resident_wgs(lds2, 1, 8);
+      if (blocks > resident) blocks = resident;
       if (blocks > SBS_MAX_PARTIAL_RECORDS - 64) blocks = SBS_MAX_PARTIAL_RECORDS - 64;   // room for the second-stage records
       q2.partials = (partials && partial_bytes >= (size_t)blocks * q2.core_off[n] * sizeof(float)) ? partials : nullptr;
 #define SBS_LAUNCH_B16_1(RR, NCV, NTV, CHV, SV)                                                    \
   do {                                                                                            \
-    (void)hipFuncSetAttribute((const void*)convsbs_bwd_mfma16_k<RR, NCV, NTV, CHV, SV>,           \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);             \
+    if (!dctn_lds_optin((const void*)convsbs_bwd_mfma16_k<RR, NCV, NTV, CHV, SV>, lds2)) return DCTN_ERR_UNSUPPORTED; \
     hipLaunchKernelGGL((convsbs_bwd_mfma16_k<RR, NCV, NTV, CHV, SV>), dim3((unsigned)blocks), dim3(256), lds2, st, \
                        (const float*)x, (const float*)dY, states, gxw, q2, gxw != nullptr);       \
   } while (0)
@@ -1686,15 +1680,12 @@ static int convsbs_bwd_mfma_one(const void* x, const int64_t xs[5], const void* 
   p.st_off[n] = so;
   p.dacc_off[n] = dacc;
   const size_t lds = (size_t)(dacc + 1) * sizeof(float);
-  if (lds > DCTN_LDS_BUDGET) return DCTN_ERR_UNSUPPORTED;
-  long long per_cu = (160 * 1024) / (long long)lds;
-  if (per_cu < 1) per_cu = 1;
-  if (per_cu > 2) per_cu = 2;
+  if (lds > dctn_lds_wg_max()) return DCTN_ERR_UNSUPPORTED;
   long long blocks = (p.ngroups + 3) / 4;
-  if (blocks > 256 * per_cu) blocks = 256 * per_cu;
+  const long long resident = dctn_resident_wgs(lds, 1, 2);
+  if (blocks > resident) blocks = resident;
 #define SBS_LAUNCH_B(RR)                                                                          \
-  (void)hipFuncSetAttribute((const void*)convsbs_bwd_mfma_k<RR>,                                  \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                \
+  if (!dctn_lds_optin((const void*)convsbs_bwd_mfma_k<RR>, lds)) return DCTN_ERR_UNSUPPORTED;    \
   hipLaunchKernelGGL((convsbs_bwd_mfma_k<RR>), dim3((unsigned)blocks), dim3(256), lds, st,        \
                      (const float*)x, (const float*)dY, states, gxw, p, gxw != nullptr)
   switch (R) {

@@ -1373,9 +1373,9 @@ bool sr_fill(SrP& p, SrPlan& pl, const void* x, const int64_t xs[5], const void*
       maxwin = nw > maxwin ? nw : maxwin;
     }
     const size_t lds = (fixed + (size_t)maxwin * NCq) * sizeof(float);
-    if (lds > DCTN_LDS_BUDGET) continue;
+    if (lds > dctn_lds_wg_max()) continue;
     best = br; pl.max_w_in_band = maxwin; pl.lds_bwd = lds;
-    if (maxwin <= SR_BWD_THREADS && (long long)B * bands >= 256) break;
+    if (maxwin <= SR_BWD_THREADS && (long long)B * bands >= dctn_dev().cus) break;
     if (maxwin <= SR_BWD_THREADS / 2) break;   // finer bands only add redundant halo windows
   }
   if (best < 0) return false;
@@ -1442,9 +1442,9 @@ bool sm_fill(SrP& p, SrPlan& pl, const void* x, const int64_t xs[5], const void*
       maxwin = nw > maxwin ? nw : maxwin;
     }
     const size_t lds = (fixed + (size_t)maxwin * NCq) * sizeof(float);
-    if (lds > DCTN_LDS_BUDGET) continue;
+    if (lds > dctn_lds_wg_max()) continue;
     best = br; pl.max_w_in_band = maxwin; pl.lds_bwd = lds;
-    if (maxwin <= SR_BWD_THREADS && (long long)B * bands >= 256) break;
+    if (maxwin <= SR_BWD_THREADS && (long long)B * bands >= dctn_dev().cus) break;
     if (maxwin <= SR_BWD_THREADS / 2) break;
   }
   if (best < 0) return false;
@@ -1554,8 +1554,7 @@ int convsbs_bwd_reg(const void* x, const int64_t xs[5], const void* const* cores
     for (int c = 0; c <= SR_MAXS * SR_MAXC; ++c) t.coff[c] = c <= SR_MAXC ? p.coff[c] : p.coff[SR_MAXC];
 #define SM_BWD(RR, QQ, TC)                                                                                            \
   do {                                                                                                                \
-    (void)hipFuncSetAttribute((const void*)convsbs_bwd_regmv_k<RR, QQ, TC, SR_MAXC>,                                  \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bwd);                           \
+    if (!dctn_lds_optin((const void*)convsbs_bwd_regmv_k<RR, QQ, TC, SR_MAXC>, pl.lds_bwd)) return DCTN_ERR_UNSUPPORTED; \
     hipLaunchKernelGGL((convsbs_bwd_regmv_k<RR, QQ, TC, SR_MAXC>), dim3((unsigned)pl.nrec), dim3(SR_BWD_THREADS), pl.lds_bwd, st, p); \
     if (dcores)                                                                                                       \
       hipLaunchKernelGGL((convsbs_regmv_tail_k<RR, QQ>), dim3((unsigned)((ent + 3) / 4)), dim3(256), 0, st, (const float*)ws, t, \
@@ -1587,8 +1586,7 @@ int convsbs_bwd_reg(const void* x, const int64_t xs[5], const void* const* cores
   const unsigned grid = (unsigned)pl.nrec;
 #define SR_BWD(RR, QQ, TC)                                                                                            \
   do {                                                                                                                \
-    (void)hipFuncSetAttribute((const void*)convsbs_bwd_reg_k<RR, QQ, TC, SR_MAXC>,                                    \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bwd);                           \
+    if (!dctn_lds_optin((const void*)convsbs_bwd_reg_k<RR, QQ, TC, SR_MAXC>, pl.lds_bwd)) return DCTN_ERR_UNSUPPORTED; \
     hipLaunchKernelGGL((convsbs_bwd_reg_k<RR, QQ, TC, SR_MAXC>), dim3(grid), dim3(SR_BWD_THREADS), pl.lds_bwd, st, p); \
   } while (0)
 #define SR_TAIL(RR, QQ)                                                                                               \
@@ -1604,8 +1602,7 @@ int convsbs_bwd_reg(const void* x, const int64_t xs[5], const void* const* cores
   for (int c = SR_MAXC; c < SR_MAXS * SR_MAXC; ++c) t.dcore[c] = nullptr;
 #define SU_BWD(RR, QQ, TC)                                                                                            \
   do {                                                                                                                \
-    (void)hipFuncSetAttribute((const void*)convsbs_bwd_regu_k<RR, QQ, TC, false>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              (int)pl.lds_bwd);                                                                       \
+    if (!dctn_lds_optin((const void*)convsbs_bwd_regu_k<RR, QQ, TC, false>, pl.lds_bwd)) return DCTN_ERR_UNSUPPORTED; \
     hipLaunchKernelGGL((convsbs_bwd_regu_k<RR, QQ, TC, false>), dim3(grid), dim3(SR_BWD_THREADS), pl.lds_bwd, st, p, p, 1);  \
   } while (0)
 #define SU_BWD_R(RR)                                                                                                  \
@@ -1673,7 +1670,7 @@ bool su_plan_many(SrP* ps, SrPlan& pl, int ns, const void* x, const int64_t xs[5
   for (int s2 = 0; s2 < ns; ++s2) ps[s2].tot_all = base;
   pl.tot = base;
   pl.lds_bwd = ((size_t)base * (SR_BWD_THREADS / 64) + (size_t)pl.max_w_in_band * n * C * q) * sizeof(float);
-  return pl.lds_bwd <= DCTN_LDS_BUDGET;
+  return pl.lds_bwd <= dctn_lds_wg_max();
 }
 }  // namespace
 
@@ -1746,8 +1743,7 @@ int convsbs_many_bwd_reg(const void* x, const int64_t xs[5], const void* const* 
   const SrP& pb = ps[ns > 1 ? 1 : 0];
 #define SU_BWD(RR, QQ, TC)                                                                                            \
   do {                                                                                                                \
-    (void)hipFuncSetAttribute((const void*)convsbs_bwd_regu_k<RR, QQ, TC, true>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              (int)pl.lds_bwd);                                                                       \
+    if (!dctn_lds_optin((const void*)convsbs_bwd_regu_k<RR, QQ, TC, true>, pl.lds_bwd)) return DCTN_ERR_UNSUPPORTED;  \
     hipLaunchKernelGGL((convsbs_bwd_regu_k<RR, QQ, TC, true>), dim3(grid), dim3(SR_BWD_THREADS), pl.lds_bwd, st, pa, pb, ns); \
   } while (0)
 #define SU_BWD_R(RR)                                                                                                  \

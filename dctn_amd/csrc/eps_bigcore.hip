@@ -1106,10 +1106,7 @@ void choose_row_groups(BigP& b, int nt, int max_rg, size_t lds_bytes) {
   const long long wpb = (long long)BC_WAVES * nt * 32;
   const long long wblocks = (b.Wn + wpb - 1) / wpb;
   const int mtiles = (b.rows + 31) / 32;
-  long long per_cu = lds_bytes > 0 ? (long long)(160 * 1024) / (long long)lds_bytes : 8;
-  if (per_cu < 1) per_cu = 1;
-  if (per_cu > 8) per_cu = 8;
-  const long long capacity = 256 * per_cu;
+  const long long capacity = dctn_resident_wgs(lds_bytes, 1, 8);
   int top = mtiles < max_rg ? mtiles : max_rg;
   if (top < 1) top = 1;
   // rough cycle model: a row tile = kdim/2 k-steps x nt column tiles x 64 cycles at ~60 % matrix-pipe
@@ -1366,8 +1363,7 @@ int launch_nd(const void* x, const void* core, const void* dY, void* out, const 
               hipStream_t st) {
   constexpr int WPB = BC_WAVES * NT * 32;
   const unsigned grid = (unsigned)((b.Wn + WPB - 1) / WPB);
-  (void)hipFuncSetAttribute((const void*)eps_bigcore_k<MODE, NT, LOGO_T, TBL, ND>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (!dctn_lds_optin((const void*)eps_bigcore_k<MODE, NT, LOGO_T, TBL, ND>, lds)) return DCTN_ERR_UNSUPPORTED;
   hipLaunchKernelGGL((eps_bigcore_k<MODE, NT, LOGO_T, TBL, ND>), dim3(grid, b.rg_count), dim3(64 * BC_WAVES), lds,
                      st, (const float*)x, (const float*)core, (const float*)dY, (float*)out, b);
   DCTN_CHECK_LAUNCH();
@@ -1437,7 +1433,7 @@ static bool bigcore_wanted(const EpsP& p) {
 bool eps_bigcore_covers(const EpsP& p, int dtype, int precision) {
   if (dtype != DCTN_F32 || precision != DCTN_PREC_EXACT || !bigcore_wanted(p)) return false;
   BigP b;
-  return fill_big(b, p, MODE_FWD);
+  return fill_big(b, p, MODE_FWD) && big_lds(b) <= (size_t)dctn_lds_wg_max();
 }
 
 size_t eps_fwd_bigcore_workspace(const EpsP& p, int dtype, int precision) {
@@ -1470,9 +1466,9 @@ static bool dp1_plan(const EpsP& p, const BigP& bf, Dp1P& d, size_t& lds, size_t
 size_t eps_bigcore_saved_bytes(const EpsP& p, int dtype, int precision) {
   if (dtype != DCTN_F32 || precision != DCTN_PREC_EXACT || !bigcore_wanted(p)) return 0;
   BigP b;
-  if (!fill_big(b, p, MODE_FWD) || big_lds(b) > DCTN_LDS_BUDGET) return 0;
+  if (!fill_big(b, p, MODE_FWD) || big_lds(b) > dctn_lds_wg_max()) return 0;
   BigP b0;
-  if (!fill_big(b0, p, MODE_G0) || big_lds(b0) > DCTN_LDS_BUDGET) return 0;
+  if (!fill_big(b0, p, MODE_G0) || big_lds(b0) > dctn_lds_wg_max()) return 0;
   Dp1P d;
   size_t lds, zbytes;
   if (!dp1_plan(p, b, d, lds, zbytes)) return 0;
@@ -1485,7 +1481,7 @@ int eps_fwd_bigcore(const void* x, const void* core, void* out, void* ws, size_t
   BigP b;
   if (!fill_big(b, p, MODE_FWD)) return DCTN_ERR_UNSUPPORTED;
   const size_t lds = big_lds(b);
-  if (lds > DCTN_LDS_BUDGET) return DCTN_ERR_UNSUPPORTED;
+  if (lds > dctn_lds_wg_max()) return DCTN_ERR_UNSUPPORTED;
   b.zsave = (float*)zsave;
   choose_row_groups(b, BC_NT_FWD, BC_MAX_RG, lds);
   const size_t need = b.rg_count > 1 ? (size_t)b.rg_count * p.Wn * p.O * sizeof(float) : 0;
@@ -1518,8 +1514,7 @@ static int launch_dp1_nd(const void* x, const void* Z, const void* dY, float* gx
   const unsigned grid = (unsigned)((d.Wn + 63) / 64);
 #define DP1_GO(ND)                                                                                                 \
   do {                                                                                                             \
-    (void)hipFuncSetAttribute((const void*)eps_bigcore_dp1_k<OXT, ND>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                              (int)lds);                                                                           \
+    if (!dctn_lds_optin((const void*)eps_bigcore_dp1_k<OXT, ND>, lds)) return DCTN_ERR_UNSUPPORTED;            \
     hipLaunchKernelGGL((eps_bigcore_dp1_k<OXT, ND>), dim3(grid), dim3(DP1_THREADS), lds, st, (const float*)x,      \
                        (const float*)Z, (const float*)dY, gxw, d);                                                 \
   } while (0)
@@ -1547,7 +1542,7 @@ static int launch_dp1(const void* x, const void* Z, const void* dY, float* gxw, 
 // windows covering each pixel).
 static bool dfactor_plan(const EpsP& p, BigP& b0, BigP& b1) {
   if (!fill_big(b0, p, MODE_G0) || !fill_big(b1, p, MODE_G1)) return false;
-  if (big_lds(b0) > DCTN_LDS_BUDGET || big_lds(b1) > DCTN_LDS_BUDGET) return false;
+  if (big_lds(b0) > dctn_lds_wg_max() || big_lds(b1) > dctn_lds_wg_max()) return false;
   const int mt0 = (b0.rows + 31) / 32, mt1 = (b1.rows + 31) / 32;
   int cap = mt0 < mt1 ? mt0 : mt1;
   if (cap > BC_MAX_RG) cap = BC_MAX_RG;
@@ -1562,7 +1557,7 @@ static bool dfactor_plan(const EpsP& p, BigP& b0, BigP& b1) {
 
 // G0 alone (half 1 comes from the saved Z): its own optimum split
 static bool g0_plan(const EpsP& p, BigP& b0) {
-  if (!fill_big(b0, p, MODE_G0) || big_lds(b0) > DCTN_LDS_BUDGET) return false;
+  if (!fill_big(b0, p, MODE_G0) || big_lds(b0) > dctn_lds_wg_max()) return false;
   choose_row_groups(b0, BC_NT_G, BC_MAX_RG, big_lds(b0));
   return true;
 }
@@ -1595,7 +1590,7 @@ int eps_bwd_dx_bigcore(const void* x, const void* core, const void* dY, void* dX
       int rc = dctn_bc::launch_g(MODE_G0, x, core, dY, gxw, b0, big_lds(b0), st);
       if (rc != DCTN_OK) return rc;
       rc = launch_dp1(x, zsaved, dY, gxw, d, lds1, st);
-      if (rc != DCTN_OK) return rc;
+      if (rc != DCTN_OK) return rc == DCTN_ERR_UNSUPPORTED ? DCTN_ERR_LAUNCH : rc;   // (after a launch: no fall-through)
       hipLaunchKernelGGL(bigcore_gather_dx_k, dim3(g2), dim3(256), 0, st, (const float*)gxw, (float*)dX, p, b0.n0,
                          b0.rg_count, 1);
       DCTN_CHECK_LAUNCH();
@@ -1611,7 +1606,7 @@ int eps_bwd_dx_bigcore(const void* x, const void* core, const void* dY, void* dX
   int rc = dctn_bc::launch_g(MODE_G0, x, core, dY, gxw, b0, big_lds(b0), st);
   if (rc != DCTN_OK) return rc;
   rc = dctn_bc::launch_g(MODE_G1, x, core, dY, gxw, b1, big_lds(b1), st);
-  if (rc != DCTN_OK) return rc;
+  if (rc != DCTN_OK) return rc == DCTN_ERR_UNSUPPORTED ? DCTN_ERR_LAUNCH : rc;   // (after a launch: no fall-through)
   hipLaunchKernelGGL(bigcore_gather_dx_k, dim3(g2), dim3(256), 0, st, (const float*)gxw, (float*)dX, p, b0.n0,
                      b0.rg_count, b0.rg_count);
   DCTN_CHECK_LAUNCH();
@@ -1647,14 +1642,14 @@ static bool dcore_plan(const EpsP& p, int dtype, int precision, DcoreP& d, long 
   const int tstride = d.nlo0 + d.nhi0 + d.nlo1 + d.nhi1 + d.OP + 1;   // + the always-zero entry
   d.tstride = tstride;
   lds = ((size_t)(DC_WC * (p.N * p.Q + 1) + 1) / 2 * 2 + (size_t)DC_ROW * tstride) * sizeof(float);
-  if (lds > DCTN_LDS_BUDGET) return false;
+  if (lds > dctn_lds_wg_max()) return false;
   const int ntile_a = (d.A + DC_WR * DC_AT * 32 - 1) / (DC_WR * DC_AT * 32);
   const int ntile_c = (d.cols + DC_WC2 * DC_BT * 32 - 1) / (DC_WC2 * DC_BT * 32);
   tiles = (long long)ntile_a * ntile_c;
   // one workgroup per CU (the kernel's LDS admits one): a workgroup's prologue, result store (128 accumulator values per
   // lane, one 64-bit address each) and its slice of the partial-sum pass are paid once per window chunk - with four rounds
   // of workgroups (1024 / tiles chunks) cfg3b's step took 2.39 ms, with one 2.12 ms (cfg3a 7.34 -> 7.08 ms)
-  chunks = 256 / tiles;
+  chunks = dctn_dev().cus / tiles;
   if (chunks < 1) chunks = 1;
   const long long max_chunks = (p.Wn + DC_WC - 1) / DC_WC;
   if (chunks > max_chunks) chunks = max_chunks;
@@ -1684,6 +1679,9 @@ int eps_bwd_dcore_bigcore(const void* x, const void* dY, void* dCore, const EpsP
   if (!dcore_plan(p, dtype, precision, d, tiles, chunks, lds)) return DCTN_ERR_UNSUPPORTED;
   const size_t slices = (size_t)chunks * p.R * p.O * sizeof(float);
   float* target = (float*)dCore;
+  const bool small = p.N * p.Q <= 40 && d.OP <= 8;
+  if (!dctn_lds_optin(small ? (const void*)eps_bigcore_dcore_k<10, 2> : (const void*)eps_bigcore_dcore_k<20, 8>, lds))
+    return DCTN_ERR_UNSUPPORTED;
   if (chunks < 2) {
     // one chunk: every element has one writer; (the kernel adds) start from zero
     if (dctn_zero_async(dCore, (size_t)p.R * p.O * sizeof(float), st) != DCTN_OK) return DCTN_ERR_LAUNCH;
@@ -1694,13 +1692,9 @@ int eps_bwd_dcore_bigcore(const void* x, const void* dY, void* dCore, const EpsP
     if (dctn_zero_async(dCore, (size_t)p.R * p.O * sizeof(float), st) != DCTN_OK) return DCTN_ERR_LAUNCH;
   }
 #define DC_LAUNCH(PX, PY)                                                                                  \
-  do {                                                                                                     \
-    (void)hipFuncSetAttribute((const void*)eps_bigcore_dcore_k<PX, PY>,                                    \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                       \
-    hipLaunchKernelGGL((eps_bigcore_dcore_k<PX, PY>), dim3((unsigned)tiles, (unsigned)chunks),            \
-                       dim3(DC_THREADS), lds, st, (const float*)x, (const float*)dY, target, d);          \
-  } while (0)
-  if (p.N * p.Q <= 40 && d.OP <= 8) DC_LAUNCH(10, 2);
+  hipLaunchKernelGGL((eps_bigcore_dcore_k<PX, PY>), dim3((unsigned)tiles, (unsigned)chunks), dim3(DC_THREADS), lds, st, \
+                     (const float*)x, (const float*)dY, target, d)
+  if (small) DC_LAUNCH(10, 2);
   else DC_LAUNCH(20, 8);
 #undef DC_LAUNCH
   DCTN_CHECK_LAUNCH();

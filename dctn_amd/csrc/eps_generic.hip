@@ -382,20 +382,18 @@ static long long hi_slices(const EpsP& p, unsigned window_blocks) {
 template <typename S, typename A>
 static int fwd_launch(const void* x, const void* core, void* out, const EpsP& p, hipStream_t st) {
   const size_t lds = fwd_lds(p, sizeof(A));
-  if (lds > DCTN_LDS_BUDGET) return DCTN_ERR_UNSUPPORTED;
+  if (lds > dctn_lds_wg_max()) return DCTN_ERR_UNSUPPORTED;
   const unsigned grid = (unsigned)((p.Wn + DCTN_WAVE - 1) / DCTN_WAVE);
   const long long slices = sizeof(S) == sizeof(A) ? hi_slices(p, grid) : 1;
   const long long hps = (p.HI + slices - 1) / slices;
   const dim3 g2(grid, (unsigned)((p.HI + hps - 1) / hps));
+  if (!dctn_lds_optin(p.O <= 4 ? (const void*)eps_fwd_generic_k<S, A, 4> : (const void*)eps_fwd_generic_k<S, A, 8>, lds))
+    return DCTN_ERR_UNSUPPORTED;
   if (g2.y > 1 && dctn_zero_async(out, (size_t)p.Wn * p.O * sizeof(S), st) != DCTN_OK) return DCTN_ERR_LAUNCH;
   if (p.O <= 4) {
-    (void)hipFuncSetAttribute((const void*)eps_fwd_generic_k<S, A, 4>,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL((eps_fwd_generic_k<S, A, 4>), g2, dim3(DCTN_WAVE), lds, st,
                        (const S*)x, (const S*)core, (S*)out, p, hps);
   } else {
-    (void)hipFuncSetAttribute((const void*)eps_fwd_generic_k<S, A, 8>,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL((eps_fwd_generic_k<S, A, 8>), g2, dim3(DCTN_WAVE), lds, st,
                        (const S*)x, (const S*)core, (S*)out, p, hps);
   }
@@ -431,7 +429,7 @@ static int bwd_launch(const void* x, const void* core, const void* dY, void* dX,
   unsigned char* wsp = (unsigned char*)ws;
   if (dX) {
     const size_t lds = dfac_lds(p, sizeof(A));
-    if (lds > DCTN_LDS_BUDGET) return DCTN_ERR_UNSUPPORTED;
+    if (lds > dctn_lds_wg_max() || !dctn_lds_optin((const void*)eps_bwd_dfactor_generic_k<S, A>, lds)) return DCTN_ERR_UNSUPPORTED;
     A* gxw = (A*)wsp;
     wsp += align256((size_t)p.Wn * p.N * p.Q * sizeof(A));
     const unsigned grid = (unsigned)((p.Wn + DCTN_WAVE - 1) / DCTN_WAVE);
@@ -440,8 +438,6 @@ static int bwd_launch(const void* x, const void* core, const void* dY, void* dX,
     const dim3 g3(grid, (unsigned)((p.HI + hps - 1) / hps));
     if (g3.y > 1 && dctn_zero_async(gxw, (size_t)p.Wn * p.N * p.Q * sizeof(A), st) != DCTN_OK)
       return DCTN_ERR_LAUNCH;
-    (void)hipFuncSetAttribute((const void*)eps_bwd_dfactor_generic_k<S, A>,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL((eps_bwd_dfactor_generic_k<S, A>), g3, dim3(DCTN_WAVE), lds, st,
                        (const S*)x, (const S*)core, (const S*)dY, gxw, p, hps);
     DCTN_CHECK_LAUNCH();
@@ -453,7 +449,9 @@ static int bwd_launch(const void* x, const void* core, const void* dY, void* dX,
   if (dCore) {
     if (p.N > 2 * (64 / p.bits)) return DCTN_ERR_UNSUPPORTED;
     const size_t lds = dcore_lds(p, sizeof(A));
-    if (lds > DCTN_LDS_BUDGET) return DCTN_ERR_UNSUPPORTED;
+    if (lds > dctn_lds_wg_max()) return DCTN_ERR_UNSUPPORTED;
+    if (!dctn_lds_optin(p.O <= 4 ? (const void*)eps_bwd_dcore_generic_k<S, A, 4> : (const void*)eps_bwd_dcore_generic_k<S, A, 8>, lds))
+      return dX ? DCTN_ERR_LAUNCH : DCTN_ERR_UNSUPPORTED;   // (dX is written by now: no fall-through)
     A* acc = sizeof(S) == sizeof(A) ? (A*)dCore : (A*)wsp;
     if (dctn_zero_async(acc, (size_t)p.R * p.O * sizeof(A), st) != DCTN_OK)
       return DCTN_ERR_LAUNCH;
@@ -468,13 +466,9 @@ static int bwd_launch(const void* x, const void* core, const void* dY, void* dX,
     chunks = (p.Wn + wpb - 1) / wpb;
     dim3 grid((unsigned)row_blocks, (unsigned)chunks);
     if (p.O <= 4) {
-      (void)hipFuncSetAttribute((const void*)eps_bwd_dcore_generic_k<S, A, 4>,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       hipLaunchKernelGGL((eps_bwd_dcore_generic_k<S, A, 4>), grid, dim3(DCTN_WAVE), lds, st,
                          (const S*)x, (const S*)dY, acc, p, wpb);
     } else {
-      (void)hipFuncSetAttribute((const void*)eps_bwd_dcore_generic_k<S, A, 8>,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       hipLaunchKernelGGL((eps_bwd_dcore_generic_k<S, A, 8>), grid, dim3(DCTN_WAVE), lds, st,
                          (const S*)x, (const S*)dY, acc, p, wpb);
     }

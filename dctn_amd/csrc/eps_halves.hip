@@ -824,9 +824,9 @@ int launch_halves_q(const S* x, S* P0, S* P1, const HalfP& h, long long w0, long
     ntab += (size_t)ipow_ll(h.p.Q, nd - nlo) + (size_t)ipow_ll(h.p.Q, nlo);
   }
   const size_t lds = (size_t)4 * ((size_t)h.p.N * h.p.Q + ntab) * sizeof(T);
-  if (lds > DCTN_LDS_BUDGET) return DCTN_ERR_UNSUPPORTED;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)halves_k<LOGQ, T, S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (lds > dctn_lds_wg_max()) return DCTN_ERR_UNSUPPORTED;
+  // (halves_shape_ok has checked the LDS plan; the calls launch before this: a refusal cannot fall through)
+  if (lds > 64 * 1024 && !dctn_lds_optin((const void*)halves_k<LOGQ, T, S>, lds)) return DCTN_ERR_LAUNCH;
   hipLaunchKernelGGL((halves_k<LOGQ, T, S>), dim3(blocks_for(nw, 4)), dim3(256), lds, st, x, P0, P1, h, w0, nw);
   DCTN_CHECK_LAUNCH();
   return DCTN_OK;
@@ -852,8 +852,7 @@ template <int LOGQ, typename T, typename S>
 int launch_dx_half_q(const S* x, const T* dP, T* gxw, const HalfP& h, int second, long long w0,
                      long long nw, hipStream_t st, DxSavedZ sz) {
   const size_t lds = dx_half_lds(h, second, sizeof(T));
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)halves_dx_half_k<LOGQ, T, S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (lds > 64 * 1024 && !dctn_lds_optin((const void*)halves_dx_half_k<LOGQ, T, S>, lds)) return DCTN_ERR_LAUNCH;
   hipLaunchKernelGGL((halves_dx_half_k<LOGQ, T, S>), dim3(blocks_for(nw, 4)), dim3(256), lds, st, x, dP, gxw, h, second, w0, nw, sz);
   DCTN_CHECK_LAUNCH();
   return DCTN_OK;
@@ -895,8 +894,8 @@ bool halves_shape_ok(const EpsP& p, size_t esz) {
   if (h.Bn > 1024 || h.A > 1024 || h.NB > (1ll << 20)) return false;   // per-wave LDS tables of the dX kernel; int-sized GEMM dims
   if (p.Wn >= (1ll << 31)) return false;
   // per-workgroup LDS of the halves kernel (features + quarter tables) and of the dX kernel (3 E per wave)
-  if ((size_t)4 * ((size_t)p.N * p.Q + 2 * (size_t)(h.A + h.Bn)) * esz > DCTN_LDS_BUDGET) return false;
-  if ((size_t)4 * ((size_t)(h.n1 > h.n0 ? h.n1 : h.n0) * p.Q + 3 * (size_t)(h.Bn > h.A ? h.Bn : h.A) + 64) * esz > DCTN_LDS_BUDGET) return false;
+  if ((size_t)4 * ((size_t)p.N * p.Q + 2 * (size_t)(h.A + h.Bn)) * esz > dctn_lds_wg_max()) return false;
+  if ((size_t)4 * ((size_t)(h.n1 > h.n0 ? h.n1 : h.n0) * p.Q + 3 * (size_t)(h.Bn > h.A ? h.Bn : h.A) + 64) * esz > dctn_lds_wg_max()) return false;
   return true;
 }
 

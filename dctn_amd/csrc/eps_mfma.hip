@@ -1827,7 +1827,6 @@ void fill_mp(MfmaP& m, const EpsP& p, const void* x, int dtype) {
 }
 
 constexpr int FWD_BLOCKS_PER_CU = 4;
-constexpr int NUM_CU = 256;
 
 // dynamic LDS of the dCore kernel: the per-wave transposition tiles of its LDST path, else nothing
 template <int N0, int N1, int OP>
@@ -1837,8 +1836,7 @@ constexpr size_t dcore_dyn_lds() {
 }
 #define DCTN_DCORE_LAUNCH(KERNEL, G, B, DYN, ST, ...)                                                  \
   do {                                                                                                 \
-    if ((DYN) > 0)                                                                                     \
-      (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(DYN)); \
+    if ((DYN) > 0 && !dctn_lds_optin((const void*)KERNEL, DYN)) return DCTN_ERR_UNSUPPORTED;       \
     hipLaunchKernelGGL(KERNEL, G, B, DYN, ST, __VA_ARGS__);                                            \
   } while (0)
 
@@ -1865,7 +1863,7 @@ bool row_vec_ok(const MfmaP& m, int OP, const void* ptr) {
 template <typename S, int N0, int N1, int OP>
 int fwd_launch_t(const void* x, const void* core, void* out, double* stats, const MfmaP& m_in, hipStream_t st) {
   MfmaP m = m_in;
-  const int blocks = plan_waves(m, 4, (long long)FWD_BLOCKS_PER_CU * NUM_CU * 4);
+  const int blocks = plan_waves(m, 4, (long long)FWD_BLOCKS_PER_CU * dctn_dev().cus * 4);
   const bool ovec = out == nullptr || row_vec_ok<S>(m, OP, out);
   const dim3 g((unsigned)blocks), b(256);
   constexpr int NN = N0 + N1;
@@ -1893,7 +1891,7 @@ int bwd_launch_t(const void* x, const void* dY, void* dCore, void* ws, const Mfm
   constexpr int A = 1 << N0, BN = 1 << N1, AT = A >= 32 ? A / 32 : 1;
   constexpr size_t DYN = dcore_dyn_lds<N0, N1, OP>();
   MfmaP m = m_in;
-  const int grid = plan_waves(m, BWD_WAVES, (long long)NUM_CU * BWD_WAVES);   // <= NUM_CU partial tiles
+  const int grid = plan_waves(m, BWD_WAVES, (long long)dctn_dev().cus * BWD_WAVES);   // <= one partial tile per CU
   const bool ovec = row_vec_ok<S>(m, OP, dY);
   const dim3 g(grid), b(64 * BWD_WAVES);
   constexpr int NN = N0 + N1;
@@ -1920,10 +1918,10 @@ int bwd_launch_t(const void* x, const void* dY, void* dCore, void* ws, const Mfm
 }
 
 // grouped wave mapping of the fused head backward: ncb chunk blocks x npg position groups workgroups
-// (<= NUM_CU: one dCore partial tile per workgroup), 8 sample chunks per chunk block
+// (<= the CU count: one dCore partial tile per workgroup), 8 sample chunks per chunk block
 int plan_grouped(MfmaP& m) {
-  if (m.npg > NUM_CU) return 0;
-  long long ncb = NUM_CU / m.npg;
+  if (m.npg > dctn_dev().cus) return 0;
+  long long ncb = dctn_dev().cus / m.npg;
   const long long need = (m.B + BWD_WAVES - 1) / BWD_WAVES;
   if (ncb > need) ncb = need;
   m.spc = (int)((m.B + ncb * BWD_WAVES - 1) / (ncb * BWD_WAVES));
@@ -1931,13 +1929,13 @@ int plan_grouped(MfmaP& m) {
   m.ncb = (m.nchunks + BWD_WAVES - 1) / BWD_WAVES;
   long long blocks = (long long)m.ncb * m.npg;
   if (blocks >= 8) blocks = (blocks + 7) / 8 * 8;
-  return blocks <= NUM_CU ? (int)blocks : 0;
+  return blocks <= dctn_dev().cus ? (int)blocks : 0;
 }
 
 size_t head_dw_partial_bytes(const EpsP& p, int Cout) {
   const long long P = (long long)p.Ho * p.Wo, npg = (P + 63) / 64;
-  if (npg > NUM_CU) return 0;
-  return (size_t)(NUM_CU / npg) * ((size_t)Cout * (size_t)(P * p.O) + 16) * sizeof(float);
+  if (npg > dctn_dev().cus) return 0;
+  return (size_t)(dctn_dev().cus / npg) * ((size_t)Cout * (size_t)(P * p.O) + 16) * sizeof(float);
 }
 
 // fused classifier-head backward (bf16 only): dLogits (B, Cout), head weight (Cout, P*O), feat (B, P*O)
@@ -1983,7 +1981,7 @@ int bwd_head_launch_t(const void* x, const void* dL, const void* hw, const void*
   const int n_core = BN * OP * AT, n_dw = gemm ? (int)(((long long)m.P * OP + DWG_FW - 1) / DWG_FW) : (int)((nW + 255) / 256);
   constexpr size_t GEMM_LDS = (size_t)DWG_WAVES * (DWG_FW / 4) * 64 * sizeof(float);
   static_assert(DWG_WAVES * 64 == 1024, "the gemm role is the whole workgroup of eps_head_reduce_k");
-  if (gemm) (void)hipFuncSetAttribute((const void*)eps_head_reduce_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEMM_LDS);
+  if (gemm && !dctn_lds_optin((const void*)eps_head_reduce_k, GEMM_LDS)) return DCTN_ERR_LAUNCH;   // (after the main kernel)
   hipLaunchKernelGGL(eps_head_reduce_k, dim3(n_core + n_dw + 1), dim3(1024), gemm ? GEMM_LDS : 0, st, (const float*)ws, (S*)dCore,
                      grid, A, BN, m.O, OP, AT * 32, n_core, (const float*)dwpart, (S*)dW, m.ncb, nW, n_dw,
                      (const S*)dL, (S*)dBias, m.B, m.Cout, (const S*)feat, gemm ? 1 : 0);
@@ -2001,7 +1999,7 @@ int fwd_head_launch_t(const void* x, const void* core, const void* hw, const voi
   if (m.O != OP || !(m.rowvec_ok && m.vec_ok) || m.npg > HEAD_FWD_MAXPG) return DCTN_ERR_UNSUPPORTED;
   // 16-byte weight fragments, (OP * 2)-byte feature rows
   if (((uintptr_t)hw % 16) != 0 || m.hw_rowb % 16 != 0 || ((uintptr_t)out % (OP * 2)) != 0) return DCTN_ERR_UNSUPPORTED;
-  int nwg = m.B < NUM_CU ? m.B : NUM_CU;
+  int nwg = m.B < dctn_dev().cus ? m.B : dctn_dev().cus;
   m.spc = (m.B + nwg - 1) / nwg;
   nwg = (m.B + m.spc - 1) / m.spc;
   constexpr int RW = (N0 + N1) == 9 ? 3 : 4;
@@ -2010,7 +2008,7 @@ int fwd_head_launch_t(const void* x, const void* core, const void* hw, const voi
     // steps pulled from a counter by 16 waves, head as a tail phase (DCTN_OPT_SMALL_CHUNKS keeps the round-4 structure:
     // a wave per position group, for same-box comparisons)
     const size_t dyn = (size_t)HEADT_GS * headt_pitch((int)F) * sizeof(short);
-    (void)hipFuncSetAttribute((const void*)eps_fwd_head_q2reg_t_k<N0, N1, OP, RW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+    if (!dctn_lds_optin((const void*)eps_fwd_head_q2reg_t_k<N0, N1, OP, RW>, dyn)) return DCTN_ERR_UNSUPPORTED;
     hipLaunchKernelGGL((eps_fwd_head_q2reg_t_k<N0, N1, OP, RW>), dim3((unsigned)nwg), dim3(64 * HEADT_WAVES), dyn, st, (const S*)x,
                        (const S*)core, (const S*)hw, (const S*)bias, (S*)out, (S*)logits, m);
     DCTN_CHECK_LAUNCH();
@@ -2068,7 +2066,7 @@ size_t eps_bwd_mfma_workspace(const EpsP& p, int dtype, int precision, int need_
   const int op = next_pow2(p.O) < 2 ? 2 : next_pow2(p.O);
   const int n0 = (p.N + 1) / 2, n1 = p.N - n0;
   const long long A = 1LL << n0, BN = 1LL << n1, acols = A >= 32 ? A : 32;
-  return (size_t)NUM_CU * (size_t)(BN * op) * (size_t)acols * sizeof(float);
+  return (size_t)dctn_dev().cus * (size_t)(BN * op) * (size_t)acols * sizeof(float);
 }
 
 // dCore only; the caller (capi) sends dX to the generic kernels.
@@ -2094,7 +2092,7 @@ static bool head_family_ok(const EpsP& p, int Cout, int dtype, int precision) {
   if (op != p.O || op > 4) return false;   // the weight slice and its gradient live in registers
   if (Cout < 2 || Cout > 16 || Cout % 2 != 0) return false;
   const long long P = (long long)p.Ho * p.Wo;
-  if ((P + 63) / 64 > NUM_CU) return false;
+  if ((P + 63) / 64 > dctn_dev().cus) return false;
   return P * p.O * 2 * Cout < (1LL << 31);
 }
 

@@ -44,7 +44,6 @@ namespace {
 
 constexpr int QF_WAVES = 8;        // waves per workgroup, both kernels: two per SIMD
 constexpr int QF_MAXN = 9;
-constexpr int QF_NUM_CU = 256;
 constexpr int QF_PITCH = 68;       // floats per row of the backward's transposition tile (64 windows + 4)
 
 struct Q2fP {
@@ -778,7 +777,8 @@ bool family_ok(const EpsP& p, int dtype, int precision) {
     if ((ext + 1) * 4 >= (1LL << 31)) return false;
     if (p.Wn * p.O * 4 >= (1LL << 31)) return false;
   }
-  return true;
+  const int n0 = (p.N + 1) / 2;   // the backward's transposition tiles must fit a workgroup's LDS
+  return bwd_dyn_lds_bytes(1 << n0, 1 << (p.N - n0), p.O <= 2 ? 2 : 4) <= (size_t)dctn_lds_wg_max();
 }
 
 // window mode of a shape / layout (template parameter WIN)
@@ -823,7 +823,7 @@ bool row_vec_ok(const Q2fP& m, int OP, const void* ptr) { return m.O == OP && ((
 template <int N0, int N1, int OP>
 int fwd_launch_t(const void* x, const void* core, void* out, Q2fP m, int win, hipStream_t st) {
   // one or two workgroups per CU (the kernel holds ~120 registers: four waves per SIMD fit)
-  int nwg = m.B < 2 * QF_NUM_CU ? m.B : 2 * QF_NUM_CU;
+  int nwg = m.B < 2 * dctn_dev().cus ? m.B : 2 * dctn_dev().cus;
   m.spc = (m.B + nwg - 1) / nwg;
   nwg = (m.B + m.spc - 1) / m.spc;
   m.ovec = row_vec_ok(m, OP, out) ? 1 : 0;
@@ -843,9 +843,8 @@ int fwd_launch_t(const void* x, const void* core, void* out, Q2fP m, int win, hi
 #define QF_FWD_HEAD_LAUNCH(WINV, HC)                                                                                       \
   do {                                                                                                                     \
     const size_t dyn = ((size_t)FWD_GS * fwd_tile_pitch(m.P * OP) + (size_t)QF_WAVES * ((HC + 3) / 4) * 4 * 64) * sizeof(float); \
-    if (dyn > 150 * 1024) return DCTN_ERR_UNSUPPORTED;                                                                      \
-    (void)hipFuncSetAttribute((const void*)eps_fwd_q2f32_k<N0, N1, OP, WINV, HC>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              (int)dyn);                                                                                   \
+    if (dyn > (size_t)dctn_lds_wg_max() || !dctn_lds_optin((const void*)eps_fwd_q2f32_k<N0, N1, OP, WINV, HC>, dyn))      \
+      return DCTN_ERR_UNSUPPORTED;                                                                                         \
     hipLaunchKernelGGL((eps_fwd_q2f32_k<N0, N1, OP, WINV, HC>), g, b, dyn, st, (const float*)x, (const float*)core,         \
                        (float*)out, (const float*)hw, (const float*)bias, (float*)logits, m);                              \
   } while (0)
@@ -858,7 +857,7 @@ int fwd_head_launch_t(const void* x, const void* core, const void* hw, const voi
   if (m.O != OP || F % 4 != 0 || F > (long long)QF_WAVES * FWD_MAXBS * 64) return DCTN_ERR_UNSUPPORTED;
   if (((uintptr_t)hw % 16) != 0 || ((uintptr_t)out % (OP * 4)) != 0) return DCTN_ERR_UNSUPPORTED;
   // one workgroup per CU (166 registers with the head's weight fragments: no second workgroup fits beside it)
-  int nwg = m.B < QF_NUM_CU ? m.B : QF_NUM_CU;
+  int nwg = m.B < dctn_dev().cus ? m.B : dctn_dev().cus;
   m.spc = (m.B + nwg - 1) / nwg;
   nwg = (m.B + m.spc - 1) / m.spc;
   m.ovec = 1;
@@ -875,10 +874,10 @@ int fwd_head_launch_t(const void* x, const void* core, const void* hw, const voi
 }
 #undef QF_FWD_HEAD_LAUNCH
 
-// the backward's grid: ncb chunk blocks x npg position groups workgroups (<= QF_NUM_CU: one partial tile each)
+// the backward's grid: ncb chunk blocks x npg position groups workgroups (<= the CU count: one partial tile each)
 int plan_bwd(Q2fP& m) {
-  if (m.npg > QF_NUM_CU) return 0;
-  long long ncb = QF_NUM_CU / m.npg;
+  if (m.npg > dctn_dev().cus) return 0;
+  long long ncb = dctn_dev().cus / m.npg;
   const long long need = (m.B + QF_WAVES - 1) / QF_WAVES;   // at least one sample per wave where the batch allows
   if (ncb > need) ncb = need;
   m.ncb = (int)ncb;
@@ -888,8 +887,7 @@ int plan_bwd(Q2fP& m) {
 
 #define QF_BWD_LAUNCH(WINV, HC)                                                                                          \
   do {                                                                                                                   \
-    (void)hipFuncSetAttribute((const void*)eps_bwd_q2f32_k<N0, N1, OP, WINV, HC>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              (int)DYN);                                                                                 \
+    if (!dctn_lds_optin((const void*)eps_bwd_q2f32_k<N0, N1, OP, WINV, HC>, DYN)) return DCTN_ERR_UNSUPPORTED;            \
     hipLaunchKernelGGL((eps_bwd_q2f32_k<N0, N1, OP, WINV, HC>), g, b, DYN, st, (const float*)x, (const float*)dY,         \
                        (const float*)hw, (float*)ws, m);                                                                 \
   } while (0)
@@ -954,7 +952,7 @@ int eps_fwd_q2f32(const void* x, const void* core, void* out, const EpsP& p, int
 
 size_t eps_bwd_q2f32_workspace(const EpsP& p, int dtype, int precision) {
   if (!family_ok(p, dtype, precision)) return 0;
-  return (size_t)QF_NUM_CU * 2 * 1024 * sizeof(float);   // one (MT <= 2) x 32 x 32 tile per workgroup
+  return (size_t)dctn_dev().cus * 2 * 1024 * sizeof(float);   // one (MT <= 2) x 32 x 32 tile per workgroup
 }
 
 // dCore only; the caller (capi) sends dX to the large-core family.
@@ -978,7 +976,7 @@ static bool head_ok(const EpsP& p, int Cout, int dtype, int precision) {
   if (p.O != 2 && p.O != 4) return false;   // the weight slice of a lane is one 8- / 16-byte piece
   if (Cout < 1 || Cout > 16) return false;
   const long long P = (long long)p.Ho * p.Wo;
-  if ((P + 63) / 64 > QF_NUM_CU) return false;
+  if ((P + 63) / 64 > dctn_dev().cus) return false;
   return P * p.O * 4 * Cout < (1LL << 31) && (long long)p.B * Cout * 4 < (1LL << 31);
 }
 

@@ -453,7 +453,7 @@ int dctn_linear_head_fwd(const void* feat, const void* weight, const void* bias,
     if (rc == DCTN_OK) dctn_set_last_kernel("linear_head_fwd_generic");
     return rc;
   }
-  if ((B + 15) / 16 >= 256)
+  if ((B + 15) / 16 >= dctn_dev().cus)   // a workgroup per CU at least: 16 rows each
     hipLaunchKernelGGL(head_fwd_k<16>, dim3((unsigned)((B + 15) / 16)), dim3(512), 0, (hipStream_t)stream,
                        (const bf16_t*)feat, (const bf16_t*)weight, (const bf16_t*)bias, (bf16_t*)out,
                        (long long)B, F, Cout);

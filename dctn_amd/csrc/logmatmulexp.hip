@@ -832,10 +832,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void l
 
 // workgroups of `threads` that are resident at once on the whole device
 long long resident_blocks(const void* fn, int threads) {
-  int per_cu = 0, dev = 0, cus = 256;
+  int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, 0) != hipSuccess || per_cu < 1) per_cu = 2;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  return (long long)per_cu * cus;
+  return (long long)per_cu * dctn_dev().cus;
 }
 
 template <int L, bool NT>
@@ -914,9 +913,8 @@ template <typename S, typename A>
 int fold_bwd_launch(const void* mats, const void* dOut, void* dMats, long long Wn, int L, int D,
                     hipStream_t st, const int* only_flagged = nullptr) {
   const size_t lds = ((size_t)(L + 2) * D * (D + 1)) * sizeof(A);
-  if (lds > DCTN_LDS_BUDGET) return DCTN_ERR_UNSUPPORTED;
-  (void)hipFuncSetAttribute((const void*)lme_fold_bwd_k<S, A>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (lds > dctn_lds_wg_max() || !dctn_lds_optin((const void*)lme_fold_bwd_k<S, A>, lds))
+    return only_flagged ? DCTN_ERR_LAUNCH : DCTN_ERR_UNSUPPORTED;   // (the flagged windows' pass follows the fold's first tiers)
   unsigned grid = (unsigned)(Wn < 256 * 32 ? Wn : 256 * 32);
   if (only_flagged) {   // one turn of D * D flags per workgroup
     const long long g = (Wn + (long long)D * D - 1) / ((long long)D * D);
@@ -1059,7 +1057,7 @@ int dctn_logmatmulexp_fold_bwd(const void* mats, const void* dOut, void* dMats, 
   if (dtype == DCTN_F32 && D == 16 && L >= 2 && L <= 16 && workspace &&
       workspace_bytes >= 256 + (size_t)Wn * sizeof(int) && ((uintptr_t)mats % 16 == 0) &&
       ((uintptr_t)dOut % 16 == 0) && ((uintptr_t)dMats % 16 == 0) && ((uintptr_t)workspace % 4 == 0) &&
-      (size_t)(L + 2) * 16 * 17 * sizeof(float) <= DCTN_LDS_BUDGET) {
+      (size_t)(L + 2) * 16 * 17 * sizeof(float) <= dctn_lds_wg_max()) {
     int* flags = reinterpret_cast<int*>(static_cast<unsigned char*>(workspace) + 256);
     const float* m = (const float*)mats;
     const float* dy = (const float*)dOut;

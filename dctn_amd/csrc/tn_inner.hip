@@ -169,8 +169,7 @@ int gram_launch(const void* A, const void* B, void* out, void* ws, long long nfi
   const int nblk = gram_blocks(nfib), P = qa * qb;
   const long long per = ((nfib + nblk - 1) / nblk + TN_TILE - 1) / TN_TILE * TN_TILE;
   const size_t lds = ((size_t)TN_TILE * (qa + qb) + TN_THREADS) * sizeof(Acc);
-  if (lds > 60 * 1024)
-    (void)hipFuncSetAttribute((const void*)tn_fiber_gram_k<S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (lds > 60 * 1024 && !dctn_lds_optin((const void*)tn_fiber_gram_k<S>, lds)) return DCTN_ERR_UNSUPPORTED;
   hipLaunchKernelGGL((tn_fiber_gram_k<S>), dim3(nblk), dim3(TN_THREADS), lds, st, (const S*)A, (const S*)B, (Acc*)ws,
                      nfib, qa, qb, post, per);
   DCTN_CHECK_LAUNCH();

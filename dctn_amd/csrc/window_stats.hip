@@ -165,7 +165,7 @@ extern "C" int dctn_window_stats(const void* x, const int64_t x_strides[5], void
   hipStream_t st = (hipStream_t)stream;
   if (dctn_zero_async(sums, 2 * sizeof(double), st) != DCTN_OK) return DCTN_ERR_LAUNCH;
   long long blocks = (p.Wn + 255) / 256;
-  if (blocks > 256 * 8) blocks = 256 * 8;
+  if (blocks > dctn_dev().cus * 8) blocks = dctn_dev().cus * 8;
   const dim3 g((unsigned)blocks), b(256);
   switch (dtype) {
     case DCTN_F32: hipLaunchKernelGGL(window_stats_k<float>, g, b, 0, st, (const float*)x, (double*)sums, p); break;
@@ -262,10 +262,10 @@ extern "C" int dctn_phi_window_stats(const void* images, void* sums, int B, int 
   if (!images || !sums) return DCTN_ERR_NULL;
   if (B < 1 || K < 1 || H < K || W < K) return DCTN_ERR_BAD_SHAPE;
   const size_t lds = (size_t)H * W * 2 * sizeof(double);
-  if (lds > DCTN_LDS_BUDGET) return DCTN_ERR_UNSUPPORTED;   // (images beyond ~97 x 97: expand, then dctn_window_stats)
+  if (lds > dctn_lds_wg_max() || !dctn_lds_optin((const void*)phi_window_stats_k, lds))
+    return DCTN_ERR_UNSUPPORTED;   // (images beyond ~97 x 97: expand, then dctn_window_stats)
   hipStream_t st = (hipStream_t)stream;
   if (dctn_zero_async(sums, 2 * sizeof(double), st) != DCTN_OK) return DCTN_ERR_LAUNCH;
-  (void)hipFuncSetAttribute((const void*)phi_window_stats_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(phi_window_stats_k, dim3((unsigned)B), dim3(256), lds, st, (const float*)images, (double*)sums, H, W, K);
   DCTN_CHECK_LAUNCH();
   dctn_set_last_kernel("phi_window_stats");

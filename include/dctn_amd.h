@@ -14,8 +14,9 @@
  *   - return value: 0 on success, negative DCTN_ERR_* otherwise (dctn_strerror()).  The Python
  *     host layer turns shape errors into AssertionError like the reference's `assert`s.
  *   - dtype codes: DCTN_F32 / DCTN_F64 / DCTN_BF16 (bf16 storage, fp32 accumulation).
- *   - re-entrant.  Nothing a call computes depends on process state: no environment variables are read, there are
- *     no setters; the one mutable global is the diagnostic name returned by dctn_last_kernel().
+ *   - re-entrant.  Nothing a call computes depends on process state beyond the device's geometry (CU count, LDS per
+ *     CU: asked once, dctn_device_limits()); there are no setters; the one mutable global is the diagnostic name
+ *     returned by dctn_last_kernel().
  */
 #ifndef DCTN_AMD_H
 #define DCTN_AMD_H
@@ -80,6 +81,11 @@ const char* dctn_strerror(int code);
 /* name of the kernel family the last successful call dispatched to
  * (diagnostics / tests: proves which HIP path ran; process-wide, last writer wins) */
 const char* dctn_last_kernel(void);
+
+/* the device geometry every plan of the library assumes: CUs and LDS bytes per CU of the current device, asked once
+ * per process (gfx950 values where the runtime cannot say).  The environment variable DCTN_DEVICE_LIMITS="cus,lds"
+ * can only lower them: tests run the plans of a smaller device (a partitioned card) with it. */
+int dctn_device_limits(int* cus, int* lds_bytes);
 
 /* ------------------------------------------------------------------------------------------
  * EPS — replaces dctn/eps.py:19-40 `eps(core, input)` (and :43-63 `eps_one_by_one`, same result)

@@ -8,9 +8,11 @@ leaves — with the arithmetic on the MI355X (CPU tensors are staged to the devi
 last-kernel name proves the HIP path ran).  Nothing here touches the oracle: the expected values are the
 independent einsum definitions the reference's tests use.
 """
+import functools
 import itertools
 import string
 
+import numpy as np
 import pytest
 import torch
 
@@ -137,3 +139,243 @@ def test_mixed_placement_raises():
 
     with pytest.raises(RuntimeError, match="one device"):
         dctn.eps.eps(torch.randn(2, 2, 2, 2, 3), torch.randn(1, 2, 4, 4, 2, device="cuda"))
+
+
+# ------------------------------------------------------------------ the device geometry the plans assume
+# The library asks the device for its CU count and LDS per CU once (dctn_device_limits); DCTN_DEVICE_LIMITS="cus,lds"
+# can only lower them.  Each family runs once at reduced size in a child process: on the card as it is, with a quarter
+# of its CUs (every family must still run, on the same kernels, and match the oracle) and with 64 KiB of LDS (a shape
+# that no longer fits must be declined - NotImplementedError - and never fail at the launch).
+def _limits_cases():
+    import dctn_amd
+    import dctn_amd.eps_plus_linear as EPL
+    from dctn_amd.conv_sbs import ConvSBS, DumbNormalInitialization, ManyConvSBS
+    from dctn_amd.conv_sbs_spec import SBSSpecCore, SBSSpecString
+    from dctn_amd.eps import eps
+    from dctn_amd.logmatmulexp import logmatmulexp_fold
+    from dctn_amd.pos2d import Pos2D
+    from dctn_amd.tn_inner import gram_over_input_dims
+    from dctn_amd.window_stats import apply_feature_map, window_mean_var
+    from oracle import ref_cpu as R
+    from tests.test_gpu_parity import bf16_close, close
+
+    dev = torch.device("cuda:0")
+    snake = [(0, 0), (0, 1), (0, 2), (1, 2), (1, 1), (1, 0), (2, 0), (2, 1), (2, 2)]
+
+    def run_eps(C, B, H, W, Q, K, O, dtype, x_grad):
+        N = K * K * C
+        if Q == 2:
+            u = torch.rand(C, B, H, W)
+            x = torch.stack((torch.sin(u * torch.pi / 2) ** 2, torch.cos(u * torch.pi / 2) ** 2), dim=-1).to(dtype)
+        else:
+            x = torch.randn(C, B, H, W, Q, dtype=dtype)
+        core = (torch.randn(*(Q,) * N, O, dtype=torch.float64) * Q ** (-N / 4)).to(dtype)
+        xd, cd = x.to(dev).requires_grad_(x_grad), core.to(dev).requires_grad_(True)
+        y = eps(cd, xd)
+        names = [dctn_amd.last_kernel()]
+        want = R.eps_4step(core.double(), x.double())
+        dy = torch.randn(*want.shape, dtype=torch.float64).to(dtype)
+        y.backward(dy.to(dev))
+        names.append(dctn_amd.last_kernel())
+        dcore, dx = R.grads(R.eps_4step, [core.double(), x.double()], dy.double())
+        if dtype == torch.bfloat16:
+            ok = bf16_close(y, want) and bf16_close(cd.grad, dcore)
+        else:
+            ok = close(y, want, dtype) and close(cd.grad, dcore, dtype) and (not x_grad or close(xd.grad, dx, dtype))
+        return ok, names
+
+    def run_head(dtype):
+        torch.manual_seed(5)
+        B, size, cout = 5, 12, 10
+        core = (torch.randn(*(2,) * 9, 4) * 2.0 ** (-3.5)).to(dtype).to(dev).requires_grad_(True)
+        w = (torch.randn(cout, 10 * 10 * 4) * 0.05).to(dtype).to(dev).requires_grad_(True)
+        bias = torch.randn(cout).to(dtype).to(dev).requires_grad_(True)
+        u = torch.rand(1, B, size, size)
+        x = torch.stack([torch.sin(u * 1.5707963) ** 2, torch.cos(u * 1.5707963) ** 2], dim=-1).to(dtype).to(dev)
+        assert EPL._EpsLinearHeadFunction.supported(core, x, w, bias)
+        out = EPL._EpsLinearHeadFunction.apply(core, x, w, bias)
+        names = [dctn_amd.last_kernel()]
+        g = torch.randn(B, cout).to(dtype)
+        out.backward(g.to(dev))
+        names.append(dctn_amd.last_kernel())
+        leaves = [t.detach().cpu().double().requires_grad_(True) for t in (core, w, bias)]
+        want = R.eps_plus_linear_forward([leaves[0]], leaves[1], leaves[2], x.cpu().double())
+        want.backward(g.double())
+        pairs = [(out, want.detach())] + [(t.grad, r.grad) for t, r in zip((core, w, bias), leaves)]
+        if dtype == torch.bfloat16:
+            return all(bf16_close(a, b) for a, b in pairs), names
+        return all(close(a, b, dtype) for a, b in pairs), names
+
+    def run_sbs(module, x, pos_of_strings):
+        ys = module(x)
+        ys = ys if isinstance(ys, (tuple, list)) else (ys,)
+        names = [dctn_amd.last_kernel()]
+        dys = [torch.randn_like(y) for y in ys]
+        torch.autograd.backward(list(ys), dys)
+        names.append(dctn_amd.last_kernel())
+        x64 = x.detach().cpu().double()
+        strings = module.strings if hasattr(module, "strings") else [module]
+        gx = torch.zeros_like(x64)
+        ok = True
+        for s, pos, y, dy in zip(strings, pos_of_strings, ys, dys):
+            cores64 = [c.detach().cpu().double() for c in s.cores]
+            ok = ok and close(y, R.convsbs_forward(cores64, pos, x64), x.dtype)
+            gr = R.grads(lambda xx, *cc: R.convsbs_forward(cc, pos, xx), [x64] + cores64, dy.cpu().double())
+            gx += gr[0]
+            ok = ok and all(close(c.grad, gc, x.dtype) for c, gc in zip(s.cores, gr[1:]))
+        return ok and close(x.grad, gx, x.dtype), names
+
+    def snake_sbs(r, q, C, B, HW, dtype=torch.float32):
+        spec = (tuple(SBSSpecCore(Pos2D(*p), 2 if i == 4 else 1) for i, p in enumerate(snake)),)
+        many = ManyConvSBS(C, q, r, False, spec, (DumbNormalInitialization((q**C * r) ** -0.5),)).to(dev).to(dtype)
+        x = torch.randn(C, B, HW, HW, q, device=dev, dtype=dtype, requires_grad=True)
+        return run_sbs(many, x, [snake])
+
+    def band_many():
+        snake_b = [(0, 0), (1, 0), (2, 0), (2, 1), (1, 1), (0, 1), (0, 2), (1, 2), (2, 2)]
+        outs = (1, 1, 1, 1, 2, 1, 1, 1, 1)
+        specs = tuple(tuple(SBSSpecCore(Pos2D(h, w), o) for (h, w), o in zip(sn, outs)) for sn in (snake, snake_b))
+        init = DumbNormalInitialization((4 * 16) ** -0.5 * 1.2)
+        many = ManyConvSBS(2, 2, 16, False, specs, (init, init)).to(dev)
+        x = torch.randn(2, 3, 7, 8, 2, device=dev, requires_grad=True)
+        return run_sbs(many, x, [snake, snake_b])
+
+    def sbs_ring():
+        cores = (SBSSpecCore(Pos2D(0, 0), 1), SBSSpecCore(Pos2D(0, 1), 3), SBSSpecCore(Pos2D(1, 0), 2), SBSSpecCore(Pos2D(1, 1), 4))
+        m = ConvSBS(SBSSpecString(cores, (3, 4, 5, 6), 2, 2)).to(dev)
+        x = torch.randn(2, 3, 4, 5, 2, device=dev, requires_grad=True)
+        return run_sbs(m, x, [[(c.position.h, c.position.w) for c in cores]])
+
+    def fold():
+        m = torch.randn(70, 9, 16, 16)
+        md = m.to(dev).requires_grad_(True)
+        y = logmatmulexp_fold(md)
+        names = [dctn_amd.last_kernel()]
+        dy = torch.randn(70, 16, 16)
+        y.backward(dy.to(dev))
+        names.append(dctn_amd.last_kernel())
+        want = R.logmatmulexp_fold_batched(m.double())
+        (gm,) = R.grads(R.logmatmulexp_fold_batched, [m.double()], dy.double())
+        ok = torch.allclose(y.cpu().double(), want, rtol=5e-5, atol=5e-5)
+        return ok and torch.allclose(md.grad.cpu().double(), gm, rtol=1e-4, atol=1e-4 * float(gm.abs().max())), names
+
+    def window_stats():
+        x = apply_feature_map(torch.rand(40, 28, 28))
+        mean, var = window_mean_var(x.to(dev), 3)
+        ref = R.window_mean_var_factor(x, 3)
+        ok = np.isclose(float(mean), float(ref[0]), rtol=1e-6) and np.isclose(float(var), float(ref[1]), rtol=1e-5)
+        return ok, [dctn_amd.last_kernel()]
+
+    def tn_inner():
+        a = torch.randn(4, 4, 4, 5, dtype=torch.float64)
+        b = torch.randn(4, 4, 4, 6, dtype=torch.float64)
+        ad, bd = a.to(dev).requires_grad_(True), b.to(dev).requires_grad_(True)
+        g = gram_over_input_dims(ad, bd)
+        names = [dctn_amd.last_kernel()]
+        dg = torch.randn(5, 6, dtype=torch.float64)
+        g.backward(dg.to(dev))
+        names.append(dctn_amd.last_kernel())
+        want = torch.einsum("ijko,ijkp->op", a, b)
+        ok = close(g, want, torch.float64)
+        ok = ok and close(ad.grad, torch.einsum("ijkp,op->ijko", b, dg), torch.float64)
+        return ok and close(bd.grad, torch.einsum("ijko,op->ijkp", a, dg), torch.float64), names
+
+    return {
+        "eps_q2reg_bf16": lambda: run_eps(1, 3, 10, 10, 2, 3, 4, torch.bfloat16, False),
+        "eps_q2f32": lambda: run_eps(1, 3, 10, 10, 2, 3, 4, torch.float32, False),
+        "eps_bigcore_f32": lambda: run_eps(1, 2, 6, 7, 4, 3, 6, torch.float32, True),
+        "eps_halves_f64": lambda: run_eps(1, 2, 28, 28, 2, 4, 2, torch.float64, True),
+        "eps_generic": lambda: run_eps(2, 2, 7, 6, 2, 2, 3, torch.float64, True),
+        "head_f32": lambda: run_head(torch.float32),
+        "head_bf16": lambda: run_head(torch.bfloat16),
+        "sbs_reg_r4": lambda: snake_sbs(4, 3, 1, 3, 12),
+        "sbs_band_r8": lambda: snake_sbs(8, 3, 1, 2, 10),
+        "sbs_band_r16": lambda: snake_sbs(16, 3, 1, 2, 8),
+        "sbs_band_many": band_many,
+        "sbs_mfma": sbs_ring,
+        "sbs_generic": lambda: snake_sbs(3, 2, 1, 2, 7, torch.float64),
+        "fold": fold,
+        "window_stats": window_stats,
+        "tn_inner": tn_inner,
+    }
+
+
+def _limits_child():
+    """Child process: every case once; one JSON line {case: {ok, kernels} or {declined} or {error}} plus the limits."""
+    import ctypes
+    import json
+
+    from dctn_amd import _lib
+
+    out = {}
+    for name, case in _limits_cases().items():
+        torch.manual_seed(sum(map(ord, name)))
+        try:
+            ok, names = case()
+            out[name] = {"ok": bool(ok), "kernels": names}
+        except NotImplementedError as e:
+            out[name] = {"declined": str(e)[:200]}
+        except Exception as e:   # a launch error or anything else: reported, the parent fails on it
+            out[name] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
+        torch.cuda.synchronize()
+    cus, lds = ctypes.c_int(), ctypes.c_int()
+    assert _lib.lib().dctn_device_limits(ctypes.byref(cus), ctypes.byref(lds)) == 0
+    print(json.dumps({"limits": [cus.value, lds.value], "cases": out}))
+
+
+def _run_limits_child(limits):
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    env.pop("DCTN_DEVICE_LIMITS", None)
+    if limits:
+        env["DCTN_DEVICE_LIMITS"] = limits
+    code = f"import sys; sys.path.insert(0, {root!r}); from tests.test_gpu_boundary import _limits_child; _limits_child()"
+    res = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                         text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-3000:]
+    return json.loads(res.stdout.strip().splitlines()[-1])
+
+
+@functools.lru_cache(maxsize=None)
+def _limits_run(limits):
+    return _run_limits_child(limits)
+
+
+def test_device_limits_are_the_mi355x_as_it_is():
+    import ctypes
+
+    from dctn_amd import _lib
+
+    cus, lds = ctypes.c_int(), ctypes.c_int()
+    assert _lib.lib().dctn_device_limits(ctypes.byref(cus), ctypes.byref(lds)) == 0
+    assert cus.value == torch.cuda.get_device_properties(0).multi_processor_count
+    if "gfx950" in torch.cuda.get_device_properties(0).gcnArchName:
+        assert lds.value == 160 * 1024   # the plans of every family were written for it: on it the helper changes nothing
+
+
+def test_fewer_cus_still_run_every_family_on_the_same_kernels():
+    full = _limits_run(None)
+    assert all(r.get("ok") for r in full["cases"].values()), full
+    few = _limits_run("64,163840")
+    assert few["limits"] == [64, full["limits"][1]]
+    for name, r in few["cases"].items():
+        assert r.get("ok"), (name, r)
+        assert r["kernels"] == full["cases"][name]["kernels"], (name, r, full["cases"][name])
+
+
+def test_less_lds_declines_cleanly():
+    full = _limits_run(None)
+    small = _limits_run("256,65536")
+    assert small["limits"] == [full["limits"][0], 65536]
+    handed = set()
+    for name, r in small["cases"].items():
+        assert "error" not in r, (name, r)
+        assert "declined" in r or r["ok"], (name, r)
+        if "declined" in r or r["kernels"] != full["cases"][name]["kernels"]:
+            handed.add(name)
+    assert {"sbs_band_r8", "sbs_band_r16", "eps_bigcore_f32", "eps_q2f32"} <= handed, small
