@@ -22,6 +22,7 @@ OPT_F32_PREFER_HALVES, OPT_SMALL_CHUNKS, OPT_MAIN_KERNEL_ONLY, OPT_GENERIC_KERNE
 ERR_BAD_SHAPE, ERR_BAD_DTYPE, ERR_UNSUPPORTED, ERR_WORKSPACE, ERR_LAUNCH, ERR_NULL = -1, -2, -3, -4, -5, -6
 SAVED, PARTIAL = 1, 2   # positive success codes (include/dctn_amd.h)
 SBS_MATRIX_CORE_SWEEP = 1 << 8   # OR-ed into the dtype argument of the dctn_convsbs_* calls
+SBS_WIDE_SWEEP = 1 << 9   # likewise: the backward on the wide family (convsbs_wide.hip) for any string it covers
 
 _DTYPE_CODE = {torch.float32: F32, torch.float64: F64, torch.bfloat16: BF16}
 

@@ -124,6 +124,24 @@ class matrix_core_sweep:
         return False
 
 
+class wide_sweep:
+    """``with wide_sweep(): ...`` - the backward of every string runs on the wide family (convsbs_wide.hip), the one
+    strings whose core gradients do not fit one workgroup's LDS fall to, instead of the family that is their default: the
+    tests hold it against the generic sweep and the expected values on strings both take (`DCTN_SBS_WIDE_SWEEP`).  The forward is
+    unchanged, and the strings of a layer go one by one."""
+
+    def __enter__(self):
+        global _sbs_flags
+        self._saved = _sbs_flags
+        _sbs_flags |= L.SBS_WIDE_SWEEP
+        return self
+
+    def __exit__(self, *exc):
+        global _sbs_flags
+        _sbs_flags = self._saved
+        return False
+
+
 class _ConvSBSFunction(torch.autograd.Function):
     """x: (C, B, H, W, q) any strides; cores in string order."""
 

@@ -162,6 +162,15 @@ int convsbs_fwd_band(const void* x, const int64_t xs[5], const void* const* core
 int convsbs_bwd_band(const void* x, const int64_t xs[5], const void* const* cores, const void* dY, void* dX,
                      float* const* dcores, int n, const int* out_sizes, const int* bond_sizes, const int* pos_h,
                      const int* pos_w, int C, int B, int H, int W, int q, int dtype, hipStream_t st, void* ws, size_t ws_bytes);
+// Wide backward for strings whose core gradients do not fit one workgroup's LDS (any bond, f32 / f64 / bf16 storage) -
+// convsbs_wide.hip.  GEMMs over HBM buffers of window chunks, fixed-order partial records, no atomics.  The per-window input
+// gradients land at the START of `ws` in the generic sweep's gxw layout ([n C q][windows]; the caller gathers dX from them
+// when need_dx).  convsbs_wide_bwd_workspace: 0 = outside the family.
+size_t convsbs_wide_bwd_workspace(int n, const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w, int C,
+                                  int B, int H, int W, int q, int dtype);
+int convsbs_bwd_wide(const void* x, const int64_t xs[5], const void* const* cores, const void* dY, int need_dx,
+                     void* const* dcores, int n, const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w,
+                     int C, int B, int H, int W, int q, int dtype, hipStream_t st, void* ws, size_t ws_bytes);
 // room for the per-workgroup partial-gradient records of the MFMA backward (deterministic dCore)
 constexpr int SBS_MAX_PARTIAL_RECORDS = 2048;
 

@@ -492,6 +492,38 @@ int bwd_launch(const void* x, const void* dY, void* dX, void* const* dCores, voi
   return DCTN_OK;
 }
 
+// Whether the LDS plan of bwd_launch takes the string when it computes core gradients (the same arithmetic as its two
+// checks; the runtime's opt-in aside): strings it declines fall to the wide family, whose workspace the query then adds.
+bool generic_bwd_fits(const SbsP& p, size_t asz) {
+  long long ce = 0;
+  for (int c = 0; c < p.n; ++c) ce += core_elems(p, c);
+  const size_t acc_bytes = (size_t)ce * asz;
+  if (acc_bytes > dctn_lds_wg_max() / 2) return false;
+  const size_t per_col = ((size_t)3 * p.vmax + 2 * p.qc + p.Otot) * asz;
+  int cs = DCTN_WAVE;
+  while (cs > 1 && per_col * (cs + 1) + acc_bytes > dctn_lds_wg_max()) cs >>= 1;
+  return per_col * (cs + 1) + acc_bytes <= dctn_lds_wg_max();
+}
+
+// The wide family (convsbs_wide.hip) writes the per-window input gradients at the start of the workspace; dX is gathered
+// from them by the generic sweep's own kernel.
+template <typename S, typename A>
+int wide_launch(const void* x, const void* dY, void* dX, void* const* dCores, void* ws, size_t ws_bytes, SbsP& p, int dtype,
+                hipStream_t st) {
+  const int rc = convsbs_bwd_wide(x, (const int64_t*)p.s, (const void* const*)p.core, dY, dX != nullptr, dCores, p.n, p.o, p.bl,
+                                  p.ph, p.pw, p.C, p.B, p.H, p.W, p.q, dtype, st, ws, ws_bytes);
+  if (rc != DCTN_OK) return rc;
+  if (dX) {
+    const long long total = (long long)p.C * p.B * p.H * p.W * p.q;
+    const unsigned g2 = (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    hipLaunchKernelGGL((convsbs_gather_dx_k<S, A>), dim3(g2), dim3(256), 0, st, (const A*)ws, (S*)dX, p);
+    DCTN_CHECK_LAUNCH();
+  }
+  dctn_set_last_kernel(dtype == DCTN_F64 ? "convsbs_bwd_wide_f64" : dtype == DCTN_BF16 ? "convsbs_bwd_wide_bf16"
+                                                                                    : "convsbs_bwd_wide_f32");
+  return DCTN_OK;
+}
+
 }  // namespace
 
 static int sbs_largest_bond(int n, const int* bond_sizes) {
@@ -513,8 +545,14 @@ size_t dctn_convsbs_workspace_bytes(int n_cores, const int* out_sizes, const int
   if (!backward) return 256;
   const size_t a = bwd_ws(p, dtype), b = convsbs_reg_bwd_workspace(n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype);
   const size_t c = convsbs_band_bwd_workspace(n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype);
-  const size_t m = a > b ? a : b;
-  return (m > c ? m : c) + 256;
+  size_t m = a > b ? a : b;
+  m = m > c ? m : c;
+  // the wide family: where the generic sweep's LDS plan declines the string, or where the flag forces it
+  if ((dtype_flags & DCTN_SBS_WIDE_SWEEP) || !generic_bwd_fits(p, dtype == DCTN_F64 ? 8 : 4)) {
+    const size_t w = convsbs_wide_bwd_workspace(n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype);
+    m = m > w ? m : w;
+  }
+  return m + 256;
 }
 
 size_t dctn_convsbs_saved_states_bytes(int n_cores, const int* out_sizes, const int* bond_sizes, int C, int B, int H,
@@ -531,7 +569,7 @@ int dctn_convsbs_fwd(const void* x, const int64_t x_strides[5], const void* cons
   if (!x || !x_strides || !cores || !out || !out_sizes || !bond_sizes || !pos_h || !pos_w)
     return DCTN_ERR_NULL;
   const int dtype = dtype_flags & DCTN_DTYPE_MASK;
-  if (dtype_flags & ~(DCTN_DTYPE_MASK | DCTN_SBS_MATRIX_CORE_SWEEP)) return DCTN_ERR_UNSUPPORTED;
+  if (dtype_flags & ~(DCTN_DTYPE_MASK | DCTN_SBS_MATRIX_CORE_SWEEP | DCTN_SBS_WIDE_SWEEP)) return DCTN_ERR_UNSUPPORTED;
   SbsP p;
   int rc = fill(p, x_strides, n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q);
   if (rc != DCTN_OK) return rc;
@@ -589,7 +627,7 @@ int dctn_convsbs_bwd_saved(const void* x, const int64_t x_strides[5], const void
   if (!x || !x_strides || !cores || !dY || !out_sizes || !bond_sizes || !pos_h || !pos_w)
     return DCTN_ERR_NULL;
   const int dtype = dtype_flags & DCTN_DTYPE_MASK;
-  if (dtype_flags & ~(DCTN_DTYPE_MASK | DCTN_SBS_MATRIX_CORE_SWEEP)) return DCTN_ERR_UNSUPPORTED;
+  if (dtype_flags & ~(DCTN_DTYPE_MASK | DCTN_SBS_MATRIX_CORE_SWEEP | DCTN_SBS_WIDE_SWEEP)) return DCTN_ERR_UNSUPPORTED;
   if (saved_states) {   // only what the forward of this very shape can have written
     const size_t sb = convsbs_saved_states_bytes(n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype);
     if (sb == 0 || saved_states_bytes < sb) saved_states = nullptr;
@@ -604,6 +642,15 @@ int dctn_convsbs_bwd_saved(const void* x, const int64_t x_strides[5], const void
     p.dcore[c] = nullptr;
   }
   hipStream_t st = (hipStream_t)stream;
+  if (dtype_flags & DCTN_SBS_WIDE_SWEEP) {   // forced: the wide family for every string it covers
+    switch (dtype) {
+      case DCTN_F32: rc = wide_launch<float, float>(x, dY, dX, dCores, workspace, workspace_bytes, p, dtype, st); break;
+      case DCTN_F64: rc = wide_launch<double, double>(x, dY, dX, dCores, workspace, workspace_bytes, p, dtype, st); break;
+      case DCTN_BF16: rc = wide_launch<bf16_t, float>(x, dY, dX, dCores, workspace, workspace_bytes, p, dtype, st); break;
+      default: return DCTN_ERR_BAD_DTYPE;
+    }
+    if (rc != DCTN_ERR_UNSUPPORTED) return rc;
+  }
   if (dtype == DCTN_F32 && !(dtype_flags & DCTN_SBS_MATRIX_CORE_SWEEP)) {
     for (int c = 0; dCores && c < n_cores; ++c)
       if (!dCores[c]) return DCTN_ERR_NULL;
@@ -619,13 +666,20 @@ int dctn_convsbs_bwd_saved(const void* x, const int64_t x_strides[5], const void
                           W, q, dtype, st, workspace, workspace_bytes);
     if (rc != DCTN_ERR_UNSUPPORTED) return rc;
   }
+  // the generic sweep declines only in its LDS plan, before it writes anything: the wide family takes those strings
   switch (dtype) {
     case DCTN_F32:
-      return bwd_launch<float, float>(x, dY, dX, dCores, workspace, workspace_bytes, p, dtype, st, saved_states);
+      rc = bwd_launch<float, float>(x, dY, dX, dCores, workspace, workspace_bytes, p, dtype, st, saved_states);
+      if (rc != DCTN_ERR_UNSUPPORTED) return rc;
+      return wide_launch<float, float>(x, dY, dX, dCores, workspace, workspace_bytes, p, dtype, st);
     case DCTN_F64:
-      return bwd_launch<double, double>(x, dY, dX, dCores, workspace, workspace_bytes, p, dtype, st);
+      rc = bwd_launch<double, double>(x, dY, dX, dCores, workspace, workspace_bytes, p, dtype, st);
+      if (rc != DCTN_ERR_UNSUPPORTED) return rc;
+      return wide_launch<double, double>(x, dY, dX, dCores, workspace, workspace_bytes, p, dtype, st);
     case DCTN_BF16:
-      return bwd_launch<bf16_t, float>(x, dY, dX, dCores, workspace, workspace_bytes, p, dtype, st);
+      rc = bwd_launch<bf16_t, float>(x, dY, dX, dCores, workspace, workspace_bytes, p, dtype, st);
+      if (rc != DCTN_ERR_UNSUPPORTED) return rc;
+      return wide_launch<bf16_t, float>(x, dY, dX, dCores, workspace, workspace_bytes, p, dtype, st);
   }
   return DCTN_ERR_BAD_DTYPE;
 }

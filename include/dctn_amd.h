@@ -33,6 +33,10 @@ enum { DCTN_F32 = 0, DCTN_F64 = 1, DCTN_BF16 = 2, DCTN_DTYPE_MASK = 0xFF };
  * DCTN_ERR_UNSUPPORTED): strings with every bond <= 4 run on the matrix-core sweep instead of the register-resident
  * sweep that is their default (cross-check of the two kernel families; same results to f32 rounding) */
 enum { DCTN_SBS_MATRIX_CORE_SWEEP = 1 << 8 };
+/* OR-ed in the same way: the backward runs on the wide family (convsbs_wide.hip: dCore GEMMs over HBM partial records,
+ * the family every string whose core gradients do not fit one workgroup's LDS falls to) for any string it covers; the
+ * forward ignores the bit (cross-check of the wide family against the generic sweep on strings both take) */
+enum { DCTN_SBS_WIDE_SWEEP = 1 << 9 };
 
 enum {
   DCTN_OK = 0,
