@@ -19,6 +19,7 @@ CSRC = os.path.join(_HERE, "csrc")
 F32, F64, BF16 = 0, 1, 2
 PREC_EXACT, PREC_BF16, PREC_MASK = 0, 1, 0xFF
 OPT_F32_PREFER_HALVES, OPT_SMALL_CHUNKS, OPT_MAIN_KERNEL_ONLY, OPT_GENERIC_KERNELS = 1 << 8, 1 << 9, 1 << 10, 1 << 11
+OPT_HEAD_FEATURES_BLOCKED4 = 1 << 12   # dctn_eps_head_fwd / _bwd only: sample-blocked feature layout
 ERR_BAD_SHAPE, ERR_BAD_DTYPE, ERR_UNSUPPORTED, ERR_WORKSPACE, ERR_LAUNCH, ERR_NULL = -1, -2, -3, -4, -5, -6
 SAVED, PARTIAL = 1, 2   # positive success codes (include/dctn_amd.h)
 SBS_MATRIX_CORE_SWEEP = 1 << 8   # OR-ed into the dtype argument of the dctn_convsbs_* calls

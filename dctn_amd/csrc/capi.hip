@@ -273,10 +273,12 @@ int dctn_eps_head_fwd(const void* x, const int64_t x_strides[5], const void* cor
   if (Cout < 1) return DCTN_ERR_BAD_SHAPE;
   EpsP p;
   const int precision = policy & DCTN_PREC_MASK;
-  const int rc = eps_fill_params(p, x_strides, C, B, H, W, Q, K, O, policy);
+  const int blk = policy & DCTN_OPT_HEAD_FEATURES_BLOCKED4;
+  const int rc = eps_fill_params(p, x_strides, C, B, H, W, Q, K, O, policy & ~blk);
   if (rc != DCTN_OK) return rc;
+  p.opts |= blk;
   const int rcm = eps_head_fwd_mfma(x, core, head_weight, head_bias, features, logits, p, Cout, dtype, precision, (hipStream_t)stream);
-  if (rcm != DCTN_ERR_UNSUPPORTED) return rcm;
+  if (rcm != DCTN_ERR_UNSUPPORTED || blk) return rcm;   // the float32 family writes row-major features only
   return eps_head_fwd_q2f32(x, core, head_weight, head_bias, features, logits, p, Cout, dtype, precision, (hipStream_t)stream);
 }
 
@@ -285,7 +287,7 @@ size_t dctn_eps_head_bwd_workspace_bytes(int C, int B, int H, int W, int Q, int 
   EpsP p;
   const int precision = policy & DCTN_PREC_MASK;
   const int64_t dummy[5] = {0, 0, 0, 0, 1};
-  if (eps_fill_params(p, dummy, C, B, H, W, Q, K, O, policy) != DCTN_OK) return 0;
+  if (eps_fill_params(p, dummy, C, B, H, W, Q, K, O, policy & ~DCTN_OPT_HEAD_FEATURES_BLOCKED4) != DCTN_OK) return 0;
   const size_t a = eps_head_bwd_mfma_workspace(p, Cout, dtype, precision), b = eps_head_bwd_q2f32_workspace(p, Cout, dtype, precision);
   return (a > b ? a : b) + 256;
 }
@@ -299,11 +301,13 @@ int dctn_eps_head_bwd(const void* x, const int64_t x_strides[5], const void* fea
   if (Cout < 1) return DCTN_ERR_BAD_SHAPE;
   EpsP p;
   const int precision = policy & DCTN_PREC_MASK;
-  const int rc = eps_fill_params(p, x_strides, C, B, H, W, Q, K, O, policy);
+  const int blk = policy & DCTN_OPT_HEAD_FEATURES_BLOCKED4;
+  const int rc = eps_fill_params(p, x_strides, C, B, H, W, Q, K, O, policy & ~blk);
   if (rc != DCTN_OK) return rc;
+  p.opts |= blk;
   const int rcm = eps_head_bwd_mfma(x, features, dLogits, head_weight, dCore, dWeight, dBias, workspace, workspace_bytes, p,
                                     Cout, dtype, precision, (hipStream_t)stream);
-  if (rcm != DCTN_ERR_UNSUPPORTED) return rcm;
+  if (rcm != DCTN_ERR_UNSUPPORTED || blk) return rcm;   // the float32 family reads row-major features only
   return eps_head_bwd_q2f32(x, features, dLogits, head_weight, dCore, dWeight, dBias, workspace, workspace_bytes, p, Cout,
                             dtype, precision, (hipStream_t)stream);
 }

@@ -835,12 +835,16 @@ __global__ __launch_bounds__(64 * HEAD_FWD_MAXPG) void eps_fwd_head_q2reg_k(cons
 // samples, k-steps of 32 features dealt over the waves; the weight fragments - 16-byte loads straight from memory in
 // operand order - are requested BEFORE the barrier that closes the group, they depend on nothing), the waves' partial
 // tiles meet in LDS and are summed in wave order.  Same arithmetic as above: bf16 products, float32 sums.
+// BLK4 (DCTN_OPT_HEAD_FEATURES_BLOCKED4): the steps leave their features in the tile only; once the group is complete
+// the workgroup writes it as ONE contiguous [F][4] block of `out` ("blocked4": out[((g0 / 4) * F + f) * 4 + i] =
+// feature f of sample g0 + i, the samples past the batch as zeros; the launcher aligns the groups to 4 samples), the
+// layout whose k-contiguous fragments the backward's dW product loads directly (head_dw_gemm_role).
 constexpr int HEADT_WAVES = 16;
 constexpr int HEADT_GS = 4;          // samples per group = columns of the head product in use
 constexpr int HEADT_MAXKS = 6;       // 32-feature steps per wave of the head product: at most 16 * 6 * 32 = 3072 features
 constexpr int headt_pitch(int F) { return (F + 31) / 32 * 32 + 8; }   // shorts per sample row of the tile (+16 bytes: the samples' banks differ)
 
-template <int N0, int N1, int OP, int ROWS>
+template <int N0, int N1, int OP, int ROWS, bool BLK4>
 __global__ __launch_bounds__(64 * HEADT_WAVES) void eps_fwd_head_q2reg_t_k(const bf16_t* __restrict__ x,
                                                                            const bf16_t* __restrict__ core,
                                                                            const bf16_t* __restrict__ hw,
@@ -989,16 +993,16 @@ __global__ __launch_bounds__(64 * HEADT_WAVES) void eps_fwd_head_q2reg_t_k(const
         pk[i] = pack_bf16(a0 + a1, c0 + c1);
       }
       if constexpr (OP == 2) {
-        __builtin_amdgcn_raw_buffer_store_b32(pk[0], rs_o, vo, so, 0);
+        if constexpr (!BLK4) __builtin_amdgcn_raw_buffer_store_b32(pk[0], rs_o, vo, so, 0);
         if (tvalid) *reinterpret_cast<unsigned*>(trow) = pk[0];
       } else if constexpr (OP == 4) {
-        __builtin_amdgcn_raw_buffer_store_b64(u32x2{pk[0], pk[1]}, rs_o, vo, so, 0);
+        if constexpr (!BLK4) __builtin_amdgcn_raw_buffer_store_b64(u32x2{pk[0], pk[1]}, rs_o, vo, so, 0);
         if (tvalid) *reinterpret_cast<u32x2*>(trow) = u32x2{pk[0], pk[1]};
       } else {
 #pragma unroll
         for (int i = 0; i < OP / 8; ++i) {
           const u32x4 q = u32x4{pk[4 * i], pk[4 * i + 1], pk[4 * i + 2], pk[4 * i + 3]};
-          __builtin_amdgcn_raw_buffer_store_b128(q, rs_o, vo, so + 16u * i, 0);
+          if constexpr (!BLK4) __builtin_amdgcn_raw_buffer_store_b128(q, rs_o, vo, so + 16u * i, 0);
           if (tvalid) *reinterpret_cast<u32x4*>(trow + 8 * i) = q;
         }
       }
@@ -1029,6 +1033,18 @@ __global__ __launch_bounds__(64 * HEADT_WAVES) void eps_fwd_head_q2reg_t_k(const
     if (c < HEADT_GS) {
 #pragma unroll
       for (int v = 0; v < 4; ++v) hsum[wv][c][4 * kg + v] = hd[v];
+    }
+    if constexpr (BLK4) {   // the group's [F][4] block: thread t stores features 2 t, 2 t + 1 of the 4 samples, 16 bytes
+      static_assert(HEADT_GS == 4, "a group is one block of the blocked4 layout");
+      const unsigned sob = (unsigned)(g0 >> 2) * (unsigned)F * 8u;   // g0 is a multiple of 4 (fwd_head_launch_t)
+      for (int f = 2 * tid; f < F; f += 2 * 64 * HEADT_WAVES) {
+        unsigned r[HEADT_GS];   // r[i] = features f, f + 1 of sample i (a sample past the batch: zeros)
+#pragma unroll
+        for (int i = 0; i < HEADT_GS; ++i) r[i] = i < ng ? *reinterpret_cast<const unsigned*>(ftile + i * LP + f) : 0u;
+        const u32x4 q = u32x4{__builtin_amdgcn_perm(r[1], r[0], 0x05040100u), __builtin_amdgcn_perm(r[3], r[2], 0x05040100u),
+                              __builtin_amdgcn_perm(r[1], r[0], 0x07060302u), __builtin_amdgcn_perm(r[3], r[2], 0x07060302u)};
+        __builtin_amdgcn_raw_buffer_store_b128(q, rs_o, (unsigned)f * 8u, sob, 0);
+      }
     }
     __syncthreads();
     if (tid < HEADT_GS * 16) {
@@ -1573,17 +1589,26 @@ __global__ __launch_bounds__(256) void eps_bwd_dcore_reduce_k(const float* __res
 //    to arrive (write-through stores, an agent-scope counter zeroed by the dCore kernel, agent-scope loads; parity
 //    green): products done after 2.5 us instead of 5.5, but the store-and-count costs 1.3 us and the last arriver's
 //    re-read 1.2 (release / acquire on the counter: 2.5 + 2.5) - the role ends at 6.0 us, no gain for the machinery.
+// BLK4: the features in the blocked4 layout (eps_fwd_head_q2reg_t_k under DCTN_OPT_HEAD_FEATURES_BLOCKED4): the 8
+// samples of lane kg are the 4-sample blocks 2 kg, 2 kg + 1 of the 32-sample block, and a block's FL features of the
+// lane are FL * 8 contiguous bytes in exactly the fragment's k order - TWO loads (FL * 8 bytes each) instead of eight,
+// no byte permutes, and a slice of the features is one contiguous (DWG_BFW * 8)-byte piece per 4 samples instead of
+// four row pieces.  Same products, same sample split over the waves, same LDS join: the same bits as the row-major role.
 constexpr int DWG_WAVES = 16;
 constexpr int DWG_FW = 32;   // features of one workgroup's slice (4 bytes of a row per lane: 64-byte pieces of 4 rows per load)
+constexpr int DWG_BFW = 16;  // ... with blocked4 features (8 bytes of a block per lane: 128-byte pieces, 169 workgroups at cfg2)
+template <int FW, bool BLK4>
 __device__ __forceinline__ void head_dw_gemm_role(const bf16_t* __restrict__ feat, const bf16_t* __restrict__ dL,
                                                   bf16_t* __restrict__ dW, int B, int Cout, long long F, int blk,
                                                   float* __restrict__ lds) {
   typedef __attribute__((ext_vector_type(4))) float f32x4v;
-  constexpr int FL = DWG_FW / 16;   // features per lane = tiles per wave
+  constexpr int FL = FW / 16;   // features per lane = tiles per wave
+  static_assert(!BLK4 || FL == 1 || FL == 2, "blocked4 pieces of 8 or 16 bytes");
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = lane & 15, kg = lane >> 4;
-  const unsigned f_bytes = (unsigned)((long long)B * F * 2), dl_bytes = (unsigned)B * (unsigned)Cout * 2u;
+  const long long fb = BLK4 ? (long long)(B + 3) / 4 * 4 * F * 2 : (long long)B * F * 2;
+  const unsigned f_bytes = (unsigned)fb, dl_bytes = (unsigned)B * (unsigned)Cout * 2u;
   const __amdgpu_buffer_rsrc_t rs_f = make_rsrc(feat, f_bytes), rs_dl = make_rsrc(dL, dl_bytes);
-  const long long fcol = (long long)blk * DWG_FW + FL * n;
+  const long long fcol = (long long)blk * FW + FL * n;
   const bool fok = fcol + FL - 1 < F;   // (F is a multiple of 4: OP == 4)
   const int spw = (((B + DWG_WAVES - 1) / DWG_WAVES) + 31) / 32 * 32;
   const int b0 = wv * spw, b1 = b0 + spw < B ? b0 + spw : B;
@@ -1591,22 +1616,42 @@ __device__ __forceinline__ void head_dw_gemm_role(const bf16_t* __restrict__ fea
 #pragma unroll
   for (int j = 0; j < FL; ++j) acc[j] = f32x4v{0.f, 0.f, 0.f, 0.f};
   constexpr int FD = FL >= 2 ? FL / 2 : 1;   // dwords of a row piece per lane
-  unsigned fr[8][FD], frn[8][FD];
+  // row-major: fr[j] = the lane's piece of sample 8 kg + j; blocked4: fr[h][.] = its 2 FL dwords of block 2 kg + h
+  constexpr int NF = BLK4 ? 2 : 8, ND = BLK4 ? 2 * FL : FD;
+  unsigned fr[NF][ND], frn[NF][ND];
   unsigned a16[8], a16n[8];
-  auto issue = [&](int kb, unsigned (&f)[8][FD], unsigned (&a)[8]) {
+  auto issue = [&](int kb, unsigned (&f)[NF][ND], unsigned (&a)[8]) {
+    if constexpr (BLK4) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {   // block (kb + 8 kg) / 4 + h: loaded if it holds a sample of the wave (past B: zeros)
+        const int b = kb + 8 * kg + 4 * h;
+        const unsigned vo = (b < b1 && fok) ? (unsigned)(((long long)(b >> 2) * F + fcol) * 8) : f_bytes;
+        if constexpr (FL == 1) {
+          const u32x2 q = __builtin_amdgcn_raw_buffer_load_b64(rs_f, vo, 0, 0);
+          f[h][0] = q.x;
+          f[h][ND - 1] = q.y;
+        } else {
+          const u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(rs_f, vo, 0, 0);
+#pragma unroll
+          for (int d = 0; d < 4; ++d) f[h][d] = q[d];
+        }
+      }
+    }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int b = kb + 8 * kg + j;
       const bool in = b < b1;
-      const unsigned vo = (in && fok) ? (unsigned)((long long)b * F * 2 + fcol * 2) : f_bytes;
-      if constexpr (FL == 1) {
-        f[j][0] = (unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rs_f, vo, 0, 0);
-      } else if constexpr (FL == 2) {
-        f[j][0] = __builtin_amdgcn_raw_buffer_load_b32(rs_f, vo, 0, 0);
-      } else {
-        const u32x2 q = __builtin_amdgcn_raw_buffer_load_b64(rs_f, vo, 0, 0);
-        f[j][0] = q.x;
-        f[j][FD - 1] = q.y;
+      if constexpr (!BLK4) {
+        const unsigned vo = (in && fok) ? (unsigned)((long long)b * F * 2 + fcol * 2) : f_bytes;
+        if constexpr (FL == 1) {
+          f[j][0] = (unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rs_f, vo, 0, 0);
+        } else if constexpr (FL == 2) {
+          f[j][0] = __builtin_amdgcn_raw_buffer_load_b32(rs_f, vo, 0, 0);
+        } else {
+          const u32x2 q = __builtin_amdgcn_raw_buffer_load_b64(rs_f, vo, 0, 0);
+          f[j][0] = q.x;
+          f[j][FD - 1] = q.y;
+        }
       }
       a[j] = (unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(
           rs_dl, (in && n < Cout) ? (unsigned)b * (unsigned)Cout * 2u + 2u * n : dl_bytes, 0, 0);
@@ -1622,20 +1667,25 @@ __device__ __forceinline__ void head_dw_gemm_role(const bf16_t* __restrict__ fea
     for (int d = 0; d < 4; ++d) at[d] = (int)(a16[2 * d] | (a16[2 * d + 1] << 16));
 #pragma unroll
     for (int j = 0; j < FL; ++j) {
-      const unsigned sel = (j & 1) ? 0x07060302u : 0x05040100u;   // the odd / even halves of two dwords
       int4v bf;
+      if constexpr (BLK4) {   // feature fcol + j of samples 0-3 and 4-7: dwords 2 j, 2 j + 1 of the two blocks
 #pragma unroll
-      for (int d = 0; d < 4; ++d)
-        bf[d] = FL == 1 ? (int)(fr[2 * d][0] | (fr[2 * d + 1][0] << 16))
-                        : (int)__builtin_amdgcn_perm(fr[2 * d + 1][j >> 1], fr[2 * d][j >> 1], sel);
+        for (int d = 0; d < 4; ++d) bf[d] = (int)fr[d >> 1][2 * j + (d & 1)];
+      } else {
+        const unsigned sel = (j & 1) ? 0x07060302u : 0x05040100u;   // the odd / even halves of two dwords
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+          bf[d] = FL == 1 ? (int)(fr[2 * d][0] | (fr[2 * d + 1][0] << 16))
+                          : (int)__builtin_amdgcn_perm(fr[2 * d + 1][j >> 1], fr[2 * d][j >> 1], sel);
+      }
       acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, at), __builtin_bit_cast(bf16x8, bf), acc[j], 0, 0, 0);
     }
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
+    for (int j = 0; j < NF; ++j)
 #pragma unroll
-      for (int e = 0; e < FD; ++e) fr[j][e] = frn[j][e];
-      a16[j] = a16n[j];
-    }
+      for (int e = 0; e < ND; ++e) fr[j][e] = frn[j][e];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a16[j] = a16n[j];
   }
   // acc[j][i] = dW[class 4 kg + i][feature DWG_FW blk + FL n + j] of this wave's samples
 #pragma unroll
@@ -1651,7 +1701,7 @@ __device__ __forceinline__ void head_dw_gemm_role(const bf16_t* __restrict__ fea
 #pragma unroll
     for (int w = 0; w < DWG_WAVES; ++w) t += lds[(w * (4 * FL) + slot) * 64 + lane];
     const int c = 4 * kg + i;
-    const long long f = (long long)blk * DWG_FW + FL * n + j;
+    const long long f = (long long)blk * FW + FL * n + j;
     if (c < Cout && f < F) dW[(long long)c * F + f] = (bf16_t)t;
   }
   DCTN_STAMP_G(4);
@@ -1669,11 +1719,15 @@ __global__ __launch_bounds__(1024) void eps_head_reduce_k(const float* __restric
   // partial tile of an element is fetched in ONE round of independent loads.
   __shared__ float red[32][33];
   const int tid = threadIdx.x;
-  if ((int)blockIdx.x < n_core) {
+  // gemm == 2 (blocked4 features): the n_dw product workgroups take the lowest block ids, they are dispatched first
+  const int bid = gemm == 2 && (int)blockIdx.x < n_core + n_dw
+                      ? ((int)blockIdx.x < n_dw ? n_core + (int)blockIdx.x : (int)blockIdx.x - n_dw)
+                      : (int)blockIdx.x;
+  if (bid < n_core) {
     DCTN_STAMP_G(0);
     const int c = tid & 31, k32 = tid >> 5;
     const long long stride = (long long)BN * OP * ACOLS;
-    const long long e = (long long)blockIdx.x * 32 + c;  // flat (m, a) index
+    const long long e = (long long)bid * 32 + c;  // flat (m, a) index
     float acc = 0.f;
     for (int k0 = 0; k0 < nblk; k0 += 256) {   // nblk <= 256: one trip
       float v[8];
@@ -1698,15 +1752,16 @@ __global__ __launch_bounds__(1024) void eps_head_reduce_k(const float* __restric
     DCTN_STAMP_G(4);
     return;
   }
-  if ((int)blockIdx.x < n_core + n_dw) {
+  if (bid < n_core + n_dw) {
     if (!dW) return;
-    if (gemm) {   // no partial tiles: the product itself (n_dw = ceil(F / 64) workgroups, nW = Cout * F)
+    if (gemm) {   // no partial tiles: the product itself (n_dw = ceil(F / slice) workgroups, nW = Cout * F)
       extern __shared__ __attribute__((aligned(16))) float gemm_lds[];
-      head_dw_gemm_role(feat, dL, dW, B, Cout, nW / Cout, (int)blockIdx.x - n_core, gemm_lds);
+      if (gemm == 2) head_dw_gemm_role<DWG_BFW, true>(feat, dL, dW, B, Cout, nW / Cout, bid - n_core, gemm_lds);
+      else head_dw_gemm_role<DWG_FW, false>(feat, dL, dW, B, Cout, nW / Cout, bid - n_core, gemm_lds);
       return;
     }
     // 4 threads per element, each up to 8 independent loads (ncb <= 32), joined by two lane shuffles
-    const long long e = (long long)((int)blockIdx.x - n_core) * 256 + (tid >> 2);
+    const long long e = (long long)(bid - n_core) * 256 + (tid >> 2);
     const int sub = tid & 3;
     float v[8];
 #pragma unroll
@@ -1938,6 +1993,20 @@ size_t head_dw_partial_bytes(const EpsP& p, int Cout) {
   return (size_t)(dctn_dev().cus / npg) * ((size_t)Cout * (size_t)(P * p.O) + 16) * sizeof(float);
 }
 
+// DCTN_OPT_HEAD_FEATURES_BLOCKED4 is honoured exactly where the fused backward takes its HEADMM path (`headmm` in
+// bwd_head_launch_t: the dCore kernel reads no features, eps_head_reduce_k's gemm role reads them all), the forward
+// runs eps_fwd_head_q2reg_t_k (the only writer of the layout; not under DCTN_OPT_SMALL_CHUNKS) and the padded buffer
+// stays inside a 32-bit buffer descriptor.  Both directions decline the same requests.
+// bytes of the blocked4 feature buffer: ceil(B / 4) blocks of [F][4] bf16
+long long blocked4_bytes(const MfmaP& m) { return (long long)(m.B + 3) / 4 * 4 * m.P * m.O * 2; }
+template <int N0, int N1, int OP>
+bool head_blocked4_ok(const MfmaP& m) {
+  constexpr int A = 1 << N0, MT = (1 << N1) * OP / 32;
+  const long long F = (long long)m.P * OP;
+  return A == 32 && MT <= 2 && OP == 4 && m.vec_ok && blocked4_bytes(m) < (1LL << 31) && !(m.opts & DCTN_OPT_SMALL_CHUNKS) &&
+         F % 8 == 0 && F <= (long long)HEADT_WAVES * HEADT_MAXKS * 32;
+}
+
 // fused classifier-head backward (bf16 only): dLogits (B, Cout), head weight (Cout, P*O), feat (B, P*O)
 template <int N0, int N1, int OP>
 int bwd_head_launch_t(const void* x, const void* dL, const void* hw, const void* feat, void* dCore, void* dW,
@@ -1946,8 +2015,10 @@ int bwd_head_launch_t(const void* x, const void* dL, const void* hw, const void*
   constexpr int A = 1 << N0, BN = 1 << N1, AT = A >= 32 ? A / 32 : 1;
   constexpr size_t DYN = dcore_dyn_lds<N0, N1, OP>();
   MfmaP m = m_in;
+  const bool blk = (m.opts & DCTN_OPT_HEAD_FEATURES_BLOCKED4) != 0;
   if (m.O != OP || m.Cout < 2 || m.Cout > 16 || m.Cout % 2 != 0) return DCTN_ERR_UNSUPPORTED;
-  if (((uintptr_t)dL % 4) != 0 || ((uintptr_t)hw % 4) != 0 || ((uintptr_t)feat % 4) != 0) return DCTN_ERR_UNSUPPORTED;
+  if (((uintptr_t)dL % 4) != 0 || ((uintptr_t)hw % 4) != 0 || ((uintptr_t)feat % (blk ? 16 : 4)) != 0) return DCTN_ERR_UNSUPPORTED;
+  if (blk && !head_blocked4_ok<N0, N1, OP>(m)) return DCTN_ERR_UNSUPPORTED;   // (before any launch)
   const int grid = plan_grouped(m);
   if (grid == 0) return DCTN_ERR_UNSUPPORTED;
   float* dwpart = reinterpret_cast<float*>(static_cast<unsigned char*>(ws) + core_ws_bytes);
@@ -1978,13 +2049,14 @@ int bwd_head_launch_t(const void* x, const void* dL, const void* hw, const void*
 #undef DCTN_HEAD_LAUNCH
   DCTN_CHECK_LAUNCH();
   if (m.opts & DCTN_OPT_MAIN_KERNEL_ONLY) return DCTN_PARTIAL;   // measurement option: partial sums only, gradients NOT written
-  const int n_core = BN * OP * AT, n_dw = gemm ? (int)(((long long)m.P * OP + DWG_FW - 1) / DWG_FW) : (int)((nW + 255) / 256);
-  constexpr size_t GEMM_LDS = (size_t)DWG_WAVES * (DWG_FW / 4) * 64 * sizeof(float);
+  const int fw = blk ? DWG_BFW : DWG_FW;   // features of a gemm workgroup's slice
+  const int n_core = BN * OP * AT, n_dw = gemm ? (int)(((long long)m.P * OP + fw - 1) / fw) : (int)((nW + 255) / 256);
+  const size_t gemm_lds = (size_t)DWG_WAVES * (fw / 4) * 64 * sizeof(float);
   static_assert(DWG_WAVES * 64 == 1024, "the gemm role is the whole workgroup of eps_head_reduce_k");
-  if (gemm && !dctn_lds_optin((const void*)eps_head_reduce_k, GEMM_LDS)) return DCTN_ERR_LAUNCH;   // (after the main kernel)
-  hipLaunchKernelGGL(eps_head_reduce_k, dim3(n_core + n_dw + 1), dim3(1024), gemm ? GEMM_LDS : 0, st, (const float*)ws, (S*)dCore,
+  if (gemm && !dctn_lds_optin((const void*)eps_head_reduce_k, gemm_lds)) return DCTN_ERR_LAUNCH;   // (after the main kernel)
+  hipLaunchKernelGGL(eps_head_reduce_k, dim3(n_core + n_dw + 1), dim3(1024), gemm ? gemm_lds : 0, st, (const float*)ws, (S*)dCore,
                      grid, A, BN, m.O, OP, AT * 32, n_core, (const float*)dwpart, (S*)dW, m.ncb, nW, n_dw,
-                     (const S*)dL, (S*)dBias, m.B, m.Cout, (const S*)feat, gemm ? 1 : 0);
+                     (const S*)dL, (S*)dBias, m.B, m.Cout, (const S*)feat, gemm ? (blk ? 2 : 1) : 0);
   DCTN_CHECK_LAUNCH();
   dctn_set_last_kernel("eps_head_bwd_mfma_q2reg");
   return DCTN_OK;
@@ -1996,21 +2068,31 @@ int fwd_head_launch_t(const void* x, const void* core, const void* hw, const voi
                       const MfmaP& m_in, hipStream_t st) {
   typedef bf16_t S;
   MfmaP m = m_in;
+  const bool blk = (m.opts & DCTN_OPT_HEAD_FEATURES_BLOCKED4) != 0;
   if (m.O != OP || !(m.rowvec_ok && m.vec_ok) || m.npg > HEAD_FWD_MAXPG) return DCTN_ERR_UNSUPPORTED;
-  // 16-byte weight fragments, (OP * 2)-byte feature rows
-  if (((uintptr_t)hw % 16) != 0 || m.hw_rowb % 16 != 0 || ((uintptr_t)out % (OP * 2)) != 0) return DCTN_ERR_UNSUPPORTED;
+  // 16-byte weight fragments, (OP * 2)-byte feature rows (blocked4: 16-byte stores)
+  if (((uintptr_t)hw % 16) != 0 || m.hw_rowb % 16 != 0 || ((uintptr_t)out % (blk ? 16 : OP * 2)) != 0) return DCTN_ERR_UNSUPPORTED;
   int nwg = m.B < dctn_dev().cus ? m.B : dctn_dev().cus;
   m.spc = (m.B + nwg - 1) / nwg;
+  if (blk) m.spc = (m.spc + HEADT_GS - 1) / HEADT_GS * HEADT_GS;   // groups = absolute 4-sample blocks
   nwg = (m.B + m.spc - 1) / m.spc;
   constexpr int RW = (N0 + N1) == 9 ? 3 : 4;
   const long long F = (long long)m.P * OP;
-  if (!(m.opts & DCTN_OPT_SMALL_CHUNKS) && F % 8 == 0 && F <= (long long)HEADT_WAVES * HEADT_MAXKS * 32) {
+  const bool tk = !(m.opts & DCTN_OPT_SMALL_CHUNKS) && F % 8 == 0 && F <= (long long)HEADT_WAVES * HEADT_MAXKS * 32;
+  if (blk) {   // only the kernel below writes blocked4, only for the shapes whose backward reads it (head_blocked4_ok)
+    if (!tk || !head_blocked4_ok<N0, N1, OP>(m)) return DCTN_ERR_UNSUPPORTED;
+    m.o_bytes = blocked4_bytes(m);
+  }
+  if (tk) {
     // steps pulled from a counter by 16 waves, head as a tail phase (DCTN_OPT_SMALL_CHUNKS keeps the round-4 structure:
     // a wave per position group, for same-box comparisons)
     const size_t dyn = (size_t)HEADT_GS * headt_pitch((int)F) * sizeof(short);
-    if (!dctn_lds_optin((const void*)eps_fwd_head_q2reg_t_k<N0, N1, OP, RW>, dyn)) return DCTN_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((eps_fwd_head_q2reg_t_k<N0, N1, OP, RW>), dim3((unsigned)nwg), dim3(64 * HEADT_WAVES), dyn, st, (const S*)x,
-                       (const S*)core, (const S*)hw, (const S*)bias, (S*)out, (S*)logits, m);
+#define DCTN_HEADT_LAUNCH(BLK)                                                                                          \
+    if (!dctn_lds_optin((const void*)eps_fwd_head_q2reg_t_k<N0, N1, OP, RW, BLK>, dyn)) return DCTN_ERR_UNSUPPORTED;    \
+    hipLaunchKernelGGL((eps_fwd_head_q2reg_t_k<N0, N1, OP, RW, BLK>), dim3((unsigned)nwg), dim3(64 * HEADT_WAVES), dyn, st, \
+                       (const S*)x, (const S*)core, (const S*)hw, (const S*)bias, (S*)out, (S*)logits, m)
+    if (blk) { DCTN_HEADT_LAUNCH(true); } else { DCTN_HEADT_LAUNCH(false); }
+#undef DCTN_HEADT_LAUNCH
     DCTN_CHECK_LAUNCH();
     dctn_set_last_kernel("eps_head_fwd_mfma_q2reg");
     return DCTN_OK;

@@ -45,8 +45,11 @@ Initialization = Union[UnitEmpiricalOutputStd, UnitTheoreticalOutputStd, Manuall
 #   FUSED_HEAD  - last EPS layer + flatten + linear head as one autograd node (`_EpsLinearHeadFunction`)
 #   HEAD_BWD    - backward of the stand-alone linear head: "hip" (`dctn_linear_head_bwd`, the default) or "blas" (library GEMMs)
 #   FUSED_HEAD_FWD - inside that node: forward of layer + head as one kernel (`dctn_eps_head_fwd`) or as two
+#   BLOCKED_FEATURES - inside that node, bf16: the saved features in the sample-blocked layout "blocked4"
+#                  (DCTN_OPT_HEAD_FEATURES_BLOCKED4, include/dctn_amd.h) where the kernels take it, row-major elsewhere
 FUSED_HEAD = True
 FUSED_HEAD_FWD = True
+BLOCKED_FEATURES = True
 HEAD_BWD = "hip"
 
 
@@ -142,13 +145,24 @@ class _EpsLinearHeadFunction(torch.autograd.Function):
         O = core.shape[-1]
         core_c, w, b = core.contiguous(), weight.contiguous(), bias.contiguous()
         prec, code = L.precision(), L.dtype_code(x)
-        feat = torch.empty((B, (H - K + 1) * (W - K + 1) * O), dtype=x.dtype, device=dev)
-        assert w.shape[1] == feat.shape[1]
+        F_ = (H - K + 1) * (W - K + 1) * O
+        assert w.shape[1] == F_
         cout = w.shape[0]
         out = torch.empty((B, cout), dtype=x.dtype, device=dev)
         # one kernel for the layer and the head (`dctn_eps_head_fwd`); shapes / layouts it does not take run as two
         rc = L.ERR_UNSUPPORTED
-        if FUSED_HEAD_FWD:
+        blocked = False
+        if FUSED_HEAD_FWD and BLOCKED_FEATURES and x.dtype == torch.bfloat16:
+            # blocked4: [ceil(B / 4)][F][4], feature f of sample 4 j + i at [j][f][i] (the backward's dW product reads
+            # it in fragment order); declined shapes retry row-major
+            feat = torch.empty(((B + 3) // 4, F_, 4), dtype=x.dtype, device=dev)
+            rc = L.lib().dctn_eps_head_fwd(x.data_ptr(), L.strides5(x), core_c.data_ptr(), w.data_ptr(), b.data_ptr(),
+                                           feat.data_ptr(), out.data_ptr(), C, B, H, W, Q, K, O, cout, code,
+                                           prec | L.OPT_HEAD_FEATURES_BLOCKED4, L.stream_ptr(dev))
+            blocked = rc != L.ERR_UNSUPPORTED
+        if not blocked:
+            feat = torch.empty((B, F_), dtype=x.dtype, device=dev)
+        if FUSED_HEAD_FWD and not blocked:
             rc = L.lib().dctn_eps_head_fwd(x.data_ptr(), L.strides5(x), core_c.data_ptr(), w.data_ptr(), b.data_ptr(),
                                            feat.data_ptr(), out.data_ptr(), C, B, H, W, Q, K, O, cout, code, prec,
                                            L.stream_ptr(dev))
@@ -165,6 +179,7 @@ class _EpsLinearHeadFunction(torch.autograd.Function):
             L.check(rc, "eps + linear head forward")
         ctx.save_for_backward(core_c, x, feat, w)
         ctx.dims = (C, B, H, W, Q, K, O, prec)
+        ctx.blocked = blocked   # the layout `feat` holds; the backward passes the same bit
         return out
 
     @staticmethod
@@ -174,8 +189,13 @@ class _EpsLinearHeadFunction(torch.autograd.Function):
         need_core, _, need_w, need_b = ctx.needs_input_grad
         dev, code = x.device, L.dtype_code(x)
         g = d_out.contiguous()
+        blk = L.OPT_HEAD_FEATURES_BLOCKED4 if ctx.blocked else 0
+
+        def rows():   # the features as (B, F) row-major, for the paths that take no blocked4 (rare: speed does not matter)
+            return feat.permute(0, 2, 1).reshape(-1, feat.shape[1])[:B].contiguous() if ctx.blocked else feat
+
         if not need_core:
-            _, d_w, d_b = _head_backward(feat, w, g, False, need_w, need_b)
+            _, d_w, d_b = _head_backward(rows(), w, g, False, need_w, need_b)
             return None, None, d_w, d_b
         cout = w.shape[0]
         # the three gradients are carved out of ONE buffer, in parameter order (epses[-1], linear.weight,
@@ -191,9 +211,9 @@ class _EpsLinearHeadFunction(torch.autograd.Function):
         rc = L.lib().dctn_eps_head_bwd(
             x.data_ptr(), L.strides5(x), feat.data_ptr(), g.data_ptr(), w.data_ptr(), d_core.data_ptr(),
             None if d_w is None else d_w.data_ptr(), None if d_b is None else d_b.data_ptr(), ws.data_ptr(),
-            ws.numel(), C, B, H, W, Q, K, O, cout, code, prec, L.stream_ptr(dev))
+            ws.numel(), C, B, H, W, Q, K, O, cout, code, prec | blk, L.stream_ptr(dev))
         if rc == L.ERR_UNSUPPORTED:   # outside the fused family: the head's own backward + the plain EPS backward
-            d_feat, d_w, d_b = _head_backward(feat, w, g, True, need_w, need_b)
+            d_feat, d_w, d_b = _head_backward(rows(), w, g, True, need_w, need_b)
             rc = L.lib().dctn_eps_bwd(x.data_ptr(), L.strides5(x), core_c.data_ptr(), d_feat.data_ptr(), None,
                                       d_core.data_ptr(), ws.data_ptr(), ws.numel(), C, B, H, W, Q, K, O, code,
                                       prec, L.stream_ptr(dev))

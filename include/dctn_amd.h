@@ -77,7 +77,10 @@ enum {
    * one factor digit after the other, no matrix cores, no Khatri-Rao halves - the independent evaluation order
    * behind `eps_one_by_one` (dctn/eps.py:43-63), which the reference's tests use to cross-check `eps` */
   DCTN_OPT_GENERIC_KERNELS = 1 << 11,
-  DCTN_OPT_ALL = (1 << 8) | (1 << 9) | (1 << 10) | (1 << 11)   /* any other bit above DCTN_PREC_MASK: DCTN_ERR_UNSUPPORTED */
+  /* dctn_eps_head_fwd / dctn_eps_head_bwd only: `features` in the sample-blocked layout "blocked4" instead of
+   * row-major (see dctn_eps_head_fwd); every other entry point returns DCTN_ERR_UNSUPPORTED for it */
+  DCTN_OPT_HEAD_FEATURES_BLOCKED4 = 1 << 12,
+  DCTN_OPT_ALL = (1 << 8) | (1 << 9) | (1 << 10) | (1 << 11) | (1 << 12)   /* any other bit above DCTN_PREC_MASK: DCTN_ERR_UNSUPPORTED */
 };
 
 int dctn_version(void);
@@ -170,9 +173,16 @@ int dctn_eps_bwd_saved(const void* x, const int64_t x_strides[5], const void* co
 /* Forward of (EPS layer -> "b h w q -> b (h w q)" -> nn.Linear), the tail of EPSesPlusLinear.forward (reference:
  * dctn/eps_plus_linear.py:144-147), as ONE kernel: a workgroup holds all window positions of a few samples, so the
  * head's sum over (position, output) closes inside the workgroup - no second launch, no re-read of the features.
- *   features : (B, H'*W'*O) contiguous, OVERWRITTEN (the layer's output; the backward reads it)
+ *   features : OVERWRITTEN (the layer's output; the backward reads it), F = H'*W'*O features per sample, in one of
+ *              two layouts chosen by the policy:
+ *              row-major (default): (B, F) contiguous;
+ *              "blocked4" (DCTN_OPT_HEAD_FEATURES_BLOCKED4): features[((j * F) + f) * 4 + i] = feature f of sample
+ *              4 j + i, ceil(B / 4) * 4 * F values, the samples past B written as zeros.  Only the bf16 register family
+ *              takes it, for the shapes whose backward forms dW as one product over the samples (N = 9, O = 4, vector
+ *              input layout, ceil(B / 4) * 4 * F * 2 < 2^31 bytes); every other shape, the float32 family and
+ *              DCTN_OPT_SMALL_CHUNKS return DCTN_ERR_UNSUPPORTED before any launch
  *   logits   : (B, Cout) contiguous, OVERWRITTEN = features @ head_weight^T + head_bias, products of the stored
- *              (bf16-rounded) features with the bf16 weight, float32 sums
+ *              (bf16-rounded) features with the bf16 weight, float32 sums (the same bits in both layouts)
  * bfloat16, contiguous x, the register-resident family with O in {2, 4}, Cout <= 16 and at most 768 window positions
  * per sample; DCTN_ERR_UNSUPPORTED otherwise (the caller then runs dctn_eps_fwd + dctn_linear_head_fwd). */
 int dctn_eps_head_fwd(const void* x, const int64_t x_strides[5], const void* core, const void* head_weight,
@@ -185,7 +195,9 @@ int dctn_eps_head_fwd(const void* x, const int64_t x_strides[5], const void* cor
  * kernel forms dY[b,h,w,o] = sum_c dLogits[b,c] * head_weight[c, (h*W'+w)*O + o] on the fly, so the
  * gradient of the features is never written to or read from HBM, and accumulates the head's own
  * gradients beside dCore.
- *   features    : (B, H'*W'*O) contiguous, the layer's forward output (input of the linear head)
+ *   features    : the layer's forward output (input of the linear head), row-major (B, H'*W'*O) contiguous, or
+ *                 "blocked4" as dctn_eps_head_fwd wrote it under DCTN_OPT_HEAD_FEATURES_BLOCKED4 (the same bit in
+ *                 `policy`; honoured on the same shapes, DCTN_ERR_UNSUPPORTED before any launch elsewhere)
  *   dLogits     : (B, Cout) contiguous;  head_weight : (Cout, H'*W'*O) contiguous
  *   dCore       : same layout as core;  dWeight : like head_weight, or NULL;  dBias : (Cout), or NULL
  *   all three OVERWRITTEN; `workspace` must hold dctn_eps_head_bwd_workspace_bytes().
