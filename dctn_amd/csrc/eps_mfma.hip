@@ -1253,26 +1253,40 @@ __global__ __launch_bounds__(64 * BWD_WAVES) void eps_bwd_dcore_q2reg_k(const S*
           a0[d] = (dv && rlow) ? v : 0;
           a1[d] = (dv && !rlow) ? v : 0;
         }
+        // Every B operand is built before the first product and none is overwritten until 16 wait states after the last
+        // one.  Interleaved, the compiler let a v_perm_b32 overwrite the B operand of the 32x32x16 product issued just
+        // before it, with no wait state between them, and gave two products a destination overlapping their own B
+        // operand; a few dY entries then changed from run to run (found by the exact-input tests, tests/test_gpu_exact.py).
+        int4v bw[OP][2];   // B[k = class 8 h + 2 d, 2 d + 1][column = position 32 hh + r]
 #pragma unroll
         for (int o = 0; o < OP; ++o) {
           const unsigned sel = (o & 1) ? 0x07060302u : 0x05040100u;   // the odd / even halves of two dwords
-          f32x16 dya;
 #pragma unroll
-          for (int v = 0; v < 16; ++v) dya[v] = 0.f;
-#pragma unroll
-          for (int hh = 0; hh < 2; ++hh) {
-            int4v bw;   // B[k = class 8 h + 2 d, 2 d + 1][column = position 32 hh + r]
+          for (int hh = 0; hh < 2; ++hh)
 #pragma unroll
             for (int d = 0; d < 4; ++d) {
               const unsigned lo = wlds[((8 * h + 2 * d) * 64 + 32 * hh + r) * 2 + (o >> 1)];
               const unsigned hi = wlds[((8 * h + 2 * d + 1) * 64 + 32 * hh + r) * 2 + (o >> 1)];
-              bw[d] = (int)__builtin_amdgcn_perm(hi, lo, sel);
+              bw[o][hh][d] = (int)__builtin_amdgcn_perm(hi, lo, sel);
             }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int o = 0; o < OP; ++o) {
+          f32x16 dya;
+#pragma unroll
+          for (int v = 0; v < 16; ++v) dya[v] = 0.f;
+#pragma unroll
+          for (int hh = 0; hh < 2; ++hh)
             dya = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, hh == 0 ? a0 : a1),
-                                                           __builtin_bit_cast(bf16x8, bw), dya, 0, 0, 0);
-          }
+                                                           __builtin_bit_cast(bf16x8, bw[o][hh]), dya, 0, 0, 0);
           dyg[o] = __builtin_shufflevector(dya, dya, 0, 1, 2, 3, 4, 5, 6, 7);
         }
+        // the operands stay live through the wait, so no product's destination and no later write can take their registers
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_nop 7\n\ts_nop 7" ::"v"(a0), "v"(a1), "v"(bw[0][0]), "v"(bw[0][1]), "v"(bw[1][0]), "v"(bw[1][1]),
+                     "v"(bw[2 % OP][0]), "v"(bw[2 % OP][1]), "v"(bw[3 % OP][0]), "v"(bw[3 % OP][1]) : "memory");
+        __builtin_amdgcn_sched_barrier(0);
       };
       group_products();
       // the 8 samples unrolled: dY of sample s is a fixed register (a run-time index costs a 7-deep select chain each)

@@ -775,7 +775,8 @@ def test_convsbs_band_family_shapes(case):
 SNAKE9B = ((0, 0), (1, 0), (2, 0), (2, 1), (1, 1), (0, 1), (0, 2), (1, 2), (2, 2))   # mnist.py:201-210
 
 
-@pytest.mark.parametrize("bond,C,q,outs_a,outs_b,B,H,W", [
+# (bond, C, q, outs of string a, outs of string b, B, H, W): two nine-core strings of one ManyConvSBS layer
+MANY_CASES = [
     (4, 1, 2, (1, 1, 1, 1, 2, 1, 1, 1, 1), (1, 1, 1, 1, 2, 1, 1, 1, 1), 5, 12, 11),     # the classifier's first layer
     (2, 2, 2, (1, 1, 1, 1, 2, 1, 1, 1, 1), (1, 1, 1, 1, 2, 1, 1, 1, 1), 130, 10, 10),   # its second layer, bond 2, several bands
     (3, 1, 3, (2, 1, 1, 1, 1, 1, 1, 1, 1), (1, 1, 1, 1, 1, 1, 1, 1, 2), 3, 9, 30),      # bond 3, q = 3, different two-valued cores
@@ -785,7 +786,10 @@ SNAKE9B = ((0, 0), (1, 0), (2, 0), (2, 1), (1, 1), (0, 1), (0, 2), (1, 2), (2, 2
     (16, 2, 2, (1, 1, 1, 1, 2, 1, 1, 1, 1), (1, 1, 2, 1, 1, 1, 1, 1, 1), 130, 10, 10),   # two channels, many images: several bands
     (12, 1, 2, (1,) * 9, (1,) * 9, 3, 9, 30),
     (16, 1, 4, (1,) * 9, (1,) * 9, 2, 8, 8),
-])
+]
+
+
+@pytest.mark.parametrize("bond,C,q,outs_a,outs_b,B,H,W", MANY_CASES)
 def test_many_convsbs_strings_in_one_launch(bond, C, q, outs_a, outs_b, B, H, W):
     """`ManyConvSBS.forward` (dctn/conv_sbs.py:367-370) for a layer of two nine-core strings over the same 3 x 3 window:
     one forward launch, one backward launch (dX written once, summed over the strings) - against the oracle per string and
