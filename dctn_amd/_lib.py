@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(_HERE, "libdctn_amd.so")
 CSRC = os.path.join(_HERE, "csrc")
 
 F32, F64, BF16 = 0, 1, 2
-PREC_EXACT, PREC_BF16, PREC_MASK = 0, 1, 0xFF
+PREC_EXACT, PREC_BF16, PREC_SPLIT, PREC_MASK = 0, 1, 2, 0xFF
 OPT_F32_PREFER_HALVES, OPT_SMALL_CHUNKS, OPT_MAIN_KERNEL_ONLY, OPT_GENERIC_KERNELS = 1 << 8, 1 << 9, 1 << 10, 1 << 11
 OPT_HEAD_FEATURES_BLOCKED4 = 1 << 12   # dctn_eps_head_fwd / _bwd only: sample-blocked feature layout
 ERR_BAD_SHAPE, ERR_BAD_DTYPE, ERR_UNSUPPORTED, ERR_WORKSPACE, ERR_LAUNCH, ERR_NULL = -1, -2, -3, -4, -5, -6
@@ -240,10 +240,23 @@ def workspace(nbytes: int, dev: torch.device) -> torch.Tensor:
 _precision = PREC_EXACT
 
 
+# mode names of set_float32_matmul_precision: PyTorch's three ("highest", "high", "medium") and the project's own
+PRECISION_MODES = {"exact": PREC_EXACT, "highest": PREC_EXACT, "high": PREC_SPLIT, "bf16": PREC_BF16, "medium": PREC_BF16}
+
+
 def set_float32_matmul_precision(mode: str) -> None:
-    """'exact' (default): f32 in / f32 accumulate.  'bf16': operands rounded to bf16, f32 accumulate."""
+    """'exact' / 'highest' (default): f32 in / f32 accumulate.
+
+    'high' (DCTN_PREC_SPLIT, bf16x3): each float32 operand value is the sum of two bf16 values, hi + lo, and each
+    product hi*hi + hi*lo + lo*hi with float32 accumulation (about 3 * 2^-18 relative error per product).  Float32 EPS
+    calls whose shape the bf16x3 large-core family plans run it, forward and backward; every other shape runs exactly
+    as under 'exact' - the same kernels and the same bits (the register-resident exact-f32 family and its fused head,
+    the two-halves path, float64, the generic kernels).  Like PyTorch's "high" it permits the faster arithmetic and
+    does not force it.
+
+    'bf16' / 'medium': operands rounded to bf16, f32 accumulate.  Any other name raises KeyError."""
     global _precision
-    _precision = {"exact": PREC_EXACT, "highest": PREC_EXACT, "bf16": PREC_BF16}[mode]
+    _precision = PRECISION_MODES[mode]
 
 
 _options = 0

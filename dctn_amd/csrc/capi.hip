@@ -119,22 +119,35 @@ static bool f32_prefers_halves(const EpsP& p, int dtype) {
 
 static bool dtype_ok(int dtype) { return dtype == DCTN_F32 || dtype == DCTN_F64 || dtype == DCTN_BF16; }
 
+// DCTN_PREC_SPLIT: the bf16x3 large-core family takes the float32 shapes it plans among those that run on the exact
+// large-core family under DCTN_PREC_EXACT (not the register-resident families' shapes, not those sent to the two-halves
+// path by DCTN_OPT_F32_PREFER_HALVES); every other call runs the existing chain as under DCTN_PREC_EXACT
+static bool bf16x3_takes(const EpsP& p, int dtype, int precision) {
+  return precision == DCTN_PREC_SPLIT && !f32_prefers_halves(p, dtype) && !eps_mfma_covers(p, dtype, DCTN_PREC_EXACT) &&
+         !eps_q2f32_covers(p, dtype, DCTN_PREC_EXACT) && eps_bigcore_covers(p, dtype, DCTN_PREC_EXACT) &&
+         eps_bf16x3_covers(p, dtype, precision);
+}
+static int chain_precision(int precision) { return precision == DCTN_PREC_SPLIT ? DCTN_PREC_EXACT : precision; }
+
 size_t dctn_eps_fwd_workspace_bytes(int C, int B, int H, int W, int Q, int K, int O, int dtype,
                                     int policy) {
   EpsP p;
   const int precision = policy & DCTN_PREC_MASK;
   const int64_t dummy[5] = {0, 0, 0, 0, 1};
   if (eps_fill_params(p, dummy, C, B, H, W, Q, K, O, policy) != DCTN_OK) return 0;
-  const size_t a = eps_fwd_bigcore_workspace(p, dtype, precision), b = eps_fwd_halves_workspace(p, dtype);
+  if (bf16x3_takes(p, dtype, precision)) return eps_fwd_bf16x3_workspace(p, dtype, precision) + 256;
+  const size_t a = eps_fwd_bigcore_workspace(p, dtype, chain_precision(precision)), b = eps_fwd_halves_workspace(p, dtype);
   return (a > b ? a : b) + 256;
 }
 
 int dctn_eps_family(int C, int B, int H, int W, int Q, int K, int O, int dtype, int policy) {
   EpsP p;
-  const int precision = policy & DCTN_PREC_MASK;
+  int precision = policy & DCTN_PREC_MASK;
   const int64_t dummy[5] = {0, 0, 0, 0, 1};
   if (!dtype_ok(dtype) || eps_fill_params(p, dummy, C, B, H, W, Q, K, O, policy) != DCTN_OK) return -1;
   if (p.opts & DCTN_OPT_GENERIC_KERNELS) return DCTN_EPS_FAMILY_GENERIC;
+  if (bf16x3_takes(p, dtype, precision)) return DCTN_EPS_FAMILY_BIGCORE_BF16X3;
+  precision = chain_precision(precision);
   if (eps_mfma_covers(p, dtype, precision)) return DCTN_EPS_FAMILY_Q2REG;
   if (eps_q2f32_covers(p, dtype, precision)) return DCTN_EPS_FAMILY_Q2REG_F32;
   if (eps_bigcore_covers(p, dtype, precision) && !f32_prefers_halves(p, dtype)) return DCTN_EPS_FAMILY_BIGCORE_F32;
@@ -150,11 +163,20 @@ static int eps_fwd_impl(const void* x, const int64_t x_strides[5], const void* c
   if (!x || !core || !out || !x_strides) return DCTN_ERR_NULL;
   if (!dtype_ok(dtype)) return DCTN_ERR_BAD_DTYPE;
   EpsP p;
-  const int precision = policy & DCTN_PREC_MASK;
+  int precision = policy & DCTN_PREC_MASK;
   int rc = eps_fill_params(p, x_strides, C, B, H, W, Q, K, O, policy);
   if (rc != DCTN_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (p.opts & DCTN_OPT_GENERIC_KERNELS) return eps_fwd_generic(x, core, out, p, dtype, st);
+  if (bf16x3_takes(p, dtype, precision)) {
+    // the kept GEMM result has the exact family's row-quad-major layout and size (dctn_eps_saved_bytes)
+    const size_t zb = saved ? eps_bf16x3_saved_bytes(p, dtype, precision) : 0;
+    const bool keep = zb > 0 && saved_bytes >= zb;
+    rc = eps_fwd_bf16x3(x, core, out, workspace, workspace_bytes, p, dtype, precision, st, keep ? saved : nullptr);
+    if (rc == DCTN_OK && keep && kept) *kept = 1;
+    return rc;
+  }
+  precision = chain_precision(precision);
   rc = eps_fwd_mfma(x, core, out, p, dtype, precision, st);
   if (rc != DCTN_ERR_UNSUPPORTED) return rc;
   // the register-resident exact-f32 family keeps nothing for a backward: a training forward whose input needs a gradient
@@ -195,10 +217,13 @@ int dctn_eps_fwd(const void* x, const int64_t x_strides[5], const void* core, vo
 
 size_t dctn_eps_saved_bytes(int C, int B, int H, int W, int Q, int K, int O, int dtype, int policy) {
   EpsP p;
-  const int precision = policy & DCTN_PREC_MASK;
+  int precision = policy & DCTN_PREC_MASK;
   const int64_t dummy[5] = {0, 0, 0, 0, 1};
   if (!dtype_ok(dtype) || eps_fill_params(p, dummy, C, B, H, W, Q, K, O, policy) != DCTN_OK) return 0;
-  if ((p.opts & DCTN_OPT_GENERIC_KERNELS) || eps_mfma_covers(p, dtype, precision)) return 0;
+  if (p.opts & DCTN_OPT_GENERIC_KERNELS) return 0;
+  if (bf16x3_takes(p, dtype, precision)) return eps_bf16x3_saved_bytes(p, dtype, precision);
+  precision = chain_precision(precision);
+  if (eps_mfma_covers(p, dtype, precision)) return 0;
   if (eps_bigcore_covers(p, dtype, precision) && !f32_prefers_halves(p, dtype)) return eps_bigcore_saved_bytes(p, dtype, precision);
   return eps_halves_saved_bytes(p, dtype);
 }
@@ -250,9 +275,15 @@ int dctn_eps_fwd_stats(const void* x, const int64_t x_strides[5], const void* co
 size_t dctn_eps_bwd_workspace_bytes(int C, int B, int H, int W, int Q, int K, int O, int dtype,
                                     int policy, int need_dx, int need_dcore) {
   EpsP p;
-  const int precision = policy & DCTN_PREC_MASK;
+  int precision = policy & DCTN_PREC_MASK;
   const int64_t dummy[5] = {0, 0, 0, 0, 1};
   if (eps_fill_params(p, dummy, C, B, H, W, Q, K, O, policy) != DCTN_OK) return 0;
+  if (!(p.opts & DCTN_OPT_GENERIC_KERNELS) && bf16x3_takes(p, dtype, precision)) {
+    const size_t a = need_dx ? eps_bwd_dfactor_bf16x3_workspace(p, dtype, precision) : 0;
+    const size_t b = need_dcore ? eps_bwd_dcore_bf16x3_workspace(p, dtype, precision) : 0;
+    return (a > b ? a : b) + 256;
+  }
+  precision = chain_precision(precision);
   const size_t a = align256(eps_bwd_mfma_workspace(p, dtype, precision, need_dx, need_dcore)) +
                    align256(need_dcore ? eps_bwd_q2f32_workspace(p, dtype, precision) : 0);
   size_t b = eps_bwd_generic_workspace(p, dtype, need_dx, need_dcore);
@@ -319,11 +350,24 @@ static int eps_bwd_impl(const void* x, const int64_t x_strides[5], const void* c
   if (!dtype_ok(dtype)) return DCTN_ERR_BAD_DTYPE;
   if (!dX && !dCore) return DCTN_OK;
   EpsP p;
-  const int precision = policy & DCTN_PREC_MASK;
+  int precision = policy & DCTN_PREC_MASK;
   int rc = eps_fill_params(p, x_strides, C, B, H, W, Q, K, O, policy);
   if (rc != DCTN_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (p.opts & DCTN_OPT_GENERIC_KERNELS) return eps_bwd_generic(x, core, dY, dX, dCore, workspace, workspace_bytes, p, dtype, st);
+  if (bf16x3_takes(p, dtype, precision)) {
+    // both gradients on the bf16x3 family (dCore's slices are summed before dX uses the same workspace: stream order)
+    if (dCore) {
+      rc = eps_bwd_dcore_bf16x3(x, dY, dCore, p, dtype, precision, st, workspace, workspace_bytes);
+      if (rc != DCTN_OK) return rc;
+    }
+    if (dX) {
+      rc = eps_bwd_dx_bf16x3(x, core, dY, dX, workspace, workspace_bytes, p, dtype, precision, st, saved, saved_bytes);
+      if (rc != DCTN_OK) return rc == DCTN_ERR_UNSUPPORTED ? DCTN_ERR_LAUNCH : rc;
+    }
+    return DCTN_OK;
+  }
+  precision = chain_precision(precision);
   // dCore on the MFMA family when it covers the shape; whatever is left goes to the generic kernels
   unsigned char* ws = (unsigned char*)workspace;
   const size_t wa = align256(eps_bwd_mfma_workspace(p, dtype, precision, 0, dCore != nullptr));

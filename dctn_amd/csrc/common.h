@@ -90,6 +90,19 @@ int eps_bwd_dx_bigcore(const void* x, const void* core, const void* dY, void* dX
                        size_t ws_bytes, const EpsP& p, int dtype, int precision, hipStream_t st,
                        const void* zsaved = nullptr, size_t zsaved_bytes = 0);
 
+// bf16x3 large-core family (DCTN_PREC_SPLIT float32: the bigcore kernels on three bf16 products) — eps_bigcore_bf16x3.hip
+bool eps_bf16x3_covers(const EpsP& p, int dtype, int precision);
+size_t eps_fwd_bf16x3_workspace(const EpsP& p, int dtype, int precision);
+size_t eps_bf16x3_saved_bytes(const EpsP& p, int dtype, int precision);
+int eps_fwd_bf16x3(const void* x, const void* core, void* out, void* ws, size_t ws_bytes, const EpsP& p, int dtype,
+                   int precision, hipStream_t st, void* zsave = nullptr);
+size_t eps_bwd_dfactor_bf16x3_workspace(const EpsP& p, int dtype, int precision);
+int eps_bwd_dx_bf16x3(const void* x, const void* core, const void* dY, void* dX, void* ws, size_t ws_bytes, const EpsP& p,
+                      int dtype, int precision, hipStream_t st, const void* zsaved = nullptr, size_t zsaved_bytes = 0);
+size_t eps_bwd_dcore_bf16x3_workspace(const EpsP& p, int dtype, int precision);
+int eps_bwd_dcore_bf16x3(const void* x, const void* dY, void* dCore, const EpsP& p, int dtype, int precision,
+                         hipStream_t st, void* ws = nullptr, size_t ws_bytes = 0);
+
 // register-resident exact-float32 family for Q = 2, N in {8, 9}, O <= 4 (cfg2 in the reference's own dtype) — eps_q2f32.hip
 bool eps_q2f32_covers(const EpsP& p, int dtype, int precision);
 int eps_fwd_q2f32(const void* x, const void* core, void* out, const EpsP& p, int dtype, int precision, hipStream_t st);

@@ -152,9 +152,10 @@ def _f32_through_bf16(core: Tensor, input: Tensor) -> bool:
 
 def _bf16_through_f32(core: Tensor, input: Tensor) -> bool:
     """bf16 tensors whose core is outside the bf16 register family (deeper layers, Q > 2) would land on the
-    generic kernels; the exact-f32 matrix-core families (bigcore, two-halves GEMMs) take them instead: bf16 storage, f32 arithmetic
-    (the casts are three small elementwise kernels next to millisecond GEMMs; autograd casts the gradients
-    back)."""
+    generic kernels; the float32 matrix-core families (bigcore, two-halves GEMMs) take them instead: bf16 storage, the
+    float32 arithmetic of the current policy (the casts are three small elementwise kernels next to millisecond GEMMs;
+    autograd casts the gradients back).  Under "high" the large cores among them go to the bf16x3 family (5), under
+    "exact" to the exact one (2)."""
     if core.dtype != torch.bfloat16 or not core.is_cuda:
         return False
     C, B, H, W, Q = input.shape
@@ -162,7 +163,7 @@ def _bf16_through_f32(core: Tensor, input: Tensor) -> bool:
     args = (C, B, H, W, Q, K, core.shape[-1])
     lib, prec = L.lib(), L.precision()
     return (lib.dctn_eps_family(*args, L.dtype_code(core), prec) == 0
-            and lib.dctn_eps_family(*args, L._DTYPE_CODE[torch.float32], prec) in (2, 3))
+            and lib.dctn_eps_family(*args, L._DTYPE_CODE[torch.float32], prec) in (2, 3, 5))
 
 
 def eps_one_by_one(core: Tensor, input: Tensor) -> Tensor:

@@ -133,8 +133,8 @@ class _EpsLinearHeadFunction(torch.autograd.Function):
         n, o, cout = core.ndim - 1, core.shape[-1], weight.shape[0]
         if not (x.shape[-1] == 2 and n in (8, 9) and o in (2, 4) and cout <= 16 and weight.data_ptr() % 16 == 0 and FUSED_HEAD):
             return False
-        if x.dtype == torch.float32:   # the exact-f32 register family (eps_q2f32.hip) under the default policy
-            return (L.precision() & L.PREC_MASK) == L.PREC_EXACT
+        if x.dtype == torch.float32:   # the exact-f32 register family (eps_q2f32.hip): "exact", and "high", which runs
+            return (L.precision() & L.PREC_MASK) in (L.PREC_EXACT, L.PREC_SPLIT)   # that family's shapes as "exact" does
         return cout % 2 == 0 and weight.shape[1] % 8 == 0
 
     @staticmethod

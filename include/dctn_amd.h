@@ -60,6 +60,13 @@ enum {
 enum {
   DCTN_PREC_EXACT = 0, /* f32 in / f32 accumulate (v_mfma_f32_32x32x2_f32 or VALU fma) */
   DCTN_PREC_BF16 = 1,  /* operands rounded to bf16, f32 accumulate (v_mfma_f32_32x32x16_bf16) */
+  /* bf16x3 ("high"): each f32 operand value is hi + lo, two bf16 values (hi = bf16_rn(v), lo = bf16_rn(v - hi)), each
+   * product hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16, f32 accumulate (relative error ~3 * 2^-18 per product).
+   * It PERMITS the faster arithmetic and does not force it: float32 calls whose shape the bf16x3 large-core family
+   * (DCTN_EPS_FAMILY_BIGCORE_BF16X3) plans run bf16x3, forward and backward; every other shape, dtype and entry point
+   * runs exactly as under DCTN_PREC_EXACT - the same kernels and the same bits (the register-resident exact-f32 family
+   * and its fused head, the two-halves path, float64, the generic kernels). */
+  DCTN_PREC_SPLIT = 2,
   DCTN_PREC_MASK = 0xFF
 };
 enum {
@@ -111,6 +118,9 @@ int dctn_device_limits(int* cus, int* lds_bytes);
 #define DCTN_EPS_FAMILY_BIGCORE_F32 2  /* exact f32 MFMA, LDS-streamed core */
 #define DCTN_EPS_FAMILY_HALVES 3       /* two-halves GEMM path: f64 MFMA, and f32 MFMA for shapes 1 and 2 leave */
 #define DCTN_EPS_FAMILY_Q2REG_F32 4    /* exact f32 MFMA, register-resident core: Q = 2, N in {8, 9}, O <= 4 */
+#define DCTN_EPS_FAMILY_BIGCORE_BF16X3 5  /* DCTN_PREC_SPLIT float32 only: bf16x3 MFMA, LDS-streamed core (the shapes of
+                                           * family 2 whose every product the bf16x3 plans take); under that policy
+                                           * every other shape answers what it answers under DCTN_PREC_EXACT */
 int dctn_eps_family(int C, int B, int H, int W, int Q, int K, int O, int dtype, int policy);
 size_t dctn_eps_fwd_workspace_bytes(int C, int B, int H, int W, int Q, int K, int O,
                                     int dtype, int policy);
