@@ -1,0 +1,247 @@
+// The reference's documented recipe trains with Adam (new_runner.py:496-498: Adam(model.parameters(), lr, weight_decay))
+// and scores with cross-entropy + accuracy per batch (dctn/evaluation.py:7-22).  Two kernels beside train_tail.hip's:
+//   adam_l2_k  : torch.optim.Adam (coupled weight decay) + the L2 regulariser over ONE flat parameter buffer, like
+//                sgd_l2_k.  The step count t and the learning rate are read from a 16-byte device block, and the
+//                launch itself advances t: a captured graph replays the same node and still gets t, t+1, t+2, ...
+//   ce_score_k : adds one batch's {sum of cross-entropies, correct rows, rows} to three float64 values
+#include "common.h"
+
+#include <cmath>
+
+namespace {
+
+constexpr long long DCTN_CE_IGNORE = -100;   // torch.nn.functional.cross_entropy's default ignore_index
+
+struct AdamState {   // include/dctn_amd.h documents this layout: it is part of the ABI
+  int steps_done;
+  float lr;
+  unsigned ticket;
+  unsigned reserved;
+};
+
+struct AdamCoef {
+  double ln_b1, ln_b2;        // ln(beta): 1 - beta^t = -expm1(t * ln beta), formed in the kernel from t
+  float b1, omb1, b2, omb2;   // beta, 1 - beta (formed in double on the host, then rounded once)
+  float eps, wd, two_l2;
+};
+
+// The arithmetic of one element; every product-sum is an explicit fmaf so that the vector and the scalar form of the
+// kernel (and any later instantiation) produce the same bits whatever the compiler would contract on its own
+__device__ __forceinline__ float adam_elem(float wi, float gi, float& m, float& v, bool reg, const AdamCoef& k,
+                                           float step, float bc2_sqrt, float& part) {
+  gi = fmaf(k.wd, wi, gi);
+  if (reg) {
+    gi = fmaf(k.two_l2, wi, gi);
+    part = fmaf(wi, wi, part);
+  }
+  m = fmaf(k.b1, m, k.omb1 * gi);
+  v = fmaf(k.b2, v, (k.omb2 * gi) * gi);
+  const float denom = sqrtf(v) / bc2_sqrt + k.eps;
+  return fmaf(-step, m / denom, wi);
+}
+
+__device__ __forceinline__ void load4(const float* p, float (&x)[4]) {
+  const float4 t = *reinterpret_cast<const float4*>(p);
+  x[0] = t.x, x[1] = t.y, x[2] = t.z, x[3] = t.w;
+}
+__device__ __forceinline__ void store4(float* p, const float (&x)[4]) {
+  *reinterpret_cast<float4*>(p) = make_float4(x[0], x[1], x[2], x[3]);
+}
+__device__ __forceinline__ void load4(const bf16_t* p, float (&x)[4]) {
+  const uint2 t = *reinterpret_cast<const uint2*>(p);   // bf16 -> f32 is the upper half of the word
+  x[0] = __uint_as_float(t.x << 16), x[1] = __uint_as_float(t.x & 0xffff0000u);
+  x[2] = __uint_as_float(t.y << 16), x[3] = __uint_as_float(t.y & 0xffff0000u);
+}
+__device__ __forceinline__ unsigned bf16_bits(float x) {
+  return __builtin_bit_cast(unsigned short, (bf16_t)x);   // the same round-to-nearest-even cast as the scalar form
+}
+__device__ __forceinline__ void store4(bf16_t* p, const float (&x)[4]) {
+  *reinterpret_cast<uint2*>(p) = make_uint2(bf16_bits(x[0]) | (bf16_bits(x[1]) << 16), bf16_bits(x[2]) | (bf16_bits(x[3]) << 16));
+}
+
+// VEC: four elements per lane and access (16 bytes of exp_avg / exp_avg_sq, 16 or 8 of the parameters) when every
+// pointer is aligned for it; the tail of n and the unaligned case take one element per lane.
+// Workgroups of 1024 threads, at most 256 of them: the ticket at the end is one atomic per workgroup on ONE address,
+// and those serialise at about 12 ns each (measured: 1024 workgroups of 256 threads took 17.7 us over 1.9 M
+// parameters where the same stream without a ticket, sgd_l2_k, takes 5.7 us).
+template <typename S, bool VEC>
+__global__ __launch_bounds__(1024) void adam_l2_k(S* __restrict__ w, const S* __restrict__ g, float* __restrict__ ea,
+                                                 float* __restrict__ eas, float* __restrict__ sq_sum,
+                                                 AdamState* __restrict__ state, long long n, long long n_reg,
+                                                 AdamCoef k) {
+  __shared__ float red[16];
+  __shared__ float scale[2];
+  // lane 0 of every workgroup reads the step count and the learning rate BEFORE it takes the workgroup's ticket below;
+  // the one write of the launch to steps_done happens after the last ticket is drawn, so no workgroup can see the new
+  // value
+  int t = 0;
+  if (threadIdx.x == 0) {
+    t = __hip_atomic_load(&state->steps_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
+    const float lr = __hip_atomic_load(&state->lr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // The two bias corrections in float64, once per workgroup, rounded once - what torch's host arithmetic gives.  In
+    // float32 the difference 1 - beta2^t cancels: at t = 1 it is 0.001 with the absolute error of 0.999, a relative
+    // 6e-5 in every update of the first steps.  (From t itself, not as running products, which drift.)
+    scale[0] = (float)((double)lr / -expm1((double)t * k.ln_b1));
+    scale[1] = (float)sqrt(-expm1((double)t * k.ln_b2));
+  }
+  __syncthreads();
+  const float step = scale[0], bc2_sqrt = scale[1];
+  float part = 0.f;
+  const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, nthr = (long long)gridDim.x * blockDim.x;
+  const long long n_vec = VEC ? (n & ~3LL) : 0;
+  if (VEC) {
+    for (long long i = tid * 4; i < n_vec; i += nthr * 4) {
+      float wi[4], gi[4], mi[4], vi[4];
+      load4(w + i, wi), load4(g + i, gi), load4(ea + i, mi), load4(eas + i, vi);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) wi[e] = adam_elem(wi[e], gi[e], mi[e], vi[e], i + e < n_reg, k, step, bc2_sqrt, part);
+      store4(ea + i, mi), store4(eas + i, vi), store4(w + i, wi);
+    }
+  }
+  for (long long i = n_vec + tid; i < n; i += nthr) {
+    float m = ea[i], v = eas[i];
+    w[i] = (S)adam_elem((float)w[i], (float)g[i], m, v, i < n_reg, k, step, bc2_sqrt, part);
+    ea[i] = m, eas[i] = v;
+  }
+  for (int off = 32; off > 0; off >>= 1) part += __shfl_down(part, off, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    // one slot per workgroup, stored (not accumulated), as sgd_l2_k
+    float total = 0.f;
+    for (int j = 0; j < 16; ++j) total += red[j];
+    if (sq_sum) sq_sum[blockIdx.x] = total;
+    // The ticket.  It orders one thing only: every workgroup's read of steps_done before the last workgroup's write of
+    // it.  No data passes between workgroups, so no release / acquire of the parameter stores is needed (the kernel
+    // boundary publishes those); the wait makes sure this lane's two state loads have returned before the ticket is
+    // drawn, and the writer below acts on the value its own ticket returned.
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    const unsigned drawn = __hip_atomic_fetch_add(&state->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (drawn == gridDim.x - 1) {   // plain vector stores; the next launch starts from ticket 0 again
+      state->steps_done = t;
+      state->ticket = 0u;
+    }
+  }
+}
+
+unsigned adam_blocks_for(long long n) {   // one vector access of every lane per workgroup, up to one workgroup per CU
+  long long b = (n + 4095) / 4096;
+  if (b > 256) b = 256;
+  return (unsigned)(b < 1 ? 1 : b);
+}
+
+__device__ __forceinline__ float ld_f32(const float* p) { return *p; }
+__device__ __forceinline__ float ld_f32(const bf16_t* p) { return (float)*p; }
+
+// ONE workgroup of 16 waves for any batch: the three sums have one fixed order, so the result is the same bits from
+// run to run, and nothing needs a fill or a float atomic (scoring batches are 1e3 .. 1e4 rows of ~10 classes: a few
+// hundred KB at most, launch latency).  A row belongs to P = min(64, next power of two >= C) neighbouring lanes; lane j of
+// them holds classes j, j + P, ...; maximum, sum of exponentials and the lowest index of a maximum are closed by xor
+// butterflies.  The exponentials are float32 (as ce_fwd_k's); everything that accumulates is float64, like `acc`.
+template <typename S>
+__global__ __launch_bounds__(1024) void ce_score_k(const S* __restrict__ logits, const long long* __restrict__ labels,
+                                                   double* __restrict__ acc, long long B, int C, int P) {
+  __shared__ double red[3][16];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = lane & (P - 1);
+  const int rows_per_wave = 64 / P;
+  double loss = 0.0, correct = 0.0, rows = 0.0;   // only a row's first lane adds to them
+  // (wave-uniform trip count: the shuffles below need every lane of the wave)
+  for (long long r0 = (long long)wave * rows_per_wave; r0 < B; r0 += 16LL * rows_per_wave) {
+    const long long b = r0 + lane / P;
+    const bool live = b < B;
+    const S* row = logits + (live ? b : 0) * C;
+    float m = -INFINITY;
+    for (int c = sub; c < C; c += P) m = fmaxf(m, ld_f32(row + c));
+    for (int off = P >> 1; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    double s = 0.0;   // float32 exponentials, summed in float64
+    int first = 0x7fffffff;   // lowest class index that holds the maximum: torch.argmax's answer on ties
+    for (int c = sub; c < C; c += P) {
+      const float x = ld_f32(row + c);
+      s += (double)expf(x - m);
+      if (x == m && c < first) first = c;
+    }
+    for (int off = P >> 1; off > 0; off >>= 1) {
+      s += __shfl_xor(s, off, 64);
+      first = min(first, __shfl_xor(first, off, 64));
+    }
+    if (live && sub == 0) {
+      const long long y = labels[b];
+      if (y != DCTN_CE_IGNORE) {
+        const bool valid = y >= 0 && y < C;
+        // log-softmax's order, -((x_y - m) - log s); x_y - m is small and (nearly) exact in float32.  The logarithm is
+        // taken in float64, one per row: this device's float32 log is low by 0.3 - 0.5 ulp on average for arguments
+        // in [2, 10] (measured against float64: -7.6e-8 on [5, 10]), a bias that adds up over the rows of a batch
+        loss += valid ? log(s) - (double)(ld_f32(row + (valid ? y : 0)) - m) : (double)__builtin_nanf("");
+        correct += valid && y == (long long)first ? 1.0 : 0.0;
+        rows += 1.0;
+      }
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    loss += __shfl_down(loss, off, 64);
+    correct += __shfl_down(correct, off, 64);
+    rows += __shfl_down(rows, off, 64);
+  }
+  if (lane == 0) red[0][wave] = loss, red[1][wave] = correct, red[2][wave] = rows;
+  __syncthreads();
+  if (threadIdx.x < 3) {   // stream order makes the read-modify-write safe: one workgroup, one launch at a time
+    double total = 0.0;
+    for (int k = 0; k < 16; ++k) total += red[threadIdx.x][k];
+    acc[threadIdx.x] += total;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t dctn_adam_state_bytes(void) { return sizeof(AdamState); }
+
+int dctn_adam_l2_num_partials(int64_t n) { return n < 1 ? 0 : (int)adam_blocks_for(n); }
+
+int dctn_adam_l2_step(void* params, const void* grads, void* exp_avg, void* exp_avg_sq, void* sq_sum, void* state,
+                      int64_t n, int64_t n_reg, double beta1, double beta2, float eps, float weight_decay, float l2,
+                      int dtype, void* stream) {
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !state) return DCTN_ERR_NULL;
+  if (n < 1 || n_reg < 0 || n_reg > n) return DCTN_ERR_BAD_SHAPE;
+  if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return DCTN_ERR_BAD_SHAPE;   // torch raises ValueError
+  if (dtype != DCTN_F32 && dtype != DCTN_BF16) return DCTN_ERR_BAD_DTYPE;
+  hipStream_t st = (hipStream_t)stream;
+  AdamCoef k;
+  k.b1 = (float)beta1, k.omb1 = (float)(1.0 - beta1), k.b2 = (float)beta2, k.omb2 = (float)(1.0 - beta2);
+  k.ln_b1 = std::log(beta1), k.ln_b2 = std::log(beta2);   // beta = 0: -inf, and 1 - beta^t = -expm1(-inf) = 1
+  k.eps = eps, k.wd = weight_decay, k.two_l2 = 2.f * l2;
+  const size_t esz = dtype == DCTN_F32 ? 4 : 2;
+  const bool vec = ((uintptr_t)params | (uintptr_t)grads) % (4 * esz) == 0 && ((uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) % 16 == 0;
+  const dim3 g(adam_blocks_for(n)), b(1024);
+  AdamState* sp = (AdamState*)state;
+#define DCTN_ADAM_LAUNCH(S, VEC)                                                                                   \
+  hipLaunchKernelGGL((adam_l2_k<S, VEC>), g, b, 0, st, (S*)params, (const S*)grads, (float*)exp_avg, (float*)exp_avg_sq, \
+                     (float*)sq_sum, sp, (long long)n, (long long)n_reg, k)
+  if (dtype == DCTN_F32) {
+    if (vec) DCTN_ADAM_LAUNCH(float, true); else DCTN_ADAM_LAUNCH(float, false);
+  } else {
+    if (vec) DCTN_ADAM_LAUNCH(bf16_t, true); else DCTN_ADAM_LAUNCH(bf16_t, false);
+  }
+#undef DCTN_ADAM_LAUNCH
+  DCTN_CHECK_LAUNCH();
+  return DCTN_OK;
+}
+
+int dctn_ce_score_accumulate(const void* logits, const void* labels, void* acc, int64_t B, int C, int dtype,
+                             void* stream) {
+  if (!logits || !labels || !acc) return DCTN_ERR_NULL;
+  if (B < 1 || C < 1) return DCTN_ERR_BAD_SHAPE;
+  if (dtype != DCTN_F32 && dtype != DCTN_BF16) return DCTN_ERR_BAD_DTYPE;
+  hipStream_t st = (hipStream_t)stream;
+  int P = 1;
+  while (P < C && P < 64) P <<= 1;
+  if (dtype == DCTN_F32)
+    hipLaunchKernelGGL(ce_score_k<float>, dim3(1), dim3(1024), 0, st, (const float*)logits, (const long long*)labels, (double*)acc, (long long)B, C, P);
+  else
+    hipLaunchKernelGGL(ce_score_k<bf16_t>, dim3(1), dim3(1024), 0, st, (const bf16_t*)logits, (const long long*)labels, (double*)acc, (long long)B, C, P);
+  DCTN_CHECK_LAUNCH();
+  return DCTN_OK;
+}
+
+}  // extern "C"

@@ -71,7 +71,7 @@ class GraphedTrainStep:
     ``graph_allreduce=True`` skips the probe and insists.
     Inputs are copied into static buffers, so
     every call must use the batch shape of the example; the optimizer must be capturable
-    (``torch.optim.SGD``, or ``Adam(..., capturable=True)``).
+    (``FlatSGD`` / ``FlatAdam`` below, ``torch.optim.SGD``, or ``torch.optim.Adam(..., capturable=True)``).
 
     The dictionary a call returns holds the graph's STATIC output buffers (no copy kernels in the iteration): the
     next call overwrites them.  A caller that keeps ``loss`` / ``output`` across iterations must ``.clone()`` them
@@ -232,26 +232,16 @@ def fused_cross_entropy(logits: Tensor, labels: Tensor) -> Tensor:
 fused_cross_entropy.accepts_low_precision = True   # train_step / GraphedTrainStep skip their float32 cast
 
 
-class FlatSGD:
-    """SGD with momentum plus the reference's L2 regulariser, as ONE kernel per step over one flat
-    parameter buffer (`dctn_sgd_l2_step`).
+class _FlatOptimizer:
+    """What FlatSGD and FlatAdam share: the parameters moved into ONE flat buffer (their ``.data`` become views of it,
+    in the order regularised + others), the gradients read in place when they already sit back to back in that
+    order (the fused EPS + head backward allocates them so) and gathered otherwise, and the regulariser's value left
+    by the step kernel as one partial sum of squares per workgroup."""
 
-    ``regularised``: the parameters whose squared Frobenius norms the regulariser sums (for
-    EPSesPlusLinear.epswise_l2_regularizer: every core and ``linear.weight``,
-    dctn/eps_plus_linear.py:149-153); ``others``: the rest (``linear.bias``).  Adding
-    ``l2 * sum ||w||^2`` to the loss and letting autograd differentiate it is the same update as adding
-    ``2 * l2 * w`` to the gradient, which is what the kernel does; ``reg_value()`` returns the term's
-    value (before the update) for logging.  The parameters are moved into one buffer (their ``.data``
-    become views of it, in the order regularised + others); when the gradients already sit back to back
-    in that order (the fused EPS + head backward allocates them so) the step reads them in place,
-    otherwise they are gathered first.  Semantics of torch.optim.SGD(momentum, dampening = 0).
-    """
-
-    def __init__(self, regularised, others=(), lr: float = 1e-3, momentum: float = 0.0, l2: float = 0.0):
+    def __init__(self, regularised, others, num_partials: Callable[[int], int]):
         self.reg_params = [p for p in regularised]
         self.params = self.reg_params + [p for p in others]
         assert self.params and len({p.dtype for p in self.params}) == 1 and len({p.device for p in self.params}) == 1
-        self.lr, self.momentum, self.l2 = float(lr), float(momentum), float(l2)
         ref = self.params[0]
         self.n = sum(p.numel() for p in self.params)
         self.n_reg = sum(p.numel() for p in self.reg_params)
@@ -263,11 +253,9 @@ class FlatSGD:
                 view.copy_(p)
                 p.data = view
                 off += p.numel()
-        self.buf = torch.zeros(self.n, dtype=torch.float32, device=ref.device)
         # one partial sum of squares per workgroup of the kernel; added up only when the value is asked for
-        self.sq_sum = torch.zeros(L.lib().dctn_sgd_l2_num_partials(self.n), dtype=torch.float32, device=ref.device)
+        self.sq_sum = torch.zeros(num_partials(self.n), dtype=torch.float32, device=ref.device)
         self.flat_grad = torch.zeros(self.n, dtype=ref.dtype, device=ref.device)
-        self._steps = 0
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         for p in self.params:
@@ -294,6 +282,32 @@ class FlatSGD:
                   out=self.flat_grad)
         return self.flat_grad
 
+    def reg_value(self) -> Tensor:
+        """l2 * sum of squared Frobenius norms of the regularised parameters, as of the last step."""
+        return self.sq_sum.sum() * self.l2
+
+
+class FlatSGD(_FlatOptimizer):
+    """SGD with momentum plus the reference's L2 regulariser, as ONE kernel per step over one flat
+    parameter buffer (`dctn_sgd_l2_step`).
+
+    ``regularised``: the parameters whose squared Frobenius norms the regulariser sums (for
+    EPSesPlusLinear.epswise_l2_regularizer: every core and ``linear.weight``,
+    dctn/eps_plus_linear.py:149-153); ``others``: the rest (``linear.bias``).  Adding
+    ``l2 * sum ||w||^2`` to the loss and letting autograd differentiate it is the same update as adding
+    ``2 * l2 * w`` to the gradient, which is what the kernel does; ``reg_value()`` returns the term's
+    value (before the update) for logging.  The parameters are moved into one buffer (their ``.data``
+    become views of it, in the order regularised + others); when the gradients already sit back to back
+    in that order (the fused EPS + head backward allocates them so) the step reads them in place,
+    otherwise they are gathered first.  Semantics of torch.optim.SGD(momentum, dampening = 0).
+    """
+
+    def __init__(self, regularised, others=(), lr: float = 1e-3, momentum: float = 0.0, l2: float = 0.0):
+        super().__init__(regularised, others, L.lib().dctn_sgd_l2_num_partials)
+        self.lr, self.momentum, self.l2 = float(lr), float(momentum), float(l2)
+        self.buf = torch.zeros(self.n, dtype=torch.float32, device=self.flat.device)
+        self._steps = 0
+
     @torch.no_grad()
     def step(self) -> None:
         g = self._grads()
@@ -304,9 +318,81 @@ class FlatSGD:
                 "fused SGD step")
         self._steps += 1
 
-    def reg_value(self) -> Tensor:
-        """l2 * sum of squared Frobenius norms of the regularised parameters, as of the last step."""
-        return self.sq_sum.sum() * self.l2
+
+class FlatAdam(_FlatOptimizer):
+    """torch.optim.Adam (coupled ``weight_decay``, no amsgrad - what the reference's recipe builds,
+    new_runner.py:496-498) plus the reference's L2 regulariser, as ONE kernel per step over one flat parameter
+    buffer (`dctn_adam_l2_step`).  Construction, gradient handling and ``reg_value()`` are FlatSGD's; the moments
+    ``m`` / ``v`` are float32 whatever the parameter dtype.
+
+    The step count ``t`` and the learning rate live in a small DEVICE block that the kernel reads and whose ``t`` the
+    same launch advances: a `GraphedTrainStep` that captured ``step()`` gets t, t+1, ... on its replays, and
+    assigning ``opt.lr`` (a tiny asynchronous write on the current stream; not allowed during a capture) changes the
+    rate of every later step, replays of an already captured graph included.  Reading ``opt.lr`` returns the host
+    copy; ``opt.t`` reads the device (it synchronises).  ``state_dict()`` / ``load_state_dict()`` carry t, lr, m, v
+    and the hyper-parameters: a run resumed from them continues bit-identically.
+    """
+
+    def __init__(self, regularised, others=(), lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, l2: float = 0.0):
+        super().__init__(regularised, others, L.lib().dctn_adam_l2_num_partials)
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0 and lr >= 0.0 and eps >= 0.0 and weight_decay >= 0.0):
+            raise ValueError(f"invalid Adam hyper-parameters: lr={lr} betas={betas} eps={eps} weight_decay={weight_decay}")
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        self.weight_decay, self.l2 = float(weight_decay), float(l2)
+        dev = self.flat.device
+        self.m = torch.zeros(self.n, dtype=torch.float32, device=dev)
+        self.v = torch.zeros(self.n, dtype=torch.float32, device=dev)
+        # {int32 steps_done, float32 lr, uint32 ticket, uint32 reserved}: include/dctn_amd.h
+        assert L.lib().dctn_adam_state_bytes() == 16
+        self._state = torch.zeros(4, dtype=torch.int32, device=dev)
+        self._lr_cell = self._state.view(torch.float32)[1:2]
+        self._lr = float("nan")
+        self.lr = lr
+
+    @property
+    def lr(self) -> float:
+        return self._lr
+
+    @lr.setter
+    def lr(self, value: float) -> None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FlatAdam.lr cannot be assigned during a graph capture: the captured step reads the "
+                               "rate from the device, assign it between replays")
+        self._lr = float(value)
+        with torch.cuda.device(self.flat.device):
+            self._lr_cell.fill_(self._lr)
+
+    @property
+    def t(self) -> int:
+        """Number of steps taken (read from the device)."""
+        return int(self._state[0].item())
+
+    @torch.no_grad()
+    def step(self) -> None:
+        g = self._grads()
+        dev = self.flat.device
+        L.check(L.lib().dctn_adam_l2_step(self.flat.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                                          self.sq_sum.data_ptr(), self._state.data_ptr(), self.n, self.n_reg,
+                                          self.betas[0], self.betas[1], self.eps, self.weight_decay, self.l2,
+                                          L.dtype_code(self.flat), L.stream_ptr(dev)), "fused Adam step")
+
+    def state_dict(self) -> Dict[str, Any]:
+        """Everything a resumed run needs besides the parameters themselves (those are the model's state_dict)."""
+        return {"t": self.t, "lr": self._lr, "m": self.m.clone(), "v": self.v.clone(), "betas": self.betas,
+                "eps": self.eps, "weight_decay": self.weight_decay, "l2": self.l2}
+
+    def load_state_dict(self, state: Dict[str, Any]) -> None:
+        if state["m"].numel() != self.n or state["v"].numel() != self.n:
+            raise ValueError(f"optimizer state holds {state['m'].numel()} values, the parameters {self.n}")
+        self.betas, self.eps = (float(state["betas"][0]), float(state["betas"][1])), float(state["eps"])
+        self.weight_decay, self.l2 = float(state["weight_decay"]), float(state["l2"])
+        with torch.no_grad():
+            self.m.copy_(state["m"].reshape(-1))
+            self.v.copy_(state["v"].reshape(-1))
+            self._state.zero_()
+            self._state[0] = int(state["t"])
+        self.lr = state["lr"]
 
 
 # ------------------------------------------------------------------------------------------------

@@ -391,6 +391,44 @@ int dctn_sgd_l2_step(void* params, const void* grads, void* momentum_buf, void* 
                      float lr, float momentum, float l2, int first_step, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Adam (torch.optim.Adam: coupled weight decay, amsgrad = False, maximize = False) plus the same L2 regulariser, as
+ * ONE launch per step over the flat parameter buffer.  Per element, float32 master arithmetic:
+ *   g = grads + weight_decay*w (+ 2*l2*w on the regularised prefix),
+ *   m = beta1*m + (1-beta1)*g,  v = beta2*v + (1-beta2)*g*g,
+ *   w -= (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)         t = number of this step, from 1.
+ * exp_avg / exp_avg_sq are float32 whatever the parameter dtype (DCTN_F32 / DCTN_BF16).  sq_sum: as dctn_sgd_l2_step
+ * (optional, dctn_adam_l2_num_partials(n) float32 slots, OVERWRITTEN, sum of w^2 over the prefix BEFORE the update).
+ * The step count and the learning rate live on the DEVICE, so that a captured graph that holds this launch advances
+ * t on every replay and follows a learning rate changed between replays.  `state`: dctn_adam_state_bytes() = 16
+ * bytes, 16-byte aligned, laid out as
+ *   int32  steps_done   number of steps taken so far (0 before the first); the launch computes with t = steps_done + 1
+ *                       and leaves steps_done + 1 here
+ *   float  lr           read by every launch; the caller may overwrite it in stream order between launches
+ *   uint32 ticket       0 between launches (workgroups count themselves out on it; the last one resets it)
+ *   uint32 reserved     0
+ * The caller creates the block once (zeroes + lr) and may read or write it in stream order between launches.
+ * beta1^t and beta2^t are formed from t in the kernel (no running products).
+ * ------------------------------------------------------------------------------------------ */
+size_t dctn_adam_state_bytes(void);
+int dctn_adam_l2_num_partials(int64_t n);
+int dctn_adam_l2_step(void* params, const void* grads, void* exp_avg, void* exp_avg_sq, void* sq_sum, void* state,
+                      int64_t n, int64_t n_reg, double beta1, double beta2, float eps, float weight_decay, float l2,
+                      int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Scoring (reference: dctn/evaluation.py:7-22): one launch per batch ADDS to acc = three float64 values
+ * {sum of the rows' cross-entropies, number of correct rows, number of rows}.  logits (B, C) contiguous, DCTN_F32 /
+ * DCTN_BF16; labels int64.  Per row a max-shifted log-sum-exp with float32 exponentials; the row's sum, its
+ * logarithm and the sums over the rows are float64, in a fixed order: the same bits from run to run (the float32
+ * logarithm of gfx950 is low by about 0.4 ulp on average for such sums, which would add up over a batch); a row is correct when its label equals the LOWEST index among the
+ * row's maxima (torch.argmax).  Rows labelled -100 are skipped and not counted; any other label outside [0, C) makes
+ * sum_loss NaN and counts as a wrong row.  acc is read and written in stream order (no atomics, no fill per batch);
+ * the caller zeroes it once.
+ * ------------------------------------------------------------------------------------------ */
+int dctn_ce_score_accumulate(const void* logits, const void* labels, void* acc, int64_t B, int C, int dtype,
+                             void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Tensor-network inner product of two stacks of EPS cores - replaces the contractions of
  * dctn/epses_composition.py:21-58 `inner_product` (Gram of the first pair of cores over their input legs:
  * dctn/eps.py:106-112 `contract_on_input_dims`; that matrix absorbed into every input leg of the next core:
