@@ -21,6 +21,7 @@ from dctn_amd.eps import eps, eps_one_by_one, keep_gemm_result, output_sums_in_s
 from dctn_amd.pos2d import Pos2D
 from oracle import ref_cpu as R
 from tests import exact_inputs as X
+from tests import guarded_buffers as G
 from tests.test_gpu_convsbs_wide import FAILS_TODAY, FORCED, WIDE
 from tests.test_gpu_fuzz import (BAND_CASES, BIGCORE_XO_CASES, F32_HALVES_CASES, F64_CASES, HEAD_CASES, MANY_CASES, MV_CASES,
                                  Q2F32_CASES, REG_CASES, SNAKE9, SNAKE9B, eps_cases, sbs_band_family_takes, sbs_mfma_cases,
@@ -59,6 +60,14 @@ KERNELS = {
 ACC = {torch.float64: torch.float64, torch.float32: torch.float32, torch.bfloat16: torch.float32}
 
 
+def on_dev(t, arena=None):
+    """Input placement: on the device - and, under a guarded arena (tests/guarded_buffers.py: the one given, else the active
+    one), inside a guarded allocation with the same values and strides.  Without an arena: `t.to(DEV)`, as ever."""
+    t = t.to(DEV)
+    arena = arena if arena is not None else G.current()
+    return t if arena is None else arena.place(t)
+
+
 def strided_copy(t):
     """The same values behind a non-contiguous view (pixel rows no longer contiguous)."""
     return t.permute(0, 1, 3, 2, 4).contiguous().permute(0, 1, 3, 2, 4)
@@ -69,7 +78,8 @@ def core_view(t):
 
 
 # ------------------------------------------------------------------------------------------------ EPS
-def run_eps(core64, x64, dy64, dtype, *, strided=False, need_dx=True, fn=eps, fwd=None, bwd=None, rounding=None, tag=""):
+def run_eps(core64, x64, dy64, dtype, *, strided=False, need_dx=True, fn=eps, fwd=None, bwd=None, rounding=None, tag="",
+            arena=None):
     """forward, dCore with dX (need_dx) or dCore alone, all exact against the oracle; returns the budget report."""
     N = core64.ndim - 1
     C = x64.shape[0]
@@ -86,14 +96,14 @@ def run_eps(core64, x64, dy64, dtype, *, strided=False, need_dx=True, fn=eps, fw
     xd = x64.to(dtype).to(DEV)
     if strided:
         xd = strided_copy(xd)
-    xd.requires_grad_(need_dx)
-    cd = core64.to(dtype).to(DEV).requires_grad_(True)
+    xd = on_dev(xd, arena).requires_grad_(need_dx)
+    cd = on_dev(core64.to(dtype), arena).requires_grad_(True)
     y = fn(cd, xd)
     kf = dctn_amd.last_kernel()
     if fwd is not None:
         assert kf == fwd, f"{tag}: forward ran {kf}, expected {fwd}"
     X.assert_exact(y, want, dtype, X.EPS_LAYOUT, f"{tag} forward [{kf}]")
-    y.backward(dy64.to(dtype).to(DEV))
+    y.backward(on_dev(dy64.to(dtype), arena))
     kb = dctn_amd.last_kernel()
     if bwd is not None:
         assert kb == bwd, f"{tag}: backward ran {kb}, expected {bwd}"
@@ -234,12 +244,16 @@ def test_eps_f32_under_the_bf16_policy(keep):
                                                  (torch.float32, 1, 2, 4, 5, 6, 7, 7), (torch.float64, 1, 3, 3, 2, 5, 9, 9)])
 def test_eps_fwd_stats(dtype, C, K, Q, O, B, H, W):
     """dctn_eps_fwd_stats: [sum y, sum y^2] over the storage-rounded y, exact in float64."""
+    run_eps_fwd_stats(dtype, C, K, Q, O, B, H, W)
+
+
+def run_eps_fwd_stats(dtype, C, K, Q, O, B, H, W, arena=None):
     x = X.one_hot_pixels(C, B, H, W, Q, B + H)
     core = X.eps_core(Q, K * K * C, O, B + H + 1)
     y = X.expected(R.eps_4step(core, x), dtype).double()
     # integer y of at most 8: the per-lane float32 sums of y and y^2 are bounded by the totals
     X.check_budget({"sum |y|": y.abs().sum().reshape(1), "sum y^2": (y * y).sum().reshape(1)}, torch.float32)
-    count, sums = output_sums_in_slices(core.to(dtype).to(DEV), x.to(dtype).to(DEV), 16)
+    count, sums = output_sums_in_slices(on_dev(core.to(dtype), arena), on_dev(x.to(dtype), arena), 16)
     assert count == y.numel()
     want = torch.stack([y.sum(), (y * y).sum()])
     assert torch.equal(sums.cpu(), want), (sums.cpu().tolist(), want.tolist())
@@ -285,14 +299,15 @@ def head_oracle(core, x, w, bias, g, closed_form=False):
 
 
 def run_head(core, x, w, bias, g, dtype, *, fused=True, fused_fwd=True, blocked=True, strided=False, oracle=None,
-             fwd=None, bwd=None, tag=""):
+             fwd=None, bwd=None, tag="", arena=None):
     from dctn_amd.eps_plus_linear import _EpsLinearHeadFunction, _LinearHeadFunction
 
     logits, dcore, dw, db, _ = oracle or head_oracle(core, x, w, bias, g)
-    cd, wd, bd = (t.to(dtype).to(DEV).requires_grad_(True) for t in (core, w, bias))
+    cd, wd, bd = (on_dev(t.to(dtype), arena).requires_grad_(True) for t in (core, w, bias))
     xd = x.to(dtype).to(DEV)
     if strided:
         xd = strided_copy(xd)
+    xd = on_dev(xd, arena)
     saved = EPL.FUSED_HEAD_FWD, EPL.BLOCKED_FEATURES
     EPL.FUSED_HEAD_FWD, EPL.BLOCKED_FEATURES = fused_fwd, blocked
     try:
@@ -302,7 +317,7 @@ def run_head(core, x, w, bias, g, dtype, *, fused=True, fused_fwd=True, blocked=
         else:
             out = _LinearHeadFunction.apply(eps(cd, xd).reshape(x.shape[1], -1), wd, bd)
         kf = dctn_amd.last_kernel()
-        out.backward(g.to(dtype).to(DEV))
+        out.backward(on_dev(g.to(dtype), arena))
         kb = dctn_amd.last_kernel()
     finally:
         EPL.FUSED_HEAD_FWD, EPL.BLOCKED_FEATURES = saved
@@ -372,17 +387,21 @@ def test_head_bf16_cfg2_batches(B, mode):
 @pytest.mark.parametrize("B,F,Cout", [(1024, 2704, 10), (37, 3176, 10), (5, 64, 3), (130, 200, 16), (128, 3174, 10),
                                       (37, 201, 10), (5, 7, 3), (70, 1000, 1)])
 def test_linear_head(B, F, Cout, dtype):
+    run_linear_head(B, F, Cout, dtype)
+
+
+def run_linear_head(B, F, Cout, dtype, arena=None):
     from dctn_amd.eps_plus_linear import _LinearHeadFunction
 
     feat = X.small_ints((B, F), B + F, 8) * (0.5 if dtype != torch.bfloat16 else 1.0)
     w, bias, g = X.head_operands(Cout, F, B, B * F)
     fa, wa, ga = X.to_grid(feat).abs(), w.abs(), g.abs()
     X.check_budget({"out": fa @ wa.T + bias.abs(), "dFeat": ga @ wa, "dW": ga.T @ fa, "dBias": ga.sum(0)}, ACC[dtype])
-    fd, wd, bd = (t.to(dtype).to(DEV).requires_grad_(True) for t in (feat, w, bias))
+    fd, wd, bd = (on_dev(t.to(dtype), arena).requires_grad_(True) for t in (feat, w, bias))
     out = _LinearHeadFunction.apply(fd, wd, bd)
     kf = dctn_amd.last_kernel()
     assert kf == ("linear_head_fwd_mfma" if dtype == torch.bfloat16 and F % 8 == 0 else "linear_head_fwd_generic")
-    out.backward(g.to(dtype).to(DEV))
+    out.backward(on_dev(g.to(dtype), arena))
     kb = dctn_amd.last_kernel()
     assert kb == ("linear_head_bwd" if kf == "linear_head_fwd_mfma" else "linear_head_bwd_generic"), kb
     X.assert_exact(out, feat @ w.T + bias, dtype, ("sample", "class"), f"out [{kf}]")
@@ -425,14 +444,19 @@ def check_sbs(y, dx, dcores, want, gr, dtype, tag):
             X.assert_exact(gc, wc, dtype, ("o", "l", "r") + ("q",) * (wc.ndim - 3), f"{tag} dCore{i}")
 
 
-def sbs_bwd_recompute(m, xd, dy):
+def sbs_bwd_recompute(m, xd, dy, arena=None):
     """The backward without the forward's saved states (`dctn_convsbs_bwd`: the states are recomputed)."""
     plan = CS._plan(m.spec)
     C, B, H, W, q = xd.shape
     code = L.dtype_code(xd) | CS._sbs_flags
     cores = [c.detach().contiguous() for c in m.cores]
-    dx = torch.empty((C, B, H, W, q), dtype=xd.dtype, device=DEV)
-    dcores = [torch.empty_like(c) for c in cores]
+    arena = arena if arena is not None else G.current()
+    if arena is None:
+        dx = torch.empty((C, B, H, W, q), dtype=xd.dtype, device=DEV)
+        dcores = [torch.empty_like(c) for c in cores]
+    else:   # the outputs of this direct library call guarded and poisoned like the host modules' own
+        dx = arena.empty((C, B, H, W, q), xd.dtype, DEV)
+        dcores = [arena.empty_like(c) for c in cores]
     ws = L.workspace(CS._workspace_bytes(plan, B, H, W, code, 1), DEV)
     L.check(L.lib().dctn_convsbs_bwd(xd.data_ptr(), L.strides5(xd), L.ptr_array(cores), dy.contiguous().data_ptr(), dx.data_ptr(),
                                      L.ptr_array(dcores), plan.n, plan.outs, plan.bonds, plan.ph, plan.pw, C, B, H, W, q,
@@ -441,7 +465,7 @@ def sbs_bwd_recompute(m, xd, dy):
 
 
 def run_sbs(spec, B, H, W, dtype, seed, *, fwd=None, bwd=None, strided=False, x_grad=True, core_grad=True, ctx=None,
-            recompute=True, p2=0.125, two_hot=True, tag=""):
+            recompute=True, p2=0.125, two_hot=True, tag="", arena=None):
     cores, x, dy, pos = sbs_operands(spec, B, H, W, dtype, seed, p2, two_hot)
     want, gr, report = sbs_oracle(cores, x, dy, pos, dtype)
     m = ConvSBS(spec).to(DEV).to(dtype)
@@ -452,18 +476,18 @@ def run_sbs(spec, B, H, W, dtype, seed, *, fwd=None, bwd=None, strided=False, x_
     xd = x.to(dtype).to(DEV)
     if strided:
         xd = strided_copy(xd)
-    xd.requires_grad_(x_grad)
+    xd = on_dev(xd, arena).requires_grad_(x_grad)
     with (ctx() if ctx else contextlib.nullcontext()):
         y = m(xd)
         kf = dctn_amd.last_kernel()
-        y.backward(dy.to(dtype).to(DEV))
+        y.backward(on_dev(dy.to(dtype), arena))
         kb = dctn_amd.last_kernel()
         assert fwd is None or kf == fwd, f"{tag}: forward ran {kf}, expected {fwd}"
         assert bwd is None or kb == bwd, f"{tag}: backward ran {kb}, expected {bwd}"
         check_sbs(y, xd.grad if x_grad else None, [c.grad for c in m.cores] if core_grad else [], want, gr, dtype,
                   f"{tag} [{kf} / {kb}]")
         if recompute and x_grad and core_grad:
-            dx2, dc2 = sbs_bwd_recompute(m, xd.detach(), dy.to(dtype).to(DEV))
+            dx2, dc2 = sbs_bwd_recompute(m, xd.detach(), on_dev(dy.to(dtype), arena), arena)
             kr = dctn_amd.last_kernel()
             assert bwd is None or kr == bwd, f"{tag}: recomputing backward ran {kr}, expected {bwd}"
             check_sbs(y, dx2, dc2, want, gr, dtype, f"{tag} recomputed states [{kr}]")
@@ -541,6 +565,10 @@ def test_convsbs_wide(name):
 @pytest.mark.parametrize("bond,C,q,outs_a,outs_b,B,H,W", MANY_CASES)
 def test_many_convsbs(bond, C, q, outs_a, outs_b, B, H, W):
     """ManyConvSBS: two nine-core strings in one launch each way, dX summed over the strings by the kernel."""
+    run_many_convsbs(bond, C, q, outs_a, outs_b, B, H, W)
+
+
+def run_many_convsbs(bond, C, q, outs_a, outs_b, B, H, W, arena=None):
     specs = (tuple(SBSSpecCore(Pos2D(h, w), o) for (h, w), o in zip(SNAKE9, outs_a)),
              tuple(SBSSpecCore(Pos2D(h, w), o) for (h, w), o in zip(SNAKE9B, outs_b)))
     many = ManyConvSBS(C, q, bond, False, specs).to(DEV)
@@ -561,11 +589,11 @@ def test_many_convsbs(bond, C, q, outs_a, outs_b, B, H, W):
         dx_sum += gr[0]
         dys.append(dy)
     X.check_budget({"dx summed over the strings": mags_dx}, torch.float32)
-    xd = x.float().to(DEV).requires_grad_(True)
+    xd = on_dev(x.float(), arena).requires_grad_(True)
     fam = "band" if bond > 4 else "reg"
     ya, yb = many(xd)
     assert dctn_amd.last_kernel() == f"convsbs_many_fwd_{fam}_f32"
-    ((ya * dys[0].float().to(DEV)).sum() + (yb * dys[1].float().to(DEV)).sum()).backward()
+    ((ya * on_dev(dys[0].float(), arena)).sum() + (yb * on_dev(dys[1].float(), arena)).sum()).backward()
     assert dctn_amd.last_kernel() == f"convsbs_many_bwd_{fam}_f32"
     for string, y, (cores, want, gr) in zip(many.strings, (ya, yb), wants):
         check_sbs(y, None, [c.grad for c in string.cores], want, gr, torch.float32, f"many {fam}")
@@ -573,7 +601,7 @@ def test_many_convsbs(bond, C, q, outs_a, outs_b, B, H, W):
 
 
 # ------------------------------------------------------------------------------------------------ determinism and replay
-def _replay_case(which):
+def _replay_case(which, arena=None):
     """(run: () -> list of results, want: list of float64 expected values, dtype) for a captured forward + backward."""
     if which.startswith("eps"):
         dtype, C, K, Q, O, B, H, W = {"eps_generic_q3": (torch.float32, 1, 2, 3, 3, 5, 6, 6),
@@ -581,9 +609,9 @@ def _replay_case(which):
                                       "eps_q2reg_bf16": (torch.bfloat16, 1, 3, 2, 4, 37, 12, 12)}[which]
         core, x, dy = eps_operands(C, K, Q, O, B, H, W, dtype, seed=7)
         want = [R.eps_4step(core, x)] + R.grads(R.eps_4step, [core, x], dy)[::-1]
-        xd = x.to(dtype).to(DEV).requires_grad_(True)
-        cd = core.to(dtype).to(DEV).requires_grad_(True)
-        g = dy.to(dtype).to(DEV)
+        xd = on_dev(x.to(dtype), arena).requires_grad_(True)
+        cd = on_dev(core.to(dtype), arena).requires_grad_(True)
+        g = on_dev(dy.to(dtype), arena)
         fn = eps_one_by_one if which == "eps_generic_q3" else eps
 
         def run():
@@ -596,8 +624,8 @@ def _replay_case(which):
         core, x, w, bias, g = head_operands(1, 3, 28, 28, 64, 4, 10, torch.bfloat16, seed=64, two_hot=False)
         logits, dcore, dw, db, _ = head_oracle(core, x, w, bias, g, closed_form=True)
         from dctn_amd.eps_plus_linear import _EpsLinearHeadFunction
-        cd, wd, bd = (t.to(torch.bfloat16).to(DEV).requires_grad_(True) for t in (core, w, bias))
-        xd, gd = x.to(torch.bfloat16).to(DEV), g.to(torch.bfloat16).to(DEV)
+        cd, wd, bd = (on_dev(t.to(torch.bfloat16), arena).requires_grad_(True) for t in (core, w, bias))
+        xd, gd = on_dev(x.to(torch.bfloat16), arena), on_dev(g.to(torch.bfloat16), arena)
 
         def run():
             cd.grad = wd.grad = bd.grad = None
@@ -616,8 +644,8 @@ def _replay_case(which):
     with torch.no_grad():
         for c, v in zip(m.cores, cores):
             c.copy_(v)
-    xd = x.to(dtype).to(DEV).requires_grad_(True)
-    g = dy.to(dtype).to(DEV)
+    xd = on_dev(x.to(dtype), arena).requires_grad_(True)
+    g = on_dev(dy.to(dtype), arena)
 
     def run():
         xd.grad = None
@@ -629,12 +657,9 @@ def _replay_case(which):
     return run, [want] + list(gr), dtype
 
 
-@pytest.mark.parametrize("which", ["eps_generic_q3", "eps_bigcore_f32", "eps_q2reg_bf16", "head_bf16_cfg2", "convsbs_generic_f64",
-                                   "convsbs_mfma_lds_12", "convsbs_band_16"])
-def test_two_calls_and_graph_replays_equal_the_oracle(which):
-    """Atomics, LDS counters and split joins give the same bits every time: two eager calls and two replays of a
-    captured graph (result buffers dirtied in between) all equal the oracle."""
-    run, want, dtype = _replay_case(which)
+def two_eager_calls(which, arena=None):
+    """The eager half of the test below: two calls in a row, each equal to the oracle; returns (run, check) for the replays."""
+    run, want, dtype = _replay_case(which, arena)
 
     def check(got, label):
         for i, (gt, wt) in enumerate(zip(got, want)):
@@ -642,6 +667,18 @@ def test_two_calls_and_graph_replays_equal_the_oracle(which):
 
     for call in range(2):
         check(run(), f"eager call {call}")
+    return run, check
+
+
+REPLAY_CASES = ["eps_generic_q3", "eps_bigcore_f32", "eps_q2reg_bf16", "head_bf16_cfg2", "convsbs_generic_f64",
+                "convsbs_mfma_lds_12", "convsbs_band_16"]
+
+
+@pytest.mark.parametrize("which", REPLAY_CASES)
+def test_two_calls_and_graph_replays_equal_the_oracle(which):
+    """Atomics, LDS counters and split joins give the same bits every time: two eager calls and two replays of a
+    captured graph (result buffers dirtied in between) all equal the oracle."""
+    run, check = two_eager_calls(which)
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):

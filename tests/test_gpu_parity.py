@@ -22,6 +22,7 @@ from dctn_amd.epses_composition import contract_with_input
 from dctn_amd.logmatmulexp import logmatmulexp, logmatmulexp_batched, logmatmulexp_fold, logmatmulexp_lowmem
 from dctn_amd.pos2d import Pos2D
 from oracle import ref_cpu as R
+from tests.guarded_buffers import guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -345,13 +346,14 @@ def test_convsbs_forward_reports_whether_it_wrote_the_saved_states():
         else:
             assert dctn_amd.last_kernel() == "convsbs_fwd_generic" and bool((states == 0xFF).all())   # untouched
         del states
-        torch.empty(nstates + (1 << 20), dtype=torch.uint8, device=DEV).fill_(0xFF)   # poison what the module allocates next
-        y = m(x)
+        with guarded(fill=0xFF) as arena:   # what the module allocates (the states, of exactly the queried size) is poisoned
+            y = m(x)
+            dy = torch.randn_like(y)
+            y.backward(dy)
+        arena.check()
         cores64 = [c.detach().cpu().double() for c in m.cores]
         want = R.convsbs_forward(cores64, pos, x.detach().cpu().double())
         assert close(y, want, torch.float32)
-        dy = torch.randn_like(y)
-        y.backward(dy)
         gr = R.grads(lambda xx, *cc: R.convsbs_forward(cc, pos, xx), [x.detach().cpu().double()] + cores64, dy.cpu().double())
         assert close(x.grad, gr[0], torch.float32)
         for c, gc in zip(m.cores, gr[1:]):
@@ -566,9 +568,10 @@ def test_eps_f32_bigcore_saved_gemm_result(C, B, H, W, Q, K, O):
         y.backward(dev(dy0, torch.float32))
         return y.detach(), x.grad, core.grad, fwd, dctn_amd.last_kernel()
 
-    torch.empty(nsaved + (1 << 20), dtype=torch.uint8, device=DEV).fill_(0xFF)   # poison what the allocator hands out next
-    y1, dx1, dc1, f1, b1 = run(True)
-    y0, dx0, dc0, f0, b0 = run(False)
+    with guarded(fill=0xFF) as arena:   # the kept buffer, the outputs and the workspaces poisoned, guarded, exactly sized
+        y1, dx1, dc1, f1, b1 = run(True)
+        y0, dx0, dc0, f0, b0 = run(False)
+    arena.check()
     assert f1 == "eps_fwd_mfma_bigcore_f32_saving" and b1 == "eps_bwd_mfma_bigcore_f32_savedz", (f1, b1)
     f32 = torch.float32
     if lib.dctn_eps_family(C, B, H, W, Q, K, O, _lib.F32, 0) == 4:

@@ -12,6 +12,7 @@ from dctn_amd import _lib as L
 from dctn_amd.eps import _f32_through_bf16, eps, keep_gemm_result
 from oracle import ref_cpu as R
 from tests import exact_inputs as X
+from tests import guarded_buffers as G
 
 pytestmark = pytest.mark.gpu
 
@@ -59,12 +60,19 @@ def normwise(got, want):
     return float((got.detach().cpu().double() - want).norm() / want.norm())
 
 
-def _run(core, x, dy, need_dx=True):
-    xd = x.to(DEV).requires_grad_(need_dx)
-    cd = core.to(DEV).requires_grad_(True)
+def _place(t, arena=None):
+    """On the device; inside a guarded allocation under an arena of tests/guarded_buffers.py (given, or the active one)."""
+    t = t.to(DEV)
+    arena = arena if arena is not None else G.current()
+    return t if arena is None else arena.place(t)
+
+
+def _run(core, x, dy, need_dx=True, arena=None):
+    xd = _place(x, arena).requires_grad_(need_dx)
+    cd = _place(core, arena).requires_grad_(True)
     y = eps(cd, xd)
     kf = dctn_amd.last_kernel()
-    y.backward(dy.to(DEV))
+    y.backward(_place(dy, arena))
     kb = dctn_amd.last_kernel()
     return y.detach(), (xd.grad.clone() if need_dx else None), cd.grad.clone(), kf, kb
 
