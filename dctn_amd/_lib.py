@@ -22,6 +22,9 @@ OPT_F32_PREFER_HALVES, OPT_SMALL_CHUNKS, OPT_MAIN_KERNEL_ONLY, OPT_GENERIC_KERNE
 OPT_HEAD_FEATURES_BLOCKED4 = 1 << 12   # dctn_eps_head_fwd / _bwd only: sample-blocked feature layout
 ERR_BAD_SHAPE, ERR_BAD_DTYPE, ERR_UNSUPPORTED, ERR_WORKSPACE, ERR_LAUNCH, ERR_NULL = -1, -2, -3, -4, -5, -6
 SAVED, PARTIAL = 1, 2   # positive success codes (include/dctn_amd.h)
+# what dctn_eps_family answers (DCTN_EPS_FAMILY_*; -1: the shape or policy is invalid)
+(EPS_FAMILY_GENERIC, EPS_FAMILY_Q2REG, EPS_FAMILY_BIGCORE_F32, EPS_FAMILY_HALVES, EPS_FAMILY_Q2REG_F32,
+ EPS_FAMILY_BIGCORE_BF16X3) = range(6)
 SBS_MATRIX_CORE_SWEEP = 1 << 8   # OR-ed into the dtype argument of the dctn_convsbs_* calls
 SBS_WIDE_SWEEP = 1 << 9   # likewise: the backward on the wide family (convsbs_wide.hip) for any string it covers
 

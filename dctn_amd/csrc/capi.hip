@@ -4,6 +4,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <algorithm>
 #include <atomic>
 
 // The library's process-wide state.  g_last_kernel, its only mutable global: a diagnostic pointer to a string literal
@@ -86,9 +87,134 @@ int dctn_zero_async(void* ptr, size_t bytes, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? DCTN_OK : DCTN_ERR_LAUNCH;
 }
 
+static bool dtype_ok(int dtype) { return dtype == DCTN_F32 || dtype == DCTN_F64 || dtype == DCTN_BF16; }
+
+static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// the EpsP of a query: no tensor, so the strides of a contiguous-like dummy
+static bool eps_query_params(EpsP& p, int C, int B, int H, int W, int Q, int K, int O, int policy) {
+  const int64_t dummy[5] = {0, 0, 0, 0, 1};
+  return eps_fill_params(p, dummy, C, B, H, W, Q, K, O, policy) == DCTN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- EPS routing
+// Which family takes a (shape, dtype, policy), decided in ONE place (DESIGN.md "EPS routing").  Every entry point and
+// every query below reads the route; no other function asks a family whether it covers a shape.
+enum { EPS_NO_FAMILY = -1 };
+enum EpsSavedLayout {
+  EPS_SAVED_NONE = 0,   // the family keeps nothing
+  EPS_SAVED_Z,       // large-core families: the GEMM result Z, row-quad-major
+  EPS_SAVED_HALVES   // two-halves path: P0 | P1 | Z
+};
+
+struct EpsRoute {
+  int precision;        // what every family but bf16x3 is called with: DCTN_PREC_SPLIT runs them as DCTN_PREC_EXACT
+  // the forward: the family that takes the call (fwd[0]: what dctn_eps_family answers), then what a run-time decline of
+  // a launcher falls to, in order; EPS_NO_FAMILY ends the list.  A forward that was handed room for the saved buffer
+  // starts at fwd[fwd_saving]
+  int fwd[6], fwd_saving;
+  int saved_layout;     // how the backward of this shape reads a saved buffer; a forward family keeps only in this layout
+  size_t saved_bytes;   // its size; 0: the shape keeps nothing
+  // the backward: a register-resident family computes dCore in a launch of its own at the head of the workspace
+  // (EPS_NO_FAMILY: none), without / with a saved buffer; `bwd` computes dX and what is left, in fall-through order
+  int dcore_reg, dcore_reg_saved;
+  int bwd[4];
+};
+
+static void eps_list(int* out, int a, int b = EPS_NO_FAMILY, int c = EPS_NO_FAMILY) {
+  out[0] = a, out[1] = b, out[2] = c, out[3] = EPS_NO_FAMILY;
+}
+
+static int eps_saved_layout_of(int family) {
+  if (family == DCTN_EPS_FAMILY_BIGCORE_F32 || family == DCTN_EPS_FAMILY_BIGCORE_BF16X3) return EPS_SAVED_Z;
+  return family == DCTN_EPS_FAMILY_HALVES ? EPS_SAVED_HALVES : EPS_SAVED_NONE;
+}
+
+static EpsRoute eps_route(const EpsP& p, int dtype, int policy) {
+  const int precision = policy & DCTN_PREC_MASK;
+  EpsRoute r = {};   // (nothing saved, the forward with room starts where the plain one does)
+  r.precision = precision == DCTN_PREC_SPLIT ? DCTN_PREC_EXACT : precision;
+  r.dcore_reg = r.dcore_reg_saved = EPS_NO_FAMILY;
+  if (p.opts & DCTN_OPT_GENERIC_KERNELS) {   // short-circuits everything
+    eps_list(r.fwd, DCTN_EPS_FAMILY_GENERIC);
+    eps_list(r.bwd, DCTN_EPS_FAMILY_GENERIC);
+    return r;
+  }
+  const bool q2reg = eps_mfma_covers(p, dtype, r.precision), q2f32 = eps_q2f32_covers(p, dtype, r.precision);
+  const bool halves = eps_halves_wanted(p, dtype);
+  // DCTN_OPT_F32_PREFER_HALVES sends float32 shapes that both exact families cover to the two-halves path
+  const bool prefer_halves = (p.opts & DCTN_OPT_F32_PREFER_HALVES) && dtype == DCTN_F32 && halves;
+  const bool bigcore = eps_bigcore_covers(p, dtype, r.precision) && !prefer_halves;
+  // DCTN_PREC_SPLIT: the bf16x3 large-core family takes the float32 shapes it plans among those that run on the exact
+  // large-core family under DCTN_PREC_EXACT; every other call runs as under DCTN_PREC_EXACT.  It never runs half a call:
+  // nothing follows it in the lists
+  if (precision == DCTN_PREC_SPLIT && bigcore && !q2reg && !q2f32 && eps_bf16x3_covers(p, dtype, precision)) {
+    eps_list(r.fwd, DCTN_EPS_FAMILY_BIGCORE_BF16X3);
+    eps_list(r.bwd, DCTN_EPS_FAMILY_BIGCORE_BF16X3);
+    r.saved_layout = EPS_SAVED_Z;
+    r.saved_bytes = eps_bf16x3_saved_bytes(p, dtype, precision);   // (the exact family's layout and size)
+    return r;
+  }
+  // the forward walks this order from the first family that covers the shape; the launchers before it would decline
+  const int order[5] = {DCTN_EPS_FAMILY_Q2REG, DCTN_EPS_FAMILY_Q2REG_F32, DCTN_EPS_FAMILY_BIGCORE_F32, DCTN_EPS_FAMILY_HALVES,
+                        DCTN_EPS_FAMILY_GENERIC};
+  const bool covers[5] = {q2reg, q2f32, bigcore, halves, true};
+  r.saved_layout = bigcore ? EPS_SAVED_Z : EPS_SAVED_HALVES;
+  r.saved_bytes = bigcore ? eps_bigcore_saved_bytes(p, dtype, r.precision) : eps_halves_saved_bytes(p, dtype);
+  int n = 0;
+  for (int i = 0; i < 5; ++i)
+    if ((n > 0 || covers[i]) && !(order[i] == DCTN_EPS_FAMILY_BIGCORE_F32 && prefer_halves)) r.fwd[n++] = order[i];
+  r.fwd[n] = EPS_NO_FAMILY;
+  // the register-resident exact-f32 family keeps nothing for a backward: a training forward whose caller brought room for
+  // Z skips it and runs on the large-core family, whose backward reads Z
+  r.fwd_saving = r.fwd[0] == DCTN_EPS_FAMILY_Q2REG_F32 && r.saved_layout == EPS_SAVED_Z && r.saved_bytes > 0;
+  // dCore of the register-resident shapes on their own family (the exact-f32 one only where the forward ran there too:
+  // without a saved buffer); dX, and dCore of every other shape, on the family whose layout the saved buffer has.  A
+  // two-halves launcher that declines falls to the large-core launchers, which take what they plan, then the generic ones
+  r.dcore_reg = q2reg ? DCTN_EPS_FAMILY_Q2REG : q2f32 ? DCTN_EPS_FAMILY_Q2REG_F32 : EPS_NO_FAMILY;
+  r.dcore_reg_saved = q2reg ? DCTN_EPS_FAMILY_Q2REG : EPS_NO_FAMILY;
+  if (r.saved_layout == EPS_SAVED_HALVES)
+    eps_list(r.bwd, DCTN_EPS_FAMILY_HALVES, DCTN_EPS_FAMILY_BIGCORE_F32, DCTN_EPS_FAMILY_GENERIC);
+  else
+    eps_list(r.bwd, DCTN_EPS_FAMILY_BIGCORE_F32, DCTN_EPS_FAMILY_GENERIC);
+  return r;
+}
+
+// one family's forward; keep: room for what the family keeps for the backward, or NULL
+static int eps_fwd_family(int family, const void* x, const void* core, void* out, void* ws, size_t ws_bytes, const EpsP& p,
+                          int dtype, const EpsRoute& r, hipStream_t st, void* keep) {
+  switch (family) {
+    case DCTN_EPS_FAMILY_BIGCORE_BF16X3: return eps_fwd_bf16x3(x, core, out, ws, ws_bytes, p, dtype, DCTN_PREC_SPLIT, st, keep);
+    case DCTN_EPS_FAMILY_Q2REG: return eps_fwd_mfma(x, core, out, p, dtype, r.precision, st);
+    case DCTN_EPS_FAMILY_Q2REG_F32: return eps_fwd_q2f32(x, core, out, p, dtype, r.precision, st);
+    case DCTN_EPS_FAMILY_BIGCORE_F32: return eps_fwd_bigcore(x, core, out, ws, ws_bytes, p, dtype, r.precision, st, keep);
+    case DCTN_EPS_FAMILY_HALVES: return eps_fwd_halves(x, core, out, ws, ws_bytes, p, dtype, st, keep);
+  }
+  return eps_fwd_generic(x, core, out, p, dtype, st);
+}
+
+// ---------------------------------------------------------------------------------------------- fused head
+// The prologue of the two head calls: the feature-layout bit is the head's own (eps_fill_params refuses it), so it is
+// stripped for the shape and set again for the launchers
+static int eps_head_params(EpsP& p, const int64_t x_strides[5], int C, int B, int H, int W, int Q, int K, int O, int Cout,
+                           int dtype, int policy) {
+  if (!dtype_ok(dtype)) return DCTN_ERR_BAD_DTYPE;
+  if (Cout < 1) return DCTN_ERR_BAD_SHAPE;
+  const int blk = policy & DCTN_OPT_HEAD_FEATURES_BLOCKED4;
+  const int rc = eps_fill_params(p, x_strides, C, B, H, W, Q, K, O, policy & ~blk);
+  p.opts |= blk;
+  return rc;
+}
+
+// the head's two families in order: the bf16 register family, then (given its return code: whether) the float32 one,
+// which knows row-major features only
+static bool eps_head_next(const EpsP& p, int rc) {
+  return rc == DCTN_ERR_UNSUPPORTED && !(p.opts & DCTN_OPT_HEAD_FEATURES_BLOCKED4);
+}
+
 extern "C" {
 
-int dctn_version(void) { return 500; }   // round 5: register-resident exact-f32 EPS family (eps_q2f32.hip), fused head both ways in float32
+int dctn_version(void) { return 500; }   // callers only check that a library answers (>= 100)
 
 const char* dctn_last_kernel(void) { return g_last_kernel.load(std::memory_order_relaxed); }
 
@@ -112,47 +238,22 @@ const char* dctn_strerror(int code) {
   return "unknown error";
 }
 
-// DCTN_OPT_F32_PREFER_HALVES sends float32 shapes that both exact families cover to the two-halves path
-static bool f32_prefers_halves(const EpsP& p, int dtype) {
-  return (p.opts & DCTN_OPT_F32_PREFER_HALVES) && dtype == DCTN_F32 && eps_halves_wanted(p, dtype);
-}
-
-static bool dtype_ok(int dtype) { return dtype == DCTN_F32 || dtype == DCTN_F64 || dtype == DCTN_BF16; }
-
-// DCTN_PREC_SPLIT: the bf16x3 large-core family takes the float32 shapes it plans among those that run on the exact
-// large-core family under DCTN_PREC_EXACT (not the register-resident families' shapes, not those sent to the two-halves
-// path by DCTN_OPT_F32_PREFER_HALVES); every other call runs the existing chain as under DCTN_PREC_EXACT
-static bool bf16x3_takes(const EpsP& p, int dtype, int precision) {
-  return precision == DCTN_PREC_SPLIT && !f32_prefers_halves(p, dtype) && !eps_mfma_covers(p, dtype, DCTN_PREC_EXACT) &&
-         !eps_q2f32_covers(p, dtype, DCTN_PREC_EXACT) && eps_bigcore_covers(p, dtype, DCTN_PREC_EXACT) &&
-         eps_bf16x3_covers(p, dtype, precision);
-}
-static int chain_precision(int precision) { return precision == DCTN_PREC_SPLIT ? DCTN_PREC_EXACT : precision; }
-
+// The workspace queries answer a maximum over what the fall-through order may reach, not the first family's need.  The two
+// forward queries never looked at DCTN_OPT_GENERIC_KERNELS (they size for the families the flag bypasses); kept.
 size_t dctn_eps_fwd_workspace_bytes(int C, int B, int H, int W, int Q, int K, int O, int dtype,
                                     int policy) {
   EpsP p;
-  const int precision = policy & DCTN_PREC_MASK;
-  const int64_t dummy[5] = {0, 0, 0, 0, 1};
-  if (eps_fill_params(p, dummy, C, B, H, W, Q, K, O, policy) != DCTN_OK) return 0;
-  if (bf16x3_takes(p, dtype, precision)) return eps_fwd_bf16x3_workspace(p, dtype, precision) + 256;
-  const size_t a = eps_fwd_bigcore_workspace(p, dtype, chain_precision(precision)), b = eps_fwd_halves_workspace(p, dtype);
-  return (a > b ? a : b) + 256;
+  if (!eps_query_params(p, C, B, H, W, Q, K, O, policy & ~DCTN_OPT_GENERIC_KERNELS)) return 0;
+  const EpsRoute r = eps_route(p, dtype, policy);
+  if (r.fwd[0] == DCTN_EPS_FAMILY_BIGCORE_BF16X3) return eps_fwd_bf16x3_workspace(p, dtype, policy & DCTN_PREC_MASK) + 256;
+  const size_t a = eps_fwd_bigcore_workspace(p, dtype, r.precision), b = eps_fwd_halves_workspace(p, dtype);
+  return std::max(a, b) + 256;
 }
 
 int dctn_eps_family(int C, int B, int H, int W, int Q, int K, int O, int dtype, int policy) {
   EpsP p;
-  int precision = policy & DCTN_PREC_MASK;
-  const int64_t dummy[5] = {0, 0, 0, 0, 1};
-  if (!dtype_ok(dtype) || eps_fill_params(p, dummy, C, B, H, W, Q, K, O, policy) != DCTN_OK) return -1;
-  if (p.opts & DCTN_OPT_GENERIC_KERNELS) return DCTN_EPS_FAMILY_GENERIC;
-  if (bf16x3_takes(p, dtype, precision)) return DCTN_EPS_FAMILY_BIGCORE_BF16X3;
-  precision = chain_precision(precision);
-  if (eps_mfma_covers(p, dtype, precision)) return DCTN_EPS_FAMILY_Q2REG;
-  if (eps_q2f32_covers(p, dtype, precision)) return DCTN_EPS_FAMILY_Q2REG_F32;
-  if (eps_bigcore_covers(p, dtype, precision) && !f32_prefers_halves(p, dtype)) return DCTN_EPS_FAMILY_BIGCORE_F32;
-  if (eps_halves_wanted(p, dtype)) return DCTN_EPS_FAMILY_HALVES;
-  return DCTN_EPS_FAMILY_GENERIC;
+  if (!dtype_ok(dtype) || !eps_query_params(p, C, B, H, W, Q, K, O, policy)) return -1;
+  return eps_route(p, dtype, policy).fwd[0];
 }
 
 // forward with an optional buffer for what the backward would otherwise recompute; *kept = 1 when it was written
@@ -163,49 +264,21 @@ static int eps_fwd_impl(const void* x, const int64_t x_strides[5], const void* c
   if (!x || !core || !out || !x_strides) return DCTN_ERR_NULL;
   if (!dtype_ok(dtype)) return DCTN_ERR_BAD_DTYPE;
   EpsP p;
-  int precision = policy & DCTN_PREC_MASK;
   int rc = eps_fill_params(p, x_strides, C, B, H, W, Q, K, O, policy);
   if (rc != DCTN_OK) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (p.opts & DCTN_OPT_GENERIC_KERNELS) return eps_fwd_generic(x, core, out, p, dtype, st);
-  if (bf16x3_takes(p, dtype, precision)) {
-    // the kept GEMM result has the exact family's row-quad-major layout and size (dctn_eps_saved_bytes)
-    const size_t zb = saved ? eps_bf16x3_saved_bytes(p, dtype, precision) : 0;
-    const bool keep = zb > 0 && saved_bytes >= zb;
-    rc = eps_fwd_bf16x3(x, core, out, workspace, workspace_bytes, p, dtype, precision, st, keep ? saved : nullptr);
+  const EpsRoute r = eps_route(p, dtype, policy);
+  const bool room = saved && r.saved_bytes > 0 && saved_bytes >= r.saved_bytes;
+  for (const int* f = r.fwd + (room ? r.fwd_saving : 0);; ++f) {
+    // a family keeps the buffer only where the backward will read it as ITS layout: a shape the large-core family claims
+    // but then declines falls to the two-halves path with nothing kept
+    const bool keep = room && eps_saved_layout_of(*f) == r.saved_layout;
+    rc = eps_fwd_family(*f, x, core, out, workspace, workspace_bytes, p, dtype, r, (hipStream_t)stream, keep ? saved : nullptr);
     if (rc == DCTN_OK && keep && kept) *kept = 1;
-    return rc;
+    // run-time declines: the runtime refuses a launcher's LDS opt-in, a bf16 core is not 16-byte aligned, the two-halves
+    // path has too little workspace
+    const bool declined = rc == DCTN_ERR_UNSUPPORTED || (rc == DCTN_ERR_WORKSPACE && *f == DCTN_EPS_FAMILY_HALVES);
+    if (!declined || f[1] == EPS_NO_FAMILY) return rc;
   }
-  precision = chain_precision(precision);
-  rc = eps_fwd_mfma(x, core, out, p, dtype, precision, st);
-  if (rc != DCTN_ERR_UNSUPPORTED) return rc;
-  // the register-resident exact-f32 family keeps nothing for a backward: a training forward whose input needs a gradient
-  // (the caller brought a buffer for the GEMM result) stays on the large-core family, whose backward reads that buffer
-  const bool wants_saved = saved && saved_bytes > 0 && saved_bytes >= eps_bigcore_saved_bytes(p, dtype, precision) &&
-                           eps_bigcore_saved_bytes(p, dtype, precision) > 0 && !f32_prefers_halves(p, dtype);
-  if (!wants_saved) {
-    rc = eps_fwd_q2f32(x, core, out, p, dtype, precision, st);
-    if (rc != DCTN_ERR_UNSUPPORTED) return rc;
-  }
-  if (!f32_prefers_halves(p, dtype)) {
-    const size_t zb = saved ? eps_bigcore_saved_bytes(p, dtype, precision) : 0;
-    const bool keep = zb > 0 && saved_bytes >= zb;
-    rc = eps_fwd_bigcore(x, core, out, workspace, workspace_bytes, p, dtype, precision, st, keep ? saved : nullptr);
-    if (rc == DCTN_OK && keep && kept) *kept = 1;
-    if (rc != DCTN_ERR_UNSUPPORTED) return rc;
-  }
-  {
-    // the two-halves family may keep the buffer only where the backward will read it as ITS layout (P0 | P1 | Z): the
-    // same routing as dctn_eps_saved_bytes and eps_bwd_impl.  A shape the large-core family claims but then declines
-    // falls through to here with nothing kept (its backward would read the buffer as row-quad-major Z).
-    const bool halves_route = dtype == DCTN_F64 || !eps_bigcore_covers(p, dtype, precision) || f32_prefers_halves(p, dtype);
-    const size_t hb = (saved && halves_route) ? eps_halves_saved_bytes(p, dtype) : 0;
-    const bool keep = hb > 0 && saved_bytes >= hb;
-    rc = eps_fwd_halves(x, core, out, workspace, workspace_bytes, p, dtype, st, keep ? saved : nullptr);
-    if (rc == DCTN_OK && keep && kept) *kept = 1;
-    if (rc != DCTN_ERR_UNSUPPORTED && rc != DCTN_ERR_WORKSPACE) return rc;
-  }
-  return eps_fwd_generic(x, core, out, p, dtype, st);
 }
 
 int dctn_eps_fwd(const void* x, const int64_t x_strides[5], const void* core, void* out,
@@ -217,15 +290,11 @@ int dctn_eps_fwd(const void* x, const int64_t x_strides[5], const void* core, vo
 
 size_t dctn_eps_saved_bytes(int C, int B, int H, int W, int Q, int K, int O, int dtype, int policy) {
   EpsP p;
-  int precision = policy & DCTN_PREC_MASK;
-  const int64_t dummy[5] = {0, 0, 0, 0, 1};
-  if (!dtype_ok(dtype) || eps_fill_params(p, dummy, C, B, H, W, Q, K, O, policy) != DCTN_OK) return 0;
-  if (p.opts & DCTN_OPT_GENERIC_KERNELS) return 0;
-  if (bf16x3_takes(p, dtype, precision)) return eps_bf16x3_saved_bytes(p, dtype, precision);
-  precision = chain_precision(precision);
-  if (eps_mfma_covers(p, dtype, precision)) return 0;
-  if (eps_bigcore_covers(p, dtype, precision) && !f32_prefers_halves(p, dtype)) return eps_bigcore_saved_bytes(p, dtype, precision);
-  return eps_halves_saved_bytes(p, dtype);
+  if (!dtype_ok(dtype) || !eps_query_params(p, C, B, H, W, Q, K, O, policy)) return 0;
+  const EpsRoute r = eps_route(p, dtype, policy);
+  // a shape of the bf16 register family keeps nothing: its forward has no GEMM result.  (Only after a run-time decline of
+  // that launcher does its forward reach a family that keeps, for a caller that brought a buffer all the same.)
+  return r.fwd[0] == DCTN_EPS_FAMILY_Q2REG ? 0 : r.saved_bytes;
 }
 
 int dctn_eps_fwd_save(const void* x, const int64_t x_strides[5], const void* core, void* out, void* saved,
@@ -237,14 +306,10 @@ int dctn_eps_fwd_save(const void* x, const int64_t x_strides[5], const void* cor
   return rc != DCTN_OK ? rc : (kept ? DCTN_SAVED : DCTN_OK);
 }
 
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 size_t dctn_eps_fwd_stats_workspace_bytes(int C, int B, int H, int W, int Q, int K, int O, int dtype, int policy) {
   EpsP p;
-  const int precision = policy & DCTN_PREC_MASK;
-  const int64_t dummy[5] = {0, 0, 0, 0, 1};
-  if (eps_fill_params(p, dummy, C, B, H, W, Q, K, O, policy) != DCTN_OK) return 0;
-  if (eps_mfma_covers(p, dtype, precision)) return 256;   // in-kernel epilogue: no scratch
+  if (!eps_query_params(p, C, B, H, W, Q, K, O, policy & ~DCTN_OPT_GENERIC_KERNELS)) return 0;
+  if (eps_route(p, dtype, policy).fwd[0] == DCTN_EPS_FAMILY_Q2REG) return 256;   // in-kernel epilogue: no scratch
   return align256((size_t)p.Wn * O * dtype_size(dtype)) + dctn_eps_fwd_workspace_bytes(C, B, H, W, Q, K, O, dtype, policy) + 256;
 }
 
@@ -254,12 +319,12 @@ int dctn_eps_fwd_stats(const void* x, const int64_t x_strides[5], const void* co
   if (!x || !core || !stats || !x_strides) return DCTN_ERR_NULL;
   if (!dtype_ok(dtype)) return DCTN_ERR_BAD_DTYPE;
   EpsP p;
-  const int precision = policy & DCTN_PREC_MASK;
   int rc = eps_fill_params(p, x_strides, C, B, H, W, Q, K, O, policy);
   if (rc != DCTN_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  // register-resident family: the statistics are an epilogue of the forward kernel, nothing is stored
-  rc = eps_fwd_mfma(x, core, nullptr, p, dtype, precision, st, (double*)stats);
+  // bf16 register family: the statistics are an epilogue of the forward kernel, nothing is stored.  (Like its workspace
+  // query this never looked at DCTN_OPT_GENERIC_KERNELS: the launcher is asked directly and declines other shapes.)
+  rc = eps_fwd_mfma(x, core, nullptr, p, dtype, policy & DCTN_PREC_MASK, st, (double*)stats);
   if (rc != DCTN_ERR_UNSUPPORTED) return rc;
   // other families: the slice's output goes to scratch (cache resident for the slice sizes of eps.py:126-137) and one
   // reduction pass folds it into the running sums
@@ -275,24 +340,20 @@ int dctn_eps_fwd_stats(const void* x, const int64_t x_strides[5], const void* co
 size_t dctn_eps_bwd_workspace_bytes(int C, int B, int H, int W, int Q, int K, int O, int dtype,
                                     int policy, int need_dx, int need_dcore) {
   EpsP p;
-  int precision = policy & DCTN_PREC_MASK;
-  const int64_t dummy[5] = {0, 0, 0, 0, 1};
-  if (eps_fill_params(p, dummy, C, B, H, W, Q, K, O, policy) != DCTN_OK) return 0;
-  if (!(p.opts & DCTN_OPT_GENERIC_KERNELS) && bf16x3_takes(p, dtype, precision)) {
-    const size_t a = need_dx ? eps_bwd_dfactor_bf16x3_workspace(p, dtype, precision) : 0;
-    const size_t b = need_dcore ? eps_bwd_dcore_bf16x3_workspace(p, dtype, precision) : 0;
-    return (a > b ? a : b) + 256;
+  if (!eps_query_params(p, C, B, H, W, Q, K, O, policy)) return 0;
+  const EpsRoute r = eps_route(p, dtype, policy);
+  if (r.bwd[0] == DCTN_EPS_FAMILY_BIGCORE_BF16X3) {
+    const size_t a = need_dx ? eps_bwd_dfactor_bf16x3_workspace(p, dtype, policy & DCTN_PREC_MASK) : 0;
+    const size_t b = need_dcore ? eps_bwd_dcore_bf16x3_workspace(p, dtype, policy & DCTN_PREC_MASK) : 0;
+    return std::max(a, b) + 256;
   }
-  precision = chain_precision(precision);
-  const size_t a = align256(eps_bwd_mfma_workspace(p, dtype, precision, need_dx, need_dcore)) +
-                   align256(need_dcore ? eps_bwd_q2f32_workspace(p, dtype, precision) : 0);
-  size_t b = eps_bwd_generic_workspace(p, dtype, need_dx, need_dcore);
-  const size_t c = need_dx ? eps_bwd_dfactor_bigcore_workspace(p, dtype, precision) : 0;
-  if (c > b) b = c;
-  const size_t c2 = need_dcore ? eps_bwd_dcore_bigcore_workspace(p, dtype, precision) : 0;
-  if (c2 > b) b = c2;
-  const size_t d = eps_bwd_halves_workspace(p, dtype, need_dx, need_dcore);
-  if (d > b) b = d;
+  // [register family's dCore | the rest]
+  const size_t a = align256(eps_bwd_mfma_workspace(p, dtype, r.precision, need_dx, need_dcore)) +
+                   align256(need_dcore ? eps_bwd_q2f32_workspace(p, dtype, r.precision) : 0);
+  size_t b = std::max(eps_bwd_generic_workspace(p, dtype, need_dx, need_dcore),
+                      eps_bwd_halves_workspace(p, dtype, need_dx, need_dcore));
+  if (need_dx) b = std::max(b, eps_bwd_dfactor_bigcore_workspace(p, dtype, r.precision));
+  if (need_dcore) b = std::max(b, eps_bwd_dcore_bigcore_workspace(p, dtype, r.precision));
   return a + b + 256;
 }
 
@@ -300,25 +361,21 @@ int dctn_eps_head_fwd(const void* x, const int64_t x_strides[5], const void* cor
                       const void* head_bias, void* features, void* logits, int C, int B, int H, int W, int Q, int K, int O,
                       int Cout, int dtype, int policy, void* stream) {
   if (!x || !core || !head_weight || !head_bias || !features || !logits || !x_strides) return DCTN_ERR_NULL;
-  if (!dtype_ok(dtype)) return DCTN_ERR_BAD_DTYPE;
-  if (Cout < 1) return DCTN_ERR_BAD_SHAPE;
   EpsP p;
-  const int precision = policy & DCTN_PREC_MASK;
-  const int blk = policy & DCTN_OPT_HEAD_FEATURES_BLOCKED4;
-  const int rc = eps_fill_params(p, x_strides, C, B, H, W, Q, K, O, policy & ~blk);
+  int rc = eps_head_params(p, x_strides, C, B, H, W, Q, K, O, Cout, dtype, policy);
   if (rc != DCTN_OK) return rc;
-  p.opts |= blk;
-  const int rcm = eps_head_fwd_mfma(x, core, head_weight, head_bias, features, logits, p, Cout, dtype, precision, (hipStream_t)stream);
-  if (rcm != DCTN_ERR_UNSUPPORTED || blk) return rcm;   // the float32 family writes row-major features only
-  return eps_head_fwd_q2f32(x, core, head_weight, head_bias, features, logits, p, Cout, dtype, precision, (hipStream_t)stream);
+  const int precision = policy & DCTN_PREC_MASK;
+  hipStream_t st = (hipStream_t)stream;
+  rc = eps_head_fwd_mfma(x, core, head_weight, head_bias, features, logits, p, Cout, dtype, precision, st);
+  if (!eps_head_next(p, rc)) return rc;
+  return eps_head_fwd_q2f32(x, core, head_weight, head_bias, features, logits, p, Cout, dtype, precision, st);
 }
 
 size_t dctn_eps_head_bwd_workspace_bytes(int C, int B, int H, int W, int Q, int K, int O, int Cout, int dtype,
                                          int policy) {
   EpsP p;
   const int precision = policy & DCTN_PREC_MASK;
-  const int64_t dummy[5] = {0, 0, 0, 0, 1};
-  if (eps_fill_params(p, dummy, C, B, H, W, Q, K, O, policy & ~DCTN_OPT_HEAD_FEATURES_BLOCKED4) != DCTN_OK) return 0;
+  if (!eps_query_params(p, C, B, H, W, Q, K, O, policy & ~DCTN_OPT_HEAD_FEATURES_BLOCKED4)) return 0;
   const size_t a = eps_head_bwd_mfma_workspace(p, Cout, dtype, precision), b = eps_head_bwd_q2f32_workspace(p, Cout, dtype, precision);
   return (a > b ? a : b) + 256;
 }
@@ -328,21 +385,19 @@ int dctn_eps_head_bwd(const void* x, const int64_t x_strides[5], const void* fea
                       size_t workspace_bytes, int C, int B, int H, int W, int Q, int K, int O, int Cout,
                       int dtype, int policy, void* stream) {
   if (!x || !features || !dLogits || !head_weight || !dCore || !x_strides) return DCTN_ERR_NULL;
-  if (!dtype_ok(dtype)) return DCTN_ERR_BAD_DTYPE;
-  if (Cout < 1) return DCTN_ERR_BAD_SHAPE;
   EpsP p;
-  const int precision = policy & DCTN_PREC_MASK;
-  const int blk = policy & DCTN_OPT_HEAD_FEATURES_BLOCKED4;
-  const int rc = eps_fill_params(p, x_strides, C, B, H, W, Q, K, O, policy & ~blk);
+  int rc = eps_head_params(p, x_strides, C, B, H, W, Q, K, O, Cout, dtype, policy);
   if (rc != DCTN_OK) return rc;
-  p.opts |= blk;
-  const int rcm = eps_head_bwd_mfma(x, features, dLogits, head_weight, dCore, dWeight, dBias, workspace, workspace_bytes, p,
-                                    Cout, dtype, precision, (hipStream_t)stream);
-  if (rcm != DCTN_ERR_UNSUPPORTED || blk) return rcm;   // the float32 family reads row-major features only
-  return eps_head_bwd_q2f32(x, features, dLogits, head_weight, dCore, dWeight, dBias, workspace, workspace_bytes, p, Cout,
-                            dtype, precision, (hipStream_t)stream);
+  const int precision = policy & DCTN_PREC_MASK;
+  hipStream_t st = (hipStream_t)stream;
+  rc = eps_head_bwd_mfma(x, features, dLogits, head_weight, dCore, dWeight, dBias, workspace, workspace_bytes, p, Cout, dtype,
+                         precision, st);
+  if (!eps_head_next(p, rc)) return rc;
+  return eps_head_bwd_q2f32(x, features, dLogits, head_weight, dCore, dWeight, dBias, workspace, workspace_bytes, p, Cout, dtype,
+                            precision, st);
 }
 
+// ---------------------------------------------------------------------------------------------- EPS backward
 static int eps_bwd_impl(const void* x, const int64_t x_strides[5], const void* core, const void* dY, const void* saved,
                         size_t saved_bytes, void* dX, void* dCore, void* workspace, size_t workspace_bytes, int C, int B,
                         int H, int W, int Q, int K, int O, int dtype, int policy, void* stream) {
@@ -350,77 +405,61 @@ static int eps_bwd_impl(const void* x, const int64_t x_strides[5], const void* c
   if (!dtype_ok(dtype)) return DCTN_ERR_BAD_DTYPE;
   if (!dX && !dCore) return DCTN_OK;
   EpsP p;
-  int precision = policy & DCTN_PREC_MASK;
   int rc = eps_fill_params(p, x_strides, C, B, H, W, Q, K, O, policy);
   if (rc != DCTN_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (p.opts & DCTN_OPT_GENERIC_KERNELS) return eps_bwd_generic(x, core, dY, dX, dCore, workspace, workspace_bytes, p, dtype, st);
-  if (bf16x3_takes(p, dtype, precision)) {
-    // both gradients on the bf16x3 family (dCore's slices are summed before dX uses the same workspace: stream order)
-    if (dCore) {
-      rc = eps_bwd_dcore_bf16x3(x, dY, dCore, p, dtype, precision, st, workspace, workspace_bytes);
-      if (rc != DCTN_OK) return rc;
-    }
-    if (dX) {
-      rc = eps_bwd_dx_bf16x3(x, core, dY, dX, workspace, workspace_bytes, p, dtype, precision, st, saved, saved_bytes);
-      if (rc != DCTN_OK) return rc == DCTN_ERR_UNSUPPORTED ? DCTN_ERR_LAUNCH : rc;
-    }
-    return DCTN_OK;
-  }
-  precision = chain_precision(precision);
-  // dCore on the MFMA family when it covers the shape; whatever is left goes to the generic kernels
+  const EpsRoute r = eps_route(p, dtype, policy);
   unsigned char* ws = (unsigned char*)workspace;
-  const size_t wa = align256(eps_bwd_mfma_workspace(p, dtype, precision, 0, dCore != nullptr));
-  if (dCore && wa > 0) {
-    if (!ws || workspace_bytes < wa) return DCTN_ERR_WORKSPACE;
-    rc = eps_bwd_mfma(x, core, dY, nullptr, dCore, ws, wa, p, dtype, precision, st);
-    if (rc == DCTN_OK) {
-      dCore = nullptr;
-    } else if (rc != DCTN_ERR_UNSUPPORTED) {
-      return rc;
+  size_t ws_bytes = workspace_bytes;
+  // dCore on a register-resident family, in the first (256-byte aligned) part of the workspace
+  const int reg = saved ? r.dcore_reg_saved : r.dcore_reg;
+  if (dCore && reg != EPS_NO_FAMILY) {
+    const size_t w = align256(reg == DCTN_EPS_FAMILY_Q2REG ? eps_bwd_mfma_workspace(p, dtype, r.precision, 0, 1)
+                                                           : eps_bwd_q2f32_workspace(p, dtype, r.precision));
+    if (!ws || ws_bytes < w) return DCTN_ERR_WORKSPACE;
+    rc = reg == DCTN_EPS_FAMILY_Q2REG ? eps_bwd_mfma(x, core, dY, nullptr, dCore, ws, w, p, dtype, r.precision, st)
+                                      : eps_bwd_q2f32(x, dY, dCore, ws, w, p, dtype, r.precision, st);
+    if (rc == DCTN_OK) dCore = nullptr;
+    else if (rc != DCTN_ERR_UNSUPPORTED) return rc;
+    ws += w;
+    ws_bytes -= w;
+  }
+  // dX and what is left of dCore, in the rest of the workspace
+  for (const int* f = r.bwd; dX || dCore; ++f) {
+    switch (*f) {
+      case DCTN_EPS_FAMILY_BIGCORE_BF16X3:
+        // (dCore's slices are summed before dX uses the same workspace: stream order)
+        if (dCore) {
+          rc = eps_bwd_dcore_bf16x3(x, dY, dCore, p, dtype, DCTN_PREC_SPLIT, st, ws, ws_bytes);
+          if (rc != DCTN_OK) return rc;
+        }
+        if (dX) {
+          rc = eps_bwd_dx_bf16x3(x, core, dY, dX, ws, ws_bytes, p, dtype, DCTN_PREC_SPLIT, st, saved, saved_bytes);
+          if (rc != DCTN_OK) return rc == DCTN_ERR_UNSUPPORTED ? DCTN_ERR_LAUNCH : rc;
+        }
+        return DCTN_OK;
+      case DCTN_EPS_FAMILY_HALVES:   // both gradients on the two-halves GEMM path
+        rc = eps_bwd_halves(x, core, dY, dX, dCore, ws, ws_bytes, p, dtype, st, saved, saved_bytes);
+        if (rc != DCTN_ERR_UNSUPPORTED && rc != DCTN_ERR_WORKSPACE) return rc;
+        break;
+      case DCTN_EPS_FAMILY_BIGCORE_F32:
+        if (dCore) {
+          // (its per-chunk slices use the workspace before dX does: the sum kernel is done with them by then)
+          rc = eps_bwd_dcore_bigcore(x, dY, dCore, p, dtype, r.precision, st, ws, ws_bytes);
+          if (rc == DCTN_OK) dCore = nullptr;
+          else if (rc != DCTN_ERR_UNSUPPORTED) return rc;
+        }
+        if (dX) {
+          rc = eps_bwd_dx_bigcore(x, core, dY, dX, ws, ws_bytes, p, dtype, r.precision, st, saved, saved_bytes);
+          if (rc == DCTN_OK) dX = nullptr;
+          else if (rc != DCTN_ERR_UNSUPPORTED && rc != DCTN_ERR_WORKSPACE) return rc;
+        }
+        break;
+      default:
+        return eps_bwd_generic(x, core, dY, dX, dCore, ws, ws_bytes, p, dtype, st);
     }
   }
-  size_t wq = 0;
-  if (dCore && wa == 0 && !saved && (wq = align256(eps_bwd_q2f32_workspace(p, dtype, precision))) > 0) {
-    if (!ws || workspace_bytes < wq) return DCTN_ERR_WORKSPACE;
-    rc = eps_bwd_q2f32(x, dY, dCore, ws, wq, p, dtype, precision, st);
-    if (rc == DCTN_OK) {
-      dCore = nullptr;
-    } else if (rc != DCTN_ERR_UNSUPPORTED) {
-      return rc;
-    }
-  }
-  if (!dX && !dCore) return DCTN_OK;
-  const size_t off = (wa + wq) <= workspace_bytes ? (wa + wq) : workspace_bytes;
-  // float64, and float32 shapes the bigcore family does not take: both gradients on the two-halves GEMM path
-  if (dtype == DCTN_F64 || !eps_bigcore_covers(p, dtype, precision) || f32_prefers_halves(p, dtype)) {
-    rc = eps_bwd_halves(x, core, dY, dX, dCore, ws ? ws + off : nullptr, workspace_bytes - off, p, dtype, st, saved,
-                        saved_bytes);
-    if (rc == DCTN_OK) return rc;
-    if (rc != DCTN_ERR_UNSUPPORTED && rc != DCTN_ERR_WORKSPACE) return rc;
-  }
-  if (dCore) {
-    // (its per-chunk slices use the tail of the workspace before dX does: the sum kernel is done with them by then)
-    rc = eps_bwd_dcore_bigcore(x, dY, dCore, p, dtype, precision, st, ws ? ws + off : nullptr, workspace_bytes - off);
-    if (rc == DCTN_OK) {
-      dCore = nullptr;
-    } else if (rc != DCTN_ERR_UNSUPPORTED) {
-      return rc;
-    }
-  }
-  if (dX) {
-    // dX on the bigcore MFMA family (it shares the tail of the workspace with the generic kernels)
-    rc = eps_bwd_dx_bigcore(x, core, dY, dX, ws ? ws + off : nullptr, workspace_bytes - off, p, dtype,
-                            precision, st, saved, saved_bytes);
-    if (rc == DCTN_OK) {
-      dX = nullptr;
-    } else if (rc != DCTN_ERR_UNSUPPORTED && rc != DCTN_ERR_WORKSPACE) {
-      return rc;
-    }
-  }
-  if (!dX && !dCore) return DCTN_OK;
-  return eps_bwd_generic(x, core, dY, dX, dCore, ws ? ws + off : nullptr, workspace_bytes - off, p,
-                         dtype, st);
+  return DCTN_OK;
 }
 
 int dctn_eps_bwd(const void* x, const int64_t x_strides[5], const void* core, const void* dY,

@@ -150,69 +150,68 @@ int eps_head_bwd_mfma(const void* x, const void* feat, const void* dLogits, cons
                       void* dW, void* dBias, void* ws, size_t ws_bytes, const EpsP& p, int Cout, int dtype,
                       int precision, hipStream_t st);
 
+// -------------------------------------------------------------------------------- ConvSBS strings
+// One string as the C-ABI describes it: n cores with their output sizes, left bonds (bond_sizes[0] closes a ring) and
+// window positions, over an input of C channels, (B, H, W) pixels and q values per pixel.  The entry points build it once;
+// every family plans from it.  For the several-strings entry points the arrays hold the strings one after the other.
+struct SbsShape {
+  int n;
+  const int *out_sizes, *bond_sizes, *pos_h, *pos_w;
+  int C, B, H, W, q, dtype;
+};
+// string i of a several-strings shape
+static inline SbsShape sbs_string(SbsShape many, int i) {
+  many.out_sizes += i * many.n;
+  many.bond_sizes += i * many.n;
+  many.pos_h += i * many.n;
+  many.pos_w += i * many.n;
+  return many;
+}
+
 // MFMA ConvSBS sweep (open chain, uniform bond) — convsbs_mfma.hip
 // save_states (optional): room of convsbs_saved_states_bytes(...) for the forward states a following backward takes over
-size_t convsbs_saved_states_bytes(int n, const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w,
-                                  int C, int B, int H, int W, int q, int dtype);
-int convsbs_fwd_mfma(const void* x, const int64_t xs[5], const void* const* cores, void* out, int n,
-                     const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w,
-                     int C, int B, int H, int W, int q, int dtype, hipStream_t st, float* save_states = nullptr);
-int convsbs_bwd_mfma(const void* x, const int64_t xs[5], const void* const* cores, const void* dY,
-                     float* states, float* gxw, float* const* dcores, int n, const int* out_sizes,
-                     const int* bond_sizes, const int* pos_h, const int* pos_w, int C, int B, int H, int W,
-                     int q, int dtype, hipStream_t st, float* partials = nullptr, size_t partial_bytes = 0,
-                     const float* saved_states = nullptr);
+size_t convsbs_saved_states_bytes(const SbsShape& sh);
+int convsbs_fwd_mfma(const void* x, const int64_t xs[5], const void* const* cores, void* out, const SbsShape& sh,
+                     hipStream_t st, float* save_states = nullptr);
+int convsbs_bwd_mfma(const void* x, const int64_t xs[5], const void* const* cores, const void* dY, float* states, float* gxw,
+                     float* const* dcores, const SbsShape& sh, hipStream_t st, float* partials = nullptr,
+                     size_t partial_bytes = 0, const float* saved_states = nullptr);
 // Band-owning backward for bonds 5..16 (two roles per SIMD, nothing kept by the forward) - convsbs_band.hip.  Strings it
 // covers keep no forward states (convsbs_saved_states_bytes returns 0 for them); `ws` holds the per-workgroup dCore
 // records and the partial sums of the pixel rows two bands share (convsbs_band_bwd_workspace; 0 = outside the family).
-bool convsbs_band_covers(int n, const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w, int C, int B,
-                         int H, int W, int q, int dtype);
-size_t convsbs_band_bwd_workspace(int n, const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w, int C,
-                                  int B, int H, int W, int q, int dtype);
-int convsbs_fwd_band(const void* x, const int64_t xs[5], const void* const* cores, void* out, int n, const int* out_sizes,
-                     const int* bond_sizes, const int* pos_h, const int* pos_w, int C, int B, int H, int W, int q, int dtype,
+bool convsbs_band_covers(const SbsShape& sh);
+size_t convsbs_band_bwd_workspace(const SbsShape& sh);
+int convsbs_fwd_band(const void* x, const int64_t xs[5], const void* const* cores, void* out, const SbsShape& sh,
                      hipStream_t st);
 int convsbs_bwd_band(const void* x, const int64_t xs[5], const void* const* cores, const void* dY, void* dX,
-                     float* const* dcores, int n, const int* out_sizes, const int* bond_sizes, const int* pos_h,
-                     const int* pos_w, int C, int B, int H, int W, int q, int dtype, hipStream_t st, void* ws, size_t ws_bytes);
+                     float* const* dcores, const SbsShape& sh, hipStream_t st, void* ws, size_t ws_bytes);
 // Wide backward for strings whose core gradients do not fit one workgroup's LDS (any bond, f32 / f64 / bf16 storage) -
 // convsbs_wide.hip.  GEMMs over HBM buffers of window chunks, fixed-order partial records, no atomics.  The per-window input
 // gradients land at the START of `ws` in the generic sweep's gxw layout ([n C q][windows]; the caller gathers dX from them
 // when need_dx).  convsbs_wide_bwd_workspace: 0 = outside the family.
-size_t convsbs_wide_bwd_workspace(int n, const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w, int C,
-                                  int B, int H, int W, int q, int dtype);
+size_t convsbs_wide_bwd_workspace(const SbsShape& sh);
 int convsbs_bwd_wide(const void* x, const int64_t xs[5], const void* const* cores, const void* dY, int need_dx,
-                     void* const* dcores, int n, const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w,
-                     int C, int B, int H, int W, int q, int dtype, hipStream_t st, void* ws, size_t ws_bytes);
+                     void* const* dcores, const SbsShape& sh, hipStream_t st, void* ws, size_t ws_bytes);
 // room for the per-workgroup partial-gradient records of the MFMA backward (deterministic dCore)
 constexpr int SBS_MAX_PARTIAL_RECORDS = 2048;
 
 // Register-resident sweep for small bonds (every bond <= 4, float32 open chains, at most one two-valued core,
 // q^C <= 4) - convsbs_reg.hip.  The backward writes dX itself (no per-window gradients, no gather launch) and needs
 // `ws` only for its per-workgroup dCore records (convsbs_reg_bwd_workspace; 0 = the string is outside the family).
-size_t convsbs_reg_bwd_workspace(int n, const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w,
-                                 int C, int B, int H, int W, int q, int dtype);
-int convsbs_fwd_reg(const void* x, const int64_t xs[5], const void* const* cores, void* out, int n, const int* out_sizes,
-                    const int* bond_sizes, const int* pos_h, const int* pos_w, int C, int B, int H, int W, int q, int dtype,
+size_t convsbs_reg_bwd_workspace(const SbsShape& sh);
+int convsbs_fwd_reg(const void* x, const int64_t xs[5], const void* const* cores, void* out, const SbsShape& sh,
                     hipStream_t st);
 int convsbs_bwd_reg(const void* x, const int64_t xs[5], const void* const* cores, const void* dY, void* dX,
-                    float* const* dcores, int n, const int* out_sizes, const int* bond_sizes, const int* pos_h,
-                    const int* pos_w, int C, int B, int H, int W, int q, int dtype, hipStream_t st, void* ws, size_t ws_bytes);
+                    float* const* dcores, const SbsShape& sh, hipStream_t st, void* ws, size_t ws_bytes);
 // several uniform strings of one layer in one launch each way (DCTN_ERR_UNSUPPORTED: run them one by one)
 // The same for strings of the band family (bonds 5..16): blockIdx.y = string, one tail kernel for all strings.
-size_t convsbs_many_band_bwd_workspace(int ns, int n, const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w,
-                                       int C, int B, int H, int W, int q, int dtype);
-int convsbs_many_fwd_band(const void* x, const int64_t xs[5], const void* const* cores, void* const* outs, int ns, int n,
-                          const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w, int C, int B, int H, int W,
-                          int q, int dtype, hipStream_t st);
+size_t convsbs_many_band_bwd_workspace(int ns, const SbsShape& sh);
+int convsbs_many_fwd_band(const void* x, const int64_t xs[5], const void* const* cores, void* const* outs, int ns,
+                          const SbsShape& sh, hipStream_t st);
 int convsbs_many_bwd_band(const void* x, const int64_t xs[5], const void* const* cores, const void* const* dYs, void* dX,
-                          float* const* dcores, int ns, int n, const int* out_sizes, const int* bond_sizes, const int* pos_h,
-                          const int* pos_w, int C, int B, int H, int W, int q, int dtype, hipStream_t st, void* ws, size_t ws_bytes);
-size_t convsbs_many_reg_bwd_workspace(int ns, int n, const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w,
-                                      int C, int B, int H, int W, int q, int dtype);
-int convsbs_many_fwd_reg(const void* x, const int64_t xs[5], const void* const* cores, void* const* outs, int ns, int n,
-                         const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w, int C, int B, int H,
-                         int W, int q, int dtype, hipStream_t st);
+                          float* const* dcores, int ns, const SbsShape& sh, hipStream_t st, void* ws, size_t ws_bytes);
+size_t convsbs_many_reg_bwd_workspace(int ns, const SbsShape& sh);
+int convsbs_many_fwd_reg(const void* x, const int64_t xs[5], const void* const* cores, void* const* outs, int ns,
+                         const SbsShape& sh, hipStream_t st);
 int convsbs_many_bwd_reg(const void* x, const int64_t xs[5], const void* const* cores, const void* const* dYs, void* dX,
-                         float* const* dcores, int ns, int n, const int* out_sizes, const int* bond_sizes, const int* pos_h,
-                         const int* pos_w, int C, int B, int H, int W, int q, int dtype, hipStream_t st, void* ws, size_t ws_bytes);
+                         float* const* dcores, int ns, const SbsShape& sh, hipStream_t st, void* ws, size_t ws_bytes);

@@ -1065,56 +1065,55 @@ struct BdPlan {
   size_t records_bytes, side_bytes;
 };
 
-int bd_plan(BdPlan& pl, const int64_t xs[5], const void* const* cores, int n, const int* out_sizes, const int* bond_sizes,
-            const int* pos_h, const int* pos_w, int C, int B, int H, int W, int q, int dtype) {
-  if (dtype != DCTN_F32 || n < 3 || n > BD_NC || bond_sizes[0] != 1) return DCTN_ERR_UNSUPPORTED;
+int bd_plan(BdPlan& pl, const int64_t xs[5], const void* const* cores, const SbsShape& sh) {
+  if (sh.dtype != DCTN_F32 || sh.n < 3 || sh.n > BD_NC || sh.bond_sizes[0] != 1) return DCTN_ERR_UNSUPPORTED;
   int Ra = 0;
-  for (int c = 1; c < n; ++c) {
-    if (bond_sizes[c] < 1) return DCTN_ERR_UNSUPPORTED;
-    Ra = bond_sizes[c] > Ra ? bond_sizes[c] : Ra;
+  for (int c = 1; c < sh.n; ++c) {
+    if (sh.bond_sizes[c] < 1) return DCTN_ERR_UNSUPPORTED;
+    Ra = sh.bond_sizes[c] > Ra ? sh.bond_sizes[c] : Ra;
   }
   if (Ra <= 4 || Ra > 16) return DCTN_ERR_UNSUPPORTED;   // (bonds <= 4: convsbs_reg takes them, lane = window)
   pl.NS = Ra <= 8 ? 2 : 4;
   int qc = 1;
-  for (int c = 0; c < C; ++c) qc *= q;
-  if (!((C == 1 && q >= 2 && q <= 4) || (C == 2 && q == 2))) return DCTN_ERR_UNSUPPORTED;
+  for (int c = 0; c < sh.C; ++c) qc *= sh.q;
+  if (!((sh.C == 1 && sh.q >= 2 && sh.q <= 4) || (sh.C == 2 && sh.q == 2))) return DCTN_ERR_UNSUPPORTED;
   BdP& p = pl.p;
   p.c2 = -1;
   int otot = 1;
-  for (int c = 0; c < n; ++c) {
-    if (out_sizes[c] < 1 || out_sizes[c] > 2) return DCTN_ERR_UNSUPPORTED;
-    if (out_sizes[c] == 2) {
-      if (p.c2 >= 0 || c == 0 || c == n - 1) return DCTN_ERR_UNSUPPORTED;
+  for (int c = 0; c < sh.n; ++c) {
+    if (sh.out_sizes[c] < 1 || sh.out_sizes[c] > 2) return DCTN_ERR_UNSUPPORTED;
+    if (sh.out_sizes[c] == 2) {
+      if (p.c2 >= 0 || c == 0 || c == sh.n - 1) return DCTN_ERR_UNSUPPORTED;
       p.c2 = c;
     }
-    otot *= out_sizes[c];
+    otot *= sh.out_sizes[c];
   }
   pl.QT = qc;
-  pl.CH = C == 2 ? 2 : 1;
-  p.n = n; p.C = C; p.q = q; p.qc = qc; p.B = B; p.H = H; p.W = W; p.Otot = otot;
+  pl.CH = sh.C == 2 ? 2 : 1;
+  p.n = sh.n; p.C = sh.C; p.q = sh.q; p.qc = qc; p.B = sh.B; p.H = sh.H; p.W = sh.W; p.Otot = otot;
   int max_h = 0, max_w = 0, nin = 1;
   p.core_off[0] = 0;
   for (int c = 0; c < BD_NC; ++c) {
-    const int cc = c < n ? c : n - 1;
-    p.o[c] = out_sizes[cc];
-    p.bl[c] = cc == 0 ? 1 : bond_sizes[cc];
-    p.br[c] = cc == n - 1 ? 1 : bond_sizes[cc + 1];
-    p.ph[c] = pos_h[cc];
-    p.pw[c] = pos_w[cc];
+    const int cc = c < sh.n ? c : sh.n - 1;
+    p.o[c] = sh.out_sizes[cc];
+    p.bl[c] = cc == 0 ? 1 : sh.bond_sizes[cc];
+    p.br[c] = cc == sh.n - 1 ? 1 : sh.bond_sizes[cc + 1];
+    p.ph[c] = sh.pos_h[cc];
+    p.pw[c] = sh.pos_w[cc];
     p.core[c] = cores ? (const float*)cores[cc] : nullptr;
-    if (c < n) {
+    if (c < sh.n) {
       p.nin[c] = nin;
-      nin *= out_sizes[c];
+      nin *= sh.out_sizes[c];
       p.core_off[c + 1] = p.core_off[c] + p.o[c] * p.bl[c] * p.br[c] * qc;
-      max_h = pos_h[c] > max_h ? pos_h[c] : max_h;
-      max_w = pos_w[c] > max_w ? pos_w[c] : max_w;
+      max_h = sh.pos_h[c] > max_h ? sh.pos_h[c] : max_h;
+      max_w = sh.pos_w[c] > max_w ? sh.pos_w[c] : max_w;
     } else {
       p.nin[c] = 1;
       p.core_off[c + 1] = p.core_off[c];
     }
   }
   p.max_h = max_h;
-  p.Ho = H - max_h; p.Wo = W - max_w;
+  p.Ho = sh.H - max_h; p.Wo = sh.W - max_w;
   if (p.Ho < 1 || p.Wo < 1) return DCTN_ERR_BAD_SHAPE;
   for (int i = 0; i < 5; ++i) p.xs[i] = xs ? xs[i] : 0;
   // LDS plan: packs, tables, per chain wave two feature buffers (+ raw values), two hand-over buffers; the band's rows
@@ -1132,13 +1131,13 @@ int bd_plan(BdPlan& pl, const int64_t xs[5], const void* const* cores, int n, co
   // bands per image: enough workgroups for the chip, every band at least max_h rows, the band's gradient rows in LDS.
   // One workgroup per CU: the plan may fill the CU's whole LDS (dctn_dev().lds, not the 15/16 other families plan with);
   // on a device with less, it declines (DCTN_ERR_UNSUPPORTED: the caller takes the matrix-core sweep)
-  int nb = (dctn_dev().cus + B - 1) / B;
+  int nb = (dctn_dev().cus + sh.B - 1) / sh.B;
   if (nb < 1) nb = 1;
   if (nb > p.Ho / min_rows) nb = p.Ho / min_rows;
   if (nb < 1) return DCTN_ERR_UNSUPPORTED;
   for (;;) {
     const int rows = (p.Ho + nb - 1) / nb;
-    const long long rows_floats = (long long)rows * p.Wo * n * RK;
+    const long long rows_floats = (long long)rows * p.Wo * sh.n * RK;
     if ((long long)(off + rows_floats) * 4 <= dctn_dev().lds) {
       p.band_rows = rows;
       break;
@@ -1149,13 +1148,13 @@ int bd_plan(BdPlan& pl, const int64_t xs[5], const void* const* cores, int n, co
   p.nb = (p.Ho + p.band_rows - 1) / p.band_rows;   // (the rounding can leave fewer bands than asked for)
   const int tiles = (p.band_rows * p.Wo + 15) / 16;
   p.iters = (tiles + 3) / 4;
-  pl.lds_bytes = (off + p.band_rows * p.Wo * n * RK) * 4;
+  pl.lds_bytes = (off + p.band_rows * p.Wo * sh.n * RK) * 4;
   pl.rec_len = BD_NPK * pl.QT * 256 + 128;
   // (the join area - two copies of the tiles + four first / last partial sums - lies in front of the band's rows: the packs
   // alone are as large as the two copies)
-  pl.nwg = B * p.nb;
+  pl.nwg = sh.B * p.nb;
   pl.records_bytes = (size_t)pl.nwg * pl.rec_len * sizeof(float);
-  pl.side_bytes = (size_t)B * (p.nb - 1) * 2 * max_h * W * C * q * sizeof(float);
+  pl.side_bytes = (size_t)sh.B * (p.nb - 1) * 2 * max_h * sh.W * sh.C * sh.q * sizeof(float);
   return DCTN_OK;
 }
 
@@ -1163,16 +1162,14 @@ size_t bd_align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
 
-bool convsbs_band_covers(int n, const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w, int C, int B,
-                         int H, int W, int q, int dtype) {
+bool convsbs_band_covers(const SbsShape& sh) {
   BdPlan pl;
-  return bd_plan(pl, nullptr, nullptr, n, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype) == DCTN_OK;
+  return bd_plan(pl, nullptr, nullptr, sh) == DCTN_OK;
 }
 
-size_t convsbs_band_bwd_workspace(int n, const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w, int C,
-                                  int B, int H, int W, int q, int dtype) {
+size_t convsbs_band_bwd_workspace(const SbsShape& sh) {
   BdPlan pl;
-  if (bd_plan(pl, nullptr, nullptr, n, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype) != DCTN_OK) return 0;
+  if (bd_plan(pl, nullptr, nullptr, sh) != DCTN_OK) return 0;
   size_t extra = 0;
 #ifdef DCTN_STAMPS
   extra = (size_t)pl.nwg * 2 * 32 * sizeof(long long);
@@ -1181,10 +1178,9 @@ size_t convsbs_band_bwd_workspace(int n, const int* out_sizes, const int* bond_s
 }
 
 int convsbs_bwd_band(const void* x, const int64_t xs[5], const void* const* cores, const void* dY, void* dX,
-                     float* const* dcores, int n, const int* out_sizes, const int* bond_sizes, const int* pos_h,
-                     const int* pos_w, int C, int B, int H, int W, int q, int dtype, hipStream_t st, void* ws, size_t ws_bytes) {
+                     float* const* dcores, const SbsShape& sh, hipStream_t st, void* ws, size_t ws_bytes) {
   BdPlan pl;
-  const int rc = bd_plan(pl, xs, cores, n, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype);
+  const int rc = bd_plan(pl, xs, cores, sh);
   if (rc != DCTN_OK) return rc;
   if (!dX && !dcores) return DCTN_OK;
   const size_t need = bd_align256(pl.records_bytes) + bd_align256(pl.side_bytes);
@@ -1219,14 +1215,14 @@ int convsbs_bwd_band(const void* x, const int64_t xs[5], const void* const* core
 #undef BD_LAUNCH
   DCTN_CHECK_LAUNCH();
   BdTailP t;
-  t.n = n; t.nrec = pl.nwg; t.total = p.core_off[n]; t.qc = p.qc; t.rec_len = pl.rec_len;
+  t.n = sh.n; t.nrec = pl.nwg; t.total = p.core_off[sh.n]; t.qc = p.qc; t.rec_len = pl.rec_len;
   for (int c = 0; c <= BD_NC; ++c) t.core_off[c] = p.core_off[c];
   for (int c = 0; c < BD_NC; ++c) { t.bl[c] = p.bl[c]; t.br[c] = p.br[c]; t.o[c] = p.o[c]; }
   t.c2 = p.c2;
-  for (int c = 0; c < BD_NC; ++c) t.dcore[c] = (dcores && c < n) ? dcores[c] : nullptr;
+  for (int c = 0; c < BD_NC; ++c) t.dcore[c] = (dcores && c < sh.n) ? dcores[c] : nullptr;
   t.records = p.records; t.side = p.side; t.dX = p.dX;
-  t.B = B; t.H = H; t.W = W; t.C = C; t.q = q; t.Cq = C * q; t.nb = p.nb; t.band_rows = p.band_rows; t.max_h = p.max_h;
-  t.nshared = p.dX ? (long long)B * (p.nb - 1) * p.max_h * W * C * q : 0;
+  t.B = sh.B; t.H = sh.H; t.W = sh.W; t.C = sh.C; t.q = sh.q; t.Cq = sh.C * sh.q; t.nb = p.nb; t.band_rows = p.band_rows; t.max_h = p.max_h;
+  t.nshared = p.dX ? (long long)sh.B * (p.nb - 1) * p.max_h * sh.W * sh.C * sh.q : 0;
   const long long blocks = (p.records ? (t.rec_len + 63) / 64 : 0) + (t.nshared + 255) / 256;
   if (blocks > 0) {
     hipLaunchKernelGGL(convsbs_band_tail_k, dim3((unsigned)blocks), dim3(256), 0, st, t);
@@ -1236,11 +1232,10 @@ int convsbs_bwd_band(const void* x, const int64_t xs[5], const void* const* core
   return DCTN_OK;
 }
 
-int convsbs_fwd_band(const void* x, const int64_t xs[5], const void* const* cores, void* out, int n, const int* out_sizes,
-                     const int* bond_sizes, const int* pos_h, const int* pos_w, int C, int B, int H, int W, int q, int dtype,
+int convsbs_fwd_band(const void* x, const int64_t xs[5], const void* const* cores, void* out, const SbsShape& sh,
                      hipStream_t st) {
   BdPlan pl;
-  const int rc = bd_plan(pl, xs, cores, n, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype);
+  const int rc = bd_plan(pl, xs, cores, sh);
   if (rc != DCTN_OK) return rc;
   const BdP& b = pl.p;
   BdFwdP p;
@@ -1249,8 +1244,8 @@ int convsbs_fwd_band(const void* x, const int64_t xs[5], const void* const* core
     p.core[c] = b.core[c]; p.o[c] = b.o[c]; p.bl[c] = b.bl[c]; p.br[c] = b.br[c]; p.ph[c] = b.ph[c]; p.pw[c] = b.pw[c]; p.nin[c] = b.nin[c];
   }
   for (int i = 0; i < 5; ++i) p.xs[i] = b.xs[i];
-  p.n = n; p.C = C; p.q = q; p.qc = b.qc; p.B = B; p.H = H; p.W = W; p.Ho = b.Ho; p.Wo = b.Wo; p.Otot = b.Otot;
-  p.Wn = (long long)B * b.Ho * b.Wo;
+  p.n = sh.n; p.C = sh.C; p.q = sh.q; p.qc = b.qc; p.B = sh.B; p.H = sh.H; p.W = sh.W; p.Ho = b.Ho; p.Wo = b.Wo; p.Otot = b.Otot;
+  p.Wn = (long long)sh.B * b.Ho * b.Wo;
   p.ntiles = (p.Wn + 15) / 16;
   const int lds_bytes = (BD_NPK * pl.QT * 256 + 128 + 8 * 2 * BD_NC * 16 * 4) * 4;   // pack + tables + 8 waves x 2 feature buffers
   long long blocks = (p.ntiles + 7) / 8;
@@ -1283,12 +1278,10 @@ int convsbs_fwd_band(const void* x, const int64_t xs[5], const void* const* core
 namespace {
 // the plans of the strings of one layer; DCTN_ERR_UNSUPPORTED unless every string is in the family with the same tile
 // shape and band geometry (the tail kernel's one pass over dX relies on it)
-int bd_plan_many(BdPlan (&pl)[BD_MANY], int ns, const int64_t xs[5], const void* const* cores, int n, const int* out_sizes,
-                 const int* bond_sizes, const int* pos_h, const int* pos_w, int C, int B, int H, int W, int q, int dtype) {
+int bd_plan_many(BdPlan (&pl)[BD_MANY], int ns, const int64_t xs[5], const void* const* cores, const SbsShape& sh) {
   if (ns != BD_MANY) return DCTN_ERR_UNSUPPORTED;
   for (int s2 = 0; s2 < ns; ++s2) {
-    const int rc = bd_plan(pl[s2], xs, cores ? cores + s2 * n : nullptr, n, out_sizes + s2 * n, bond_sizes + s2 * n, pos_h + s2 * n,
-                           pos_w + s2 * n, C, B, H, W, q, dtype);
+    const int rc = bd_plan(pl[s2], xs, cores ? cores + s2 * sh.n : nullptr, sbs_string(sh, s2));
     if (rc != DCTN_OK) return rc;
     if (s2 > 0) {
       const BdP &a = pl[0].p, &b = pl[s2].p;
@@ -1301,21 +1294,19 @@ int bd_plan_many(BdPlan (&pl)[BD_MANY], int ns, const int64_t xs[5], const void*
 }
 }  // namespace
 
-size_t convsbs_many_band_bwd_workspace(int ns, int n, const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w,
-                                       int C, int B, int H, int W, int q, int dtype) {
+size_t convsbs_many_band_bwd_workspace(int ns, const SbsShape& sh) {
   BdPlan pl[BD_MANY];
-  if (bd_plan_many(pl, ns, nullptr, nullptr, n, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype) != DCTN_OK) return 0;
+  if (bd_plan_many(pl, ns, nullptr, nullptr, sh) != DCTN_OK) return 0;
   size_t tot = 256;
   for (int s2 = 0; s2 < ns; ++s2) tot += bd_align256(pl[s2].records_bytes) + bd_align256(pl[s2].side_bytes);
-  tot += (size_t)(ns - 1) * bd_align256((size_t)C * B * H * W * q * sizeof(float));   // the other strings' shares of dX
+  tot += (size_t)(ns - 1) * bd_align256((size_t)sh.C * sh.B * sh.H * sh.W * sh.q * sizeof(float));   // the other strings' shares of dX
   return tot;
 }
 
-int convsbs_many_fwd_band(const void* x, const int64_t xs[5], const void* const* cores, void* const* outs, int ns, int n,
-                          const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w, int C, int B, int H, int W,
-                          int q, int dtype, hipStream_t st) {
+int convsbs_many_fwd_band(const void* x, const int64_t xs[5], const void* const* cores, void* const* outs, int ns,
+                          const SbsShape& sh, hipStream_t st) {
   BdPlan pl[BD_MANY];
-  const int rc = bd_plan_many(pl, ns, xs, cores, n, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype);
+  const int rc = bd_plan_many(pl, ns, xs, cores, sh);
   if (rc != DCTN_OK) return rc;
   BdFwdPMany pp;
   for (int s2 = 0; s2 < ns; ++s2) {
@@ -1327,8 +1318,8 @@ int convsbs_many_fwd_band(const void* x, const int64_t xs[5], const void* const*
       p.core[c] = b.core[c]; p.o[c] = b.o[c]; p.bl[c] = b.bl[c]; p.br[c] = b.br[c]; p.ph[c] = b.ph[c]; p.pw[c] = b.pw[c]; p.nin[c] = b.nin[c];
     }
     for (int i = 0; i < 5; ++i) p.xs[i] = b.xs[i];
-    p.n = n; p.C = C; p.q = q; p.qc = b.qc; p.B = B; p.H = H; p.W = W; p.Ho = b.Ho; p.Wo = b.Wo; p.Otot = b.Otot;
-    p.Wn = (long long)B * b.Ho * b.Wo;
+    p.n = sh.n; p.C = sh.C; p.q = sh.q; p.qc = b.qc; p.B = sh.B; p.H = sh.H; p.W = sh.W; p.Ho = b.Ho; p.Wo = b.Wo; p.Otot = b.Otot;
+    p.Wn = (long long)sh.B * b.Ho * b.Wo;
     p.ntiles = (p.Wn + 15) / 16;
   }
   const int lds_bytes = (BD_NPK * pl[0].QT * 256 + 128 + 8 * 2 * BD_NC * 16 * 4) * 4;
@@ -1359,13 +1350,12 @@ int convsbs_many_fwd_band(const void* x, const int64_t xs[5], const void* const*
 }
 
 int convsbs_many_bwd_band(const void* x, const int64_t xs[5], const void* const* cores, const void* const* dYs, void* dX,
-                          float* const* dcores, int ns, int n, const int* out_sizes, const int* bond_sizes, const int* pos_h,
-                          const int* pos_w, int C, int B, int H, int W, int q, int dtype, hipStream_t st, void* ws, size_t ws_bytes) {
+                          float* const* dcores, int ns, const SbsShape& sh, hipStream_t st, void* ws, size_t ws_bytes) {
   BdPlan pl[BD_MANY];
-  const int rc = bd_plan_many(pl, ns, xs, cores, n, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype);
+  const int rc = bd_plan_many(pl, ns, xs, cores, sh);
   if (rc != DCTN_OK) return rc;
   if (!dX && !dcores) return DCTN_OK;
-  const size_t need = convsbs_many_band_bwd_workspace(ns, n, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype);
+  const size_t need = convsbs_many_band_bwd_workspace(ns, sh);
   if (!ws || ws_bytes < need || ((uintptr_t)ws % 16)) return DCTN_ERR_WORKSPACE;
   BdPMany pp;
   BdTailMany tt;
@@ -1384,18 +1374,18 @@ int convsbs_many_bwd_band(const void* x, const int64_t xs[5], const void* const*
     else if (s2 == 0) p.dX = (float*)dX;
     else {
       p.dX = (float*)cur;
-      cur += bd_align256((size_t)C * B * H * W * q * sizeof(float));
+      cur += bd_align256((size_t)sh.C * sh.B * sh.H * sh.W * sh.q * sizeof(float));
     }
     p.stamps = nullptr;
     pp.s[s2] = p;
     BdTailP& t = tt.s[s2];
-    t.n = n; t.nrec = pl[s2].nwg; t.total = p.core_off[n]; t.qc = p.qc; t.rec_len = pl[s2].rec_len;
+    t.n = sh.n; t.nrec = pl[s2].nwg; t.total = p.core_off[sh.n]; t.qc = p.qc; t.rec_len = pl[s2].rec_len;
     for (int c = 0; c <= BD_NC; ++c) t.core_off[c] = p.core_off[c];
     for (int c = 0; c < BD_NC; ++c) { t.bl[c] = p.bl[c]; t.br[c] = p.br[c]; t.o[c] = p.o[c]; }
     t.c2 = p.c2;
-    for (int c = 0; c < BD_NC; ++c) t.dcore[c] = (dcores && c < n) ? dcores[s2 * n + c] : nullptr;
+    for (int c = 0; c < BD_NC; ++c) t.dcore[c] = (dcores && c < sh.n) ? dcores[s2 * sh.n + c] : nullptr;
     t.records = p.records; t.side = p.side; t.dX = p.dX;
-    t.B = B; t.H = H; t.W = W; t.C = C; t.q = q; t.Cq = C * q; t.nb = p.nb; t.band_rows = p.band_rows; t.max_h = p.max_h;
+    t.B = sh.B; t.H = sh.H; t.W = sh.W; t.C = sh.C; t.q = sh.q; t.Cq = sh.C * sh.q; t.nb = p.nb; t.band_rows = p.band_rows; t.max_h = p.max_h;
     t.nshared = 0;
   }
 #define BD_LAUNCH(QTV, CHV, NSV)                                                                                          \
@@ -1419,7 +1409,7 @@ int convsbs_many_bwd_band(const void* x, const int64_t xs[5], const void* const*
 #undef BD_LAUNCH
   DCTN_CHECK_LAUNCH();
   const long long rec_blocks = dcores ? (long long)ns * ((pl[0].rec_len + 63) / 64) : 0;
-  const long long dx_blocks = dX ? ((long long)C * B * H * W * q + 255) / 256 : 0;
+  const long long dx_blocks = dX ? ((long long)sh.C * sh.B * sh.H * sh.W * sh.q + 255) / 256 : 0;
   if (rec_blocks + dx_blocks > 0) {
     hipLaunchKernelGGL(convsbs_band_tail_many_k, dim3((unsigned)(rec_blocks + dx_blocks)), dim3(256), 0, st, tt);
     DCTN_CHECK_LAUNCH();

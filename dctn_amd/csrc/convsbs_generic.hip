@@ -287,54 +287,59 @@ __global__ void convert_sbs_k(const A* __restrict__ src, S* __restrict__ dst, lo
     dst[i] = (S)src[i];
 }
 
-int fill(SbsP& p, const int64_t xs[5], int n, const int* out_sizes, const int* bond_sizes,
-         const int* pos_h, const int* pos_w, int C, int B, int H, int W, int q) {
-  if (n < 1 || n > SBS_MAXC) return n < 1 ? DCTN_ERR_BAD_SHAPE : DCTN_ERR_UNSUPPORTED;
-  if (C < 1 || B < 1 || q < 1) return DCTN_ERR_BAD_SHAPE;
+// cores (optional): the calls' core pointers, every one non-NULL
+int fill(SbsP& p, const int64_t xs[5], const SbsShape& sh, const void* const* cores = nullptr) {
+  if (sh.n < 1 || sh.n > SBS_MAXC) return sh.n < 1 ? DCTN_ERR_BAD_SHAPE : DCTN_ERR_UNSUPPORTED;
+  if (sh.C < 1 || sh.B < 1 || sh.q < 1) return DCTN_ERR_BAD_SHAPE;
   int max_h = 0, max_w = 0, min_h = 1 << 30, min_w = 1 << 30;
-  for (int c = 0; c < n; ++c) {
-    if (out_sizes[c] < 1 || bond_sizes[c] < 1 || pos_h[c] < 0 || pos_w[c] < 0)
+  for (int c = 0; c < sh.n; ++c) {
+    if (sh.out_sizes[c] < 1 || sh.bond_sizes[c] < 1 || sh.pos_h[c] < 0 || sh.pos_w[c] < 0)
       return DCTN_ERR_BAD_SHAPE;
-    max_h = pos_h[c] > max_h ? pos_h[c] : max_h;
-    max_w = pos_w[c] > max_w ? pos_w[c] : max_w;
-    min_h = pos_h[c] < min_h ? pos_h[c] : min_h;
-    min_w = pos_w[c] < min_w ? pos_w[c] : min_w;
+    max_h = sh.pos_h[c] > max_h ? sh.pos_h[c] : max_h;
+    max_w = sh.pos_w[c] > max_w ? sh.pos_w[c] : max_w;
+    min_h = sh.pos_h[c] < min_h ? sh.pos_h[c] : min_h;
+    min_w = sh.pos_w[c] < min_w ? sh.pos_w[c] : min_w;
   }
   if (min_h != 0 || min_w != 0) return DCTN_ERR_BAD_SHAPE;  // dctn/align.py:18-19
-  if (H <= max_h || W <= max_w) return DCTN_ERR_BAD_SHAPE;
-  p.n = n; p.C = C; p.B = B; p.H = H; p.W = W; p.q = q;
+  if (sh.H <= max_h || sh.W <= max_w) return DCTN_ERR_BAD_SHAPE;
+  p.n = sh.n; p.C = sh.C; p.B = sh.B; p.H = sh.H; p.W = sh.W; p.q = sh.q;
   long long qc = 1;
-  for (int c = 0; c < C; ++c) { qc *= q; if (qc > 4096) return DCTN_ERR_UNSUPPORTED; }
+  for (int c = 0; c < sh.C; ++c) { qc *= sh.q; if (qc > 4096) return DCTN_ERR_UNSUPPORTED; }
   p.qc = (int)qc;
-  p.Ho = H - max_h; p.Wo = W - max_w;
-  p.Wn = (long long)B * p.Ho * p.Wo;
+  p.Ho = sh.H - max_h; p.Wo = sh.W - max_w;
+  p.Wn = (long long)sh.B * p.Ho * p.Wo;
   for (int i = 0; i < 5; ++i) p.s[i] = xs ? xs[i] : 0;
-  p.l0 = bond_sizes[0];
+  p.l0 = sh.bond_sizes[0];
   long long oacc = 1, off = 0;
   int vmax = p.l0;
-  for (int c = 0; c < n; ++c) {
-    p.o[c] = out_sizes[c];
-    p.bl[c] = bond_sizes[c];
-    p.br[c] = bond_sizes[(c + 1) % n];
-    p.ph[c] = pos_h[c];
-    p.pw[c] = pos_w[c];
+  for (int c = 0; c < sh.n; ++c) {
+    p.o[c] = sh.out_sizes[c];
+    p.bl[c] = sh.bond_sizes[c];
+    p.br[c] = sh.bond_sizes[(c + 1) % sh.n];
+    p.ph[c] = sh.pos_h[c];
+    p.pw[c] = sh.pos_w[c];
     p.oacc[c] = (int)oacc;
     p.st_off[c] = off;
     off += oacc * p.bl[c];
-    oacc *= out_sizes[c];
+    oacc *= sh.out_sizes[c];
     if (oacc * p.br[c] > (1 << 20)) return DCTN_ERR_UNSUPPORTED;
     if ((int)(oacc * p.br[c]) > vmax) vmax = (int)(oacc * p.br[c]);
   }
-  p.oacc[n] = (int)oacc;
-  p.st_off[n] = off;
+  p.oacc[sh.n] = (int)oacc;
+  p.st_off[sh.n] = off;
   p.cmax = 0;
-  for (int c = 0; c < n; ++c) {
+  for (int c = 0; c < sh.n; ++c) {
     const long long e = (long long)p.o[c] * p.bl[c] * p.br[c] * p.qc;
     if (e > (1 << 20)) return DCTN_ERR_UNSUPPORTED;
     if ((int)e > p.cmax) p.cmax = (int)e;
   }
   p.Otot = (int)oacc;
   p.vmax = vmax;
+  for (int c = 0; cores && c < sh.n; ++c) {
+    if (!cores[c]) return DCTN_ERR_NULL;
+    p.core[c] = cores[c];
+    p.dcore[c] = nullptr;
+  }
   return DCTN_OK;
 }
 
@@ -391,8 +396,9 @@ size_t bwd_ws(const SbsP& p, int dtype) {
 }
 
 template <typename S, typename A>
-int bwd_launch(const void* x, const void* dY, void* dX, void* const* dCores, void* ws,
-               size_t ws_bytes, SbsP& p, int dtype, hipStream_t st, const void* saved = nullptr) {
+int bwd_launch(const void* x, const void* dY, void* dX, void* const* dCores, void* ws, size_t ws_bytes, SbsP& p,
+               const SbsShape& sh, hipStream_t st, const void* saved) {
+  const int dtype = sh.dtype;
   if (!ws || bwd_ws(p, dtype) > ws_bytes) return DCTN_ERR_WORKSPACE;
   p.core_off[0] = 0;
   for (int c = 0; c < p.n; ++c) p.core_off[c + 1] = p.core_off[c] + core_elems(p, c);
@@ -444,16 +450,12 @@ int bwd_launch(const void* x, const void* dY, void* dX, void* const* dCores, voi
   if constexpr (sizeof(S) == 4 && sizeof(A) == 4) {
     // float32 strings of the MFMA family: register-resident sweep on the matrix cores
     if (need_dcore) {
-      int outs[SBS_MAXC], bonds[SBS_MAXC];
-      float* dcp[SBS_MAXC];
-      const void* cp[SBS_MAXC];
-      for (int c = 0; c < p.n; ++c) { outs[c] = p.o[c]; bonds[c] = p.bl[c]; dcp[c] = (float*)p.dcore[c]; cp[c] = p.core[c]; }
       size_t ce = 0;
       for (int c = 0; c < p.n; ++c) ce += (size_t)core_elems(p, c);
       const size_t pbytes = (size_t)SBS_MAX_PARTIAL_RECORDS * ce * sizeof(float);
       float* partials = ((size_t)((unsigned char*)ws + ws_bytes - wsp) >= pbytes) ? (float*)wsp : nullptr;
-      const int rcm = convsbs_bwd_mfma(x, (const int64_t*)p.s, cp, dY, (float*)states, dX ? (float*)gxw : nullptr, dcp, p.n, outs,
-                                       bonds, p.ph, p.pw, p.C, p.B, p.H, p.W, p.q, dtype, st, partials, pbytes, (const float*)saved);
+      const int rcm = convsbs_bwd_mfma(x, (const int64_t*)p.s, (const void* const*)p.core, dY, (float*)states,
+                                       dX ? (float*)gxw : nullptr, (float* const*)p.dcore, sh, st, partials, pbytes, (const float*)saved);
       if (rcm == DCTN_OK) {
         if (dX) {
           const long long total = (long long)p.C * p.B * p.H * p.W * p.q;
@@ -508,10 +510,10 @@ bool generic_bwd_fits(const SbsP& p, size_t asz) {
 // The wide family (convsbs_wide.hip) writes the per-window input gradients at the start of the workspace; dX is gathered
 // from them by the generic sweep's own kernel.
 template <typename S, typename A>
-int wide_launch(const void* x, const void* dY, void* dX, void* const* dCores, void* ws, size_t ws_bytes, SbsP& p, int dtype,
-                hipStream_t st) {
-  const int rc = convsbs_bwd_wide(x, (const int64_t*)p.s, (const void* const*)p.core, dY, dX != nullptr, dCores, p.n, p.o, p.bl,
-                                  p.ph, p.pw, p.C, p.B, p.H, p.W, p.q, dtype, st, ws, ws_bytes);
+int wide_launch(const void* x, const void* dY, void* dX, void* const* dCores, void* ws, size_t ws_bytes, SbsP& p,
+                const SbsShape& sh, hipStream_t st) {
+  const int dtype = sh.dtype;
+  const int rc = convsbs_bwd_wide(x, (const int64_t*)p.s, (const void* const*)p.core, dY, dX != nullptr, dCores, sh, st, ws, ws_bytes);
   if (rc != DCTN_OK) return rc;
   if (dX) {
     const long long total = (long long)p.C * p.B * p.H * p.W * p.q;
@@ -524,13 +526,28 @@ int wide_launch(const void* x, const void* dY, void* dX, void* const* dCores, vo
   return DCTN_OK;
 }
 
-}  // namespace
-
-static int sbs_largest_bond(int n, const int* bond_sizes) {
-  int m = 0;
-  for (int c = 0; c < n; ++c) m = bond_sizes[c] > m ? bond_sizes[c] : m;
-  return m;
+// f(S(), A()) with the storage and accumulator types of a dtype code
+template <typename F>
+int with_types(int dtype, F f) {
+  switch (dtype) {
+    case DCTN_F32: return f(float(), float());
+    case DCTN_F64: return f(double(), double());
+    case DCTN_BF16: return f(bf16_t(), float());
+  }
+  return DCTN_ERR_BAD_DTYPE;
 }
+
+// bonds 5..16 go to the band family, except that under DCTN_SBS_MATRIX_CORE_SWEEP bonds up to 8 stay on the matrix-core
+// sweep (the tests hold both against the oracle)
+bool band_family_first(const SbsShape& sh, int dtype_flags) {
+  int largest = 0;
+  for (int c = 0; c < sh.n; ++c) largest = sh.bond_sizes[c] > largest ? sh.bond_sizes[c] : largest;
+  return !((dtype_flags & DCTN_SBS_MATRIX_CORE_SWEEP) && largest <= 8);
+}
+
+constexpr int SBS_FLAGS = DCTN_SBS_MATRIX_CORE_SWEEP | DCTN_SBS_WIDE_SWEEP;
+
+}  // namespace
 
 extern "C" {
 
@@ -538,18 +555,17 @@ size_t dctn_convsbs_workspace_bytes(int n_cores, const int* out_sizes, const int
                                     int C, int B, int H, int W, int q, const int* pos_h,
                                     const int* pos_w, int dtype_flags, int backward) {
   const int dtype = dtype_flags & DCTN_DTYPE_MASK;   // (the query covers every family: flags only select among them)
-  SbsP p;
   if (!out_sizes || !bond_sizes || !pos_h || !pos_w) return 0;
-  if (fill(p, nullptr, n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q) != DCTN_OK)
-    return 0;
+  const SbsShape sh{n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype};
+  SbsP p;
+  if (fill(p, nullptr, sh) != DCTN_OK) return 0;
   if (!backward) return 256;
-  const size_t a = bwd_ws(p, dtype), b = convsbs_reg_bwd_workspace(n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype);
-  const size_t c = convsbs_band_bwd_workspace(n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype);
+  const size_t a = bwd_ws(p, dtype), b = convsbs_reg_bwd_workspace(sh), c = convsbs_band_bwd_workspace(sh);
   size_t m = a > b ? a : b;
   m = m > c ? m : c;
   // the wide family: where the generic sweep's LDS plan declines the string, or where the flag forces it
   if ((dtype_flags & DCTN_SBS_WIDE_SWEEP) || !generic_bwd_fits(p, dtype == DCTN_F64 ? 8 : 4)) {
-    const size_t w = convsbs_wide_bwd_workspace(n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype);
+    const size_t w = convsbs_wide_bwd_workspace(sh);
     m = m > w ? m : w;
   }
   return m + 256;
@@ -557,9 +573,8 @@ size_t dctn_convsbs_workspace_bytes(int n_cores, const int* out_sizes, const int
 
 size_t dctn_convsbs_saved_states_bytes(int n_cores, const int* out_sizes, const int* bond_sizes, int C, int B, int H,
                                        int W, int q, const int* pos_h, const int* pos_w, int dtype_flags) {
-  const int dtype = dtype_flags & DCTN_DTYPE_MASK;
   if (!out_sizes || !bond_sizes || !pos_h || !pos_w) return 0;
-  return convsbs_saved_states_bytes(n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype);
+  return convsbs_saved_states_bytes({n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype_flags & DCTN_DTYPE_MASK});
 }
 
 int dctn_convsbs_fwd(const void* x, const int64_t x_strides[5], const void* const* cores,
@@ -568,44 +583,32 @@ int dctn_convsbs_fwd(const void* x, const int64_t x_strides[5], const void* cons
                      void* workspace, size_t workspace_bytes, int dtype_flags, void* stream) {
   if (!x || !x_strides || !cores || !out || !out_sizes || !bond_sizes || !pos_h || !pos_w)
     return DCTN_ERR_NULL;
-  const int dtype = dtype_flags & DCTN_DTYPE_MASK;
-  if (dtype_flags & ~(DCTN_DTYPE_MASK | DCTN_SBS_MATRIX_CORE_SWEEP | DCTN_SBS_WIDE_SWEEP)) return DCTN_ERR_UNSUPPORTED;
+  if (dtype_flags & ~(DCTN_DTYPE_MASK | SBS_FLAGS)) return DCTN_ERR_UNSUPPORTED;
+  const SbsShape sh{n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype_flags & DCTN_DTYPE_MASK};
   SbsP p;
-  int rc = fill(p, x_strides, n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q);
+  int rc = fill(p, x_strides, sh, cores);
   if (rc != DCTN_OK) return rc;
-  for (int c = 0; c < n_cores; ++c) {
-    if (!cores[c]) return DCTN_ERR_NULL;
-    p.core[c] = cores[c];
-    p.dcore[c] = nullptr;
-  }
   hipStream_t st = (hipStream_t)stream;
   // a workspace of dctn_convsbs_saved_states_bytes(...) bytes: the forward leaves its states there for
   // dctn_convsbs_bwd_saved (a training forward); anything smaller: plain forward
   // small bonds: the register-resident sweep (keeps nothing: its backward recomputes the chain in registers)
   if (!(dtype_flags & DCTN_SBS_MATRIX_CORE_SWEEP)) {
-    rc = convsbs_fwd_reg(x, x_strides, cores, out, n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype, st);
+    rc = convsbs_fwd_reg(x, x_strides, cores, out, sh, st);
     if (rc != DCTN_ERR_UNSUPPORTED) return rc;
   }
-  // bonds 5..16: the band family's forward (nothing kept: its backward recomputes the chain in registers); under
-  // DCTN_SBS_MATRIX_CORE_SWEEP bonds up to 8 stay on the matrix-core sweep below (the tests hold both against the oracle)
-  if (!((dtype_flags & DCTN_SBS_MATRIX_CORE_SWEEP) && sbs_largest_bond(n_cores, bond_sizes) <= 8)) {
-    rc = convsbs_fwd_band(x, x_strides, cores, out, n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype, st);
+  // bonds 5..16: the band family's forward (nothing kept: its backward recomputes the chain in registers)
+  if (band_family_first(sh, dtype_flags)) {
+    rc = convsbs_fwd_band(x, x_strides, cores, out, sh, st);
     if (rc != DCTN_ERR_UNSUPPORTED) return rc;
   }
-  const size_t sb = convsbs_saved_states_bytes(n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype);
+  const size_t sb = convsbs_saved_states_bytes(sh);
   float* save = (sb > 0 && workspace && workspace_bytes >= sb) ? (float*)workspace : nullptr;
-  rc = convsbs_fwd_mfma(x, x_strides, cores, out, n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q,
-                        dtype, st, save);
+  rc = convsbs_fwd_mfma(x, x_strides, cores, out, sh, st, save);
   // the caller learns whether the states were WRITTEN: only the matrix-core sweep writes them, and it can still decline
   // a string the size query accepted (its LDS plan); the generic sweep below leaves the buffer untouched
   if (rc == DCTN_OK) return save ? DCTN_SAVED : DCTN_OK;
   if (rc != DCTN_ERR_UNSUPPORTED) return rc;
-  switch (dtype) {
-    case DCTN_F32: return fwd_launch<float, float>(x, out, p, st);
-    case DCTN_F64: return fwd_launch<double, double>(x, out, p, st);
-    case DCTN_BF16: return fwd_launch<bf16_t, float>(x, out, p, st);
-  }
-  return DCTN_ERR_BAD_DTYPE;
+  return with_types(sh.dtype, [&](auto s, auto a) { return fwd_launch<decltype(s), decltype(a)>(x, out, p, st); });
 }
 
 int dctn_convsbs_bwd(const void* x, const int64_t x_strides[5], const void* const* cores,
@@ -613,9 +616,8 @@ int dctn_convsbs_bwd(const void* x, const int64_t x_strides[5], const void* cons
                      const int* out_sizes, const int* bond_sizes, const int* pos_h,
                      const int* pos_w, int C, int B, int H, int W, int q, void* workspace,
                      size_t workspace_bytes, int dtype_flags, void* stream) {
-  const int dtype = dtype_flags;   // (decoded by dctn_convsbs_bwd_saved)
   return dctn_convsbs_bwd_saved(x, x_strides, cores, dY, dX, dCores, n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H,
-                                W, q, workspace, workspace_bytes, nullptr, 0, dtype, stream);
+                                W, q, workspace, workspace_bytes, nullptr, 0, dtype_flags, stream);
 }
 
 int dctn_convsbs_bwd_saved(const void* x, const int64_t x_strides[5], const void* const* cores,
@@ -626,73 +628,49 @@ int dctn_convsbs_bwd_saved(const void* x, const int64_t x_strides[5], const void
                            void* stream) {
   if (!x || !x_strides || !cores || !dY || !out_sizes || !bond_sizes || !pos_h || !pos_w)
     return DCTN_ERR_NULL;
-  const int dtype = dtype_flags & DCTN_DTYPE_MASK;
-  if (dtype_flags & ~(DCTN_DTYPE_MASK | DCTN_SBS_MATRIX_CORE_SWEEP | DCTN_SBS_WIDE_SWEEP)) return DCTN_ERR_UNSUPPORTED;
+  if (dtype_flags & ~(DCTN_DTYPE_MASK | SBS_FLAGS)) return DCTN_ERR_UNSUPPORTED;
+  const SbsShape sh{n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype_flags & DCTN_DTYPE_MASK};
   if (saved_states) {   // only what the forward of this very shape can have written
-    const size_t sb = convsbs_saved_states_bytes(n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype);
+    const size_t sb = convsbs_saved_states_bytes(sh);
     if (sb == 0 || saved_states_bytes < sb) saved_states = nullptr;
   }
   if (!dX && !dCores) return DCTN_OK;
   SbsP p;
-  int rc = fill(p, x_strides, n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q);
+  int rc = fill(p, x_strides, sh, cores);
   if (rc != DCTN_OK) return rc;
-  for (int c = 0; c < n_cores; ++c) {
-    if (!cores[c]) return DCTN_ERR_NULL;
-    p.core[c] = cores[c];
-    p.dcore[c] = nullptr;
-  }
   hipStream_t st = (hipStream_t)stream;
+  const auto wide = [&](auto s, auto a) {
+    return wide_launch<decltype(s), decltype(a)>(x, dY, dX, dCores, workspace, workspace_bytes, p, sh, st);
+  };
   if (dtype_flags & DCTN_SBS_WIDE_SWEEP) {   // forced: the wide family for every string it covers
-    switch (dtype) {
-      case DCTN_F32: rc = wide_launch<float, float>(x, dY, dX, dCores, workspace, workspace_bytes, p, dtype, st); break;
-      case DCTN_F64: rc = wide_launch<double, double>(x, dY, dX, dCores, workspace, workspace_bytes, p, dtype, st); break;
-      case DCTN_BF16: rc = wide_launch<bf16_t, float>(x, dY, dX, dCores, workspace, workspace_bytes, p, dtype, st); break;
-      default: return DCTN_ERR_BAD_DTYPE;
+    rc = with_types(sh.dtype, wide);
+    if (rc != DCTN_ERR_UNSUPPORTED) return rc;
+  }
+  if (sh.dtype == DCTN_F32 && band_family_first(sh, dtype_flags)) {   // (true whenever the register family is tried)
+    for (int c = 0; dCores && c < n_cores; ++c)
+      if (!dCores[c]) return DCTN_ERR_NULL;
+    if (!(dtype_flags & DCTN_SBS_MATRIX_CORE_SWEEP)) {
+      rc = convsbs_bwd_reg(x, x_strides, cores, dY, dX, (float* const*)dCores, sh, st, workspace, workspace_bytes);
+      if (rc != DCTN_ERR_UNSUPPORTED) return rc;
     }
-    if (rc != DCTN_ERR_UNSUPPORTED) return rc;
-  }
-  if (dtype == DCTN_F32 && !(dtype_flags & DCTN_SBS_MATRIX_CORE_SWEEP)) {
-    for (int c = 0; dCores && c < n_cores; ++c)
-      if (!dCores[c]) return DCTN_ERR_NULL;
-    rc = convsbs_bwd_reg(x, x_strides, cores, dY, dX, (float* const*)dCores, n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H,
-                         W, q, dtype, st, workspace, workspace_bytes);
-    if (rc != DCTN_ERR_UNSUPPORTED) return rc;
-  }
-  if (dtype == DCTN_F32 && !((dtype_flags & DCTN_SBS_MATRIX_CORE_SWEEP) && sbs_largest_bond(n_cores, bond_sizes) <= 8)) {
     // bonds 5..16: the band-owning backward (recomputes the chain; no saved states, no helper launches)
-    for (int c = 0; dCores && c < n_cores; ++c)
-      if (!dCores[c]) return DCTN_ERR_NULL;
-    rc = convsbs_bwd_band(x, x_strides, cores, dY, dX, (float* const*)dCores, n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H,
-                          W, q, dtype, st, workspace, workspace_bytes);
+    rc = convsbs_bwd_band(x, x_strides, cores, dY, dX, (float* const*)dCores, sh, st, workspace, workspace_bytes);
     if (rc != DCTN_ERR_UNSUPPORTED) return rc;
   }
   // the generic sweep declines only in its LDS plan, before it writes anything: the wide family takes those strings
-  switch (dtype) {
-    case DCTN_F32:
-      rc = bwd_launch<float, float>(x, dY, dX, dCores, workspace, workspace_bytes, p, dtype, st, saved_states);
-      if (rc != DCTN_ERR_UNSUPPORTED) return rc;
-      return wide_launch<float, float>(x, dY, dX, dCores, workspace, workspace_bytes, p, dtype, st);
-    case DCTN_F64:
-      rc = bwd_launch<double, double>(x, dY, dX, dCores, workspace, workspace_bytes, p, dtype, st);
-      if (rc != DCTN_ERR_UNSUPPORTED) return rc;
-      return wide_launch<double, double>(x, dY, dX, dCores, workspace, workspace_bytes, p, dtype, st);
-    case DCTN_BF16:
-      rc = bwd_launch<bf16_t, float>(x, dY, dX, dCores, workspace, workspace_bytes, p, dtype, st);
-      if (rc != DCTN_ERR_UNSUPPORTED) return rc;
-      return wide_launch<bf16_t, float>(x, dY, dX, dCores, workspace, workspace_bytes, p, dtype, st);
-  }
-  return DCTN_ERR_BAD_DTYPE;
+  rc = with_types(sh.dtype, [&](auto s, auto a) {
+    return bwd_launch<decltype(s), decltype(a)>(x, dY, dX, dCores, workspace, workspace_bytes, p, sh, st, saved_states);
+  });
+  return rc != DCTN_ERR_UNSUPPORTED ? rc : with_types(sh.dtype, wide);
 }
 
 // ---- several strings of one layer (ManyConvSBS, dctn/conv_sbs.py:314-370) in one launch each way
 size_t dctn_convsbs_many_workspace_bytes(int n_strings, int n_cores, const int* out_sizes, const int* bond_sizes, int C, int B,
                                          int H, int W, int q, const int* pos_h, const int* pos_w, int dtype) {
   if (!out_sizes || !bond_sizes || !pos_h || !pos_w) return 0;
-  const size_t a = convsbs_many_reg_bwd_workspace(n_strings, n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q,
-                                                  dtype & DCTN_DTYPE_MASK);
-  if (a > 0) return a;
-  return convsbs_many_band_bwd_workspace(n_strings, n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q,
-                                         dtype & DCTN_DTYPE_MASK);
+  const SbsShape sh{n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype & DCTN_DTYPE_MASK};
+  const size_t a = convsbs_many_reg_bwd_workspace(n_strings, sh);
+  return a > 0 ? a : convsbs_many_band_bwd_workspace(n_strings, sh);
 }
 
 int dctn_convsbs_many_fwd(const void* x, const int64_t x_strides[5], const void* const* cores, void* const* outs,
@@ -703,11 +681,10 @@ int dctn_convsbs_many_fwd(const void* x, const int64_t x_strides[5], const void*
   if (dtype & ~DCTN_DTYPE_MASK) return DCTN_ERR_UNSUPPORTED;
   for (int i = 0; i < n_strings * n_cores; ++i)
     if (!cores[i]) return DCTN_ERR_NULL;
-  const int rc = convsbs_many_fwd_reg(x, x_strides, cores, outs, n_strings, n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H,
-                                      W, q, dtype, (hipStream_t)stream);
+  const SbsShape sh{n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype};
+  const int rc = convsbs_many_fwd_reg(x, x_strides, cores, outs, n_strings, sh, (hipStream_t)stream);
   if (rc != DCTN_ERR_UNSUPPORTED) return rc;
-  return convsbs_many_fwd_band(x, x_strides, cores, outs, n_strings, n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q,
-                               dtype, (hipStream_t)stream);
+  return convsbs_many_fwd_band(x, x_strides, cores, outs, n_strings, sh, (hipStream_t)stream);
 }
 
 int dctn_convsbs_many_bwd(const void* x, const int64_t x_strides[5], const void* const* cores, const void* const* dYs, void* dX,
@@ -720,11 +697,12 @@ int dctn_convsbs_many_bwd(const void* x, const int64_t x_strides[5], const void*
   if (!dX && !dCores) return DCTN_OK;
   for (int i = 0; i < n_strings * n_cores; ++i)
     if (!cores[i] || (dCores && !dCores[i])) return DCTN_ERR_NULL;
-  const int rc = convsbs_many_bwd_reg(x, x_strides, cores, dYs, dX, (float* const*)dCores, n_strings, n_cores, out_sizes, bond_sizes,
-                                      pos_h, pos_w, C, B, H, W, q, dtype, (hipStream_t)stream, workspace, workspace_bytes);
+  const SbsShape sh{n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype};
+  const int rc = convsbs_many_bwd_reg(x, x_strides, cores, dYs, dX, (float* const*)dCores, n_strings, sh, (hipStream_t)stream,
+                                      workspace, workspace_bytes);
   if (rc != DCTN_ERR_UNSUPPORTED) return rc;
-  return convsbs_many_bwd_band(x, x_strides, cores, dYs, dX, (float* const*)dCores, n_strings, n_cores, out_sizes, bond_sizes,
-                               pos_h, pos_w, C, B, H, W, q, dtype, (hipStream_t)stream, workspace, workspace_bytes);
+  return convsbs_many_bwd_band(x, x_strides, cores, dYs, dX, (float* const*)dCores, n_strings, sh, (hipStream_t)stream, workspace,
+                               workspace_bytes);
 }
 
 }  // extern "C"

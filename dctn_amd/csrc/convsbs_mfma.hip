@@ -1313,65 +1313,63 @@ __global__ __launch_bounds__(256) void convsbs_dcore_reduce_k(SbsMP p, int nrec)
 
 // Family check + parameter block shared by forward and backward; *lds_floats = floats of LDS used
 // by the core packs and tables.  DCTN_ERR_UNSUPPORTED when the string is outside the family.
-static int sbsm_fill(SbsMP& p, int& R, int& lds_floats, const int64_t xs[5], const void* const* cores, int n,
-                     const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w,
-                     int C, int B, int H, int W, int q, int dtype) {
-  if (dtype != DCTN_F32 || n < 3 || n > SBSM_MAXC) return DCTN_ERR_UNSUPPORTED;
+static int sbsm_fill(SbsMP& p, int& R, int& lds_floats, const int64_t xs[5], const void* const* cores, const SbsShape& sh) {
+  if (sh.dtype != DCTN_F32 || sh.n < 3 || sh.n > SBSM_MAXC) return DCTN_ERR_UNSUPPORTED;
   // any bonds 1..32 (they need not be equal) run on the next of the kernels' tile sizes {4, 8, 16, 32} above the largest:
   // packs and tables are zero beyond a core's own bonds, so are the states, and only the real entries of a gradient are
   // written back
-  if (bond_sizes[0] != 1) return DCTN_ERR_UNSUPPORTED;
+  if (sh.bond_sizes[0] != 1) return DCTN_ERR_UNSUPPORTED;
   int Ra = 0;
-  for (int c = 1; c < n; ++c) {
-    if (bond_sizes[c] < 1 || bond_sizes[c] > 32) return DCTN_ERR_UNSUPPORTED;
-    Ra = bond_sizes[c] > Ra ? bond_sizes[c] : Ra;
+  for (int c = 1; c < sh.n; ++c) {
+    if (sh.bond_sizes[c] < 1 || sh.bond_sizes[c] > 32) return DCTN_ERR_UNSUPPORTED;
+    Ra = sh.bond_sizes[c] > Ra ? sh.bond_sizes[c] : Ra;
   }
   if (Ra < 2) return DCTN_ERR_UNSUPPORTED;
   R = Ra <= 4 ? 4 : Ra <= 8 ? 8 : Ra <= 16 ? 16 : 32;
   p.Ra = Ra;
-  for (int c = 0; c < n; ++c) {
-    p.bl[c] = c == 0 ? 1 : bond_sizes[c];
-    p.br[c] = c == n - 1 ? 1 : bond_sizes[c + 1];
+  for (int c = 0; c < sh.n; ++c) {
+    p.bl[c] = c == 0 ? 1 : sh.bond_sizes[c];
+    p.br[c] = c == sh.n - 1 ? 1 : sh.bond_sizes[c + 1];
   }
   long long qc = 1;
-  for (int c = 0; c < C; ++c) qc *= q;
-  if (qc > 4 || C > 2 || q > 4) return DCTN_ERR_UNSUPPORTED;
+  for (int c = 0; c < sh.C; ++c) qc *= sh.q;
+  if (qc > 4 || sh.C > 2 || sh.q > 4) return DCTN_ERR_UNSUPPORTED;
   for (int qq = 0; qq < 4; ++qq) {
     int t = qq;
-    for (int ch = C - 1; ch >= 0; --ch) { p.digit[qq][ch] = (unsigned char)(t % q); t /= q; }
-    for (int ch = C; ch < 4; ++ch) p.digit[qq][ch] = 0;
+    for (int ch = sh.C - 1; ch >= 0; --ch) { p.digit[qq][ch] = (unsigned char)(t % sh.q); t /= sh.q; }
+    for (int ch = sh.C; ch < 4; ++ch) p.digit[qq][ch] = 0;
   }
   long long otot = 1;
-  for (int c = 0; c < n; ++c) {
-    if (out_sizes[c] < 1 || out_sizes[c] > 2) return DCTN_ERR_UNSUPPORTED;
-    otot *= out_sizes[c];
+  for (int c = 0; c < sh.n; ++c) {
+    if (sh.out_sizes[c] < 1 || sh.out_sizes[c] > 2) return DCTN_ERR_UNSUPPORTED;
+    otot *= sh.out_sizes[c];
   }
-  if (otot > 2 || out_sizes[0] != 1 || out_sizes[n - 1] != 1) return DCTN_ERR_UNSUPPORTED;
-  p.n = n; p.C = C; p.B = B; p.H = H; p.W = W; p.q = q; p.qc = (int)qc; p.Otot = (int)otot;
+  if (otot > 2 || sh.out_sizes[0] != 1 || sh.out_sizes[sh.n - 1] != 1) return DCTN_ERR_UNSUPPORTED;
+  p.n = sh.n; p.C = sh.C; p.B = sh.B; p.H = sh.H; p.W = sh.W; p.q = sh.q; p.qc = (int)qc; p.Otot = (int)otot;
   p.ostride = (int)otot; p.obase = 0; p.ostep = 1; p.accum = 0; p.out_accum = 0; p.last_stride = (int)qc; p.save = nullptr;
   int max_h = 0, max_w = 0;
-  for (int c = 0; c < n; ++c) {
-    p.o[c] = out_sizes[c]; p.ph[c] = pos_h[c]; p.pw[c] = pos_w[c];
+  for (int c = 0; c < sh.n; ++c) {
+    p.o[c] = sh.out_sizes[c]; p.ph[c] = sh.pos_h[c]; p.pw[c] = sh.pos_w[c];
     p.core[c] = (const float*)cores[c];
     p.dcore[c] = nullptr;
     p.partials = nullptr;
-    max_h = pos_h[c] > max_h ? pos_h[c] : max_h;
-    max_w = pos_w[c] > max_w ? pos_w[c] : max_w;
+    max_h = sh.pos_h[c] > max_h ? sh.pos_h[c] : max_h;
+    max_w = sh.pos_w[c] > max_w ? sh.pos_w[c] : max_w;
   }
-  p.Ho = H - max_h; p.Wo = W - max_w;
+  p.Ho = sh.H - max_h; p.Wo = sh.W - max_w;
   if (p.Ho < 1 || p.Wo < 1) return DCTN_ERR_BAD_SHAPE;
-  p.Wn = (long long)B * p.Ho * p.Wo;
+  p.Wn = (long long)sh.B * p.Ho * p.Wo;
   p.ngroups = (p.Wn + 31) / 32;
   for (int i = 0; i < 5; ++i) p.s[i] = xs[i];
   const int KS = R / 2, TILES = R >= 8 ? R / 8 : 1;
   int off = 0;
-  for (int c = 1; c + 1 < n; ++c) {
+  for (int c = 1; c + 1 < sh.n; ++c) {
     p.apack_off[c] = off;
     off += p.o[c] * TILES * KS * ROWP;
   }
   p.first_off = off; off += R * 4;
   p.last_off = off; off += R * 4;
-  p.fs_off = off; off += 4 * n * 128;
+  p.fs_off = off; off += 4 * sh.n * 128;
   lds_floats = off;
   return DCTN_OK;
 }
@@ -1385,24 +1383,22 @@ struct SbsSlice {   // one launch of a string that runs in slices (many-valued c
   int sliced, obase, ostride, accum, out_accum, last_stride, ostep;
 };
 
-static int convsbs_fwd_mfma_one(const void* x, const int64_t xs[5], const void* const* cores, void* out, int n,
-                                const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w,
-                                int C, int B, int H, int W, int q, int dtype, hipStream_t st, const SbsSlice& sl,
-                                float* save) {
+static int convsbs_fwd_mfma_one(const void* x, const int64_t xs[5], const void* const* cores, void* out, const SbsShape& sh,
+                                hipStream_t st, const SbsSlice& sl, float* save) {
   SbsMP p;
   int R, off;
-  const int rcf = sbsm_fill(p, R, off, xs, cores, n, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype);
+  const int rcf = sbsm_fill(p, R, off, xs, cores, sh);
   if (rcf != DCTN_OK) return rcf;
   if (sl.sliced) { p.ostride = sl.ostride; p.obase = sl.obase; p.ostep = sl.ostep; p.out_accum = sl.out_accum; p.last_stride = sl.last_stride; }
   if (save && !sl.sliced && R <= 16) {   // input states of cores 1 .. n-1 for the backward (same offsets as its own sweep)
     long long so = 0;
     int oacc = 1;
-    for (int c = 0; c < n; ++c) {
+    for (int c = 0; c < sh.n; ++c) {
       p.st_off[c] = so;
       if (c >= 1) so += (long long)oacc * R;
       oacc *= p.o[c];
     }
-    p.st_off[n] = so;
+    p.st_off[sh.n] = so;
     p.save = save;
   }
   const size_t lds = (size_t)off * sizeof(float);
@@ -1441,16 +1437,18 @@ static int convsbs_fwd_mfma_one(const void* x, const int64_t xs[5], const void* 
 //   * the PAIR core m = the last middle core with more than one output: its outputs go two per launch;
 //   * every other core with several outputs is walked one output at a time (the [l][r][q] block of that output).
 // The flat output index is row-major over the cores in string order, so a slice's two outputs are prod(o_c, c > m) apart.
-// `visit` gets the slice's core views (as element offsets into the cores - the gradients use the same), output sizes, bonds
+// `visit` gets the slice's core views (as element offsets into the cores - the gradients use the same), its shape
 // and SbsSlice; a non-OK return stops the walk (the first slice decides: all later ones have the same LDS plan).
 constexpr int SBSM_MAX_SLICES = 96;   // beyond that the generic sweep's single launch wins
-static bool sbsm_whole(int n, const int* out_sizes, const int* bond_sizes) {
+static bool sbsm_whole(const SbsShape& sh) {
   long long otot = 1;
-  for (int c = 0; c < n; ++c) otot *= out_sizes[c];
-  return bond_sizes[0] == 1 && otot <= 2 && out_sizes[0] == 1 && out_sizes[n - 1] == 1;
+  for (int c = 0; c < sh.n; ++c) otot *= sh.out_sizes[c];
+  return sh.bond_sizes[0] == 1 && otot <= 2 && sh.out_sizes[0] == 1 && sh.out_sizes[sh.n - 1] == 1;
 }
 template <typename F>
-static int sbsm_for_slices(int n, const void* const* cores, const int* out_sizes, const int* bond_sizes, int C, int q, F visit) {
+static int sbsm_for_slices(const SbsShape& sh, F visit) {
+  const int n = sh.n, C = sh.C, q = sh.q;
+  const int *out_sizes = sh.out_sizes, *bond_sizes = sh.bond_sizes;
   if (n < 3 || n > SBSM_MAXC) return DCTN_ERR_UNSUPPORTED;
   long long otot = 1, qc = 1;
   for (int c = 0; c < n; ++c) {
@@ -1462,9 +1460,12 @@ static int sbsm_for_slices(int n, const void* const* cores, const int* out_sizes
   int outs[SBSM_MAXC], bonds[SBSM_MAXC];
   long long coff[SBSM_MAXC];
   for (int c = 0; c < n; ++c) { outs[c] = out_sizes[c]; bonds[c] = bond_sizes[c]; coff[c] = 0; }
-  if (sbsm_whole(n, out_sizes, bond_sizes)) {
+  SbsShape slice = sh;   // the string of one launch: this string with the slice's output sizes and bonds
+  slice.out_sizes = outs;
+  slice.bond_sizes = bonds;
+  if (sbsm_whole(sh)) {
     const SbsSlice whole{0, 0, 0, 0, 0, 0, 1};
-    return visit(coff, outs, bonds, whole);
+    return visit(coff, slice, whole);
   }
   const int R0 = bond_sizes[0];   // the closing bond of a ring (1: open chain)
   const bool ring = R0 > 1;
@@ -1498,7 +1499,7 @@ static int sbsm_for_slices(int n, const void* const* cores, const int* out_sizes
         coff[n - 1] += (long long)l0 * qc;
       }
       const SbsSlice sl{1, (int)obase, (int)otot, !first, l0 > 0, (int)(ring ? R0 * qc : qc), m >= 0 ? (int)ostr[m] : 1};
-      const int rc = visit(coff, outs, bonds, sl);
+      const int rc = visit(coff, slice, sl);
       if (rc != DCTN_OK) return rc == DCTN_ERR_UNSUPPORTED && !first ? DCTN_ERR_LAUNCH : rc;   // (earlier slices ran: no fall-through)
       first = false;
     }
@@ -1515,38 +1516,34 @@ static int sbsm_for_slices(int n, const void* const* cores, const int* out_sizes
 
 // Bytes of the forward states a training forward can leave for the backward (0: this string recomputes them - slices,
 // bonds above 16, shapes outside the family).
-size_t convsbs_saved_states_bytes(int n, const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w,
-                                  int C, int B, int H, int W, int q, int dtype) {
-  if (dtype != DCTN_F32 || n < 3 || n > SBSM_MAXC) return 0;
-  if (!sbsm_whole(n, out_sizes, bond_sizes)) return 0;
+size_t convsbs_saved_states_bytes(const SbsShape& sh) {
+  if (sh.dtype != DCTN_F32 || sh.n < 3 || sh.n > SBSM_MAXC) return 0;
+  if (!sbsm_whole(sh)) return 0;
   // strings the band-owning backward takes (convsbs_band.hip) recompute the chain in registers: nothing to keep
-  if (convsbs_band_covers(n, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype)) return 0;
+  if (convsbs_band_covers(sh)) return 0;
   SbsMP p;
   int R, off;
   const int64_t dummy[5] = {0, 0, 0, 0, 1};
   const void* none[SBSM_MAXC] = {};
-  if (sbsm_fill(p, R, off, dummy, none, n, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype) != DCTN_OK || R > 16) return 0;
+  if (sbsm_fill(p, R, off, dummy, none, sh) != DCTN_OK || R > 16) return 0;
   if (R < 8) return 0;   // bond <= 4: storing costs the forward what the backward saves (80 -> 83 us at the cfg4 shape)
   long long so = 0;
   int oacc = 1;
-  for (int c = 0; c < n; ++c) {
+  for (int c = 0; c < sh.n; ++c) {
     if (c >= 1) so += (long long)oacc * R;
     oacc *= p.o[c];
   }
   return (size_t)so * (size_t)p.Wn * sizeof(float);
 }
 
-int convsbs_fwd_mfma(const void* x, const int64_t xs[5], const void* const* cores, void* out, int n,
-                     const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w,
-                     int C, int B, int H, int W, int q, int dtype, hipStream_t st, float* save_states) {
-  if (dtype != DCTN_F32) return DCTN_ERR_UNSUPPORTED;
-  return sbsm_for_slices(n, cores, out_sizes, bond_sizes, C, q,
-                         [&](const long long* coff, const int* outs, const int* bonds, const SbsSlice& sl) {
-                           const void* cp[SBSM_MAXC];
-                           for (int c = 0; c < n; ++c) cp[c] = (const float*)cores[c] + coff[c];
-                           return convsbs_fwd_mfma_one(x, xs, cp, out, n, outs, bonds, pos_h, pos_w, C, B, H, W, q, dtype, st, sl,
-                                                       save_states);
-                         });
+int convsbs_fwd_mfma(const void* x, const int64_t xs[5], const void* const* cores, void* out, const SbsShape& sh,
+                     hipStream_t st, float* save_states) {
+  if (sh.dtype != DCTN_F32) return DCTN_ERR_UNSUPPORTED;
+  return sbsm_for_slices(sh, [&](const long long* coff, const SbsShape& slice, const SbsSlice& sl) {
+    const void* cp[SBSM_MAXC];
+    for (int c = 0; c < sh.n; ++c) cp[c] = (const float*)cores[c] + coff[c];
+    return convsbs_fwd_mfma_one(x, xs, cp, out, slice, st, sl, save_states);
+  });
 }
 
 // Backward of the same family (R <= 16).  `states` must hold sum_c oacc_c * R floats per window
@@ -1554,14 +1551,12 @@ int convsbs_fwd_mfma(const void* x, const int64_t xs[5], const void* const* core
 // [(c*C + ch)*q + qv][Wn] (may be NULL when dX is not needed), `dcores[c]` zero-initialised float
 // accumulators (may be NULL array when no core gradient is needed... the kernel still runs its
 // dCore part into LDS only).
-static int convsbs_bwd_mfma_one(const void* x, const int64_t xs[5], const void* const* cores, const void* dY,
-                                float* states, float* gxw, float* const* dcores, int n, const int* out_sizes,
-                                const int* bond_sizes, const int* pos_h, const int* pos_w, int C, int B, int H, int W,
-                                int q, int dtype, hipStream_t st, float* partials, size_t partial_bytes,
-                                const SbsSlice& sl, const float* saved) {
+static int convsbs_bwd_mfma_one(const void* x, const int64_t xs[5], const void* const* cores, const void* dY, float* states,
+                                float* gxw, float* const* dcores, const SbsShape& sh, hipStream_t st, float* partials,
+                                size_t partial_bytes, const SbsSlice& sl, const float* saved) {
   SbsMP p;
   int R, off;
-  const int rcf = sbsm_fill(p, R, off, xs, cores, n, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype);
+  const int rcf = sbsm_fill(p, R, off, xs, cores, sh);
   if (rcf != DCTN_OK) return rcf;
   if (R > 16 || !dcores || !states) return DCTN_ERR_UNSUPPORTED;
   if (sl.sliced) { p.ostride = sl.ostride; p.obase = sl.obase; p.ostep = sl.ostep; p.accum = sl.accum; p.last_stride = sl.last_stride; }
@@ -1570,42 +1565,42 @@ static int convsbs_bwd_mfma_one(const void* x, const int64_t xs[5], const void* 
   if (use_saved) states = const_cast<float*>(saved);
   long long so = 0;
   int oacc = 1;
-  for (int c = 0; c < n; ++c) {
+  for (int c = 0; c < sh.n; ++c) {
     p.st_off[c] = so;
     if (c >= 1) so += (long long)oacc * R;
     oacc *= p.o[c];
     p.dcore[c] = dcores[c];
   }
-  p.st_off[n] = so;
+  p.st_off[sh.n] = so;
   {
     // second version (16x16x4 tiles): its own LDS plan - two packs of every middle core, the accumulators in
     // accumulator layout, the per-wave feature slices and transposition tiles
     const int MT = R / 4, KS = R / 4, KA = R, ZROW = 4 * R + 16;
     int o2 = 0;
     SbsMP q2 = p;
-    for (int c = 1; c + 1 < n; ++c) { q2.apack_off[c] = o2; o2 += p.o[c] * MT * KS * 64; }
-    for (int c = 1; c + 1 < n; ++c) { q2.apack2_off[c] = o2; o2 += p.o[c] * MT * KS * 64; }
+    for (int c = 1; c + 1 < sh.n; ++c) { q2.apack_off[c] = o2; o2 += p.o[c] * MT * KS * 64; }
+    for (int c = 1; c + 1 < sh.n; ++c) { q2.apack2_off[c] = o2; o2 += p.o[c] * MT * KS * 64; }
     q2.first_off = o2; o2 += R * 4;
     q2.last_off = o2; o2 += R * 4;
     const int NT16 = 2;   // window tiles per wave iteration (4 was tried for r = 16: 892 bytes of scratch per lane, slower)
     const int chmode = p.C == 1 ? 1 : (p.C == 2 && p.q == 2) ? 2 : 0;   // compiled channel handling (ONECH)
-    q2.fs_off = o2; o2 += 4 * n * 4 * 16 * NT16 * (chmode == 2 ? 2 : 1);
+    q2.fs_off = o2; o2 += 4 * sh.n * 4 * 16 * NT16 * (chmode == 2 ? 2 : 1);
     q2.zt_off = o2; o2 += 4 * 16 * ZROW;
     q2.vt_off = o2; o2 += 4 * 16 * 17;
     // the workgroup's dCore accumulator: with the register accumulators (n <= 9) it is only used by the final flush,
     // when the packs are dead, and lies over them; otherwise it is a region of its own
-    int o3 = (n <= 9) ? 0 : o2;
-    for (int c = 0; c < n; ++c) {
+    int o3 = (sh.n <= 9) ? 0 : o2;
+    for (int c = 0; c < sh.n; ++c) {
       q2.dacc_off[c] = o3;
-      o3 += (c == 0 || c == n - 1) ? ((R * p.qc + 3) / 4 * 4) : p.o[c] * MT * 256;
+      o3 += (c == 0 || c == sh.n - 1) ? ((R * p.qc + 3) / 4 * 4) : p.o[c] * MT * 256;
     }
-    q2.dacc_off[n] = o3;
+    q2.dacc_off[sh.n] = o3;
     if (o3 > o2) o2 = o3;
     const size_t lds2 = (size_t)o2 * sizeof(float);
     p.ngroups = (p.Wn + 16 * NT16 - 1) / (16 * NT16);
     q2.ngroups = p.ngroups;
     q2.core_off[0] = 0;
-    for (int c = 0; c < n; ++c) {
+    for (int c = 0; c < sh.n; ++c) {
       q2.core_off[c + 1] = q2.core_off[c] + p.o[c] * p.bl[c] * p.br[c] * p.qc;
     }
     if (lds2 <= dctn_lds_wg_max()) {
@@ -1615,7 +1610,7 @@ static int convsbs_bwd_mfma_one(const void* x, const int64_t xs[5], const void* 
       const long long resident = dctn_resident_wgs(lds2, 1, 8);
       if (blocks > resident) blocks = resident;
       if (blocks > SBS_MAX_PARTIAL_RECORDS - 64) blocks = SBS_MAX_PARTIAL_RECORDS - 64;   // room for the second-stage records
-      q2.partials = (partials && partial_bytes >= (size_t)blocks * q2.core_off[n] * sizeof(float)) ? partials : nullptr;
+      q2.partials = (partials && partial_bytes >= (size_t)blocks * q2.core_off[sh.n] * sizeof(float)) ? partials : nullptr;
 #define SBS_LAUNCH_B16_1(RR, NCV, NTV, CHV, SV)                                                    \
   do {                                                                                            \
     if (!dctn_lds_optin((const void*)convsbs_bwd_mfma16_k<RR, NCV, NTV, CHV, SV>, lds2)) return DCTN_ERR_UNSUPPORTED; \
@@ -1633,9 +1628,9 @@ static int convsbs_bwd_mfma_one(const void* x, const int64_t xs[5], const void* 
     if (use_saved) SBS_LAUNCH_B16_S(RR, NCV, NTV, true); else SBS_LAUNCH_B16_S(RR, NCV, NTV, false); \
   } while (0)
       switch (R) {   // up to 9 cores (mnist.py:189-223): register accumulators; longer strings: LDS accumulators
-        case 4: if (n <= 9) SBS_LAUNCH_B16(4, 9, 2); else SBS_LAUNCH_B16(4, 0, 2); break;
-        case 8: if (n <= 9) SBS_LAUNCH_B16(8, 9, 2); else SBS_LAUNCH_B16(8, 0, 2); break;
-        case 16: if (n <= 9) SBS_LAUNCH_B16(16, 9, 2); else SBS_LAUNCH_B16(16, 0, 2); break;
+        case 4: if (sh.n <= 9) SBS_LAUNCH_B16(4, 9, 2); else SBS_LAUNCH_B16(4, 0, 2); break;
+        case 8: if (sh.n <= 9) SBS_LAUNCH_B16(8, 9, 2); else SBS_LAUNCH_B16(8, 0, 2); break;
+        case 16: if (sh.n <= 9) SBS_LAUNCH_B16(16, 9, 2); else SBS_LAUNCH_B16(16, 0, 2); break;
         default: return DCTN_ERR_UNSUPPORTED;
       }
 #undef SBS_LAUNCH_B16
@@ -1644,7 +1639,7 @@ static int convsbs_bwd_mfma_one(const void* x, const int64_t xs[5], const void* 
       DCTN_CHECK_LAUNCH();
       if (q2.partials) {
         int nrec = (int)blocks;
-        const int total = q2.core_off[n], n2 = (nrec + 31) / 32;
+        const int total = q2.core_off[sh.n], n2 = (nrec + 31) / 32;
         // many records of a small core: two stages (the one-stage form ran 13 workgroups over 768 records: 21 us)
         if (nrec > 64 && partial_bytes >= (size_t)(nrec + n2) * total * sizeof(float)) {
           hipLaunchKernelGGL(convsbs_dcore_prereduce_k, dim3((unsigned)((total + 255) / 256), (unsigned)n2), dim3(256), 0, st,
@@ -1662,23 +1657,23 @@ static int convsbs_bwd_mfma_one(const void* x, const int64_t xs[5], const void* 
   }
   // first version (32x32x2 tiles, R <= 16): strings whose packs do not fit the second version's LDS plan
   bool full_tiles = true;   // every inner bond equal to the tile size
-  for (int c = 1; c < n; ++c) full_tiles = full_tiles && bond_sizes[c] == R;
+  for (int c = 1; c < sh.n; ++c) full_tiles = full_tiles && sh.bond_sizes[c] == R;
   if (sl.sliced || !full_tiles || use_saved) return DCTN_ERR_UNSUPPORTED;   // (slices, padded bonds, saved states: second version only)
   p.ngroups = (p.Wn + 31) / 32;
   so = 0;
   oacc = 1;
   int dacc = off;
-  for (int c = 0; c < n; ++c) {
+  for (int c = 0; c < sh.n; ++c) {
     p.st_off[c] = so;
     if (c >= 1) so += (long long)oacc * R;
     oacc *= p.o[c];
     p.dacc_off[c] = dacc;
-    const int L = c == 0 ? 1 : R, Rr = c == n - 1 ? 1 : R;
+    const int L = c == 0 ? 1 : R, Rr = c == sh.n - 1 ? 1 : R;
     dacc += p.o[c] * L * Rr * p.qc;
     p.dcore[c] = dcores[c];
   }
-  p.st_off[n] = so;
-  p.dacc_off[n] = dacc;
+  p.st_off[sh.n] = so;
+  p.dacc_off[sh.n] = dacc;
   const size_t lds = (size_t)(dacc + 1) * sizeof(float);
   if (lds > dctn_lds_wg_max()) return DCTN_ERR_UNSUPPORTED;
   long long blocks = (p.ngroups + 3) / 4;
@@ -1700,20 +1695,17 @@ static int convsbs_bwd_mfma_one(const void* x, const int64_t xs[5], const void* 
   return DCTN_OK;
 }
 
-int convsbs_bwd_mfma(const void* x, const int64_t xs[5], const void* const* cores, const void* dY,
-                     float* states, float* gxw, float* const* dcores, int n, const int* out_sizes,
-                     const int* bond_sizes, const int* pos_h, const int* pos_w, int C, int B, int H, int W,
-                     int q, int dtype, hipStream_t st, float* partials, size_t partial_bytes, const float* saved_states) {
-  if (dtype != DCTN_F32 || !dcores) return DCTN_ERR_UNSUPPORTED;
-  return sbsm_for_slices(n, cores, out_sizes, bond_sizes, C, q,
-                         [&](const long long* coff, const int* outs, const int* bonds, const SbsSlice& sl) {
-                           const void* cp[SBSM_MAXC];
-                           float* dcp[SBSM_MAXC];   // the gradient views follow the core views
-                           for (int c = 0; c < n; ++c) {
-                             cp[c] = (const float*)cores[c] + coff[c];
-                             dcp[c] = dcores[c] + coff[c];
-                           }
-                           return convsbs_bwd_mfma_one(x, xs, cp, dY, states, gxw, dcp, n, outs, bonds, pos_h, pos_w, C, B, H,
-                                                       W, q, dtype, st, partials, partial_bytes, sl, saved_states);
-                         });
+int convsbs_bwd_mfma(const void* x, const int64_t xs[5], const void* const* cores, const void* dY, float* states, float* gxw,
+                     float* const* dcores, const SbsShape& sh, hipStream_t st, float* partials, size_t partial_bytes,
+                     const float* saved_states) {
+  if (sh.dtype != DCTN_F32 || !dcores) return DCTN_ERR_UNSUPPORTED;
+  return sbsm_for_slices(sh, [&](const long long* coff, const SbsShape& slice, const SbsSlice& sl) {
+    const void* cp[SBSM_MAXC];
+    float* dcp[SBSM_MAXC];   // the gradient views follow the core views
+    for (int c = 0; c < sh.n; ++c) {
+      cp[c] = (const float*)cores[c] + coff[c];
+      dcp[c] = dcores[c] + coff[c];
+    }
+    return convsbs_bwd_mfma_one(x, xs, cp, dY, states, gxw, dcp, slice, st, partials, partial_bytes, sl, saved_states);
+  });
 }

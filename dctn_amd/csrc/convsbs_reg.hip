@@ -1314,60 +1314,59 @@ struct SrPlan {
   size_t lds_bwd;
 };
 
-bool sr_fill(SrP& p, SrPlan& pl, const void* x, const int64_t xs[5], const void* const* cores, int n, const int* out_sizes,
-             const int* bond_sizes, const int* pos_h, const int* pos_w, int C, int B, int H, int W, int q, int dtype) {
-  if (dtype != DCTN_F32 || n < 2 || n > SR_MAXC) return false;
-  if (bond_sizes[0] != 1) return false;            // open chains (rings are walked as slices by the matrix-core family)
+bool sr_fill(SrP& p, SrPlan& pl, const void* x, const int64_t xs[5], const void* const* cores, const SbsShape& sh) {
+  if (sh.dtype != DCTN_F32 || sh.n < 2 || sh.n > SR_MAXC) return false;
+  if (sh.bond_sizes[0] != 1) return false;            // open chains (rings are walked as slices by the matrix-core family)
   int qc = 1;
-  for (int c = 0; c < C; ++c) qc *= q;
-  if (!((C == 1 && q >= 2 && q <= 4) || (C == 2 && q == 2))) return false;
+  for (int c = 0; c < sh.C; ++c) qc *= sh.q;
+  if (!((sh.C == 1 && sh.q >= 2 && sh.q <= 4) || (sh.C == 2 && sh.q == 2))) return false;
   int maxb = 1, otot = 1, max_h = 0, max_w = 0;
-  for (int c = 0; c < n; ++c) {
-    const int bl = bond_sizes[c], br = bond_sizes[(c + 1) % n];
+  for (int c = 0; c < sh.n; ++c) {
+    const int bl = sh.bond_sizes[c], br = sh.bond_sizes[(c + 1) % sh.n];
     if (bl < 1 || br < 1 || bl > 4 || br > 4) return false;
-    if (out_sizes[c] != 1 && out_sizes[c] != 2) return false;
-    otot *= out_sizes[c];
+    if (sh.out_sizes[c] != 1 && sh.out_sizes[c] != 2) return false;
+    otot *= sh.out_sizes[c];
     maxb = bl > maxb ? bl : maxb;
     maxb = br > maxb ? br : maxb;
-    max_h = pos_h[c] > max_h ? pos_h[c] : max_h;
-    max_w = pos_w[c] > max_w ? pos_w[c] : max_w;
+    max_h = sh.pos_h[c] > max_h ? sh.pos_h[c] : max_h;
+    max_w = sh.pos_w[c] > max_w ? sh.pos_w[c] : max_w;
     p.core[c] = cores ? (const float*)cores[c] : nullptr;
-    p.o[c] = out_sizes[c]; p.bl[c] = bl; p.br[c] = br; p.ph[c] = pos_h[c]; p.pw[c] = pos_w[c];
+    p.o[c] = sh.out_sizes[c]; p.bl[c] = bl; p.br[c] = br; p.ph[c] = sh.pos_h[c]; p.pw[c] = sh.pos_w[c];
   }
   if (otot > 2 || maxb < 2) return false;
-  for (int c = n; c < SR_MAXC; ++c) { p.core[c] = nullptr; p.o[c] = 1; p.bl[c] = 1; p.br[c] = 1; p.ph[c] = 0; p.pw[c] = 0; }
-  if (H <= max_h || W <= max_w) return false;
+  for (int c = sh.n; c < SR_MAXC; ++c) { p.core[c] = nullptr; p.o[c] = 1; p.bl[c] = 1; p.br[c] = 1; p.ph[c] = 0; p.pw[c] = 0; }
+  if (sh.H <= max_h || sh.W <= max_w) return false;
   p.x = (const float*)x;
   for (int i = 0; i < 5; ++i) p.xs[i] = xs ? xs[i] : 0;
-  p.n = n; p.C = C; p.q = q; p.B = B; p.H = H; p.W = W; p.Ho = H - max_h; p.Wo = W - max_w; p.Otot = otot; p.max_h = max_h;
-  p.Wn = (long long)B * p.Ho * p.Wo;
+  p.n = sh.n; p.C = sh.C; p.q = sh.q; p.B = sh.B; p.H = sh.H; p.W = sh.W; p.Ho = sh.H - max_h; p.Wo = sh.W - max_w; p.Otot = otot; p.max_h = max_h;
+  p.Wn = (long long)sh.B * p.Ho * p.Wo;
   p.dY = nullptr; p.dX = nullptr; p.part = nullptr;
   p.mv = -1; p.O = 0;
   pl.R = maxb <= 2 ? 2 : 4;
   pl.QC = qc;
-  pl.twoch = C == 2;
-  pl.uniform = n == SU_NC;
-  for (int c = 0; c < n && pl.uniform; ++c)
-    if (bond_sizes[c] != (c == 0 ? 1 : maxb)) pl.uniform = 0;
+  pl.twoch = sh.C == 2;
+  pl.uniform = sh.n == SU_NC;
+  for (int c = 0; c < sh.n && pl.uniform; ++c)
+    if (sh.bond_sizes[c] != (c == 0 ? 1 : maxb)) pl.uniform = 0;
   if (pl.uniform) pl.R = maxb;
   p.coff[0] = 0;
-  for (int c = 0; c < SR_MAXC; ++c) p.coff[c + 1] = p.coff[c] + (c < n ? p.o[c] * p.bl[c] * p.br[c] * qc : 0);
+  for (int c = 0; c < SR_MAXC; ++c) p.coff[c + 1] = p.coff[c] + (c < sh.n ? p.o[c] * p.bl[c] * p.br[c] * qc : 0);
   pl.tot = p.coff[SR_MAXC];
   p.out = nullptr;
   p.tot_all = pl.tot;
   for (int c = 0; c < SR_MAXC; ++c) p.slot[c] = c;
   // bands of pixel rows: the fewest per image whose windows fit one pass of the workgroup's lanes, more (down to
   // ~2 workgroups per CU) when the batch is small
-  const int NCq = n * C * q;
+  const int NCq = sh.n * sh.C * sh.q;
   const size_t PK = (size_t)SR_MAXC * 2 * pl.R * pl.R * pl.QC;
   const size_t fixed = pl.uniform ? (size_t)pl.tot * (SR_BWD_THREADS / 64) : PK * (1 + SR_BWD_THREADS / 64);
   int best = -1;
-  for (int nb = 1; nb <= H; ++nb) {
-    const int br = (H + nb - 1) / nb;
-    const int bands = (H + br - 1) / br;
+  for (int nb = 1; nb <= sh.H; ++nb) {
+    const int br = (sh.H + nb - 1) / nb;
+    const int bands = (sh.H + br - 1) / br;
     int maxwin = 0;
     for (int b2 = 0; b2 < bands; ++b2) {
-      const int r0 = b2 * br, r1 = r0 + br < H ? r0 + br : H;
+      const int r0 = b2 * br, r1 = r0 + br < sh.H ? r0 + br : sh.H;
       const int wr0 = r0 - max_h > 0 ? r0 - max_h : 0, wr1 = r1 < p.Ho ? r1 : p.Ho;
       const int nw = wr1 > wr0 ? (wr1 - wr0) * p.Wo : 0;
       maxwin = nw > maxwin ? nw : maxwin;
@@ -1375,68 +1374,67 @@ bool sr_fill(SrP& p, SrPlan& pl, const void* x, const int64_t xs[5], const void*
     const size_t lds = (fixed + (size_t)maxwin * NCq) * sizeof(float);
     if (lds > dctn_lds_wg_max()) continue;
     best = br; pl.max_w_in_band = maxwin; pl.lds_bwd = lds;
-    if (maxwin <= SR_BWD_THREADS && (long long)B * bands >= dctn_dev().cus) break;
+    if (maxwin <= SR_BWD_THREADS && (long long)sh.B * bands >= dctn_dev().cus) break;
     if (maxwin <= SR_BWD_THREADS / 2) break;   // finer bands only add redundant halo windows
   }
   if (best < 0) return false;
   pl.band_rows = best;
-  pl.bands = (H + best - 1) / best;
-  pl.nrec = B * pl.bands;
+  pl.bands = (sh.H + best - 1) / best;
+  pl.nrec = sh.B * pl.bands;
   p.band_rows = pl.band_rows; p.bands = pl.bands; p.nrec = pl.nrec;
   return true;
 }
 
 
 // the same for a string with ONE many-valued core (3..16 values; every other core one value)
-bool sm_fill(SrP& p, SrPlan& pl, const void* x, const int64_t xs[5], const void* const* cores, int n, const int* out_sizes,
-             const int* bond_sizes, const int* pos_h, const int* pos_w, int C, int B, int H, int W, int q, int dtype) {
-  if (dtype != DCTN_F32 || n < 2 || n > SR_MAXC || bond_sizes[0] != 1) return false;
+bool sm_fill(SrP& p, SrPlan& pl, const void* x, const int64_t xs[5], const void* const* cores, const SbsShape& sh) {
+  if (sh.dtype != DCTN_F32 || sh.n < 2 || sh.n > SR_MAXC || sh.bond_sizes[0] != 1) return false;
   int qc = 1;
-  for (int c = 0; c < C; ++c) qc *= q;
-  if (!((C == 1 && q >= 2 && q <= 4) || (C == 2 && q == 2))) return false;
+  for (int c = 0; c < sh.C; ++c) qc *= sh.q;
+  if (!((sh.C == 1 && sh.q >= 2 && sh.q <= 4) || (sh.C == 2 && sh.q == 2))) return false;
   int maxb = 1, max_h = 0, max_w = 0, mv = -1;
-  for (int c = 0; c < n; ++c) {
-    const int bl = bond_sizes[c], br = bond_sizes[(c + 1) % n];
+  for (int c = 0; c < sh.n; ++c) {
+    const int bl = sh.bond_sizes[c], br = sh.bond_sizes[(c + 1) % sh.n];
     if (bl < 1 || br < 1 || bl > 4 || br > 4) return false;
-    if (out_sizes[c] != 1) {
-      if (mv >= 0 || out_sizes[c] < 3 || out_sizes[c] > 16) return false;
+    if (sh.out_sizes[c] != 1) {
+      if (mv >= 0 || sh.out_sizes[c] < 3 || sh.out_sizes[c] > 16) return false;
       mv = c;
     }
     maxb = bl > maxb ? bl : maxb;
     maxb = br > maxb ? br : maxb;
-    max_h = pos_h[c] > max_h ? pos_h[c] : max_h;
-    max_w = pos_w[c] > max_w ? pos_w[c] : max_w;
+    max_h = sh.pos_h[c] > max_h ? sh.pos_h[c] : max_h;
+    max_w = sh.pos_w[c] > max_w ? sh.pos_w[c] : max_w;
     p.core[c] = cores ? (const float*)cores[c] : nullptr;
-    p.o[c] = out_sizes[c]; p.bl[c] = bl; p.br[c] = br; p.ph[c] = pos_h[c]; p.pw[c] = pos_w[c];
+    p.o[c] = sh.out_sizes[c]; p.bl[c] = bl; p.br[c] = br; p.ph[c] = sh.pos_h[c]; p.pw[c] = sh.pos_w[c];
   }
   if (mv < 0 || maxb < 2) return false;
-  for (int c = n; c < SR_MAXC; ++c) { p.core[c] = nullptr; p.o[c] = 1; p.bl[c] = 1; p.br[c] = 1; p.ph[c] = 0; p.pw[c] = 0; }
-  if (H <= max_h || W <= max_w) return false;
+  for (int c = sh.n; c < SR_MAXC; ++c) { p.core[c] = nullptr; p.o[c] = 1; p.bl[c] = 1; p.br[c] = 1; p.ph[c] = 0; p.pw[c] = 0; }
+  if (sh.H <= max_h || sh.W <= max_w) return false;
   p.x = (const float*)x;
   for (int i = 0; i < 5; ++i) p.xs[i] = xs ? xs[i] : 0;
-  p.n = n; p.C = C; p.q = q; p.B = B; p.H = H; p.W = W; p.Ho = H - max_h; p.Wo = W - max_w; p.max_h = max_h;
-  p.mv = mv; p.O = out_sizes[mv]; p.Otot = p.O;
-  p.Wn = (long long)B * p.Ho * p.Wo;
+  p.n = sh.n; p.C = sh.C; p.q = sh.q; p.B = sh.B; p.H = sh.H; p.W = sh.W; p.Ho = sh.H - max_h; p.Wo = sh.W - max_w; p.max_h = max_h;
+  p.mv = mv; p.O = sh.out_sizes[mv]; p.Otot = p.O;
+  p.Wn = (long long)sh.B * p.Ho * p.Wo;
   p.dY = nullptr; p.dX = nullptr; p.part = nullptr; p.out = nullptr;
   pl.R = maxb <= 2 ? 2 : 4;
   pl.QC = qc;
-  pl.twoch = C == 2;
+  pl.twoch = sh.C == 2;
   pl.uniform = 0;
   p.coff[0] = 0;
-  for (int c = 0; c < SR_MAXC; ++c) p.coff[c + 1] = p.coff[c] + (c < n ? p.o[c] * p.bl[c] * p.br[c] * qc : 0);
+  for (int c = 0; c < SR_MAXC; ++c) p.coff[c + 1] = p.coff[c] + (c < sh.n ? p.o[c] * p.bl[c] * p.br[c] * qc : 0);
   pl.tot = p.coff[SR_MAXC];
   p.tot_all = pl.tot;
   for (int c = 0; c < SR_MAXC; ++c) p.slot[c] = c;
-  const int NCq = n * C * q;
+  const int NCq = sh.n * sh.C * sh.q;
   const size_t PK = (size_t)(SR_MAXC + p.O) * pl.R * pl.R * pl.QC;
   const size_t fixed = PK * (1 + SR_BWD_THREADS / 64);
   int best = -1;
-  for (int nb = 1; nb <= H; ++nb) {
-    const int br = (H + nb - 1) / nb;
-    const int bands = (H + br - 1) / br;
+  for (int nb = 1; nb <= sh.H; ++nb) {
+    const int br = (sh.H + nb - 1) / nb;
+    const int bands = (sh.H + br - 1) / br;
     int maxwin = 0;
     for (int b2 = 0; b2 < bands; ++b2) {
-      const int r0 = b2 * br, r1 = r0 + br < H ? r0 + br : H;
+      const int r0 = b2 * br, r1 = r0 + br < sh.H ? r0 + br : sh.H;
       const int wr0 = r0 - max_h > 0 ? r0 - max_h : 0, wr1 = r1 < p.Ho ? r1 : p.Ho;
       const int nw = wr1 > wr0 ? (wr1 - wr0) * p.Wo : 0;
       maxwin = nw > maxwin ? nw : maxwin;
@@ -1444,13 +1442,13 @@ bool sm_fill(SrP& p, SrPlan& pl, const void* x, const int64_t xs[5], const void*
     const size_t lds = (fixed + (size_t)maxwin * NCq) * sizeof(float);
     if (lds > dctn_lds_wg_max()) continue;
     best = br; pl.max_w_in_band = maxwin; pl.lds_bwd = lds;
-    if (maxwin <= SR_BWD_THREADS && (long long)B * bands >= dctn_dev().cus) break;
+    if (maxwin <= SR_BWD_THREADS && (long long)sh.B * bands >= dctn_dev().cus) break;
     if (maxwin <= SR_BWD_THREADS / 2) break;
   }
   if (best < 0) return false;
   pl.band_rows = best;
-  pl.bands = (H + best - 1) / best;
-  pl.nrec = B * pl.bands;
+  pl.bands = (sh.H + best - 1) / best;
+  pl.nrec = sh.B * pl.bands;
   p.band_rows = pl.band_rows; p.bands = pl.bands; p.nrec = pl.nrec;
   return true;
 }
@@ -1458,26 +1456,24 @@ bool sm_fill(SrP& p, SrPlan& pl, const void* x, const int64_t xs[5], const void*
 }  // namespace
 
 // room for the per-workgroup dCore records of the register-resident backward (0: the string is not in the family)
-size_t convsbs_reg_bwd_workspace(int n, const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w,
-                                 int C, int B, int H, int W, int q, int dtype) {
+size_t convsbs_reg_bwd_workspace(const SbsShape& sh) {
   SrP p;
   SrPlan pl;
-  if (!sr_fill(p, pl, nullptr, nullptr, nullptr, n, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype)) {
-    if (!sm_fill(p, pl, nullptr, nullptr, nullptr, n, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype)) return 0;
+  if (!sr_fill(p, pl, nullptr, nullptr, nullptr, sh)) {
+    if (!sm_fill(p, pl, nullptr, nullptr, nullptr, sh)) return 0;
     return (size_t)(SR_MAXC + p.O) * pl.R * pl.R * pl.QC * pl.nrec * sizeof(float) + 256;
   }
   const size_t ent = pl.uniform ? (size_t)pl.tot : (size_t)SR_MAXC * 2 * pl.R * pl.R * pl.QC;
   return ent * pl.nrec * sizeof(float) + 256;
 }
 
-int convsbs_fwd_reg(const void* x, const int64_t xs[5], const void* const* cores, void* out, int n, const int* out_sizes,
-                    const int* bond_sizes, const int* pos_h, const int* pos_w, int C, int B, int H, int W, int q, int dtype,
+int convsbs_fwd_reg(const void* x, const int64_t xs[5], const void* const* cores, void* out, const SbsShape& sh,
                     hipStream_t st) {
   SrP p;
   SrPlan pl;
-  if (!sr_fill(p, pl, x, xs, cores, n, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype)) {
+  if (!sr_fill(p, pl, x, xs, cores, sh)) {
     // one many-valued core (the classifier's ten-label string): prefix state, suffix vector, one dot product per output
-    if (!sm_fill(p, pl, x, xs, cores, n, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype)) return DCTN_ERR_UNSUPPORTED;
+    if (!sm_fill(p, pl, x, xs, cores, sh)) return DCTN_ERR_UNSUPPORTED;
     long long blocks = (p.Wn + SR_FWD_THREADS - 1) / SR_FWD_THREADS;
     if (blocks > 2048) blocks = 2048;
     const size_t lds = (size_t)(SR_MAXC + p.O) * pl.R * pl.R * pl.QC * sizeof(float);
@@ -1535,12 +1531,11 @@ int convsbs_fwd_reg(const void* x, const int64_t xs[5], const void* const* cores
 }
 
 int convsbs_bwd_reg(const void* x, const int64_t xs[5], const void* const* cores, const void* dY, void* dX,
-                    float* const* dcores, int n, const int* out_sizes, const int* bond_sizes, const int* pos_h,
-                    const int* pos_w, int C, int B, int H, int W, int q, int dtype, hipStream_t st, void* ws, size_t ws_bytes) {
+                    float* const* dcores, const SbsShape& sh, hipStream_t st, void* ws, size_t ws_bytes) {
   SrP p;
   SrPlan pl;
-  if (!sr_fill(p, pl, x, xs, cores, n, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype)) {
-    if (!sm_fill(p, pl, x, xs, cores, n, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype)) return DCTN_ERR_UNSUPPORTED;
+  if (!sr_fill(p, pl, x, xs, cores, sh)) {
+    if (!sm_fill(p, pl, x, xs, cores, sh)) return DCTN_ERR_UNSUPPORTED;
     const int ent = (SR_MAXC + p.O) * pl.R * pl.R * pl.QC;
     if (dcores && (!ws || ws_bytes < (size_t)ent * pl.nrec * sizeof(float))) return DCTN_ERR_WORKSPACE;
     if ((uintptr_t)ws % 16) return DCTN_ERR_WORKSPACE;
@@ -1548,9 +1543,9 @@ int convsbs_bwd_reg(const void* x, const int64_t xs[5], const void* const* cores
     p.dX = (float*)dX;
     p.part = dcores ? (float*)ws : nullptr;
     SrTailP t;
-    for (int c = 0; c < SR_MAXS * SR_MAXC; ++c) t.dcore[c] = (dcores && c < n) ? dcores[c] : nullptr;
+    for (int c = 0; c < SR_MAXS * SR_MAXC; ++c) t.dcore[c] = (dcores && c < sh.n) ? dcores[c] : nullptr;
     for (int c = 0; c < SR_MAXC; ++c) { t.o[c] = p.o[c]; t.bl[c] = p.bl[c]; t.br[c] = p.br[c]; }
-    t.n = n; t.nrec = pl.nrec;
+    t.n = sh.n; t.nrec = pl.nrec;
     for (int c = 0; c <= SR_MAXS * SR_MAXC; ++c) t.coff[c] = c <= SR_MAXC ? p.coff[c] : p.coff[SR_MAXC];
 #define SM_BWD(RR, QQ, TC)                                                                                            \
   do {                                                                                                                \
@@ -1590,14 +1585,14 @@ int convsbs_bwd_reg(const void* x, const int64_t xs[5], const void* const* cores
     hipLaunchKernelGGL((convsbs_bwd_reg_k<RR, QQ, TC, SR_MAXC>), dim3(grid), dim3(SR_BWD_THREADS), pl.lds_bwd, st, p); \
   } while (0)
 #define SR_TAIL(RR, QQ)                                                                                               \
-  hipLaunchKernelGGL((convsbs_reg_tail_k<RR, QQ>), dim3((unsigned)((n * 2 * RR * RR * QQ + 3) / 4)), dim3(256), 0, st, \
+  hipLaunchKernelGGL((convsbs_reg_tail_k<RR, QQ>), dim3((unsigned)((sh.n * 2 * RR * RR * QQ + 3) / 4)), dim3(256), 0, st, \
                      (const float*)ws, t)
   SrTailP t;
   for (int c = 0; c < SR_MAXC; ++c) {
-    t.dcore[c] = (dcores && c < n) ? dcores[c] : nullptr;
+    t.dcore[c] = (dcores && c < sh.n) ? dcores[c] : nullptr;
     t.o[c] = p.o[c]; t.bl[c] = p.bl[c]; t.br[c] = p.br[c];
   }
-  t.n = n; t.nrec = pl.nrec;
+  t.n = sh.n; t.nrec = pl.nrec;
   for (int c = 0; c <= SR_MAXS * SR_MAXC; ++c) t.coff[c] = c <= SR_MAXC ? p.coff[c] : p.coff[SR_MAXC];
   for (int c = SR_MAXC; c < SR_MAXS * SR_MAXC; ++c) t.dcore[c] = nullptr;
 #define SU_BWD(RR, QQ, TC)                                                                                            \
@@ -1643,23 +1638,20 @@ int convsbs_bwd_reg(const void* x, const int64_t xs[5], const void* const* cores
 // its window through every string; the strings' feature gradients meet in the same per-window LDS row, so dX is written
 // once, already summed) plus the one tail kernel.
 namespace {
-bool su_plan_many(SrP* ps, SrPlan& pl, int ns, const void* x, const int64_t xs[5], const void* const* cores, int n,
-                  const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w, int C, int B, int H, int W,
-                  int q, int dtype) {
+bool su_plan_many(SrP* ps, SrPlan& pl, int ns, const void* x, const int64_t xs[5], const void* const* cores,
+                  const SbsShape& sh) {
   if (ns < 1 || ns > SR_MAXS) return false;
   int base = 0;
   for (int s2 = 0; s2 < ns; ++s2) {
     SrPlan pls;
-    if (!sr_fill(ps[s2], pls, x, xs, cores ? cores + s2 * n : nullptr, n, out_sizes + s2 * n, bond_sizes + s2 * n, pos_h + s2 * n,
-                 pos_w + s2 * n, C, B, H, W, q, dtype))
-      return false;
+    if (!sr_fill(ps[s2], pls, x, xs, cores ? cores + s2 * sh.n : nullptr, sbs_string(sh, s2))) return false;
     if (!pls.uniform) return false;
     if (s2 == 0) pl = pls;
     else if (pls.R != pl.R || pls.QC != pl.QC || pls.twoch != pl.twoch || ps[s2].max_h != ps[0].max_h || ps[s2].Wo != ps[0].Wo)
       return false;
-    for (int c = 0; c < n; ++c) {   // the pixel of core c in the first string's order
+    for (int c = 0; c < sh.n; ++c) {   // the pixel of core c in the first string's order
       int found = -1;
-      for (int c0 = 0; c0 < n; ++c0)
+      for (int c0 = 0; c0 < sh.n; ++c0)
         if (ps[0].ph[c0] == ps[s2].ph[c] && ps[0].pw[c0] == ps[s2].pw[c]) found = c0;
       if (found < 0) return false;
       ps[s2].slot[c] = found;
@@ -1669,25 +1661,23 @@ bool su_plan_many(SrP* ps, SrPlan& pl, int ns, const void* x, const int64_t xs[5
   }
   for (int s2 = 0; s2 < ns; ++s2) ps[s2].tot_all = base;
   pl.tot = base;
-  pl.lds_bwd = ((size_t)base * (SR_BWD_THREADS / 64) + (size_t)pl.max_w_in_band * n * C * q) * sizeof(float);
+  pl.lds_bwd = ((size_t)base * (SR_BWD_THREADS / 64) + (size_t)pl.max_w_in_band * sh.n * sh.C * sh.q) * sizeof(float);
   return pl.lds_bwd <= dctn_lds_wg_max();
 }
 }  // namespace
 
-size_t convsbs_many_reg_bwd_workspace(int ns, int n, const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w,
-                                      int C, int B, int H, int W, int q, int dtype) {
+size_t convsbs_many_reg_bwd_workspace(int ns, const SbsShape& sh) {
   SrP ps[SR_MAXS];
   SrPlan pl;
-  if (!su_plan_many(ps, pl, ns, nullptr, nullptr, nullptr, n, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype)) return 0;
+  if (!su_plan_many(ps, pl, ns, nullptr, nullptr, nullptr, sh)) return 0;
   return (size_t)pl.tot * pl.nrec * sizeof(float) + 256;
 }
 
-int convsbs_many_fwd_reg(const void* x, const int64_t xs[5], const void* const* cores, void* const* outs, int ns, int n,
-                         const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w, int C, int B, int H,
-                         int W, int q, int dtype, hipStream_t st) {
+int convsbs_many_fwd_reg(const void* x, const int64_t xs[5], const void* const* cores, void* const* outs, int ns,
+                         const SbsShape& sh, hipStream_t st) {
   SrP ps[SR_MAXS];
   SrPlan pl;
-  if (!su_plan_many(ps, pl, ns, x, xs, cores, n, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype)) return DCTN_ERR_UNSUPPORTED;
+  if (!su_plan_many(ps, pl, ns, x, xs, cores, sh)) return DCTN_ERR_UNSUPPORTED;
   for (int s2 = 0; s2 < ns; ++s2) {
     if (!outs[s2]) return DCTN_ERR_NULL;
     ps[s2].out = (float*)outs[s2];
@@ -1714,11 +1704,10 @@ int convsbs_many_fwd_reg(const void* x, const int64_t xs[5], const void* const* 
 }
 
 int convsbs_many_bwd_reg(const void* x, const int64_t xs[5], const void* const* cores, const void* const* dYs, void* dX,
-                         float* const* dcores, int ns, int n, const int* out_sizes, const int* bond_sizes, const int* pos_h,
-                         const int* pos_w, int C, int B, int H, int W, int q, int dtype, hipStream_t st, void* ws, size_t ws_bytes) {
+                         float* const* dcores, int ns, const SbsShape& sh, hipStream_t st, void* ws, size_t ws_bytes) {
   SrP ps[SR_MAXS];
   SrPlan pl;
-  if (!su_plan_many(ps, pl, ns, x, xs, cores, n, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype)) return DCTN_ERR_UNSUPPORTED;
+  if (!su_plan_many(ps, pl, ns, x, xs, cores, sh)) return DCTN_ERR_UNSUPPORTED;
   const size_t need = (size_t)pl.tot * pl.nrec * sizeof(float);
   if (dcores && (!ws || ws_bytes < need || ((uintptr_t)ws % 16))) return DCTN_ERR_WORKSPACE;
   for (int s2 = 0; s2 < ns; ++s2) {
@@ -1731,8 +1720,8 @@ int convsbs_many_bwd_reg(const void* x, const int64_t xs[5], const void* const* 
   for (int c = 0; c < SR_MAXC; ++c) { t.o[c] = 1; t.bl[c] = 1; t.br[c] = 1; }
   for (int s2 = 0; s2 < SR_MAXS; ++s2)
     for (int c = 0; c < SR_MAXC; ++c) {
-      const bool live = s2 < ns && c < n;
-      t.dcore[s2 * SR_MAXC + c] = (dcores && live) ? dcores[s2 * n + c] : nullptr;
+      const bool live = s2 < ns && c < sh.n;
+      t.dcore[s2 * SR_MAXC + c] = (dcores && live) ? dcores[s2 * sh.n + c] : nullptr;
       t.coff[s2 * SR_MAXC + c] = s2 < ns ? ps[s2].coff[c] : pl.tot;
     }
   t.coff[SR_MAXS * SR_MAXC] = pl.tot;

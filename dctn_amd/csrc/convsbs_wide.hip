@@ -50,36 +50,35 @@ struct WideLayout {
 
 size_t wd_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
-int wide_fill(WideP& p, int n, const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w, int C, int B,
-              int H, int W, int q) {
-  if (n < 1 || n > WIDE_MAXC || C < 1 || B < 1 || q < 1) return DCTN_ERR_UNSUPPORTED;
+int wide_fill(WideP& p, const SbsShape& sh) {
+  if (sh.n < 1 || sh.n > WIDE_MAXC || sh.C < 1 || sh.B < 1 || sh.q < 1) return DCTN_ERR_UNSUPPORTED;
   int max_h = 0, max_w = 0;
-  for (int c = 0; c < n; ++c) {
-    if (out_sizes[c] < 1 || bond_sizes[c] < 1 || pos_h[c] < 0 || pos_w[c] < 0) return DCTN_ERR_BAD_SHAPE;
-    max_h = pos_h[c] > max_h ? pos_h[c] : max_h;
-    max_w = pos_w[c] > max_w ? pos_w[c] : max_w;
+  for (int c = 0; c < sh.n; ++c) {
+    if (sh.out_sizes[c] < 1 || sh.bond_sizes[c] < 1 || sh.pos_h[c] < 0 || sh.pos_w[c] < 0) return DCTN_ERR_BAD_SHAPE;
+    max_h = sh.pos_h[c] > max_h ? sh.pos_h[c] : max_h;
+    max_w = sh.pos_w[c] > max_w ? sh.pos_w[c] : max_w;
   }
-  if (H <= max_h || W <= max_w) return DCTN_ERR_BAD_SHAPE;
-  p.n = n; p.C = C; p.B = B; p.H = H; p.W = W; p.q = q;
+  if (sh.H <= max_h || sh.W <= max_w) return DCTN_ERR_BAD_SHAPE;
+  p.n = sh.n; p.C = sh.C; p.B = sh.B; p.H = sh.H; p.W = sh.W; p.q = sh.q;
   long long qc = 1;
-  for (int c = 0; c < C; ++c) { qc *= q; if (qc > 4096) return DCTN_ERR_UNSUPPORTED; }
+  for (int c = 0; c < sh.C; ++c) { qc *= sh.q; if (qc > 4096) return DCTN_ERR_UNSUPPORTED; }
   p.qc = (int)qc;
-  p.Ho = H - max_h; p.Wo = W - max_w;
-  p.Wn = (long long)B * p.Ho * p.Wo;
-  p.l0 = bond_sizes[0];
+  p.Ho = sh.H - max_h; p.Wo = sh.W - max_w;
+  p.Wn = (long long)sh.B * p.Ho * p.Wo;
+  p.l0 = sh.bond_sizes[0];
   long long oacc = 1, off = 0;
   p.emax = p.gmax = p.cemax = p.cetot = 0;
-  for (int c = 0; c < n; ++c) {
-    p.o[c] = out_sizes[c];
-    p.bl[c] = bond_sizes[c];
-    p.br[c] = bond_sizes[(c + 1) % n];
-    p.ph[c] = pos_h[c];
-    p.pw[c] = pos_w[c];
+  for (int c = 0; c < sh.n; ++c) {
+    p.o[c] = sh.out_sizes[c];
+    p.bl[c] = sh.bond_sizes[c];
+    p.br[c] = sh.bond_sizes[(c + 1) % sh.n];
+    p.ph[c] = sh.pos_h[c];
+    p.pw[c] = sh.pos_w[c];
     p.oacc[c] = (int)oacc;
     p.st_off[c] = off;
     const long long gin = oacc * p.bl[c];
     off += gin;
-    oacc *= out_sizes[c];
+    oacc *= sh.out_sizes[c];
     const long long gout = oacc * p.br[c];
     if (gout > (1 << 20)) return DCTN_ERR_UNSUPPORTED;   // (fill()'s limits)
     const long long e = (long long)p.o[c] * p.bl[c] * p.br[c];
@@ -90,8 +89,8 @@ int wide_fill(WideP& p, int n, const int* out_sizes, const int* bond_sizes, cons
     p.cemax = e * p.qc > p.cemax ? e * p.qc : p.cemax;
     p.cetot += e * p.qc;
   }
-  p.oacc[n] = (int)oacc;
-  p.st_off[n] = off;
+  p.oacc[sh.n] = (int)oacc;
+  p.st_off[sh.n] = off;
   p.Otot = (int)oacc;
   return DCTN_OK;
 }
@@ -488,31 +487,29 @@ int wide_run(const void* xv, const void* const* cores, const void* dYv, int need
 
 }  // namespace
 
-size_t convsbs_wide_bwd_workspace(int n, const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w, int C,
-                                  int B, int H, int W, int q, int dtype) {
-  if (dtype != DCTN_F32 && dtype != DCTN_F64 && dtype != DCTN_BF16) return 0;
+size_t convsbs_wide_bwd_workspace(const SbsShape& sh) {
+  if (sh.dtype != DCTN_F32 && sh.dtype != DCTN_F64 && sh.dtype != DCTN_BF16) return 0;
   WideP p;
-  if (wide_fill(p, n, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q) != DCTN_OK) return 0;
-  return wide_layout(p, dtype).total;
+  if (wide_fill(p, sh) != DCTN_OK) return 0;
+  return wide_layout(p, sh.dtype).total;
 }
 
 int convsbs_bwd_wide(const void* x, const int64_t xs[5], const void* const* cores, const void* dY, int need_dx,
-                     void* const* dcores, int n, const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w,
-                     int C, int B, int H, int W, int q, int dtype, hipStream_t st, void* ws, size_t ws_bytes) {
+                     void* const* dcores, const SbsShape& sh, hipStream_t st, void* ws, size_t ws_bytes) {
   WideP p;
-  const int rc = wide_fill(p, n, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q);
+  const int rc = wide_fill(p, sh);
   if (rc != DCTN_OK) return rc;
   for (int i = 0; i < 5; ++i) p.s[i] = xs[i];
   // the family's only LDS is the GEMM tiles (static): a device whose workgroups get less declines before any write
-  const size_t tile_lds = (size_t)16 * (64 + 4 + 64 + 4) * (dtype == DCTN_F64 ? 8 : 4);
-  const size_t tile_lds_narrow = (size_t)16 * (256 + 4 + 16 + 4) * (dtype == DCTN_F64 ? 8 : 4);
+  const size_t tile_lds = (size_t)16 * (64 + 4 + 64 + 4) * (sh.dtype == DCTN_F64 ? 8 : 4);
+  const size_t tile_lds_narrow = (size_t)16 * (256 + 4 + 16 + 4) * (sh.dtype == DCTN_F64 ? 8 : 4);
   if ((tile_lds > tile_lds_narrow ? tile_lds : tile_lds_narrow) > (size_t)dctn_lds_wg_max()) return DCTN_ERR_UNSUPPORTED;
-  const WideLayout L = wide_layout(p, dtype);
+  const WideLayout L = wide_layout(p, sh.dtype);
   if (!ws || ws_bytes < L.total) return DCTN_ERR_WORKSPACE;
-  for (int c = 0; c < n; ++c)
+  for (int c = 0; c < sh.n; ++c)
     if (!cores[c] || (dcores && !dcores[c])) return DCTN_ERR_NULL;
   unsigned char* w = (unsigned char*)ws;
-  switch (dtype) {
+  switch (sh.dtype) {
     case DCTN_F32: return wide_run<float, float>(x, cores, dY, need_dx, dcores, w, p, L, st);
     case DCTN_F64: return wide_run<double, double>(x, cores, dY, need_dx, dcores, w, p, L, st);
     case DCTN_BF16: return wide_run<bf16_t, float>(x, cores, dY, need_dx, dcores, w, p, L, st);

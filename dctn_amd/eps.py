@@ -146,24 +146,25 @@ def _f32_through_bf16(core: Tensor, input: Tensor) -> bool:
     K = math.isqrt((core.ndim - 1) // C)
     args = (C, B, H, W, Q, K, core.shape[-1])
     lib = L.lib()
-    return (lib.dctn_eps_family(*args, L._DTYPE_CODE[torch.float32], L.PREC_BF16) != 1
-            and lib.dctn_eps_family(*args, L._DTYPE_CODE[torch.bfloat16], L.PREC_BF16) == 3)
+    return (lib.dctn_eps_family(*args, L.F32, L.PREC_BF16) != L.EPS_FAMILY_Q2REG
+            and lib.dctn_eps_family(*args, L.BF16, L.PREC_BF16) == L.EPS_FAMILY_HALVES)
 
 
 def _bf16_through_f32(core: Tensor, input: Tensor) -> bool:
     """bf16 tensors whose core is outside the bf16 register family (deeper layers, Q > 2) would land on the
     generic kernels; the float32 matrix-core families (bigcore, two-halves GEMMs) take them instead: bf16 storage, the
     float32 arithmetic of the current policy (the casts are three small elementwise kernels next to millisecond GEMMs;
-    autograd casts the gradients back).  Under "high" the large cores among them go to the bf16x3 family (5), under
-    "exact" to the exact one (2)."""
+    autograd casts the gradients back).  Under "high" the large cores among them go to the bf16x3 family, under
+    "exact" to the exact one."""
     if core.dtype != torch.bfloat16 or not core.is_cuda:
         return False
     C, B, H, W, Q = input.shape
     K = math.isqrt((core.ndim - 1) // C)
     args = (C, B, H, W, Q, K, core.shape[-1])
     lib, prec = L.lib(), L.precision()
-    return (lib.dctn_eps_family(*args, L.dtype_code(core), prec) == 0
-            and lib.dctn_eps_family(*args, L._DTYPE_CODE[torch.float32], prec) in (2, 3, 5))
+    return (lib.dctn_eps_family(*args, L.BF16, prec) == L.EPS_FAMILY_GENERIC
+            and lib.dctn_eps_family(*args, L.F32, prec)
+            in (L.EPS_FAMILY_BIGCORE_F32, L.EPS_FAMILY_HALVES, L.EPS_FAMILY_BIGCORE_BF16X3))
 
 
 def eps_one_by_one(core: Tensor, input: Tensor) -> Tensor:

@@ -41,6 +41,13 @@ def test_library_exports_every_declared_symbol():
     assert _lib.lib().dctn_strerror(-1) == b"inconsistent shape"
 
 
+def test_eps_family_names_equal_the_header():
+    header = open(os.path.join(ROOT, "include", "dctn_amd.h")).read()
+    defined = {name: int(value) for name, value in re.findall(r"#define\s+DCTN_(EPS_FAMILY_[A-Z0-9_]+)\s+(-?\d+)", header)}
+    assert len(defined) == 6, defined
+    assert defined == {name: getattr(_lib, name) for name in dir(_lib) if name.startswith("EPS_FAMILY_")}
+
+
 def test_argument_validation_without_gpu():
     """Validation happens on the host before any launch, so it is checkable here."""
     lib = _lib.lib()
