@@ -185,6 +185,17 @@ void dctn_reduce_stamps_set(unsigned long long* p) { (void)hipMemcpyToSymbol(HIP
     if ((P).stamps && threadIdx.x == (TID)) (P).stamps[(long long)blockIdx.x * 8 + (SLOT)] = t_;  \
     __builtin_amdgcn_sched_barrier(0);                                                           \
   } while (0)
+// the dW role waves of the dCore kernel: the first role wave's lane 0, in the rows behind DCTN_STAMP_ROLE_ROW
+#define DCTN_STAMP_ROLE_ROW 1024
+#define DCTN_STAMP_R(P, SLOT)                                                                    \
+  do {                                                                                           \
+    __builtin_amdgcn_sched_barrier(0);                                                           \
+    unsigned long long t_;                                                                       \
+    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");               \
+    if ((P).stamps && threadIdx.x == 64 * 8)                                                     \
+      (P).stamps[(long long)(DCTN_STAMP_ROLE_ROW + blockIdx.x) * 8 + (SLOT)] = t_;               \
+    __builtin_amdgcn_sched_barrier(0);                                                           \
+  } while (0)
 #define DCTN_STAMP_G(SLOT)                                                                       \
   do {                                                                                           \
     __builtin_amdgcn_sched_barrier(0);                                                           \
@@ -197,6 +208,7 @@ void dctn_reduce_stamps_set(unsigned long long* p) { (void)hipMemcpyToSymbol(HIP
 #define DCTN_STAMP(P, SLOT) do { } while (0)
 #define DCTN_STAMP_T(P, SLOT, TID) do { } while (0)
 #define DCTN_STAMP_G(SLOT) do { } while (0)
+#define DCTN_STAMP_R(P, SLOT) do { } while (0)
 #endif
 
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
@@ -1079,13 +1091,20 @@ constexpr size_t dcore_dyn_lds_bytes(int mt) { return (size_t)BWD_WAVES * (1 + m
 // is a plain (Cout x B) x (B x P*O) product that needs nothing of this kernel; formed here it cost 4 of the 12 matrix
 // instructions of a group, 64 accumulator registers, the loads of `feat`, a 1.7 us LDS epilogue and 2.5 MB of partial
 // tiles written and read back (the "1.6x traffic" of rounds 2-3).
-template <typename S, int N0, int N1, int OP, bool XVEC, bool OVEC, int ROWS, int HEADC>
-__global__ __launch_bounds__(64 * BWD_WAVES) void eps_bwd_dcore_q2reg_k(const S* __restrict__ x,
+// DWROLE (0 or 4; the HEADMM shapes with blocked4 features): the workgroup has DWROLE more waves, which form dW on the
+// wave slots the dCore waves leave free (162 VGPRs: a third wave per SIMD fits) - head_dw_role_waves, below the
+// finishing kernel's gemm role whose arithmetic it shares.  Waves 0 .. BWD_WAVES - 1 are what they are without it.
+__device__ __forceinline__ void head_dw_role_waves(const bf16_t* __restrict__ feat, const bf16_t* __restrict__ dL,
+                                                   bf16_t* __restrict__ dW, int B, int Cout, long long F, int n_dw,
+                                                   int rw, float* __restrict__ lds, const MfmaP& p);
+template <typename S, int N0, int N1, int OP, bool XVEC, bool OVEC, int ROWS, int HEADC, int DWROLE = 0>
+__global__ __launch_bounds__(64 * (BWD_WAVES + DWROLE)) void eps_bwd_dcore_q2reg_k(const S* __restrict__ x,
                                                              const S* __restrict__ dY,
                                                              const S* __restrict__ hw,
                                                              const S* __restrict__ feat,
                                                              float* __restrict__ partial,
-                                                             float* __restrict__ dwpart, MfmaP p) {
+                                                             float* __restrict__ dwpart, MfmaP p,
+                                                             S* __restrict__ dW, int n_dw) {
   constexpr int N = N0 + N1, A = 1 << N0, BN = 1 << N1, KS = A / 16, MT = BN * OP / 32;
   constexpr int AT = A >= 32 ? A / 32 : 1;
   constexpr int LOGO = ilog2(OP);
@@ -1100,6 +1119,18 @@ __global__ __launch_bounds__(64 * BWD_WAVES) void eps_bwd_dcore_q2reg_k(const S*
   extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5, wv = tid >> 6;
   DCTN_STAMP(p, 0);
+  if constexpr (DWROLE > 0) {
+    static_assert(HEADC > 0 && HEADC <= 16 && LDST && OVEC && XVEC && sizeof(S) == 2 && OP == 4, "the dW role rides the HEADMM path");
+    const int rw = __builtin_amdgcn_readfirstlane(wv) - BWD_WAVES;
+    if (rw >= 0) {   // (wave-uniform: the role waves meet the dCore waves at the three barriers only)
+      head_dw_role_waves(feat, dY, dW, p.B, p.Cout, (long long)p.P * OP, n_dw, rw,
+                         reinterpret_cast<float*>(dsm + dcore_dyn_lds_bytes(MT) + 8192), p);
+      return;
+    }
+#ifdef DCTN_DWROLE_PRIO
+    __builtin_amdgcn_s_setprio(DCTN_DWROLE_PRIO);
+#endif
+  }
   short* tiles = reinterpret_cast<short*>(dsm) + wv * ((1 + MT) * 64 * LROW);
   const TrLane trl = tr_lane(lane);
 
@@ -1611,95 +1642,134 @@ __global__ __launch_bounds__(256) void eps_bwd_dcore_reduce_k(const float* __res
 constexpr int DWG_WAVES = 16;
 constexpr int DWG_FW = 32;   // features of one workgroup's slice (4 bytes of a row per lane: 64-byte pieces of 4 rows per load)
 constexpr int DWG_BFW = 16;  // ... with blocked4 features (8 bytes of a block per lane: 128-byte pieces, 169 workgroups at cfg2)
+typedef __attribute__((ext_vector_type(4))) float f32x4v;
+// The loaded operands of one 32-sample block of the product, as the lane holds them.  row-major: f[j] = the lane's piece
+// of sample 8 kg + j; blocked4: f[h][.] = its 2 FL dwords of block 2 kg + h; a[j] = dLogits of sample 8 kg + j, the dword
+// that holds class n (a 16-bit load's widening is an instruction that waits for the load where it was issued).
+template <int FW, bool BLK4>
+struct DwBlock {
+  static constexpr int FL = FW / 16;               // features per lane = tiles per wave
+  static constexpr int FD = FL >= 2 ? FL / 2 : 1;   // dwords of a row piece per lane
+  static constexpr int NF = BLK4 ? 2 : 8, ND = BLK4 ? 2 * FL : FD;
+  static_assert(!BLK4 || FL == 1 || FL == 2, "blocked4 pieces of 8 or 16 bytes");
+  unsigned f[NF][ND];
+  unsigned a[8];
+};
+// The lane's share of a slice: lane (n, kg) = (lane % 16, lane / 16), features fcol .. fcol + FL - 1.  Every address of
+// a block is "per-lane offset inside the block + the block's scalar offset": fo[j] / ao[j] are the lane's byte offsets of
+// its j-th feature piece / dLogits dword in block 0 (out of range for a lane without a feature or a class), the block
+// adds kb * F * 2 / kb * Cout * 2 as the loads' scalar offset - a whole block inside the batch costs no address
+// arithmetic at all (what the role waves of the dCore kernel issue next to its prologue).
+template <int NF>
+struct DwLane {
+  unsigned f_bytes, dl_bytes;
+  unsigned frow2, arow;   // bytes of a sample's features / dLogits
+  unsigned fo[NF], ao[8];
+  int n, kg;
+  unsigned asel;   // v_perm selector of class n's half of two dLogits dwords
+};
+template <int FW, bool BLK4>
+__device__ __forceinline__ DwLane<DwBlock<FW, BLK4>::NF> dw_lane(int B, int Cout, long long F, int blk) {
+  constexpr int FL = FW / 16, NF = DwBlock<FW, BLK4>::NF;
+  const int lane = threadIdx.x & 63;
+  DwLane<NF> l;
+  const long long fb = BLK4 ? (long long)(B + 3) / 4 * 4 * F * 2 : (long long)B * F * 2;
+  l.f_bytes = (unsigned)fb;
+  l.dl_bytes = (unsigned)B * (unsigned)Cout * 2u;
+  l.frow2 = (unsigned)F * 2u;
+  l.arow = (unsigned)Cout * 2u;
+  l.n = lane & 15;
+  l.kg = lane >> 4;
+  l.asel = (l.n & 1) ? 0x07060302u : 0x05040100u;
+  const long long fcol = (long long)blk * FW + FL * l.n;
+  const bool fok = fcol + FL - 1 < F;   // (F is a multiple of 4: OP == 4)
+#pragma unroll
+  for (int j = 0; j < NF; ++j)   // blocked4: the 4-sample block 2 kg + j; row-major: sample 8 kg + j
+    l.fo[j] = !fok ? l.f_bytes : BLK4 ? (unsigned)(((long long)(2 * l.kg + j) * F + fcol) * 8) : (unsigned)((8 * l.kg + j) * F * 2 + fcol * 2);
+#pragma unroll
+  for (int j = 0; j < 8; ++j)   // (Cout is even and dLogits 4-byte aligned: the dword of the classes n & ~1, n | 1)
+    l.ao[j] = l.n < Cout ? (unsigned)(8 * l.kg + j) * l.arow + 2u * (unsigned)(l.n & ~1) : l.dl_bytes;
+  return l;
+}
+// samples per (virtual) wave of the product: the batch split DWG_WAVES ways in whole 32-sample blocks
+__device__ __forceinline__ int dw_spw(int B) { return (((B + DWG_WAVES - 1) / DWG_WAVES) + 31) / 32 * 32; }
+// issue the loads of the block of samples kb .. kb + 31 (samples >= b1: zeros)
+template <int FW, bool BLK4>
+__device__ __forceinline__ void dw_block_issue(const __amdgpu_buffer_rsrc_t rs_f, const __amdgpu_buffer_rsrc_t rs_dl,
+                                               const DwLane<DwBlock<FW, BLK4>::NF>& l, int kb, int b1, DwBlock<FW, BLK4>& q) {
+  constexpr int FL = DwBlock<FW, BLK4>::FL, NF = DwBlock<FW, BLK4>::NF, ND = DwBlock<FW, BLK4>::ND;
+  const unsigned so_f = (unsigned)kb * l.frow2, so_a = (unsigned)kb * l.arow;
+  auto loads = [&](auto whole) {   // whole: every sample of the block is one of the wave's (wave-uniform)
+#pragma unroll
+    for (int j = 0; j < NF; ++j) {   // a piece is loaded if it holds a sample of the wave (past the batch: zeros)
+      const unsigned vo = (decltype(whole)::value || kb + 8 * l.kg + (BLK4 ? 4 : 1) * j < b1) ? l.fo[j] : l.f_bytes;
+      if constexpr (ND == 1 && !BLK4 && FL == 1) {
+        q.f[j][0] = (unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rs_f, vo, so_f, 0);
+      } else if constexpr (ND == 1) {
+        q.f[j][0] = __builtin_amdgcn_raw_buffer_load_b32(rs_f, vo, so_f, 0);
+      } else if constexpr (ND == 2) {
+        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs_f, vo, so_f, 0);
+        q.f[j][0] = v.x;
+        q.f[j][1] = v.y;
+      } else {
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs_f, vo, so_f, 0);
+#pragma unroll
+        for (int d = 0; d < 4; ++d) q.f[j][d] = v[d];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      q.a[j] = __builtin_amdgcn_raw_buffer_load_b32(
+          rs_dl, (decltype(whole)::value || kb + 8 * l.kg + j < b1) ? l.ao[j] : l.dl_bytes, so_a, 0);
+  };
+  if (kb + 32 <= b1) loads(std::true_type{}); else loads(std::false_type{});
+}
+// acc[j] += dLogits^T x features of the block, tile j = the features FL n + j
+template <int FW, bool BLK4>
+__device__ __forceinline__ void dw_block_mfma(const DwBlock<FW, BLK4>& q, unsigned asel, f32x4v (&acc)[FW / 16]) {
+  constexpr int FL = DwBlock<FW, BLK4>::FL;
+  int4v at;
+#pragma unroll
+  for (int d = 0; d < 4; ++d) at[d] = (int)__builtin_amdgcn_perm(q.a[2 * d + 1], q.a[2 * d], asel);
+#pragma unroll
+  for (int j = 0; j < FL; ++j) {
+    int4v bf;
+    if constexpr (BLK4) {   // feature fcol + j of samples 0-3 and 4-7: dwords 2 j, 2 j + 1 of the two blocks
+#pragma unroll
+      for (int d = 0; d < 4; ++d) bf[d] = (int)q.f[d >> 1][2 * j + (d & 1)];
+    } else {
+      const unsigned sel = (j & 1) ? 0x07060302u : 0x05040100u;   // the odd / even halves of two dwords
+#pragma unroll
+      for (int d = 0; d < 4; ++d)
+        bf[d] = FL == 1 ? (int)(q.f[2 * d][0] | (q.f[2 * d + 1][0] << 16))
+                        : (int)__builtin_amdgcn_perm(q.f[2 * d + 1][j >> 1], q.f[2 * d][j >> 1], sel);
+    }
+    acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, at), __builtin_bit_cast(bf16x8, bf), acc[j], 0, 0, 0);
+  }
+}
+
 template <int FW, bool BLK4>
 __device__ __forceinline__ void head_dw_gemm_role(const bf16_t* __restrict__ feat, const bf16_t* __restrict__ dL,
                                                   bf16_t* __restrict__ dW, int B, int Cout, long long F, int blk,
                                                   float* __restrict__ lds) {
-  typedef __attribute__((ext_vector_type(4))) float f32x4v;
-  constexpr int FL = FW / 16;   // features per lane = tiles per wave
-  static_assert(!BLK4 || FL == 1 || FL == 2, "blocked4 pieces of 8 or 16 bytes");
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = lane & 15, kg = lane >> 4;
-  const long long fb = BLK4 ? (long long)(B + 3) / 4 * 4 * F * 2 : (long long)B * F * 2;
-  const unsigned f_bytes = (unsigned)fb, dl_bytes = (unsigned)B * (unsigned)Cout * 2u;
-  const __amdgpu_buffer_rsrc_t rs_f = make_rsrc(feat, f_bytes), rs_dl = make_rsrc(dL, dl_bytes);
-  const long long fcol = (long long)blk * FW + FL * n;
-  const bool fok = fcol + FL - 1 < F;   // (F is a multiple of 4: OP == 4)
-  const int spw = (((B + DWG_WAVES - 1) / DWG_WAVES) + 31) / 32 * 32;
+  constexpr int FL = FW / 16;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const auto l = dw_lane<FW, BLK4>(B, Cout, F, blk);
+  const int n = l.n, kg = l.kg;
+  const __amdgpu_buffer_rsrc_t rs_f = make_rsrc(feat, l.f_bytes), rs_dl = make_rsrc(dL, l.dl_bytes);
+  const int spw = dw_spw(B);
   const int b0 = wv * spw, b1 = b0 + spw < B ? b0 + spw : B;
   f32x4v acc[FL];
 #pragma unroll
   for (int j = 0; j < FL; ++j) acc[j] = f32x4v{0.f, 0.f, 0.f, 0.f};
-  constexpr int FD = FL >= 2 ? FL / 2 : 1;   // dwords of a row piece per lane
-  // row-major: fr[j] = the lane's piece of sample 8 kg + j; blocked4: fr[h][.] = its 2 FL dwords of block 2 kg + h
-  constexpr int NF = BLK4 ? 2 : 8, ND = BLK4 ? 2 * FL : FD;
-  unsigned fr[NF][ND], frn[NF][ND];
-  unsigned a16[8], a16n[8];
-  auto issue = [&](int kb, unsigned (&f)[NF][ND], unsigned (&a)[8]) {
-    if constexpr (BLK4) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {   // block (kb + 8 kg) / 4 + h: loaded if it holds a sample of the wave (past B: zeros)
-        const int b = kb + 8 * kg + 4 * h;
-        const unsigned vo = (b < b1 && fok) ? (unsigned)(((long long)(b >> 2) * F + fcol) * 8) : f_bytes;
-        if constexpr (FL == 1) {
-          const u32x2 q = __builtin_amdgcn_raw_buffer_load_b64(rs_f, vo, 0, 0);
-          f[h][0] = q.x;
-          f[h][ND - 1] = q.y;
-        } else {
-          const u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(rs_f, vo, 0, 0);
-#pragma unroll
-          for (int d = 0; d < 4; ++d) f[h][d] = q[d];
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int b = kb + 8 * kg + j;
-      const bool in = b < b1;
-      if constexpr (!BLK4) {
-        const unsigned vo = (in && fok) ? (unsigned)((long long)b * F * 2 + fcol * 2) : f_bytes;
-        if constexpr (FL == 1) {
-          f[j][0] = (unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rs_f, vo, 0, 0);
-        } else if constexpr (FL == 2) {
-          f[j][0] = __builtin_amdgcn_raw_buffer_load_b32(rs_f, vo, 0, 0);
-        } else {
-          const u32x2 q = __builtin_amdgcn_raw_buffer_load_b64(rs_f, vo, 0, 0);
-          f[j][0] = q.x;
-          f[j][FD - 1] = q.y;
-        }
-      }
-      a[j] = (unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(
-          rs_dl, (in && n < Cout) ? (unsigned)b * (unsigned)Cout * 2u + 2u * n : dl_bytes, 0, 0);
-    }
-  };
+  DwBlock<FW, BLK4> cur, nxt;
   DCTN_STAMP_G(0);
-  if (b0 < b1) issue(b0, fr, a16);
+  if (b0 < b1) dw_block_issue<FW, BLK4>(rs_f, rs_dl, l, b0, b1, cur);
   for (int kb = b0; kb < b1; kb += 32) {
-    if (kb + 32 < b1) issue(kb + 32, frn, a16n);
+    if (kb + 32 < b1) dw_block_issue<FW, BLK4>(rs_f, rs_dl, l, kb + 32, b1, nxt);
     __builtin_amdgcn_sched_barrier(0);
-    int4v at;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) at[d] = (int)(a16[2 * d] | (a16[2 * d + 1] << 16));
-#pragma unroll
-    for (int j = 0; j < FL; ++j) {
-      int4v bf;
-      if constexpr (BLK4) {   // feature fcol + j of samples 0-3 and 4-7: dwords 2 j, 2 j + 1 of the two blocks
-#pragma unroll
-        for (int d = 0; d < 4; ++d) bf[d] = (int)fr[d >> 1][2 * j + (d & 1)];
-      } else {
-        const unsigned sel = (j & 1) ? 0x07060302u : 0x05040100u;   // the odd / even halves of two dwords
-#pragma unroll
-        for (int d = 0; d < 4; ++d)
-          bf[d] = FL == 1 ? (int)(fr[2 * d][0] | (fr[2 * d + 1][0] << 16))
-                          : (int)__builtin_amdgcn_perm(fr[2 * d + 1][j >> 1], fr[2 * d][j >> 1], sel);
-      }
-      acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, at), __builtin_bit_cast(bf16x8, bf), acc[j], 0, 0, 0);
-    }
-#pragma unroll
-    for (int j = 0; j < NF; ++j)
-#pragma unroll
-      for (int e = 0; e < ND; ++e) fr[j][e] = frn[j][e];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) a16[j] = a16n[j];
+    dw_block_mfma<FW, BLK4>(cur, l.asel, acc);
+    cur = nxt;
   }
   // acc[j][i] = dW[class 4 kg + i][feature DWG_FW blk + FL n + j] of this wave's samples
 #pragma unroll
@@ -1719,6 +1789,113 @@ __device__ __forceinline__ void head_dw_gemm_role(const bf16_t* __restrict__ fea
     if (c < Cout && f < F) dW[(long long)c * F + f] = (bf16_t)t;
   }
   DCTN_STAMP_G(4);
+}
+
+// The same product on the spare wave slots of eps_bwd_dcore_q2reg_k<.., DWROLE> (blocked4 features): the dCore
+// workgroup's waves BWD_WAVES .. BWD_WAVES + DWR_WAVES - 1 form the slice `blockIdx.x` together, each as DWR_VPW of the
+// finishing kernel's DWG_WAVES waves ("virtual waves": same sample range, one accumulator from zero per virtual wave,
+// its 64 x 4 tile in LDS, the same ordered join - the bits of head_dw_gemm_role<DWG_BFW, true>).  Up to DWR_DEPTH blocks
+// of a wave are in flight at once (B = 1024: all 8 of a wave); larger batches go round by round.
+// Grids smaller than the number of slices (small batches): the slices past the first round are dealt to single role
+// waves, which run all DWG_WAVES virtual waves of a slice one after the other - the join is lane-local (tile element
+// (i, lane) of every virtual wave sits in register i of the same lane), so the wave sums in registers in the same order
+// and needs no hand-over between waves: the kernel keeps its three workgroup barriers.
+// All DWR_WAVES waves execute the three barriers of the HEADMM path: (1) the weight slice is published - the role takes
+// no part in it, a bare s_barrier that lets its loads stay in flight; (2) every dCore wave has left its loop - the
+// role's tiles are in LDS by then; (3) the dCore tiles are in LDS.  The join and the dW stores come after (3), next to
+// the dCore tile sums of waves 0 .. BWD_WAVES - 1: nothing of the role lies between the dCore loop and its epilogue.
+constexpr int DWR_WAVES = 4, DWR_VPW = DWG_WAVES / DWR_WAVES, DWR_DEPTH = 8;
+constexpr size_t DWR_LDS_BYTES = (size_t)DWG_WAVES * 4 * 64 * sizeof(float);   // the 16 virtual waves' tiles
+static_assert(DWG_BFW == 16, "one tile per virtual wave");
+#ifndef DCTN_DWROLE_EARLY_LOADS
+// 1: the role's first loads go out in front of barrier (1).  Off: stamped, the role's 320 loads per CU were in the memory
+// path's queue ahead of the weight slice and held barrier (1) back from 1.3 to 3.3 us
+#define DCTN_DWROLE_EARLY_LOADS 0
+#endif
+__device__ __forceinline__ void head_dw_role_waves(const bf16_t* __restrict__ feat, const bf16_t* __restrict__ dL,
+                                                   bf16_t* __restrict__ dW, int B, int Cout, long long F, int n_dw,
+                                                   int rw, float* __restrict__ lds, const MfmaP& p) {
+  typedef DwBlock<DWG_BFW, true> Blk;
+  const int lane = threadIdx.x & 63;
+  const int nb = dw_spw(B) / 32;   // 32-sample blocks of a virtual wave
+  const int slice0 = (int)blockIdx.x;
+  const bool coop = slice0 < n_dw;
+  auto l = dw_lane<DWG_BFW, true>(B, Cout, F, slice0);
+  const __amdgpu_buffer_rsrc_t rs_f = make_rsrc(feat, l.f_bytes), rs_dl = make_rsrc(dL, l.dl_bytes);
+  Blk q[DWR_DEPTH];
+  // A virtual wave's samples are whole 32-sample blocks, so the blocks of consecutive virtual waves are consecutive
+  // blocks of the batch: the wave walks the blocks [gi, ge) of its slice, DWR_DEPTH at a time, and a tile is complete
+  // after every nb-th one.  gi = the next block to issue, gc = the next to consume (block kc of virtual wave vc).
+  int s = slice0, gi = rw * DWR_VPW * nb, ge = gi + DWR_VPW * nb, gc = gi, kc = 0, vc = rw * DWR_VPW;
+  bool solo = false;
+  auto issue_round = [&]() {
+    const int b1 = 32 * ge < B ? 32 * ge : B;   // (blocks past the wave's share or the batch: no address in range, zeros)
+#pragma unroll
+    for (int j = 0; j < DWR_DEPTH; ++j) dw_block_issue<DWG_BFW, true>(rs_f, rs_dl, l, 32 * (gi + j), b1, q[j]);
+    gi += DWR_DEPTH;
+  };
+  f32x4v acc[1] = {f32x4v{0.f, 0.f, 0.f, 0.f}};
+  f32x4v t4 = f32x4v{0.f, 0.f, 0.f, 0.f};   // a solo slice's join, in registers
+  auto consume_round = [&]() {
+#pragma unroll
+    for (int j = 0; j < DWR_DEPTH; ++j)
+      if (gc < ge) {
+        if (32 * gc < B) dw_block_mfma<DWG_BFW, true>(q[j], l.asel, acc);   // (as the finishing kernel: no product past the batch)
+        ++gc;
+        if (++kc == nb) {   // virtual wave vc is complete
+          if (solo) {
+            t4 += acc[0];
+          } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) lds[(vc * 4 + i) * 64 + lane] = acc[0][i];
+          }
+          acc[0] = f32x4v{0.f, 0.f, 0.f, 0.f};
+          kc = 0;
+          ++vc;
+        }
+      }
+  };
+  if (DCTN_DWROLE_EARLY_LOADS && coop) issue_round();
+  __builtin_amdgcn_s_barrier();   // (1)
+  if (coop) {
+    if (!DCTN_DWROLE_EARLY_LOADS) issue_round();
+    DCTN_STAMP_R(p, 0);
+    for (;;) {
+      __builtin_amdgcn_sched_barrier(0);
+      consume_round();
+      if (gc >= ge) {   // the slice is done: on to the next one no workgroup takes in the first round, this wave alone
+        if (solo) {
+          const long long f = (long long)s * DWG_BFW + l.n;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int c = 4 * l.kg + i;
+            if (c < Cout && f < F) dW[(long long)c * F + f] = (bf16_t)t4[i];
+          }
+        } else {
+          DCTN_STAMP_R(p, 1);
+        }
+        s += (int)gridDim.x * (solo ? DWR_WAVES : 1 + rw);
+        if (s >= n_dw) break;
+        solo = true;
+        l = dw_lane<DWG_BFW, true>(B, Cout, F, s);
+        gi = gc = kc = vc = 0;
+        ge = DWG_WAVES * nb;
+        t4 = f32x4v{0.f, 0.f, 0.f, 0.f};
+      }
+      issue_round();
+    }
+  }
+  __syncthreads();                // (2)
+  __builtin_amdgcn_s_barrier();   // (3)
+  if (coop) {   // thread (slot = rw, lane) sums element (rw, lane) of the 16 tiles in wave order, as head_dw_gemm_role does
+    float t = 0.f;
+#pragma unroll
+    for (int w = 0; w < DWG_WAVES; ++w) t += lds[(w * 4 + rw) * 64 + lane];
+    const int c = 4 * (lane >> 4) + rw;
+    const long long f = (long long)slice0 * DWG_BFW + (lane & 15);
+    if (c < Cout && f < F) dW[(long long)c * F + f] = (bf16_t)t;
+  }
+  DCTN_STAMP_R(p, 2);
 }
 
 __global__ __launch_bounds__(1024) void eps_head_reduce_k(const float* __restrict__ partial,
@@ -1967,16 +2144,16 @@ int bwd_launch_t(const void* x, const void* dY, void* dCore, void* ws, const Mfm
   constexpr int RW = NN == 9 ? 3 : 4;
   if (m.rowvec_ok && m.vec_ok && ovec && sizeof(S) == 2)
     DCTN_DCORE_LAUNCH((eps_bwd_dcore_q2reg_k<S, N0, N1, OP, true, true, RW, 0>), g, b, DYN, st,
-                       (const S*)x, (const S*)dY, (const S*)nullptr, (const S*)nullptr, (float*)ws, (float*)nullptr, m);
+                       (const S*)x, (const S*)dY, (const S*)nullptr, (const S*)nullptr, (float*)ws, (float*)nullptr, m, (S*)nullptr, 0);
   else if (m.vec_ok && ovec)
     DCTN_DCORE_LAUNCH((eps_bwd_dcore_q2reg_k<S, N0, N1, OP, true, true, 0, 0>), g, b, DYN, st,
-                       (const S*)x, (const S*)dY, (const S*)nullptr, (const S*)nullptr, (float*)ws, (float*)nullptr, m);
+                       (const S*)x, (const S*)dY, (const S*)nullptr, (const S*)nullptr, (float*)ws, (float*)nullptr, m, (S*)nullptr, 0);
   else if (m.vec_ok)
     DCTN_DCORE_LAUNCH((eps_bwd_dcore_q2reg_k<S, N0, N1, OP, true, false, 0, 0>), g, b, DYN, st,
-                       (const S*)x, (const S*)dY, (const S*)nullptr, (const S*)nullptr, (float*)ws, (float*)nullptr, m);
+                       (const S*)x, (const S*)dY, (const S*)nullptr, (const S*)nullptr, (float*)ws, (float*)nullptr, m, (S*)nullptr, 0);
   else
     DCTN_DCORE_LAUNCH((eps_bwd_dcore_q2reg_k<S, N0, N1, OP, false, false, 0, 0>), g, b, DYN, st,
-                       (const S*)x, (const S*)dY, (const S*)nullptr, (const S*)nullptr, (float*)ws, (float*)nullptr, m);
+                       (const S*)x, (const S*)dY, (const S*)nullptr, (const S*)nullptr, (float*)ws, (float*)nullptr, m, (S*)nullptr, 0);
   DCTN_CHECK_LAUNCH();
   if (m.opts & DCTN_OPT_MAIN_KERNEL_ONLY) return DCTN_PARTIAL;   // measurement option: partial sums only, gradients NOT written
   hipLaunchKernelGGL((eps_bwd_dcore_reduce_k<S>), dim3(BN * OP * AT), dim3(256), 0, st,
@@ -2050,10 +2227,36 @@ int bwd_head_launch_t(const void* x, const void* dL, const void* hw, const void*
   const dim3 g(grid), b(64 * BWD_WAVES);
   constexpr int NN = N0 + N1;
   constexpr int RW = NN == 9 ? 3 : 4;
+  // blocked4 features: dW is formed by DWR_WAVES more waves of the dCore workgroups (head_dw_role_waves), whose tiles
+  // take DWR_LDS_BYTES more of dynamic LDS; where that opt-in is refused the finishing kernel's gemm role forms dW
+  const int n_slices = (int)(((long long)m.P * OP + DWG_BFW - 1) / DWG_BFW);
+  bool dwrole = false;
+  if constexpr (A == 32 && MT <= 2 && OP == 4) {
+    constexpr size_t RDYN = DYN + 8192 + DWR_LDS_BYTES;
+#define DCTN_HEAD_ROLE_LAUNCH(ROWSV, HC)                                                                          \
+  do {                                                                                                            \
+    const void* kfn = (const void*)eps_bwd_dcore_q2reg_k<S, N0, N1, OP, true, true, ROWSV, HC, DWR_WAVES>;        \
+    if (dctn_lds_optin(kfn, RDYN)) {                                                                              \
+      hipLaunchKernelGGL((eps_bwd_dcore_q2reg_k<S, N0, N1, OP, true, true, ROWSV, HC, DWR_WAVES>), g,             \
+                         dim3(64 * (BWD_WAVES + DWR_WAVES)), RDYN, st, (const S*)x, (const S*)dL, (const S*)hw,   \
+                         (const S*)feat, (float*)ws, dwpart, m, (S*)dW, dW ? n_slices : 0);                       \
+      dwrole = true;                                                                                              \
+    }                                                                                                             \
+  } while (0)
+    if (blk && headmm) {
+      if (m.rowvec_ok) {
+        if (m.Cout <= 10) DCTN_HEAD_ROLE_LAUNCH(RW, 10); else DCTN_HEAD_ROLE_LAUNCH(RW, 16);
+      } else {
+        if (m.Cout <= 10) DCTN_HEAD_ROLE_LAUNCH(0, 10); else DCTN_HEAD_ROLE_LAUNCH(0, 16);
+      }
+    }
+#undef DCTN_HEAD_ROLE_LAUNCH
+  }
 #define DCTN_HEAD_LAUNCH(XV, ROWSV, HC)                                                                        \
   DCTN_DCORE_LAUNCH((eps_bwd_dcore_q2reg_k<S, N0, N1, OP, XV, true, ROWSV, HC>), g, b, (DYN > 0 ? DYN + 8192 : 0), st, (const S*)x, \
-                     (const S*)dL, (const S*)hw, (const S*)feat, (float*)ws, dwpart, m)
-  if (m.rowvec_ok && m.vec_ok) {
+                     (const S*)dL, (const S*)hw, (const S*)feat, (float*)ws, dwpart, m, (S*)nullptr, 0)
+  if (dwrole) {   // (launched above)
+  } else if (m.rowvec_ok && m.vec_ok) {
     if (m.Cout <= 10) DCTN_HEAD_LAUNCH(true, RW, 10); else DCTN_HEAD_LAUNCH(true, RW, 16);
   } else if (m.vec_ok) {
     if (m.Cout <= 10) DCTN_HEAD_LAUNCH(true, 0, 10); else DCTN_HEAD_LAUNCH(true, 0, 16);
@@ -2064,7 +2267,16 @@ int bwd_head_launch_t(const void* x, const void* dL, const void* hw, const void*
   DCTN_CHECK_LAUNCH();
   if (m.opts & DCTN_OPT_MAIN_KERNEL_ONLY) return DCTN_PARTIAL;   // measurement option: partial sums only, gradients NOT written
   const int fw = blk ? DWG_BFW : DWG_FW;   // features of a gemm workgroup's slice
-  const int n_core = BN * OP * AT, n_dw = gemm ? (int)(((long long)m.P * OP + fw - 1) / fw) : (int)((nW + 255) / 256);
+  const int n_core = BN * OP * AT;
+  if (dwrole) {   // dW is written: the finishing kernel keeps its dCore and dBias roles (no LDS opt-in)
+    hipLaunchKernelGGL(eps_head_reduce_k, dim3(n_core + 1), dim3(1024), 0, st, (const float*)ws, (S*)dCore, grid, A, BN, m.O, OP,
+                       AT * 32, n_core, (const float*)dwpart, (S*)nullptr, m.ncb, nW, 0, (const S*)dL, (S*)dBias, m.B, m.Cout,
+                       (const S*)feat, 0);
+    DCTN_CHECK_LAUNCH();
+    dctn_set_last_kernel("eps_head_bwd_mfma_q2reg");
+    return DCTN_OK;
+  }
+  const int n_dw = gemm ? (int)(((long long)m.P * OP + fw - 1) / fw) : (int)((nW + 255) / 256);
   const size_t gemm_lds = (size_t)DWG_WAVES * (fw / 4) * 64 * sizeof(float);
   static_assert(DWG_WAVES * 64 == 1024, "the gemm role is the whole workgroup of eps_head_reduce_k");
   if (gemm && !dctn_lds_optin((const void*)eps_head_reduce_k, gemm_lds)) return DCTN_ERR_LAUNCH;   // (after the main kernel)

@@ -78,7 +78,9 @@ enum {
   DCTN_OPT_SMALL_CHUNKS = 1 << 9,
   /* measurement only: dctn_eps_bwd / dctn_eps_head_bwd on the register-resident family launch their dominant
    * kernel (per-workgroup partial sums) and skip the small reduction kernel, so that the kernel can be timed
-   * alone; the gradients are NOT written and the call returns DCTN_PARTIAL (2), not DCTN_OK */
+   * alone; the gradients are NOT written and the call returns DCTN_PARTIAL (2), not DCTN_OK.  One exception:
+   * dctn_eps_head_bwd with DCTN_OPT_HEAD_FEATURES_BLOCKED4 forms the head weight gradient on spare waves of that
+   * dominant kernel, so there the kernel also writes d_weight (and its time includes that product) */
   DCTN_OPT_MAIN_KERNEL_ONLY = 1 << 10,
   /* dctn_eps_fwd / dctn_eps_bwd on the generic kernels whatever the shape: one lane per window walks the core rows
    * one factor digit after the other, no matrix cores, no Khatri-Rao halves - the independent evaluation order

@@ -12,6 +12,20 @@
 #include <vector>
 
 void dctn_set_last_kernel(const char*) {}
+// the parts of capi.hip the launchers need
+const DctnDev& dctn_dev() {
+  static const DctnDev d = [] {
+    DctnDev v{256, 160 * 1024};
+    hipDeviceProp_t pr;
+    if (hipGetDeviceProperties(&pr, 0) == hipSuccess && pr.multiProcessorCount > 0) v.cus = pr.multiProcessorCount;
+    return v;
+  }();
+  return d;
+}
+bool dctn_lds_optin(const void* fn, size_t bytes) {
+  return bytes <= (size_t)dctn_dev().lds &&
+         hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+}
 
 // the part of eps_fill_params (eps_generic.hip) this tool needs
 int eps_fill_params(EpsP& p, const int64_t xs[5], int C, int B, int H, int W, int Q, int K, int O, int policy) {
@@ -28,9 +42,15 @@ int eps_fill_params(EpsP& p, const int64_t xs[5], int C, int B, int H, int W, in
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e_), __LINE__); return 1; } } while (0)
 
-static void report(const char* name, const std::vector<unsigned long long>& st, int nblk, int nslots, const char* const* labels) {
+// origin: the first workgroup's entry, or `origin` when given (rows that carry no entry stamp of their own)
+static unsigned long long first_entry(const std::vector<unsigned long long>& st, int nblk) {
   unsigned long long t0 = ~0ull;
   for (int b = 0; b < nblk; ++b) if (st[b * 8]) t0 = std::min(t0, st[b * 8]);
+  return t0;
+}
+static void report(const char* name, const std::vector<unsigned long long>& st, int nblk, int nslots, const char* const* labels,
+                   unsigned long long origin = 0) {
+  const unsigned long long t0 = origin ? origin : first_entry(st, nblk);
   printf("%s: %d workgroups; times in us relative to the first workgroup's entry (min / median / max over workgroups)\n", name, nblk);
   for (int s = 0; s < nslots; ++s) {
     std::vector<double> v;
@@ -52,9 +72,9 @@ int main(int argc, char** argv) {
   for (auto& v : hc) v = bf(((float)(rand() % 4096) / 4096.f - 0.5f) * 0.1f);
   for (auto& v : hw) v = bf(((float)(rand() % 4096) / 4096.f - 0.5f) * 0.1f);
   for (auto& v : hdl) v = bf(((float)(rand() % 4096) / 4096.f - 0.5f) * 0.1f);
-  void *x, *core, *feat, *wgt, *dl, *dcore, *dw, *db, *ws, *logit;
+  void *x, *core, *feat, *featb, *wgt, *dl, *dcore, *dw, *db, *ws, *logit;
   unsigned long long* stamps;
-  CK(hipMalloc(&x, nx * 2)); CK(hipMalloc(&core, nc * 2)); CK(hipMalloc(&feat, nf * 2)); CK(hipMalloc(&wgt, nw * 2));
+  CK(hipMalloc(&x, nx * 2)); CK(hipMalloc(&core, nc * 2)); CK(hipMalloc(&feat, nf * 2)); CK(hipMalloc(&featb, (size_t)(B + 3) / 4 * 4 * P * O * 2)); CK(hipMalloc(&wgt, nw * 2));
   CK(hipMalloc(&dl, hdl.size() * 2)); CK(hipMalloc(&dcore, nc * 2)); CK(hipMalloc(&dw, nw * 2)); CK(hipMalloc(&db, 64)); CK(hipMemset(db, 0, 64)); CK(hipMalloc(&logit, (size_t)B * Cout * 2));
   CK(hipMemcpy(x, hx.data(), nx * 2, hipMemcpyHostToDevice)); CK(hipMemcpy(core, hc.data(), nc * 2, hipMemcpyHostToDevice));
   CK(hipMemcpy(wgt, hw.data(), nw * 2, hipMemcpyHostToDevice)); CK(hipMemcpy(dl, hdl.data(), hdl.size() * 2, hipMemcpyHostToDevice));
@@ -72,6 +92,8 @@ int main(int argc, char** argv) {
   const char* hl[] = {"entry", "core staged, fragments in regs", "first sample done", "last group's samples done (wave 0)", "end", "", "", ""};
   const char* bl[] = {"entry", "head-weight slice arrived", "first sample's loads arrived", "loop done", "dCore tile reduced + stored",
                       "end", "loop done, last wave", "every wave out of the loop (barrier)"};
+  const char* wl[] = {"dW role (blocked4): first loads issued", "dW role: products done, tiles in LDS", "dW role: join done, dW stored",
+                      "", "", "", "", ""};
   const char* rl[] = {"entry (dCore roles: blocks 0-63; gemm roles after)", "gemm: products done, tile in LDS", "gemm: barrier passed",
                       "", "end", "", "", ""};
   for (int rep = 0; rep < 3; ++rep) {   // the last repetition is reported (warm caches, as inside a replayed step)
@@ -99,6 +121,35 @@ int main(int argc, char** argv) {
     CK(hipStreamSynchronize(st));
     CK(hipMemcpy(hs.data(), stamps, NB * 8 * 8, hipMemcpyDeviceToHost));
     if (rep == 2) report("eps_bwd_dcore_q2reg_k (fused head)", hs, NB, 8, bl);
+    // the same kernel with blocked4 features: four more waves per workgroup form dW (their stamps: rows from DCTN_STAMP_ROLE_ROW)
+    CK(hipMemset(stamps, 0, NB * 8 * 8));
+    p.opts = DCTN_OPT_HEAD_FEATURES_BLOCKED4;
+    dctn_stamps_set(nullptr);
+    if (eps_head_fwd_mfma(x, core, wgt, db, featb, logit, p, Cout, DCTN_BF16, 0, st) != DCTN_OK) { printf("blocked4 fwd failed\n"); return 1; }
+    dctn_stamps_set(stamps);
+    p.opts = DCTN_OPT_HEAD_FEATURES_BLOCKED4 | DCTN_OPT_MAIN_KERNEL_ONLY;
+    if (eps_head_bwd_mfma(x, featb, dl, wgt, dcore, dw, db, ws, wsb, p, Cout, DCTN_BF16, 0, st) != DCTN_PARTIAL) return 1;
+    p.opts = 0;
+    CK(hipStreamSynchronize(st));
+    CK(hipMemcpy(hs.data(), stamps, NB * 8 * 8, hipMemcpyDeviceToHost));
+    if (rep == 2) {
+      std::vector<unsigned long long> a(hs.begin(), hs.begin() + DCTN_STAMP_ROLE_ROW * 8), b(hs.begin() + DCTN_STAMP_ROLE_ROW * 8, hs.end());
+      report("eps_bwd_dcore_q2reg_k (fused head, blocked4: + dW role waves), dCore waves", a, DCTN_STAMP_ROLE_ROW, 8, bl);
+      report("eps_bwd_dcore_q2reg_k (fused head, blocked4), dW role waves", b, NB - DCTN_STAMP_ROLE_ROW, 3, wl, first_entry(a, DCTN_STAMP_ROLE_ROW));
+    }
+    {   // the finishing kernel behind it: dCore tile sums and dBias only
+      dctn_stamps_set(nullptr);
+      CK(hipMemset(stamps, 0, NB * 8 * 8));
+      dctn_reduce_stamps_set(stamps);
+      p.opts = DCTN_OPT_HEAD_FEATURES_BLOCKED4;
+      if (eps_head_bwd_mfma(x, featb, dl, wgt, dcore, dw, db, ws, wsb, p, Cout, DCTN_BF16, 0, st) != DCTN_OK) return 1;
+      p.opts = 0;
+      CK(hipStreamSynchronize(st));
+      dctn_reduce_stamps_set(nullptr);
+      CK(hipMemcpy(hs.data(), stamps, NB * 8 * 8, hipMemcpyDeviceToHost));
+      if (rep == 2) report("eps_head_reduce_k behind it (dCore roles + dBias)", hs, NB, 5, rl);
+      dctn_stamps_set(stamps);
+    }
     // the finishing kernel (eager: its own launch, after the dCore kernel has drained)
     dctn_stamps_set(nullptr);
     CK(hipMemset(stamps, 0, NB * 8 * 8));
