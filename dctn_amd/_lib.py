@@ -63,10 +63,14 @@ SIGNATURES = {
     "dctn_sgd_l2_num_partials": (c_int, [c_i64]),
     "dctn_sgd_l2_step": (c_int, [c_void, c_void, c_void, c_void, c_i64, c_i64, ctypes.c_float, ctypes.c_float,
                                  ctypes.c_float, c_int, c_int, c_void]),
+    "dctn_sgd_l2_step_master": (c_int, [c_void] * 5 + [c_i64, c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                        c_int, c_void]),
     "dctn_adam_state_bytes": (c_size, []),
     "dctn_adam_l2_num_partials": (c_int, [c_i64]),
     "dctn_adam_l2_step": (c_int, [c_void] * 6 + [c_i64, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_float,
                                   ctypes.c_float, ctypes.c_float, c_int, c_void]),
+    "dctn_adam_l2_step_master": (c_int, [c_void] * 7 + [c_i64, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_float,
+                                         ctypes.c_float, ctypes.c_float, c_void]),
     "dctn_ce_score_accumulate": (c_int, [c_void, c_void, c_void, c_i64, c_int, c_int, c_void]),
     "dctn_window_stats": (c_int, [c_void, _I64x5, c_void] + [c_int] * 6 + [c_int, c_void]),
     "dctn_phi_window_stats": (c_int, [c_void, c_void, c_int, c_int, c_int, c_int, c_void]),

@@ -3,6 +3,8 @@
 //   adam_l2_k  : torch.optim.Adam (coupled weight decay) + the L2 regulariser over ONE flat parameter buffer, like
 //                sgd_l2_k.  The step count t and the learning rate are read from a 16-byte device block, and the
 //                launch itself advances t: a captured graph replays the same node and still gets t, t+1, t+2, ...
+//                MASTER form (bf16 parameters): the step runs on a float32 master copy, which is read and written;
+//                the bf16 cell only receives the rounded result and is never read.
 //   ce_score_k : adds one batch's {sum of cross-entropies, correct rows, rows} to three float64 values
 #include "common.h"
 
@@ -61,14 +63,17 @@ __device__ __forceinline__ void store4(bf16_t* p, const float (&x)[4]) {
 
 // VEC: four elements per lane and access (16 bytes of exp_avg / exp_avg_sq, 16 or 8 of the parameters) when every
 // pointer is aligned for it; the tail of n and the unaligned case take one element per lane.
+// MASTER (S = bf16_t): the weight comes from and goes back to the float32 array `wm`; `w` gets its bf16 rounding and is
+// not read.  adam_elem sees the same float32 values in the same order as the float instantiation does, so `wm`, the
+// moments and the sq_sum slots are that instantiation's bits.  Without MASTER `wm` is unused (null).
 // Workgroups of 1024 threads, at most 256 of them: the ticket at the end is one atomic per workgroup on ONE address,
 // and those serialise at about 12 ns each (measured: 1024 workgroups of 256 threads took 17.7 us over 1.9 M
 // parameters where the same stream without a ticket, sgd_l2_k, takes 5.7 us).
-template <typename S, bool VEC>
-__global__ __launch_bounds__(1024) void adam_l2_k(S* __restrict__ w, const S* __restrict__ g, float* __restrict__ ea,
-                                                 float* __restrict__ eas, float* __restrict__ sq_sum,
-                                                 AdamState* __restrict__ state, long long n, long long n_reg,
-                                                 AdamCoef k) {
+template <typename S, bool VEC, bool MASTER>
+__global__ __launch_bounds__(1024) void adam_l2_k(S* __restrict__ w, float* __restrict__ wm, const S* __restrict__ g,
+                                                 float* __restrict__ ea, float* __restrict__ eas,
+                                                 float* __restrict__ sq_sum, AdamState* __restrict__ state, long long n,
+                                                 long long n_reg, AdamCoef k) {
   __shared__ float red[16];
   __shared__ float scale[2];
   // lane 0 of every workgroup reads the step count and the learning rate BEFORE it takes the workgroup's ticket below;
@@ -92,15 +97,19 @@ __global__ __launch_bounds__(1024) void adam_l2_k(S* __restrict__ w, const S* __
   if (VEC) {
     for (long long i = tid * 4; i < n_vec; i += nthr * 4) {
       float wi[4], gi[4], mi[4], vi[4];
-      load4(w + i, wi), load4(g + i, gi), load4(ea + i, mi), load4(eas + i, vi);
+      if (MASTER) load4(wm + i, wi); else load4(w + i, wi);
+      load4(g + i, gi), load4(ea + i, mi), load4(eas + i, vi);
 #pragma unroll
       for (int e = 0; e < 4; ++e) wi[e] = adam_elem(wi[e], gi[e], mi[e], vi[e], i + e < n_reg, k, step, bc2_sqrt, part);
       store4(ea + i, mi), store4(eas + i, vi), store4(w + i, wi);
+      if (MASTER) store4(wm + i, wi);
     }
   }
   for (long long i = n_vec + tid; i < n; i += nthr) {
     float m = ea[i], v = eas[i];
-    w[i] = (S)adam_elem((float)w[i], (float)g[i], m, v, i < n_reg, k, step, bc2_sqrt, part);
+    const float wi = adam_elem(MASTER ? wm[i] : (float)w[i], (float)g[i], m, v, i < n_reg, k, step, bc2_sqrt, part);
+    w[i] = (S)wi;
+    if (MASTER) wm[i] = wi;
     ea[i] = m, eas[i] = v;
   }
   for (int off = 32; off > 0; off >>= 1) part += __shfl_down(part, off, 64);
@@ -199,9 +208,11 @@ size_t dctn_adam_state_bytes(void) { return sizeof(AdamState); }
 
 int dctn_adam_l2_num_partials(int64_t n) { return n < 1 ? 0 : (int)adam_blocks_for(n); }
 
-int dctn_adam_l2_step(void* params, const void* grads, void* exp_avg, void* exp_avg_sq, void* sq_sum, void* state,
-                      int64_t n, int64_t n_reg, double beta1, double beta2, float eps, float weight_decay, float l2,
-                      int dtype, void* stream) {
+// master == nullptr: the parameters are updated in their own dtype; otherwise they are bf16, written only, and the step
+// runs on the float32 `master`
+static int adam_launch(void* master, void* params, const void* grads, void* exp_avg, void* exp_avg_sq, void* sq_sum,
+                       void* state, int64_t n, int64_t n_reg, double beta1, double beta2, float eps, float weight_decay,
+                       float l2, int dtype, void* stream) {
   if (!params || !grads || !exp_avg || !exp_avg_sq || !state) return DCTN_ERR_NULL;
   if (n < 1 || n_reg < 0 || n_reg > n) return DCTN_ERR_BAD_SHAPE;
   if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return DCTN_ERR_BAD_SHAPE;   // torch raises ValueError
@@ -212,20 +223,38 @@ int dctn_adam_l2_step(void* params, const void* grads, void* exp_avg, void* exp_
   k.ln_b1 = std::log(beta1), k.ln_b2 = std::log(beta2);   // beta = 0: -inf, and 1 - beta^t = -expm1(-inf) = 1
   k.eps = eps, k.wd = weight_decay, k.two_l2 = 2.f * l2;
   const size_t esz = dtype == DCTN_F32 ? 4 : 2;
-  const bool vec = ((uintptr_t)params | (uintptr_t)grads) % (4 * esz) == 0 && ((uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) % 16 == 0;
+  const bool vec = ((uintptr_t)params | (uintptr_t)grads) % (4 * esz) == 0 &&
+                   ((uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)master) % 16 == 0;
   const dim3 g(adam_blocks_for(n)), b(1024);
   AdamState* sp = (AdamState*)state;
-#define DCTN_ADAM_LAUNCH(S, VEC)                                                                                   \
-  hipLaunchKernelGGL((adam_l2_k<S, VEC>), g, b, 0, st, (S*)params, (const S*)grads, (float*)exp_avg, (float*)exp_avg_sq, \
-                     (float*)sq_sum, sp, (long long)n, (long long)n_reg, k)
-  if (dtype == DCTN_F32) {
-    if (vec) DCTN_ADAM_LAUNCH(float, true); else DCTN_ADAM_LAUNCH(float, false);
+#define DCTN_ADAM_LAUNCH(S, VEC, MASTER)                                                                            \
+  hipLaunchKernelGGL((adam_l2_k<S, VEC, MASTER>), g, b, 0, st, (S*)params, (float*)master, (const S*)grads,        \
+                     (float*)exp_avg, (float*)exp_avg_sq, (float*)sq_sum, sp, (long long)n, (long long)n_reg, k)
+  if (master) {
+    if (vec) DCTN_ADAM_LAUNCH(bf16_t, true, true); else DCTN_ADAM_LAUNCH(bf16_t, false, true);
+  } else if (dtype == DCTN_F32) {
+    if (vec) DCTN_ADAM_LAUNCH(float, true, false); else DCTN_ADAM_LAUNCH(float, false, false);
   } else {
-    if (vec) DCTN_ADAM_LAUNCH(bf16_t, true); else DCTN_ADAM_LAUNCH(bf16_t, false);
+    if (vec) DCTN_ADAM_LAUNCH(bf16_t, true, false); else DCTN_ADAM_LAUNCH(bf16_t, false, false);
   }
 #undef DCTN_ADAM_LAUNCH
   DCTN_CHECK_LAUNCH();
   return DCTN_OK;
+}
+
+int dctn_adam_l2_step(void* params, const void* grads, void* exp_avg, void* exp_avg_sq, void* sq_sum, void* state,
+                      int64_t n, int64_t n_reg, double beta1, double beta2, float eps, float weight_decay, float l2,
+                      int dtype, void* stream) {
+  return adam_launch(nullptr, params, grads, exp_avg, exp_avg_sq, sq_sum, state, n, n_reg, beta1, beta2, eps,
+                     weight_decay, l2, dtype, stream);
+}
+
+int dctn_adam_l2_step_master(void* master, void* params, const void* grads, void* exp_avg, void* exp_avg_sq,
+                             void* sq_sum, void* state, int64_t n, int64_t n_reg, double beta1, double beta2, float eps,
+                             float weight_decay, float l2, void* stream) {
+  if (!master) return DCTN_ERR_NULL;
+  return adam_launch(master, params, grads, exp_avg, exp_avg_sq, sq_sum, state, n, n_reg, beta1, beta2, eps,
+                     weight_decay, l2, DCTN_BF16, stream);
 }
 
 int dctn_ce_score_accumulate(const void* logits, const void* labels, void* acc, int64_t B, int C, int dtype,

@@ -9,7 +9,9 @@
 //   ce_bwd_k   : dLogits = (softmax - onehot) * dLoss / n, in the logits' dtype
 //   sgd_l2_k   : over ONE flat buffer holding all parameters: g += 2 * l2 * w on the regularised
 //                prefix, buf = momentum * buf + g, w -= lr * buf; the regulariser's value
-//                sum w^2 is left as one partial sum per workgroup (float32 master arithmetic, storage dtype kept)
+//                sum w^2 is left as one partial sum per workgroup (float32 arithmetic; the result is rounded back
+//                into the parameter's cell).  MASTER form (bf16 parameters): the step runs on a float32 master
+//                copy, which is read and written; the bf16 cell only receives the rounded result
 #include "common.h"
 
 namespace {
@@ -95,22 +97,33 @@ __global__ __launch_bounds__(256) void ce_bwd_k(const S* __restrict__ logits, co
   }
 }
 
-template <typename S>
-__global__ __launch_bounds__(256) void sgd_l2_k(S* __restrict__ w, const S* __restrict__ g, float* __restrict__ buf,
-                                                float* __restrict__ sq_sum, long long n, long long n_reg, float lr,
-                                                float momentum, float l2, int first_step) {
+// The arithmetic of one element; every product-sum is an explicit fmaf (the contraction the compiler chose for the
+// plain expressions), so that every instantiation of the kernel produces the same bits
+__device__ __forceinline__ float sgd_elem(float wi, float gi, float* __restrict__ buf, bool reg, float lr, float momentum,
+                                          float two_l2, int first_step, float& part) {
+  if (reg) {
+    gi = fmaf(two_l2, wi, gi);
+    part = fmaf(wi, wi, part);
+  }
+  const float bi = first_step ? gi : fmaf(momentum, *buf, gi);   // torch.optim.SGD: the first step copies g
+  *buf = bi;
+  return fmaf(-lr, bi, wi);
+}
+
+// MASTER (S = bf16_t): the weight comes from and goes back to the float32 array `wm`; `w` gets its bf16 rounding and is
+// not read, and `wm` and the sq_sum slots are the float instantiation's bits.  Without MASTER `wm` is unused (null).
+template <typename S, bool MASTER>
+__global__ __launch_bounds__(256) void sgd_l2_k(S* __restrict__ w, float* __restrict__ wm, const S* __restrict__ g,
+                                                float* __restrict__ buf, float* __restrict__ sq_sum, long long n,
+                                                long long n_reg, float lr, float momentum, float l2, int first_step) {
   __shared__ float red[4];
   float part = 0.f;
+  const float two_l2 = 2.f * l2;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const float wi = (float)w[i];
-    float gi = (float)g[i];
-    if (i < n_reg) {
-      gi += 2.f * l2 * wi;
-      part += wi * wi;
-    }
-    const float bi = first_step ? gi : momentum * buf[i] + gi;   // torch.optim.SGD: the first step copies g
-    buf[i] = bi;
-    w[i] = (S)(wi - lr * bi);
+    const float wi = sgd_elem(MASTER ? wm[i] : (float)w[i], (float)g[i], buf + i, i < n_reg, lr, momentum, two_l2,
+                              first_step, part);
+    w[i] = (S)wi;
+    if (MASTER) wm[i] = wi;
   }
   for (int off = 32; off > 0; off >>= 1) part += __shfl_down(part, off, 64);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
@@ -180,19 +193,33 @@ int dctn_ce_loss_bwd(const void* logits, const void* labels, const void* dloss, 
 
 int dctn_sgd_l2_num_partials(int64_t n) { return n < 1 ? 0 : (int)blocks_for(n); }
 
-int dctn_sgd_l2_step(void* params, const void* grads, void* momentum_buf, void* sq_sum, int64_t n, int64_t n_reg,
-                     float lr, float momentum, float l2, int first_step, int dtype, void* stream) {
+// master == nullptr: the parameters are updated in their own dtype; otherwise they are bf16, written only
+static int sgd_launch(void* master, void* params, const void* grads, void* momentum_buf, void* sq_sum, int64_t n,
+                      int64_t n_reg, float lr, float momentum, float l2, int first_step, int dtype, void* stream) {
   if (!params || !grads || !momentum_buf) return DCTN_ERR_NULL;
   if (n < 1 || n_reg < 0 || n_reg > n) return DCTN_ERR_BAD_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   if (dtype != DCTN_F32 && dtype != DCTN_BF16) return DCTN_ERR_BAD_DTYPE;
   const dim3 g(blocks_for(n)), b(256);
-  if (dtype == DCTN_F32)
-    hipLaunchKernelGGL(sgd_l2_k<float>, g, b, 0, st, (float*)params, (const float*)grads, (float*)momentum_buf, (float*)sq_sum, (long long)n, (long long)n_reg, lr, momentum, l2, first_step);
+  if (master)
+    hipLaunchKernelGGL((sgd_l2_k<bf16_t, true>), g, b, 0, st, (bf16_t*)params, (float*)master, (const bf16_t*)grads, (float*)momentum_buf, (float*)sq_sum, (long long)n, (long long)n_reg, lr, momentum, l2, first_step);
+  else if (dtype == DCTN_F32)
+    hipLaunchKernelGGL((sgd_l2_k<float, false>), g, b, 0, st, (float*)params, (float*)nullptr, (const float*)grads, (float*)momentum_buf, (float*)sq_sum, (long long)n, (long long)n_reg, lr, momentum, l2, first_step);
   else
-    hipLaunchKernelGGL(sgd_l2_k<bf16_t>, g, b, 0, st, (bf16_t*)params, (const bf16_t*)grads, (float*)momentum_buf, (float*)sq_sum, (long long)n, (long long)n_reg, lr, momentum, l2, first_step);
+    hipLaunchKernelGGL((sgd_l2_k<bf16_t, false>), g, b, 0, st, (bf16_t*)params, (float*)nullptr, (const bf16_t*)grads, (float*)momentum_buf, (float*)sq_sum, (long long)n, (long long)n_reg, lr, momentum, l2, first_step);
   DCTN_CHECK_LAUNCH();
   return DCTN_OK;
+}
+
+int dctn_sgd_l2_step(void* params, const void* grads, void* momentum_buf, void* sq_sum, int64_t n, int64_t n_reg,
+                     float lr, float momentum, float l2, int first_step, int dtype, void* stream) {
+  return sgd_launch(nullptr, params, grads, momentum_buf, sq_sum, n, n_reg, lr, momentum, l2, first_step, dtype, stream);
+}
+
+int dctn_sgd_l2_step_master(void* master, void* params, const void* grads, void* momentum_buf, void* sq_sum,
+                            int64_t n, int64_t n_reg, float lr, float momentum, float l2, int first_step, void* stream) {
+  if (!master) return DCTN_ERR_NULL;
+  return sgd_launch(master, params, grads, momentum_buf, sq_sum, n, n_reg, lr, momentum, l2, first_step, DCTN_BF16, stream);
 }
 
 }  // extern "C"

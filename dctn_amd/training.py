@@ -236,9 +236,13 @@ class _FlatOptimizer:
     """What FlatSGD and FlatAdam share: the parameters moved into ONE flat buffer (their ``.data`` become views of it,
     in the order regularised + others), the gradients read in place when they already sit back to back in that
     order (the fused EPS + head backward allocates them so) and gathered otherwise, and the regulariser's value left
-    by the step kernel as one partial sum of squares per workgroup."""
+    by the step kernel as one partial sum of squares per workgroup.
 
-    def __init__(self, regularised, others, num_partials: Callable[[int], int]):
+    ``master_weights=True`` with bfloat16 parameters adds ``master``: a float32 copy of the flat buffer (initialised
+    by exact widening) that the step kernel updates; the bfloat16 parameters then only receive its rounding.  With
+    float32 parameters the option changes nothing and ``master`` is None."""
+
+    def __init__(self, regularised, others, num_partials: Callable[[int], int], master_weights: bool = False):
         self.reg_params = [p for p in regularised]
         self.params = self.reg_params + [p for p in others]
         assert self.params and len({p.dtype for p in self.params}) == 1 and len({p.device for p in self.params}) == 1
@@ -256,6 +260,29 @@ class _FlatOptimizer:
         # one partial sum of squares per workgroup of the kernel; added up only when the value is asked for
         self.sq_sum = torch.zeros(num_partials(self.n), dtype=torch.float32, device=ref.device)
         self.flat_grad = torch.zeros(self.n, dtype=ref.dtype, device=ref.device)
+        self.master: Optional[Tensor] = None
+        if master_weights and ref.dtype == torch.bfloat16:
+            self.master = self.flat.to(torch.float32)
+
+    def refresh_master(self) -> None:
+        """Rebuilds the float32 master copy from the current bfloat16 parameters (nothing to do without one).  Call it
+        after anything wrote the parameters behind the optimizer's back - ``model.load_state_dict``,
+        ``ddp.broadcast_parameters`` - or the next step starts from the values the master held before."""
+        if self.master is not None:
+            with torch.no_grad():
+                self.master.copy_(self.flat)
+
+    def _load_master(self, state: Dict[str, Any]) -> None:
+        if self.master is None:
+            return
+        saved = state.get("master")
+        if saved is None:   # a state written without the option: the parameters are all there is
+            self.refresh_master()
+            return
+        if saved.numel() != self.n:
+            raise ValueError(f"optimizer state holds {saved.numel()} master values, the parameters {self.n}")
+        with torch.no_grad():
+            self.master.copy_(saved.reshape(-1))
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         for p in self.params:
@@ -300,10 +327,16 @@ class FlatSGD(_FlatOptimizer):
     become views of it, in the order regularised + others); when the gradients already sit back to back
     in that order (the fused EPS + head backward allocates them so) the step reads them in place,
     otherwise they are gathered first.  Semantics of torch.optim.SGD(momentum, dampening = 0).
+
+    ``master_weights=True``: bfloat16 parameters get a float32 master copy that the kernel updates
+    (`dctn_sgd_l2_step_master`); an update below half an ulp of the bfloat16 value is then kept instead of rounded
+    away.  ``state_dict()`` / ``load_state_dict()`` carry the momentum buffer, the step count, the hyper-parameters
+    and the master copy.
     """
 
-    def __init__(self, regularised, others=(), lr: float = 1e-3, momentum: float = 0.0, l2: float = 0.0):
-        super().__init__(regularised, others, L.lib().dctn_sgd_l2_num_partials)
+    def __init__(self, regularised, others=(), lr: float = 1e-3, momentum: float = 0.0, l2: float = 0.0,
+                 master_weights: bool = False):
+        super().__init__(regularised, others, L.lib().dctn_sgd_l2_num_partials, master_weights)
         self.lr, self.momentum, self.l2 = float(lr), float(momentum), float(l2)
         self.buf = torch.zeros(self.n, dtype=torch.float32, device=self.flat.device)
         self._steps = 0
@@ -312,11 +345,33 @@ class FlatSGD(_FlatOptimizer):
     def step(self) -> None:
         g = self._grads()
         dev = self.flat.device
-        L.check(L.lib().dctn_sgd_l2_step(self.flat.data_ptr(), g.data_ptr(), self.buf.data_ptr(), self.sq_sum.data_ptr(),
-                                         self.n, self.n_reg, self.lr, self.momentum, self.l2,
-                                         1 if self._steps == 0 else 0, L.dtype_code(self.flat), L.stream_ptr(dev)),
-                "fused SGD step")
+        first = 1 if self._steps == 0 else 0
+        if self.master is not None:
+            L.check(L.lib().dctn_sgd_l2_step_master(self.master.data_ptr(), self.flat.data_ptr(), g.data_ptr(),
+                                                    self.buf.data_ptr(), self.sq_sum.data_ptr(), self.n, self.n_reg,
+                                                    self.lr, self.momentum, self.l2, first, L.stream_ptr(dev)),
+                    "fused SGD step (master weights)")
+        else:
+            L.check(L.lib().dctn_sgd_l2_step(self.flat.data_ptr(), g.data_ptr(), self.buf.data_ptr(),
+                                             self.sq_sum.data_ptr(), self.n, self.n_reg, self.lr, self.momentum, self.l2,
+                                             first, L.dtype_code(self.flat), L.stream_ptr(dev)), "fused SGD step")
         self._steps += 1
+
+    def state_dict(self) -> Dict[str, Any]:
+        """Everything a resumed run needs besides the parameters themselves (those are the model's state_dict)."""
+        state = {"steps": self._steps, "lr": self.lr, "momentum": self.momentum, "l2": self.l2, "buf": self.buf.clone()}
+        if self.master is not None:
+            state["master"] = self.master.clone()
+        return state
+
+    def load_state_dict(self, state: Dict[str, Any]) -> None:
+        if state["buf"].numel() != self.n:
+            raise ValueError(f"optimizer state holds {state['buf'].numel()} values, the parameters {self.n}")
+        self.lr, self.momentum, self.l2 = float(state["lr"]), float(state["momentum"]), float(state["l2"])
+        with torch.no_grad():
+            self.buf.copy_(state["buf"].reshape(-1))
+        self._steps = int(state["steps"])
+        self._load_master(state)
 
 
 class FlatAdam(_FlatOptimizer):
@@ -329,13 +384,19 @@ class FlatAdam(_FlatOptimizer):
     same launch advances: a `GraphedTrainStep` that captured ``step()`` gets t, t+1, ... on its replays, and
     assigning ``opt.lr`` (a tiny asynchronous write on the current stream; not allowed during a capture) changes the
     rate of every later step, replays of an already captured graph included.  Reading ``opt.lr`` returns the host
-    copy; ``opt.t`` reads the device (it synchronises).  ``state_dict()`` / ``load_state_dict()`` carry t, lr, m, v
-    and the hyper-parameters: a run resumed from them continues bit-identically.
+    copy; ``opt.t`` reads the device (it synchronises).  ``state_dict()`` / ``load_state_dict()`` carry t, lr, m, v,
+    the hyper-parameters and the master copy when there is one: a run resumed from them continues bit-identically.
+
+    ``master_weights=True``: bfloat16 parameters get a float32 master copy ``master`` that the same launch updates
+    (`dctn_adam_l2_step_master`); the parameters receive its rounding and are never read by the step.  Without it a
+    bfloat16 weight whose Adam step (about ``lr``) is below half an ulp of its value does not move at all.  The
+    master follows, bit for bit, what FlatAdam does on float32 parameters given the same gradients.  Call
+    ``refresh_master()`` after writing the parameters from outside.
     """
 
     def __init__(self, regularised, others=(), lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0, l2: float = 0.0):
-        super().__init__(regularised, others, L.lib().dctn_adam_l2_num_partials)
+                 weight_decay: float = 0.0, l2: float = 0.0, master_weights: bool = False):
+        super().__init__(regularised, others, L.lib().dctn_adam_l2_num_partials, master_weights)
         if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0 and lr >= 0.0 and eps >= 0.0 and weight_decay >= 0.0):
             raise ValueError(f"invalid Adam hyper-parameters: lr={lr} betas={betas} eps={eps} weight_decay={weight_decay}")
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
@@ -372,6 +433,13 @@ class FlatAdam(_FlatOptimizer):
     def step(self) -> None:
         g = self._grads()
         dev = self.flat.device
+        if self.master is not None:
+            L.check(L.lib().dctn_adam_l2_step_master(self.master.data_ptr(), self.flat.data_ptr(), g.data_ptr(),
+                                                     self.m.data_ptr(), self.v.data_ptr(), self.sq_sum.data_ptr(),
+                                                     self._state.data_ptr(), self.n, self.n_reg, self.betas[0],
+                                                     self.betas[1], self.eps, self.weight_decay, self.l2,
+                                                     L.stream_ptr(dev)), "fused Adam step (master weights)")
+            return
         L.check(L.lib().dctn_adam_l2_step(self.flat.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
                                           self.sq_sum.data_ptr(), self._state.data_ptr(), self.n, self.n_reg,
                                           self.betas[0], self.betas[1], self.eps, self.weight_decay, self.l2,
@@ -379,8 +447,11 @@ class FlatAdam(_FlatOptimizer):
 
     def state_dict(self) -> Dict[str, Any]:
         """Everything a resumed run needs besides the parameters themselves (those are the model's state_dict)."""
-        return {"t": self.t, "lr": self._lr, "m": self.m.clone(), "v": self.v.clone(), "betas": self.betas,
-                "eps": self.eps, "weight_decay": self.weight_decay, "l2": self.l2}
+        state = {"t": self.t, "lr": self._lr, "m": self.m.clone(), "v": self.v.clone(), "betas": self.betas,
+                 "eps": self.eps, "weight_decay": self.weight_decay, "l2": self.l2}
+        if self.master is not None:
+            state["master"] = self.master.clone()
+        return state
 
     def load_state_dict(self, state: Dict[str, Any]) -> None:
         if state["m"].numel() != self.n or state["v"].numel() != self.n:
@@ -393,6 +464,7 @@ class FlatAdam(_FlatOptimizer):
             self._state.zero_()
             self._state[0] = int(state["t"])
         self.lr = state["lr"]
+        self._load_master(state)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -432,6 +504,10 @@ def train(dl, model, optimizer, dev, loss_fn, reg_fn, reg_coeff: float, at_iter_
         ddp.broadcast_parameters(list(st_x["model"].parameters()) + list(st_x["model"].buffers()))
         if hasattr(st_x["model"], "_refresh_p"):
             st_x["model"]._refresh_p()
+        # the optimizer was built before this broadcast: a float32 master copy of the parameters (FlatAdam / FlatSGD
+        # with master_weights) still holds this rank's own initialisation
+        if getattr(optimizer, "refresh_master", None) is not None:
+            optimizer.refresh_master()
         reducer = ddp.FlatGradAllReducer(st_x["model"].parameters(), average=True)
     st_it: StIt = {}
 

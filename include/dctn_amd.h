@@ -375,7 +375,15 @@ int dctn_phi_expand(const void* images, void* x, int64_t n_pixels, float scale, 
  *                      OVERWRITTEN): slot b = workgroup b's part of the sum of w^2 over the prefix BEFORE the
  *                      update; their sum is the regulariser's value / its coefficient (stored, not
  *                      accumulated: no fill launch and no atomics in the iteration).
- *                      momentum_buf is float32 whatever the parameter dtype.
+ *                      momentum_buf is float32 whatever the parameter dtype.  The arithmetic is float32 and
+ *                      the result is rounded back into the parameter's own cell: NO float32 copy of a bf16
+ *                      parameter is kept (dctn_sgd_l2_step_master below keeps one).
+ *   dctn_sgd_l2_step_master (version 501) : the same step for bf16 parameters with a float32 master copy.
+ *                      master (float32, n values) is READ and OVERWRITTEN: the update above runs on it, and
+ *                      sq_sum is the MASTER's sum of w^2 before the update.  params (bf16, n values) is
+ *                      OVERWRITTEN with the new master value rounded to nearest even and is NEVER READ.
+ *                      grads are bf16.  The master values are, bit for bit, what dctn_sgd_l2_step leaves in
+ *                      float32 parameters given the same gradients.  Same validation and return codes.
  * logits (B, C) contiguous, labels int64; dtypes DCTN_F32 / DCTN_BF16.  Rows labelled -100 (F.cross_entropy's default
  * ignore_index) add nothing to the loss, get a zero gradient row and do not count in the mean (n = the other rows; n = 0:
  * NaN, as torch).  Any other label outside [0, C) makes the loss and that sample's gradient row NaN (F.cross_entropy
@@ -391,10 +399,14 @@ int dctn_ce_loss_bwd(const void* logits, const void* labels, const void* dloss, 
 int dctn_sgd_l2_num_partials(int64_t n);
 int dctn_sgd_l2_step(void* params, const void* grads, void* momentum_buf, void* sq_sum, int64_t n, int64_t n_reg,
                      float lr, float momentum, float l2, int first_step, int dtype, void* stream);
+int dctn_sgd_l2_step_master(void* master, void* params, const void* grads, void* momentum_buf, void* sq_sum,
+                            int64_t n, int64_t n_reg, float lr, float momentum, float l2, int first_step, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Adam (torch.optim.Adam: coupled weight decay, amsgrad = False, maximize = False) plus the same L2 regulariser, as
- * ONE launch per step over the flat parameter buffer.  Per element, float32 master arithmetic:
+ * ONE launch per step over the flat parameter buffer.  Per element, in float32 arithmetic (the parameter is widened,
+ * updated and rounded back into its own cell; dctn_adam_l2_step STORES no float32 copy of a bf16 parameter, so an
+ * update below half an ulp of the bf16 value is lost - dctn_adam_l2_step_master keeps that copy):
  *   g = grads + weight_decay*w (+ 2*l2*w on the regularised prefix),
  *   m = beta1*m + (1-beta1)*g,  v = beta2*v + (1-beta2)*g*g,
  *   w -= (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)         t = number of this step, from 1.
@@ -410,12 +422,23 @@ int dctn_sgd_l2_step(void* params, const void* grads, void* momentum_buf, void* 
  *   uint32 reserved     0
  * The caller creates the block once (zeroes + lr) and may read or write it in stream order between launches.
  * beta1^t and beta2^t are formed from t in the kernel (no running products).
+ *
+ * dctn_adam_l2_step_master (version 501): the same launch for bf16 parameters with a float32 master copy.
+ *   master : float32, n values, READ and OVERWRITTEN - the step above runs on it (weight decay, the 2*l2*w term and
+ *            sq_sum all see the master value; sq_sum is the MASTER's sum of w^2 before the update)
+ *   params : bf16, n values, OVERWRITTEN with the new master value rounded to nearest even; NEVER READ
+ *   grads  : bf16;  exp_avg / exp_avg_sq / sq_sum / state and the partial and state sizes: as above
+ * The master values, the moments and t are, bit for bit, what dctn_adam_l2_step leaves in float32 parameters given
+ * the same gradients.  Same validation and return codes (no dtype argument: the dtypes are fixed).
  * ------------------------------------------------------------------------------------------ */
 size_t dctn_adam_state_bytes(void);
 int dctn_adam_l2_num_partials(int64_t n);
 int dctn_adam_l2_step(void* params, const void* grads, void* exp_avg, void* exp_avg_sq, void* sq_sum, void* state,
                       int64_t n, int64_t n_reg, double beta1, double beta2, float eps, float weight_decay, float l2,
                       int dtype, void* stream);
+int dctn_adam_l2_step_master(void* master, void* params, const void* grads, void* exp_avg, void* exp_avg_sq,
+                             void* sq_sum, void* state, int64_t n, int64_t n_reg, double beta1, double beta2, float eps,
+                             float weight_decay, float l2, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Scoring (reference: dctn/evaluation.py:7-22): one launch per batch ADDS to acc = three float64 values

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""The complete graphed cfg2 bf16 training iteration (B = 1024) under four optimizers, and scoring with and without
+"""The complete graphed cfg2 bf16 training iteration (B = 1024) under four optimizers (the two flat ones also with
+float32 master weights), and scoring with and without
 the fused accumulate kernel - one process, the variants alternated round by round, so that the differences are
 read against the spread of one variant repeated.
 
@@ -40,10 +41,13 @@ def make(kind):
     model = EPSesPlusLinear(((3, 4),), UnitTheoreticalOutputStd(), 1.0, dev, torch.bfloat16)
     flat = (list(model.epses) + [model.linear.weight], [model.linear.bias])
     reg = dict(reg_fn=lambda m: m.epswise_l2_regularizer(), reg_coeff=L2)   # what the folded l2 term replaces
-    if kind == "flat_sgd":
-        return GraphedTrainStep(model, x, y, fused_cross_entropy, FlatSGD(*flat, lr=1e-3, momentum=0.9, l2=L2), warmup=2)
-    if kind == "flat_adam":
-        return GraphedTrainStep(model, x, y, fused_cross_entropy, FlatAdam(*flat, lr=1e-3, weight_decay=1e-4, l2=L2), warmup=2)
+    master = kind.endswith("_master")
+    if kind in ("flat_sgd", "flat_sgd_master"):
+        opt = FlatSGD(*flat, lr=1e-3, momentum=0.9, l2=L2, master_weights=master)
+        return GraphedTrainStep(model, x, y, fused_cross_entropy, opt, warmup=2)
+    if kind in ("flat_adam", "flat_adam_master"):
+        opt = FlatAdam(*flat, lr=1e-3, weight_decay=1e-4, l2=L2, master_weights=master)
+        return GraphedTrainStep(model, x, y, fused_cross_entropy, opt, warmup=2)
     fused = kind == "torch_adam_fused"
     opt = torch.optim.Adam(model.parameters(), lr=1e-3, weight_decay=1e-4, capturable=True, fused=fused or None)
     return GraphedTrainStep(model, x, y, fused_cross_entropy, opt, warmup=2, **reg)
@@ -60,7 +64,7 @@ def timed(fn, iters):
 
 
 steps, skipped = {}, {}
-for kind in ("flat_sgd", "torch_adam", "torch_adam_fused", "flat_adam"):
+for kind in ("flat_sgd", "flat_sgd_master", "torch_adam", "torch_adam_fused", "flat_adam", "flat_adam_master"):
     try:
         steps[kind] = make(kind)
     except Exception as e:   # this torch build may refuse fused=True, capturable=True on ROCm: recorded, not hidden
@@ -91,11 +95,11 @@ for _ in range(args.rounds):
 # the optimizer launch alone as a stream: cfg3a's parameter count (1.9 M), 20 steps per captured graph
 N_STREAM, STEPS_PER_GRAPH = 1_900_000, 20
 stream_graphs = {}
-for dtype in (torch.bfloat16, torch.float32):
+for dtype, master in ((torch.bfloat16, False), (torch.bfloat16, True), (torch.float32, False)):
     for name, cls, kw in (("flat_sgd", FlatSGD, dict(momentum=0.9)), ("flat_adam", FlatAdam, dict(weight_decay=1e-4))):
         p = torch.nn.Parameter(torch.randn(N_STREAM, device=dev).to(dtype) * 0.1)
         p.grad = (torch.randn(N_STREAM, device=dev) * 0.01).to(dtype)
-        opt = cls([p], lr=1e-4, l2=1e-3, **kw)
+        opt = cls([p], lr=1e-4, l2=1e-3, master_weights=master, **kw)
         opt.step()
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
@@ -103,7 +107,7 @@ for dtype in (torch.bfloat16, torch.float32):
             for _ in range(STEPS_PER_GRAPH):
                 opt.step()
         g.replay()
-        stream_graphs[f"{name}_{str(dtype).split('.')[-1]}"] = (g, opt)
+        stream_graphs[f"{name}_{str(dtype).split('.')[-1]}{'_master' if master else ''}"] = (g, opt)
 stream_times = {k: [] for k in stream_graphs}
 for _ in range(args.rounds):
     for k, (g, _) in stream_graphs.items():
