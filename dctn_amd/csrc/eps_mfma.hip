@@ -156,6 +156,7 @@ struct MfmaP {
   int Cout;                     // fused-head backward: number of classes (rows of the head weight)
   unsigned hw_rowb, hw_bytes;   //   bytes per row (P * O * 2) and in total
   int ncb;                      //   chunk blocks (8 sample chunks each) of the grouped wave mapping
+  int skew;                     //   grouped mapping: the first half of a block's waves takes spc + skew samples each, the second spc - skew
   int opts;                     // DCTN_OPT_* flags of the call
 #ifdef DCTN_STAMPS
   unsigned long long* stamps;   // diagnostic build only (tools/stamp_cfg2.hip): per-workgroup phase time stamps
@@ -196,6 +197,17 @@ void dctn_reduce_stamps_set(unsigned long long* p) { (void)hipMemcpyToSymbol(HIP
       (P).stamps[(long long)(DCTN_STAMP_ROLE_ROW + blockIdx.x) * 8 + (SLOT)] = t_;               \
     __builtin_amdgcn_sched_barrier(0);                                                           \
   } while (0)
+// every dCore wave's lane 0, slot = wave index, in the rows behind DCTN_STAMP_WAVE_ROW
+#define DCTN_STAMP_WAVE_ROW 1536
+#define DCTN_STAMP_W(P, WV)                                                                      \
+  do {                                                                                           \
+    __builtin_amdgcn_sched_barrier(0);                                                           \
+    unsigned long long t_;                                                                       \
+    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");               \
+    if ((P).stamps && (threadIdx.x & 63) == 0 && (WV) < 8)                                        \
+      (P).stamps[(long long)(DCTN_STAMP_WAVE_ROW + blockIdx.x) * 8 + (WV)] = t_;                 \
+    __builtin_amdgcn_sched_barrier(0);                                                           \
+  } while (0)
 #define DCTN_STAMP_G(SLOT)                                                                       \
   do {                                                                                           \
     __builtin_amdgcn_sched_barrier(0);                                                           \
@@ -209,6 +221,7 @@ void dctn_reduce_stamps_set(unsigned long long* p) { (void)hipMemcpyToSymbol(HIP
 #define DCTN_STAMP_T(P, SLOT, TID) do { } while (0)
 #define DCTN_STAMP_G(SLOT) do { } while (0)
 #define DCTN_STAMP_R(P, SLOT) do { } while (0)
+#define DCTN_STAMP_W(P, WV) do { } while (0)
 #endif
 
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
@@ -429,6 +442,17 @@ __device__ __forceinline__ WaveJob wave_job(const MfmaP& p, int waves_per_block,
   WaveJob j;
   j.b0 = chunk < p.nchunks ? chunk * p.spc : 0;
   j.b1 = chunk < p.nchunks ? (j.b0 + p.spc < p.B ? j.b0 + p.spc : p.B) : 0;
+  if (grouped && p.skew > 0) {
+    // uneven split (plan_grouped): the block's waves_per_block * spc consecutive samples go to its first half of waves
+    // - the older wave of every SIMD - in runs of spc + skew and to the second half in runs of spc - skew
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), half = waves_per_block / 2;
+    const int n_old = p.spc + p.skew, n_young = p.spc - p.skew;
+    const int s0 = (vb / p.npg) * waves_per_block * p.spc + (w < half ? w * n_old : half * n_old + (w - half) * n_young);
+    const int s1 = s0 + (w < half ? n_old : n_young);
+    const bool live = vb / p.npg < p.ncb && s0 < p.B;
+    j.b0 = live ? s0 : 0;
+    j.b1 = live ? (s1 < p.B ? s1 : p.B) : 0;
+  }
   j.pos = pg * 64 + (int)(threadIdx.x & 63);
   j.valid = j.pos < p.P;
   const unsigned pu = j.valid ? (unsigned)j.pos : 0u;
@@ -878,6 +902,12 @@ __global__ __launch_bounds__(64 * HEADT_WAVES) void eps_fwd_head_q2reg_t_k(const
   const int b0 = (int)blockIdx.x * p.spc, b1 = b0 + p.spc < p.B ? b0 + p.spc : p.B;
   const int F = p.P * OP, LP = headt_pitch(F);
   const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(x, p.x_bytes), rs_o = make_rsrc(out, p.o_bytes);
+  __shared__ float bias_s[16];
+  DCTN_STAMP(p, 0);
+  // The bias of the final sums is staged in LDS by wave 0 and published by the barrier below, so no load follows a
+  // group's last barrier.  Its load goes out BEHIND the core's first loads and in front of their LDS stores: a wave's
+  // loads return in order, so it neither holds the core back nor waits for a round trip of its own.
+  float bias_v = 0.f;
   // core -> LDS in fragment order (as eps_fwd_q2reg_k): 4 elements per thread and batch, the loads of a batch in flight together
   for (int e0 = 0; e0 < TOT; e0 += 4 * 64 * HEADT_WAVES) {
     S tmp[4];
@@ -886,6 +916,7 @@ __global__ __launch_bounds__(64 * HEADT_WAVES) void eps_fwd_head_q2reg_t_k(const
       const int ec = e0 + tid + i * 64 * HEADT_WAVES, e = ec < TOT ? ec : TOT - 1, o = e % OP, ab = e / OP;
       tmp[i] = core[(long long)ab * p.O + (o < p.O ? o : 0)];
     }
+    if (e0 == 0 && wv == 0) bias_v = (float)bias[(lane & 15) < p.Cout ? (lane & 15) : 0];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int e = e0 + tid + i * 64 * HEADT_WAVES, o = e % OP, ab = e / OP, bb = ab % BN, aa = ab / BN;
@@ -895,6 +926,7 @@ __global__ __launch_bounds__(64 * HEADT_WAVES) void eps_fwd_head_q2reg_t_k(const
       if (e < TOT) cs[dst] = o < p.O ? tmp[i] : (bf16_t)0.f;
     }
   }
+  if (wv == 0) bias_s[lane & 15] = bias_v;
   // the tile's features past F meet zero weights: they must be finite
   for (int e = tid; e < HEADT_GS * (LP - F); e += 64 * HEADT_WAVES) ftile[(e / (LP - F)) * LP + F + e % (LP - F)] = 0;
   __syncthreads();
@@ -904,6 +936,7 @@ __global__ __launch_bounds__(64 * HEADT_WAVES) void eps_fwd_head_q2reg_t_k(const
 #pragma unroll
     for (int s = 0; s < KS; ++s)
       cf[t][s] = *reinterpret_cast<const bf16x8*>(&cs[((t * KS + s) * 64 + lane) * 8]);
+  DCTN_STAMP(p, 1);
 
   auto lane_at = [&](int pg, bool live, unsigned& voff_x, unsigned& voff_o, int& pos) {
     pos = pg * 64 + lane;
@@ -929,7 +962,13 @@ __global__ __launch_bounds__(64 * HEADT_WAVES) void eps_fwd_head_q2reg_t_k(const
     unsigned voff_x, voff_o;
     lane_at(pg, cur < nsteps, voff_x, voff_o, pos);
     RawWindow<S, N, true, ROWS> raw;
+    // (built and dropped: this first window - a static ticket - sent in front of the core staging, and at the end of
+    //  the group before for later groups: 122 VGPRs, no scratch; in the stamps the core fragments came 0.17 us later,
+    //  the first step was done 0.18 us earlier and the step was 0.16 us SLOWER - NOTEBOOK, "critical path of cfg2")
     issue_window<S, N, true, ROWS>(rs_x, voff_x, (unsigned)(g0 + (cur < nsteps ? s : 0)) * p.s1b, p, raw);
+#ifdef DCTN_STAMPS
+    bool first_step = true;
+#endif
     while (cur < nsteps) {
       float xv[N][2];
       unpack_window<S, N, true, ROWS>(raw, xv);
@@ -1018,7 +1057,13 @@ __global__ __launch_bounds__(64 * HEADT_WAVES) void eps_fwd_head_q2reg_t_k(const
           if (tvalid) *reinterpret_cast<u32x4*>(trow + 8 * i) = q;
         }
       }
+#ifdef DCTN_STAMPS
+      if (first_step) DCTN_STAMP(p, 2);
+      first_step = false;
+#endif
     }
+    DCTN_STAMP(p, 3);
+    DCTN_STAMP_T(p, 4, 64 * (HEADT_WAVES - 1));
     // ---- the group's head product: weight fragments first (they depend on nothing of the group)
     const int nks = (F + 31) / 32;
     const int c = lane & 15, kg = lane >> 4;
@@ -1031,6 +1076,22 @@ __global__ __launch_bounds__(64 * HEADT_WAVES) void eps_fwd_head_q2reg_t_k(const
       wf[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_hw, vo2, 0, 0);
     }
     __syncthreads();   // every wave's feature rows of the group are in the tile
+    DCTN_STAMP(p, 5);
+    // (in front of the head product: the stores are on their way while the logits are formed; behind the partial tiles
+    //  they were the last thing before the group's second barrier: +0.1 us per step)
+    if constexpr (BLK4) {   // the group's [F][4] block: thread t stores features 2 t, 2 t + 1 of the 4 samples, 16 bytes
+      static_assert(HEADT_GS == 4, "a group is one block of the blocked4 layout");
+      const unsigned sob = (unsigned)(g0 >> 2) * (unsigned)F * 8u;   // g0 is a multiple of 4 (fwd_head_launch_t)
+      for (int f = 2 * tid; f < F; f += 2 * 64 * HEADT_WAVES) {
+        unsigned r[HEADT_GS];   // r[i] = features f, f + 1 of sample i (a sample past the batch: zeros)
+#pragma unroll
+        for (int i = 0; i < HEADT_GS; ++i) r[i] = i < ng ? *reinterpret_cast<const unsigned*>(ftile + i * LP + f) : 0u;
+        const u32x4 q = u32x4{__builtin_amdgcn_perm(r[1], r[0], 0x05040100u), __builtin_amdgcn_perm(r[3], r[2], 0x05040100u),
+                              __builtin_amdgcn_perm(r[1], r[0], 0x07060302u), __builtin_amdgcn_perm(r[3], r[2], 0x07060302u)};
+        __builtin_amdgcn_raw_buffer_store_b128(q, rs_o, (unsigned)f * 8u, sob, 0);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
     f32x4v hd = {0.f, 0.f, 0.f, 0.f};
     const short* brd = ftile + (c < HEADT_GS ? c : HEADT_GS - 1) * LP + 8 * kg;
 #pragma unroll
@@ -1046,23 +1107,11 @@ __global__ __launch_bounds__(64 * HEADT_WAVES) void eps_fwd_head_q2reg_t_k(const
 #pragma unroll
       for (int v = 0; v < 4; ++v) hsum[wv][c][4 * kg + v] = hd[v];
     }
-    if constexpr (BLK4) {   // the group's [F][4] block: thread t stores features 2 t, 2 t + 1 of the 4 samples, 16 bytes
-      static_assert(HEADT_GS == 4, "a group is one block of the blocked4 layout");
-      const unsigned sob = (unsigned)(g0 >> 2) * (unsigned)F * 8u;   // g0 is a multiple of 4 (fwd_head_launch_t)
-      for (int f = 2 * tid; f < F; f += 2 * 64 * HEADT_WAVES) {
-        unsigned r[HEADT_GS];   // r[i] = features f, f + 1 of sample i (a sample past the batch: zeros)
-#pragma unroll
-        for (int i = 0; i < HEADT_GS; ++i) r[i] = i < ng ? *reinterpret_cast<const unsigned*>(ftile + i * LP + f) : 0u;
-        const u32x4 q = u32x4{__builtin_amdgcn_perm(r[1], r[0], 0x05040100u), __builtin_amdgcn_perm(r[3], r[2], 0x05040100u),
-                              __builtin_amdgcn_perm(r[1], r[0], 0x07060302u), __builtin_amdgcn_perm(r[3], r[2], 0x07060302u)};
-        __builtin_amdgcn_raw_buffer_store_b128(q, rs_o, (unsigned)f * 8u, sob, 0);
-      }
-    }
     __syncthreads();
     if (tid < HEADT_GS * 16) {
       const int sl = tid >> 4, cc = tid & 15;
       if (sl < ng && cc < p.Cout) {
-        float t = (float)bias[cc];
+        float t = bias_s[cc];
 #pragma unroll
         for (int w = 0; w < HEADT_WAVES; ++w) t += hsum[w][sl][cc];
         logits[(long long)(g0 + sl) * p.Cout + cc] = (bf16_t)t;
@@ -1071,6 +1120,7 @@ __global__ __launch_bounds__(64 * HEADT_WAVES) void eps_fwd_head_q2reg_t_k(const
     // (the next group's steps write the tile only behind the barrier at its start; its partial tiles behind its own
     //  first barrier after that: the sums just read are safe)
   }
+  DCTN_STAMP(p, 6);
 }
 
 // ------------------------------------------------------------------------------ backward: dCore
@@ -1265,13 +1315,17 @@ __global__ __launch_bounds__(64 * (BWD_WAVES + DWROLE)) void eps_bwd_dcore_q2reg
       wv4 = __builtin_amdgcn_raw_buffer_load_b128(rs_hw, voff, (unsigned)c * p.hw_rowb, 0);
       if (pos + 1 >= p.P) { wv4.z = 0u; wv4.w = 0u; }   // the second position lies in the next class's row (or past the end)
     }
+    // the first group's dLogits go out behind the weight slice and in front of the barrier that publishes it: one
+    // 16-byte load of 16 lanes per wave whose round trip the slice's hides (an empty wave: out of range, zeros)
+    issue_group(job.b0);
     *reinterpret_cast<u32x4*>(dsm + dcore_dyn_lds_bytes(MT) + (size_t)tid * 16) = wv4;
     __syncthreads();
     const unsigned* wlds = reinterpret_cast<const unsigned*>(dsm + dcore_dyn_lds_bytes(MT));   // [class][position][2 dwords]
     DCTN_STAMP(p, 1);
     for (int g0 = job.b0; g0 < job.b1; g0 += 8) {
-      issue_group(g0);   // (issued in front of the barrier that publishes the weight slice the first group's loads made
-                         // the kernel slower, 250 VGPRs: 32.3 against 32.1 us per step)
+      // (round 3, the kernel at 254 registers with dW inside: the first group's loads in front of the barrier made it
+      //  slower, 250 VGPRs, 32.3 against 32.1 us per step)
+      if (g0 != job.b0) issue_group(g0);
       f32x8 dyg[OP];   // registers 0..7 = the 8 samples of the group at the lane's position
       // dY of the group's samples and the group's share of dW (formed in front of the group's first sample: inside its
       // step, behind the window's own products, the operands' registers met P0 / P1's and the kernel spilled: 15.3 us)
@@ -1493,6 +1547,7 @@ __global__ __launch_bounds__(64 * (BWD_WAVES + DWROLE)) void eps_bwd_dcore_q2reg
   }   // !HEADMM
 
   DCTN_STAMP(p, 3);
+  DCTN_STAMP_W(p, wv);
   // workgroup reduction of the per-wave partial dCoreT tiles, then one coalesced store per block
   float* dst = partial + (long long)blockIdx.x * (MT * 32) * (AT * 32);
   if constexpr (LDST) {
@@ -2065,7 +2120,7 @@ void fill_mp(MfmaP& m, const EpsP& p, const void* x, int dtype) {
   m.o_bytes = (unsigned)(p.Wn * p.O * esz);
   m.vec_ok = p.s[4] == 1 && p.s[0] % 2 == 0 && p.s[1] % 2 == 0 && p.s[2] % 2 == 0 &&
              p.s[3] % 2 == 0 && ((uintptr_t)x % 4) == 0;
-  m.Cout = 0; m.hw_rowb = 0; m.hw_bytes = 0; m.ncb = 0;
+  m.Cout = 0; m.hw_rowb = 0; m.hw_bytes = 0; m.ncb = 0; m.skew = 0;
   m.opts = p.opts;
 #ifdef DCTN_STAMPS
   m.stamps = g_stamps;
@@ -2163,6 +2218,15 @@ int bwd_launch_t(const void* x, const void* dY, void* dCore, void* ws, const Mfm
   return DCTN_OK;
 }
 
+// Uneven split of a chunk block's samples over its waves (wave_job): n_old = spc + k for waves 0-3, n_young = spc - k
+// for waves 4-7.  The two dCore waves of a SIMD do not share it evenly: the older one (waves 0-3) wins the arbitration
+// and ran its spc samples in 8.4 us where the younger one needed 10.7 (per-wave stamps, B = 1024), so the older takes
+// more.  k = spc / 3 is the measured choice (spc = 6: k = 2 of 0 .. 5; spc = 23: k = 7 of 0, 4, 7, 11);
+// the macro is the build-time switch of that comparison.
+#ifndef DCTN_DCORE_SKEW
+#define DCTN_DCORE_SKEW(spc) ((spc) / 3)
+#endif
+
 // grouped wave mapping of the fused head backward: ncb chunk blocks x npg position groups workgroups
 // (<= the CU count: one dCore partial tile per workgroup), 8 sample chunks per chunk block
 int plan_grouped(MfmaP& m) {
@@ -2223,6 +2287,9 @@ int bwd_head_launch_t(const void* x, const void* dL, const void* hw, const void*
   const bool headmm = A == 32 && MT <= 2 && OP == 4 && m.vec_ok;
   if (headmm && (long long)m.B * m.P * OP * 2 >= (1LL << 31)) return DCTN_ERR_UNSUPPORTED;
   const bool gemm = headmm;
+  // the HEADMM kernels index nothing by sample chunk: their waves may take uneven runs of a block's samples
+  m.skew = headmm ? DCTN_DCORE_SKEW(m.spc) : 0;
+  if (m.skew >= m.spc) m.skew = m.spc - 1;
 
   const dim3 g(grid), b(64 * BWD_WAVES);
   constexpr int NN = N0 + N1;

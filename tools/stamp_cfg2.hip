@@ -61,6 +61,18 @@ static void report(const char* name, const std::vector<unsigned long long>& st, 
   }
 }
 
+// the dCore waves' own exits from the loop (DCTN_STAMP_W: row DCTN_STAMP_WAVE_ROW + workgroup, slot = wave index)
+static void report_waves(const std::vector<unsigned long long>& st, unsigned long long t0) {
+  printf("  out of the loop, per dCore wave (min / median / max over workgroups):\n");
+  for (int w = 0; w < 8; ++w) {
+    std::vector<double> v;
+    for (int b = DCTN_STAMP_WAVE_ROW; b < (int)(st.size() / 8); ++b) if (st[b * 8 + w]) v.push_back((double)(st[b * 8 + w] - t0) * 0.01);
+    if (v.empty()) continue;
+    std::sort(v.begin(), v.end());
+    printf("    wave %d %26s %7.2f %7.2f %7.2f   (%zu stamps)\n", w, "", v.front(), v[v.size() / 2], v.back(), v.size());
+  }
+}
+
 int main(int argc, char** argv) {
   const int B = argc > 1 ? atoi(argv[1]) : 1024, H = 28, W = 28, Q = 2, K = 3, O = 4, C = 1, Cout = 10;
   const int Ho = H - K + 1, P = Ho * Ho;
@@ -89,7 +101,8 @@ int main(int argc, char** argv) {
   CK(hipStreamCreate(&st));
   std::vector<unsigned long long> hs(NB * 8);
   const char* fl[] = {"entry", "core staged, fragments in regs", "first sample done", "loop done", "", "", "", ""};
-  const char* hl[] = {"entry", "core staged, fragments in regs", "first sample done", "last group's samples done (wave 0)", "end", "", "", ""};
+  const char* hl[] = {"entry", "core fragments in registers", "first step done (wave 0)", "last step done, wave 0", "last step done, wave 15",
+                      "group barrier passed", "end", ""};
   const char* bl[] = {"entry", "head-weight slice arrived", "first sample's loads arrived", "loop done", "dCore tile reduced + stored",
                       "end", "loop done, last wave", "every wave out of the loop (barrier)"};
   const char* wl[] = {"dW role (blocked4): first loads issued", "dW role: products done, tiles in LDS", "dW role: join done, dW stored",
@@ -113,14 +126,24 @@ int main(int argc, char** argv) {
     if (eps_head_fwd_mfma(x, core, wgt, db, feat, logit, p, Cout, DCTN_BF16, 0, st) != DCTN_OK) { printf("fused fwd failed\n"); return 1; }
     CK(hipStreamSynchronize(st));
     CK(hipMemcpy(hs.data(), stamps, NB * 8 * 8, hipMemcpyDeviceToHost));
-    if (rep == 2) report("eps_fwd_head_q2reg_k (layer + head)", hs, NB, 5, hl);
+    if (rep == 2) report("eps_fwd_head_q2reg_t_k (layer + head)", hs, NB, 7, hl);
+    CK(hipMemset(stamps, 0, NB * 8 * 8));
+    p.opts = DCTN_OPT_HEAD_FEATURES_BLOCKED4;
+    if (eps_head_fwd_mfma(x, core, wgt, db, featb, logit, p, Cout, DCTN_BF16, 0, st) != DCTN_OK) { printf("blocked4 fwd failed\n"); return 1; }
+    p.opts = 0;
+    CK(hipStreamSynchronize(st));
+    CK(hipMemcpy(hs.data(), stamps, NB * 8 * 8, hipMemcpyDeviceToHost));
+    if (rep == 2) report("eps_fwd_head_q2reg_t_k (layer + head, blocked4 features)", hs, NB, 7, hl);
     CK(hipMemset(stamps, 0, NB * 8 * 8));
     p.opts = DCTN_OPT_MAIN_KERNEL_ONLY;
     if (eps_head_bwd_mfma(x, feat, dl, wgt, dcore, dw, db, ws, wsb, p, Cout, DCTN_BF16, 0, st) != DCTN_PARTIAL) return 1;
     p.opts = 0;
     CK(hipStreamSynchronize(st));
     CK(hipMemcpy(hs.data(), stamps, NB * 8 * 8, hipMemcpyDeviceToHost));
-    if (rep == 2) report("eps_bwd_dcore_q2reg_k (fused head)", hs, NB, 8, bl);
+    if (rep == 2) {
+      report("eps_bwd_dcore_q2reg_k (fused head)", hs, DCTN_STAMP_ROLE_ROW, 8, bl);
+      report_waves(hs, first_entry(hs, DCTN_STAMP_ROLE_ROW));
+    }
     // the same kernel with blocked4 features: four more waves per workgroup form dW (their stamps: rows from DCTN_STAMP_ROLE_ROW)
     CK(hipMemset(stamps, 0, NB * 8 * 8));
     p.opts = DCTN_OPT_HEAD_FEATURES_BLOCKED4;
@@ -133,9 +156,11 @@ int main(int argc, char** argv) {
     CK(hipStreamSynchronize(st));
     CK(hipMemcpy(hs.data(), stamps, NB * 8 * 8, hipMemcpyDeviceToHost));
     if (rep == 2) {
-      std::vector<unsigned long long> a(hs.begin(), hs.begin() + DCTN_STAMP_ROLE_ROW * 8), b(hs.begin() + DCTN_STAMP_ROLE_ROW * 8, hs.end());
+      std::vector<unsigned long long> a(hs.begin(), hs.begin() + DCTN_STAMP_ROLE_ROW * 8),
+          b(hs.begin() + DCTN_STAMP_ROLE_ROW * 8, hs.begin() + DCTN_STAMP_WAVE_ROW * 8);
       report("eps_bwd_dcore_q2reg_k (fused head, blocked4: + dW role waves), dCore waves", a, DCTN_STAMP_ROLE_ROW, 8, bl);
-      report("eps_bwd_dcore_q2reg_k (fused head, blocked4), dW role waves", b, NB - DCTN_STAMP_ROLE_ROW, 3, wl, first_entry(a, DCTN_STAMP_ROLE_ROW));
+      report_waves(hs, first_entry(a, DCTN_STAMP_ROLE_ROW));
+      report("eps_bwd_dcore_q2reg_k (fused head, blocked4), dW role waves", b, DCTN_STAMP_WAVE_ROW - DCTN_STAMP_ROLE_ROW, 3, wl, first_entry(a, DCTN_STAMP_ROLE_ROW));
     }
     {   // the finishing kernel behind it: dCore tile sums and dBias only
       dctn_stamps_set(nullptr);
