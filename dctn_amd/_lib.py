@@ -32,6 +32,7 @@ _DTYPE_CODE = {torch.float32: F32, torch.float64: F64, torch.bfloat16: BF16}
 
 c_int, c_i64, c_void, c_size = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t
 _I64x5 = ctypes.POINTER(c_i64)
+_I64P = ctypes.POINTER(c_i64)
 _IntP = ctypes.POINTER(c_int)
 _PtrP = ctypes.POINTER(c_void)
 
@@ -72,6 +73,10 @@ SIGNATURES = {
     "dctn_adam_l2_step_master": (c_int, [c_void] * 7 + [c_i64, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_float,
                                          ctypes.c_float, ctypes.c_float, c_void]),
     "dctn_ce_score_accumulate": (c_int, [c_void, c_void, c_void, c_i64, c_int, c_int, c_void]),
+    "dctn_core_dropout_state_bytes": (c_size, []),
+    "dctn_core_dropout_fwd": (c_int, [_PtrP, _PtrP, _I64P, c_int, c_void, c_void, c_void, c_int, c_void]),
+    "dctn_core_dropout_bwd": (c_int, [_PtrP, _PtrP, _I64P, c_int, c_void, c_void, c_int, c_void]),
+    "dctn_core_dropout_mask": (c_int, [_PtrP, _I64P, c_int, c_void, c_void, c_int, c_void]),
     "dctn_window_stats": (c_int, [c_void, _I64x5, c_void] + [c_int] * 6 + [c_int, c_void]),
     "dctn_phi_window_stats": (c_int, [c_void, c_void, c_int, c_int, c_int, c_int, c_void]),
     "dctn_phi_expand": (c_int, [c_void, c_void, c_i64, ctypes.c_float, c_int, c_void]),
@@ -223,6 +228,10 @@ def strides5(t: torch.Tensor):
 
 def int_array(values: Sequence[int]):
     return (c_int * len(values))(*[int(v) for v in values])
+
+
+def i64_array(values: Sequence[int]):
+    return (c_i64 * len(values))(*[int(v) for v in values])
 
 
 def ptr_array(tensors: Sequence[Optional[torch.Tensor]]):

@@ -18,7 +18,7 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from . import _lib as L
-from . import eps, epses_composition
+from . import dropout, eps, epses_composition
 from .utils import OneTensorInitialization, ZeroCenteredNormalInitialization, ZeroCenteredUniformInitialization
 
 
@@ -285,6 +285,10 @@ class EPSesPlusLinear(nn.Module):
         # synchronisation, impossible under graph capture).  `p` is part of the state_dict, so the copy is
         # refreshed whenever a checkpoint is loaded.
         self._p_float = float(p)
+        # `use_fused_dropout` puts the 16-byte dropout state block here (a non-persistent buffer: the state_dict keys stay
+        # the reference's); None = component dropout runs on the torch ops below
+        self.register_buffer("_dropout_state", None, persistent=False)
+        self.dropout_record = None   # the draw record of the last fused-dropout forward (int32[4] on the device)
         self.register_load_state_dict_post_hook(_refresh_p_after_load)   # a module-level function: the model stays picklable
 
     def _refresh_p(self) -> None:
@@ -304,7 +308,12 @@ class EPSesPlusLinear(nn.Module):
     def _forward_on_device(self, input: Tensor, cores: Tuple[Tensor, ...], weight: Tensor, bias: Tensor,
                            p: Tensor) -> Tensor:
         if self._p_float < 1.0 and self.training:   # component dropout, dctn/eps_plus_linear.py:139-143
-            cores = tuple(self.dropout_mask(core, p) * core / p for core in cores)
+            state = self._dropout_state
+            if state is not None and state.device == cores[0].device and state.is_cuda:
+                # one launch for all cores; the mask comes from (seed, draw, core number, element) - dropout.py
+                cores, self.dropout_record = dropout.core_dropout(cores, p, state)
+            else:   # the default, and a model staged from the CPU
+                cores = tuple(self.dropout_mask(core, p) * core / p for core in cores)
         x = input
         for core in cores[:-1]:   # as epses_composition.contract_with_input
             x = eps.eps(core, x).unsqueeze(0)
@@ -322,6 +331,39 @@ class EPSesPlusLinear(nn.Module):
         """Bernoulli(p) keep-mask of one core (the reference draws ``self.p.expand_as(core).bernoulli()``); a
         method of its own so that a test can pin the mask."""
         return p.expand_as(core).bernoulli()
+
+    def use_fused_dropout(self, seed: int) -> None:
+        """Component dropout through the fused kernels (`dctn_core_dropout_fwd` / `_bwd`: one launch each way for all
+        cores) instead of torch's element-wise ops, from now on.  The keep mask of a training forward is then a pure
+        function of ``seed``, the number of training forwards so far, the core's number and the element's index
+        (dropout.py): every rank that holds this model's buffers draws the same mask (`training.train` broadcasts them),
+        and `dropout_state_dict()` is all a resumed run needs to repeat its masks.  Same gate as before: nothing is
+        launched in eval mode or with ``p == 1``.  The cores must live on the GPU (the kernels are the only
+        implementation); ``dropout_mask`` is not consulted on this path."""
+        if not all(core.is_cuda for core in self.epses) or not self.p.is_cuda:
+            raise RuntimeError("use_fused_dropout: the fused component dropout runs on an MI355X device only and this "
+                               "model's cores live on the CPU; move the model to the GPU first (a CPU model keeps the "
+                               "torch-op dropout of its staged forward)")
+        if len(self.epses) > dropout.MAX_CORES:
+            raise NotImplementedError(f"use_fused_dropout: at most {dropout.MAX_CORES} cores in one launch")
+        self._dropout_state = dropout.new_state(seed, self.p.device)
+
+    def dropout_state_dict(self) -> dict:
+        """``{"seed", "draws_done"}`` of the fused dropout (reads the device: it synchronises)."""
+        if self._dropout_state is None:
+            raise RuntimeError("dropout_state_dict: call use_fused_dropout(seed) first")
+        return dropout.read_state(self._dropout_state)
+
+    def load_dropout_state_dict(self, state: dict) -> None:
+        """Continues the mask sequence of a saved run: the next training forward draws number ``state["draws_done"]``
+        of ``state["seed"]``.  Not allowed during a graph capture (a captured forward reads the block on replay)."""
+        if self._dropout_state is None:
+            raise RuntimeError("load_dropout_state_dict: call use_fused_dropout(seed) first")
+        if self._dropout_state.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("load_dropout_state_dict cannot run during a graph capture")
+        new = dropout.new_state(int(state["seed"]), torch.device("cpu"), int(state["draws_done"]))
+        with torch.no_grad():
+            self._dropout_state.copy_(new)
 
     def epswise_l2_regularizer(self) -> Tensor:
         """||linear.weight||^2 + sum of squared Frobenius norms of the cores (bias excluded)."""

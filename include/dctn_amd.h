@@ -454,6 +454,56 @@ int dctn_ce_score_accumulate(const void* logits, const void* labels, void* acc, 
                              void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Component dropout of the EPS cores (version 502; reference: dctn/eps_plus_linear.py:139-143, `mask * core / p` with
+ * mask ~ Bernoulli(p) per component of every core): ONE launch each way for all cores of a model, and a mask that is
+ * stored nowhere - a pure function of (seed, draw, core number, element index).
+ *
+ * Mask definition (normative; dctn_amd/dropout.py `expected_keep` restates it in Python).  The generator is
+ * Philox4x32-10: multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57; the key (k0, k1) grows by (0x9E3779B9, 0xBB67AE85)
+ * after every round; one round maps the counter (c0, c1, c2, c3) to
+ *   (hi(M1*c2) ^ c1 ^ k0,  lo(M1*c2),  hi(M0*c0) ^ c3 ^ k1,  lo(M0*c0)).
+ * Element e of the s-th core of a call (s = its index in the pointer arrays), under draw d and the 64-bit seed:
+ *   counter = (e >> 2, 0, d, s),  key = (seed & 0xFFFFFFFF, seed >> 32),  word = output word (e & 3);
+ *   the element is KEPT iff word < T,  T = min(floor(p * 2^32), 2^32 - 1), formed in double from the value of p as
+ *   the tensor dtype stores it (the bfloat16 "0.9" is 0.8984375 - the probability the reference's bernoulli() sees too).
+ * fwd : out = keep ? core / p : 0        bwd : d_core = keep ? d_out / p : 0        mask : keep ? 1 : 0
+ * One division in float32 (double for DCTN_F64), rounded once to the tensor dtype.  For finite inputs fwd compares
+ * equal to the reference's `mask * core / p` evaluated in the tensor dtype (a dropped value is +0 here and a zero of
+ * either sign there; bfloat16 is rounded once here as there, since mask * core is exact).  A NON-FINITE dropped
+ * component gives 0 here where the reference's 0 * inf gives NaN.
+ *
+ * Arguments.  cores / out / d_out / d_core / mask: HOST arrays of n_cores device pointers, numel: HOST array of their
+ * element counts (contiguous tensors of `dtype`: DCTN_F32 / DCTN_F64 / DCTN_BF16, aligned to their element size; a core
+ * whose bases are 16-byte aligned (bf16: 8) moves in vector accesses).  1 <= n_cores <= 8 (more: DCTN_ERR_UNSUPPORTED);
+ * 1 <= numel[i] < 2^34 (DCTN_ERR_BAD_SHAPE: e >> 2 is one 32-bit counter word).  p: DEVICE pointer to one value of
+ * `dtype`, 0 < p <= 1.  d_core[i] may be the same pointer as d_out[i] (in place); no other overlap is allowed.  In
+ * dctn_core_dropout_bwd a core whose d_out[i] and d_core[i] are both NULL is skipped (a frozen core); it keeps its number.
+ *
+ * `state`: dctn_core_dropout_state_bytes() = 16 bytes on the device, 16-byte aligned, laid out as
+ *   uint32 seed_lo, uint32 seed_hi   the seed; read by every forward launch
+ *   uint32 draws_done                number of forward launches so far; a launch draws with d = draws_done as read at
+ *                                    its start and leaves d + 1 here
+ *   uint32 ticket                    0 between launches (workgroups count themselves out on it; the last one resets it)
+ * The caller creates the block once (seed, 0, 0) and may read or write it in stream order between launches.  `record`:
+ * 16 bytes on the device, 4-byte aligned; the forward OVERWRITES it with {seed_lo, seed_hi, d, 0}; the backward and the
+ * mask kernel read it and `p` and nothing else of the state - they never touch the block.  No entry point reads the
+ * device on the host: every call only enqueues, so a captured graph that holds the forward draws d, d + 1, ... on its
+ * replays, and its backward node follows through the record.
+ *
+ * Buffer contract: out / d_core / mask are fully OVERWRITTEN (every element, whatever they held - NaN included),
+ * nothing outside them, the record and (fwd) the block is written, and no result depends on what an output held
+ * before (in-place bwd reads d_out, which is then the output, by definition).  No workspace.
+ * dctn_last_kernel(): core_dropout_{fwd,bwd,mask}_{f32,f64,bf16}.
+ * ------------------------------------------------------------------------------------------ */
+size_t dctn_core_dropout_state_bytes(void);
+int dctn_core_dropout_fwd(const void* const* cores, void* const* out, const int64_t* numel, int n_cores, const void* p,
+                          void* state, void* record, int dtype, void* stream);
+int dctn_core_dropout_bwd(const void* const* d_out, void* const* d_core, const int64_t* numel, int n_cores, const void* p,
+                          const void* record, int dtype, void* stream);
+int dctn_core_dropout_mask(void* const* mask, const int64_t* numel, int n_cores, const void* p, const void* record,
+                           int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Tensor-network inner product of two stacks of EPS cores - replaces the contractions of
  * dctn/epses_composition.py:21-58 `inner_product` (Gram of the first pair of cores over their input legs:
  * dctn/eps.py:106-112 `contract_on_input_dims`; that matrix absorbed into every input leg of the next core:
