@@ -27,6 +27,8 @@ SAVED, PARTIAL = 1, 2   # positive success codes (include/dctn_amd.h)
  EPS_FAMILY_BIGCORE_BF16X3) = range(6)
 SBS_MATRIX_CORE_SWEEP = 1 << 8   # OR-ed into the dtype argument of the dctn_convsbs_* calls
 SBS_WIDE_SWEEP = 1 << 9   # likewise: the backward on the wide family (convsbs_wide.hip) for any string it covers
+BATCH_SRC_U8_TABLE, BATCH_SRC_ROWS = 0, 1   # DCTN_BATCH_SRC_*: `src_kind` of dctn_batch_draw / dctn_batch_gather
+BATCH_IDENTITY_ORDER = 1                    # `flags` of dctn_batch_draw
 
 _DTYPE_CODE = {torch.float32: F32, torch.float64: F64, torch.bfloat16: BF16}
 
@@ -77,6 +79,9 @@ SIGNATURES = {
     "dctn_core_dropout_fwd": (c_int, [_PtrP, _PtrP, _I64P, c_int, c_void, c_void, c_void, c_int, c_void]),
     "dctn_core_dropout_bwd": (c_int, [_PtrP, _PtrP, _I64P, c_int, c_void, c_void, c_int, c_void]),
     "dctn_core_dropout_mask": (c_int, [_PtrP, _I64P, c_int, c_void, c_void, c_int, c_void]),
+    "dctn_batch_state_bytes": (c_size, []),
+    "dctn_batch_draw": (c_int, [c_void] * 7 + [c_i64] * 5 + [c_int] * 4 + [c_void]),
+    "dctn_batch_gather": (c_int, [c_void] * 7 + [c_i64] * 3 + [c_int] * 3 + [c_void]),
     "dctn_window_stats": (c_int, [c_void, _I64x5, c_void] + [c_int] * 6 + [c_int, c_void]),
     "dctn_phi_window_stats": (c_int, [c_void, c_void, c_int, c_int, c_int, c_int, c_void]),
     "dctn_phi_expand": (c_int, [c_void, c_void, c_i64, ctypes.c_float, c_int, c_void]),

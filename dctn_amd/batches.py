@@ -1,0 +1,302 @@
+"""Batches drawn on the device (dctn_amd/csrc/batch_source.hip): the input side of the reference's ``train(dl, ...)``.
+
+The reference makes a batch with ``__getitem__`` per sample, ``collate_quantum``, pinning and a copy
+(dctn/dataset_loading.py:69-70, 282-286, 319-325).  Here the whole data set lives on the device - the raw uint8
+intensities, or an already-expanded feature tensor - and ONE launch picks the samples of a batch, applies the feature map
+and the scale (a 256-row table), casts to the model dtype and advances a device counter.  The epoch order is a pure
+function of (seed, epoch, position) - a 6-round Feistel network with cycle walking, keyed by the Philox4x32-10 of
+`dropout` - so nothing of the size of the data set is shuffled or stored, every rank that holds the same 16-byte block
+draws its shard of the same global batch, a resumed run repeats its batches from ``{"seed", "batches_done"}``, and a
+captured graph that holds the launch draws batch k, k + 1, ... on its replays.  include/dctn_amd.h holds the normative
+definition; `round_keys`, `order_at` and `expected_indices` restate it in plain Python.
+"""
+from __future__ import annotations
+
+from typing import Callable, Dict, Iterator, List, Optional, Sequence, Tuple
+
+import torch
+import torch.distributed as dist
+from torch import Tensor
+
+from . import _lib as L
+from .dropout import _MASK32, philox4x32_10
+from .window_stats import φ_cos_sin_squared_1
+
+TAG = 0x53485546   # counter word c3 of the round keys; dropout's c3 is a core number below 8
+MAX_WIDTH = 4      # table columns / channels of one launch (include/dctn_amd.h)
+
+
+def round_keys(seed: int, epoch: int) -> Tuple[int, ...]:
+    """The six 32-bit round keys of epoch ``epoch`` under the 64-bit ``seed``."""
+    key = (seed & _MASK32, (seed >> 32) & _MASK32)
+    return (philox4x32_10((0, 0, epoch, TAG), key) + philox4x32_10((1, 0, epoch, TAG), key))[:6]
+
+
+def mix32(h: int) -> int:
+    """murmur3's finaliser in 32-bit arithmetic."""
+    h ^= h >> 16
+    h = h * 0x85EBCA6B & _MASK32
+    h ^= h >> 13
+    h = h * 0xC2B2AE35 & _MASK32
+    return h ^ (h >> 16)
+
+
+def perm_once(v: int, b: int, K: Sequence[int]) -> int:
+    """One pass of the unbalanced Feistel network: a bijection on [0, 2**b)."""
+    wl, wr = b // 2, b - b // 2
+    left, right = v >> wr, v & ((1 << wr) - 1)
+    for j in range(6):
+        left, right = right, left ^ (mix32(right ^ K[j]) & ((1 << wl) - 1))
+        wl, wr = wr, wl
+    return (left << wr) | right
+
+
+def _walk(v: int, n: int, b: int, K: Sequence[int]) -> int:
+    while True:   # cycle walking: v < n lies on a cycle of the bijection, so the walk comes back below n
+        v = perm_once(v, b, K)
+        if v < n:
+            return v
+
+
+def order_at(seed: int, epoch: int, n: int, i: int) -> int:
+    """The sample at position ``i`` of epoch ``epoch`` over ``n`` samples (1 <= n < 2**31)."""
+    return _walk(i, n, max(2, (n - 1).bit_length()), round_keys(seed, epoch))
+
+
+def order(seed: int, epoch: int, n: int) -> List[int]:
+    """The whole epoch: a permutation of ``range(n)``."""
+    b, K = max(2, (n - 1).bit_length()), round_keys(seed, epoch)
+    return [_walk(i, n, b, K) for i in range(n)]
+
+
+def steps_per_epoch(n: int, batch_size: int, drop_last: bool = True) -> int:
+    """S: the batches of one pass.  ``batch_size`` is the GLOBAL batch."""
+    if batch_size < 1 or n // batch_size < 1:
+        raise ValueError(f"a global batch of {batch_size} needs 1 <= batch_size <= number of samples ({n})")
+    return n // batch_size if drop_last else -(-n // batch_size)
+
+
+def local_batch(batch_size: int, rank: int, world: int) -> int:
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError(f"rank {rank} of world {world}")
+    if batch_size % world:
+        raise ValueError(f"the global batch ({batch_size}) must be a multiple of the number of ranks ({world})")
+    return batch_size // world
+
+
+def expected_indices(seed: int, k: int, n: int, batch_size: int, rank: int = 0, world: int = 1,
+                     shuffle: bool = True) -> List[int]:
+    """The sample numbers of draw ``k`` (the device counter) for ``rank`` of ``world``: epoch ``k // S``, positions
+    ``(k % S) * batch_size + rank * Bl + j`` for ``j < Bl = batch_size // world``."""
+    S, Bl = steps_per_epoch(n, batch_size), local_batch(batch_size, rank, world)
+    first = (k % S) * batch_size + rank * Bl
+    if not shuffle:
+        return list(range(first, first + Bl))
+    b, K = max(2, (n - 1).bit_length()), round_keys(seed, k // S)
+    return [_walk(first + j, n, b, K) for j in range(Bl)]
+
+
+def _new_state(seed: int, device: torch.device, batches_done: int = 0) -> Tensor:
+    """The 16-byte device block {uint32 seed_lo, seed_hi, batches_done, ticket} as four int32 (same bits)."""
+    assert L.lib().dctn_batch_state_bytes() == 16
+    return torch.tensor(_state_words(seed, batches_done), dtype=torch.int32).to(device)
+
+
+def _state_words(seed: int, batches_done: int) -> List[int]:
+    if not 0 <= int(seed) < 1 << 64:
+        raise ValueError(f"the batch seed is a 64-bit unsigned integer, got {seed}")
+    if not 0 <= int(batches_done) < 1 << 32:
+        raise ValueError(f"batches_done is a 32-bit unsigned integer, got {batches_done}")
+    words = [int(seed) & _MASK32, int(seed) >> 32, int(batches_done), 0]
+    return [w - (1 << 32) if w >= 1 << 31 else w for w in words]
+
+
+def feature_table(phi: Sequence[Callable[[Tensor], Tensor]], scale: float, dtype: torch.dtype) -> Tensor:
+    """(256, len(phi)): what the reference's float32 ops (dataset_loading.py:60-63 and the runner's ``x *= scale``) give for
+    each of the 256 intensities, cast to ``dtype``.  Built on the CPU."""
+    u = torch.arange(256, dtype=torch.uint8).float() / 255.0
+    return (scale * torch.stack(tuple(f(u) for f in phi), dim=1)).to(dtype).contiguous()
+
+
+class DeviceBatches:
+    """``(x, y, indices)`` batches of a data set that lives on the device, in place of the reference's train ``DataLoader``.
+
+    ``images_u8``: (n, height, width) uint8 intensities (what ``torchvision_dataset.data`` holds); ``labels``: n integers.
+    ``batch_size`` is the GLOBAL batch; ``rank`` of ``world`` takes its ``batch_size // world`` samples of it (they default
+    to ``torch.distributed``'s when a process group is up, else 0 / 1; when they default, rank 0's 16-byte block is
+    broadcast, so every rank draws the same global batch whatever seed it was given).  ``x`` comes out as
+    (1, Bl, height, width, len(phi)) in ``dtype``: ``scale * phi(intensity / 255)`` evaluated with the reference's own
+    float32 ops once per intensity (`feature_table`), then cast.  `from_features` takes a tensor that is already expanded.
+    CPU inputs are moved to the device once, here; without a GPU the constructor raises.
+
+    ``draw_into(x, y, indices)`` enqueues one launch into caller-owned buffers and never reads the device: it can be
+    captured, and the replays draw the following batches (``GraphedTrainStep(batch_source=...)`` does so).  ``draw()``
+    returns fresh tensors.  Iterating yields ``len(self)`` batches, so ``training.train(dl=src, ...)``,
+    ``batches_forever`` and ``evaluation.score_fused`` work unchanged.  One difference from a ``DataLoader``: a pass that
+    is abandoned early does not reshuffle - the next pass continues from the device counter.
+
+    ``shuffle=False`` gives the identity order.  ``drop_last=False`` (with ``shuffle=False`` only: the form of the
+    reference's validation and test loaders) makes every pass a sequential walk over ALL samples through
+    `dctn_batch_gather`, the last batch short; such a pass is eager and does not touch the counter.
+    """
+
+    def __init__(self, images_u8: Tensor, labels: Tensor, batch_size: int, *, dtype: torch.dtype, seed: int,
+                 scale: float = 1.0, phi: Sequence[Callable[[Tensor], Tensor]] = φ_cos_sin_squared_1,
+                 shuffle: bool = True, drop_last: bool = True, rank: Optional[int] = None,
+                 world: Optional[int] = None, device=None):
+        if images_u8.dtype != torch.uint8 or images_u8.ndim != 3:
+            raise TypeError("DeviceBatches takes (samples, height, width) uint8 intensities; float-valued sources go "
+                            f"through DeviceBatches.from_features (got {images_u8.dtype}, {tuple(images_u8.shape)})")
+        if not 1 <= len(phi) <= MAX_WIDTH:
+            raise NotImplementedError(f"the table of one launch has 1 .. {MAX_WIDTH} columns, phi has {len(phi)}")
+        L.dtype_code(torch.empty(0, dtype=dtype))
+        n, H, W = images_u8.shape
+        self._plan(n, labels, batch_size, seed, shuffle, drop_last, rank, world)
+        dev = self._device(device, images_u8)
+        self.kind, self.dtype = L.BATCH_SRC_U8_TABLE, dtype
+        self.src = images_u8.to(dev).contiguous()
+        self.table = feature_table(phi, scale, dtype).to(dev)
+        self.row_len, self.width = H * W, len(phi)
+        self.x_shape = lambda count: (1, count, H, W, len(phi))
+        self._finish(labels, dev)
+
+    @classmethod
+    def from_features(cls, x_full: Tensor, labels: Tensor, batch_size: int, *, seed: int, shuffle: bool = True,
+                      drop_last: bool = True, rank: Optional[int] = None,
+                      world: Optional[int] = None) -> "DeviceBatches":
+        """A source over features that are already expanded: ``x_full`` (channels, samples, ...) in the model dtype,
+        channels <= 4 (colour, constant-channel or normalised variants, whose values no 256-row table holds).  ``x`` comes
+        out as (channels, Bl, ...): a row copy."""
+        self = cls.__new__(cls)
+        if x_full.ndim < 2:
+            raise TypeError(f"from_features takes (channels, samples, ...) features, got {tuple(x_full.shape)}")
+        if not 1 <= x_full.shape[0] <= MAX_WIDTH:
+            raise NotImplementedError(f"one launch moves 1 .. {MAX_WIDTH} channels, got {x_full.shape[0]}")
+        L.dtype_code(x_full)
+        C, n, rest = x_full.shape[0], x_full.shape[1], tuple(x_full.shape[2:])
+        self._plan(n, labels, batch_size, seed, shuffle, drop_last, rank, world)
+        dev = self._device(None, x_full)
+        self.kind, self.dtype = L.BATCH_SRC_ROWS, x_full.dtype
+        self.src = x_full.to(dev).contiguous()
+        self.table = None
+        self.row_len, self.width = max(1, x_full[0, 0].numel()), C
+        self.x_shape = lambda count: (C, count) + rest
+        self._finish(labels, dev)
+        return self
+
+    # ---------------------------------------------------------------------------------------------- construction
+    def _plan(self, n, labels, batch_size, seed, shuffle, drop_last, rank, world) -> None:
+        """Everything that needs no device, first: the arithmetic errors are ValueErrors with or without a GPU."""
+        if not 1 <= n < 1 << 31:
+            raise ValueError(f"1 <= number of samples < 2^31, got {n}")
+        if labels.shape != (n,):
+            raise ValueError(f"{n} samples need labels of shape ({n},), got {tuple(labels.shape)}")
+        self.defaulted = rank is None and world is None
+        if self.defaulted and dist.is_available() and dist.is_initialized():
+            rank, world = dist.get_rank(), dist.get_world_size()
+        self.rank, self.world = (0 if rank is None else int(rank)), (1 if world is None else int(world))
+        self.n, self.batch_size, self.seed = int(n), int(batch_size), int(seed)
+        self.shuffle, self.drop_last = bool(shuffle), bool(drop_last)
+        if shuffle and not drop_last:
+            raise ValueError("drop_last=False is the sequential form: it needs shuffle=False")
+        self.steps = steps_per_epoch(self.n, self.batch_size)             # S of the device counter: whole batches
+        self.local_batch = local_batch(self.batch_size, self.rank, self.world)
+        _state_words(self.seed, 0)
+
+    @staticmethod
+    def _device(device, tensor: Tensor) -> torch.device:
+        if not torch.cuda.is_available():
+            raise RuntimeError("dctn_amd: a DeviceBatches source lives on an MI355X device, but no GPU is visible. "
+                               "There is deliberately no CPU implementation of this path.")
+        if device is not None:
+            return torch.device(device)
+        return tensor.device if tensor.is_cuda else torch.device("cuda", torch.cuda.current_device())
+
+    def _finish(self, labels: Tensor, dev: torch.device) -> None:
+        self.device = dev
+        self.labels = labels.to(dev, torch.int64).contiguous()
+        self._state = _new_state(self.seed, dev)
+        if self.defaulted and self.world > 1:   # every rank draws from rank 0's block
+            dist.broadcast(self._state, src=0)
+            self.seed = self.state_dict()["seed"]
+        self._all = None   # arange(n) for the sequential passes, made on first use
+
+    # ---------------------------------------------------------------------------------------------- batches
+    def __len__(self) -> int:
+        return steps_per_epoch(self.n, self.batch_size, self.drop_last)
+
+    def empty_batch(self, count: Optional[int] = None) -> Tuple[Tensor, Tensor, Tensor]:
+        """Uninitialised ``(x, y, indices)`` of this rank's batch shape (static buffers for a capture)."""
+        count = self.local_batch if count is None else count
+        return (torch.empty(self.x_shape(count), dtype=self.dtype, device=self.device),
+                torch.empty(count, dtype=torch.int64, device=self.device),
+                torch.empty(count, dtype=torch.int64, device=self.device))
+
+    def _check_out(self, x: Tensor, y: Tensor, indices: Tensor, count: int) -> None:
+        L.require_device(x, y, indices, self.src)
+        if (tuple(x.shape) != self.x_shape(count) or x.dtype != self.dtype or y.shape != (count,)
+                or indices.shape != (count,) or y.dtype != torch.int64 or indices.dtype != torch.int64
+                or not (x.is_contiguous() and y.is_contiguous() and indices.is_contiguous())):
+            raise ValueError(f"a batch of {count} samples needs contiguous x {self.x_shape(count)} in {self.dtype} and "
+                             f"int64 y, indices of shape ({count},)")
+
+    def draw_into(self, x: Tensor, y: Tensor, indices: Tensor) -> None:
+        """The next batch (this rank's shard of it) into caller-owned buffers: one launch, capturable."""
+        self._check_out(x, y, indices, self.local_batch)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().dctn_batch_draw(
+                self.src.data_ptr(), None if self.table is None else self.table.data_ptr(), self.labels.data_ptr(),
+                x.data_ptr(), y.data_ptr(), indices.data_ptr(), self._state.data_ptr(), self.n, self.batch_size,
+                self.local_batch, self.rank * self.local_batch, self.row_len, self.width, self.kind,
+                0 if self.shuffle else L.BATCH_IDENTITY_ORDER, L.dtype_code(x), L.stream_ptr(self.device)), "batch draw")
+
+    def draw(self) -> Tuple[Tensor, Tensor, Tensor]:
+        out = self.empty_batch()
+        self.draw_into(*out)
+        return out
+
+    def gather(self, sample_idx: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+        """The batch made of the given samples (a device int64 vector, every entry in [0, n): not checked).  Reads no
+        state."""
+        L.require_device(sample_idx, self.src)
+        if sample_idx.dtype != torch.int64 or sample_idx.ndim != 1 or sample_idx.numel() < 1:
+            raise ValueError("gather takes a non-empty int64 vector of sample numbers")
+        idx = sample_idx.contiguous()
+        x, y, indices = self.empty_batch(idx.numel())
+        with torch.cuda.device(self.device):
+            L.check(L.lib().dctn_batch_gather(
+                self.src.data_ptr(), None if self.table is None else self.table.data_ptr(), self.labels.data_ptr(),
+                idx.data_ptr(), x.data_ptr(), y.data_ptr(), indices.data_ptr(), self.n, idx.numel(), self.row_len,
+                self.width, self.kind, L.dtype_code(x), L.stream_ptr(self.device)), "batch gather")
+        return x, y, indices
+
+    def __iter__(self) -> Iterator[Tuple[Tensor, Tensor, Tensor]]:
+        if self.drop_last:
+            for _ in range(len(self)):
+                yield self.draw()
+            return
+        if self._all is None:
+            self._all = torch.arange(self.n, dtype=torch.int64, device=self.device)
+        for step in range(len(self)):   # sequential: this rank's slice of every batch, the last one short
+            first, count = step * self.batch_size, min(self.batch_size, self.n - step * self.batch_size)
+            lo, hi = first + count * self.rank // self.world, first + count * (self.rank + 1) // self.world
+            if hi > lo:
+                yield self.gather(self._all[lo:hi])
+
+    def expected_indices(self, k: int) -> List[int]:
+        """Host restatement: the sample numbers draw ``k`` gives this rank."""
+        return expected_indices(self.seed, k, self.n, self.batch_size, self.rank, self.world, self.shuffle)
+
+    # ---------------------------------------------------------------------------------------------- resume
+    def state_dict(self) -> Dict[str, int]:
+        """``{"seed", "batches_done"}`` (reads the device: it synchronises).  Save it beside the optimizer's and the
+        dropout's; a source built from the same data and arguments that loads it repeats the batches from there."""
+        w = [int(v) & _MASK32 for v in self._state.cpu().tolist()]
+        return {"seed": w[0] | (w[1] << 32), "batches_done": w[2]}
+
+    def load_state_dict(self, state: Dict[str, int]) -> None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("DeviceBatches.load_state_dict writes the device block from the host: not during a capture")
+        words = _state_words(state["seed"], state["batches_done"])
+        self._state.copy_(torch.tensor(words, dtype=torch.int32))   # in place: a captured graph keeps its pointer
+        self.seed = int(state["seed"])

@@ -27,18 +27,6 @@ struct DropSegs {   // passed by value in the kernel argument
 
 enum { DROP_FWD = 0, DROP_BWD = 1, DROP_MASK = 2 };
 
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
-                                              unsigned k1, unsigned (&w)[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0, c1 = lo1, c2 = hi0 ^ c3 ^ k1, c3 = lo0;
-    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-  }
-  w[0] = c0, w[1] = c1, w[2] = c2, w[3] = c3;
-}
-
 // the arithmetic type of the one division: float32 (double for float64), rounded once to the tensor dtype
 template <typename S> struct DropArith { typedef float type; };
 template <> struct DropArith<double> { typedef double type; };

@@ -76,16 +76,27 @@ class GraphedTrainStep:
     The dictionary a call returns holds the graph's STATIC output buffers (no copy kernels in the iteration): the
     next call overwrites them.  A caller that keeps ``loss`` / ``output`` across iterations must ``.clone()`` them
     (``train_step`` returns fresh tensors).
+
+    ``batch_source`` (a ``batches.DeviceBatches``): the graph then holds the ENTIRE iteration - its first node draws the
+    batch into the static buffers (``batch_source.draw_into``), every replay trains on the next batch of the source, and
+    the step is called with no arguments.  ``example_x`` / ``example_y`` may be None (the buffers take the source's
+    shapes), and the returned dictionary gains ``"indices"``, the sample numbers of the batch (a static buffer like the
+    others).  The warm-up iterations consume real draws and are real training steps, as they already are on the example
+    batch: after construction the source stands at batch ``warmup``.
     """
 
-    def __init__(self, model: torch.nn.Module, example_x: Tensor, example_y: Tensor,
+    def __init__(self, model: torch.nn.Module, example_x: Optional[Tensor], example_y: Optional[Tensor],
                  loss_fn: Callable[[Tensor, Tensor], Tensor], optimizer: torch.optim.Optimizer,
                  reg_fn: Optional[Callable[[torch.nn.Module], Tensor]] = None, reg_coeff: float = 0.0,
                  reducer: Optional[ddp.FlatGradAllReducer] = None, warmup: int = 3,
-                 graph_allreduce: Optional[bool] = None):
+                 graph_allreduce: Optional[bool] = None, batch_source=None):
         self.model, self.optimizer, self.reducer = model, optimizer, reducer
-        self.x, self.y = example_x.clone(), example_y.clone()
-        dev = example_x.device
+        self.batch_source = batch_source
+        if batch_source is None:
+            self.x, self.y = example_x.clone(), example_y.clone()
+        else:
+            self.x, self.y, self.indices = batch_source.empty_batch()
+        dev = self.x.device
         reduces = reducer is not None and (reducer.world > 1 or not reducer.skip_single_rank)
         if reduces and graph_allreduce is None:
             graph_allreduce = False
@@ -98,6 +109,8 @@ class GraphedTrainStep:
         split = reduces
 
         def fwd_bwd():
+            if batch_source is not None:
+                batch_source.draw_into(self.x, self.y, self.indices)
             model.train()
             out = model(self.x)
             loss = loss_fn(out if getattr(loss_fn, "accepts_low_precision", False) else out.float(), self.y)
@@ -149,16 +162,25 @@ class GraphedTrainStep:
             with torch.cuda.graph(self.g_opt, capture_error_mode="thread_local"):
                 optimizer.step()
 
-    def __call__(self, x: Tensor, y: Tensor) -> Dict[str, Tensor]:
-        if x is not self.x:   # a data pipeline may fill the static buffers `step.x` / `step.y` itself and pass them
-            self.x.copy_(x, non_blocking=True)
-        if y is not self.y:
-            self.y.copy_(y, non_blocking=True)
+    def __call__(self, x: Optional[Tensor] = None, y: Optional[Tensor] = None) -> Dict[str, Tensor]:
+        if self.batch_source is not None:
+            if x is not None or y is not None:
+                raise TypeError("a GraphedTrainStep with a batch_source draws its own batches: call it without arguments")
+        else:
+            if x is None or y is None:
+                raise TypeError("GraphedTrainStep.__call__ needs the batch (x, y)")
+            if x is not self.x:   # a data pipeline may fill the static buffers `step.x` / `step.y` itself and pass them
+                self.x.copy_(x, non_blocking=True)
+            if y is not self.y:
+                self.y.copy_(y, non_blocking=True)
         self.g_main.replay()
         if self.g_opt is not None:
             self.reducer()
             self.g_opt.replay()
-        return {"output": self.out, "loss": self.loss, "reg_term": self.reg}
+        result = {"output": self.out, "loss": self.loss, "reg_term": self.reg}
+        if self.batch_source is not None:
+            result["indices"] = self.indices
+        return result
 
 
 # ------------------------------------------------------------------------------- fused iteration tail

@@ -504,6 +504,69 @@ int dctn_core_dropout_mask(void* const* mask, const int64_t* numel, int n_cores,
                            int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Device-resident batch source (version 503; reference: the train DataLoader of dctn/dataset_loading.py:69-70, 282-286,
+ * 319-325 - __getitem__ per sample, collate_quantum, pinning and a copy).  ONE launch picks the samples of a batch, moves
+ * them into the model's input layout and dtype and advances a device counter; the epoch order is stored nowhere - a pure
+ * function of (seed, epoch, position).
+ *
+ * Order definition (normative; dctn_amd/batches.py `round_keys` / `order_at` restate it in Python).  Position i of epoch
+ * e over n samples (1 <= n < 2^31) under the 64-bit seed maps to a sample through a bijection on [0, 2^b),
+ * b = max(2, bit length of n - 1), applied again while the value is >= n (cycle walking: i < n lies on a cycle of the
+ * bijection, so the walk comes back below n; the result is a bijection on [0, n)).
+ *   round keys  K[0..5] = the first six words of Philox4x32-10(counter (0, 0, e, TAG), key) followed by
+ *               Philox4x32-10(counter (1, 0, e, TAG), key), TAG = 0x53485546, key = (seed & 0xFFFFFFFF, seed >> 32) - the
+ *               generator of the dropout section above, whose counters keep c3 below 8
+ *   mix32(h)    h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16      (32-bit arithmetic)
+ *   one pass    wl = b / 2, wr = b - wl;  L = v >> wr, R = v & (2^wr - 1);
+ *               six times, j = 0..5:  (L, R) = (R, L ^ (mix32(R ^ K[j]) & (2^wl - 1))), then wl and wr change places;
+ *               result (L << wr) | R
+ * Batch k (the device counter) with global batch G and S = n / G batches per epoch (the remainder of an epoch is dropped):
+ * epoch e = k / S; the launch of a rank whose shard starts at rank_offset takes positions (k % S) * G + rank_offset + j,
+ * j < local_batch.  With DCTN_BATCH_IDENTITY_ORDER in `flags` the sample IS the position (a sequential pass).
+ *
+ * dctn_batch_draw   : sample numbers from `state`; the launch draws batch k = batches_done as read at its start and
+ *                     leaves k + 1.  It only enqueues and never reads the device on the host: a captured graph that holds
+ *                     it draws k, k + 1, ... on its replays.
+ * dctn_batch_gather : the same data movement for `count` sample numbers given as a DEVICE int64 array; reads no state and
+ *                     takes no ticket (sequential evaluation passes, eager use).  Every number must lie in [0, n): the
+ *                     caller's contract, not checked.
+ * Source kinds (`row_len`, `width` describe the geometry):
+ *   DCTN_BATCH_SRC_U8_TABLE : src = raw uint8 intensities (n, P), P = row_len pixels (what torchvision's `.data` holds);
+ *       table = (256, Q) values of `dtype`, Q = width, 1 <= Q <= 4 (phi, the scale and the cast, folded in by the caller);
+ *       x = (1, local_batch, P, Q):  x[0, j, p, :] = table[src[s_j, p], :].  The workgroup stages the table in LDS; four
+ *       pixels move per 32-bit load when P % 4 == 0 and src is 4-byte aligned (and x 16-byte aligned; 8 for bf16 with
+ *       odd Q), pixel by pixel otherwise.
+ *   DCTN_BATCH_SRC_ROWS     : src = features already expanded, (C, n, R) values of `dtype`, R = row_len, C = width <= 4;
+ *       x = (C, local_batch, R):  x[c, j, :] = src[c, s_j, :] (16-byte accesses when both bases and R * sizeof allow);
+ *       table is ignored (may be NULL).
+ * Both write y[j] = labels[s_j] and indices[j] = s_j (int64; labels: n int64 values).  dtype: DCTN_F32 / F64 / BF16; all
+ * tensors contiguous and aligned to their element size.
+ *
+ * `state`: dctn_batch_state_bytes() = 16 bytes on the device, 16-byte aligned, laid out as
+ *   uint32 seed_lo, uint32 seed_hi   the seed; read by every draw
+ *   uint32 batches_done              number of draws so far (a 32-bit counter: it wraps after 2^32 batches)
+ *   uint32 ticket                    0 between launches (workgroups count themselves out on it; the last one resets it)
+ * The caller creates the block once (seed, 0, 0) and may read or write it in stream order between launches; ranks that
+ * hold the same block and pass their own rank_offset draw disjoint shards of the same global batch.
+ *
+ * Buffer contract: x, y, indices are fully OVERWRITTEN (every element, whatever they held), nothing outside them is
+ * touched; src, table, labels and sample_idx are never written; of the block only batches_done and ticket change.
+ * Return codes, all decided on the host before any launch: DCTN_ERR_NULL; DCTN_ERR_BAD_SHAPE (n < 1, n >= 2^31,
+ * global_batch > n or < 1, local_batch / count < 1, rank_offset + local_batch > global_batch, row_len or width < 1, an
+ * unknown src_kind or flag); DCTN_ERR_BAD_DTYPE; DCTN_ERR_UNSUPPORTED (width > 4).  No workspace.
+ * dctn_last_kernel(): batch_{draw,gather}_{u8,rows}_{f32,f64,bf16}.
+ * ------------------------------------------------------------------------------------------ */
+enum { DCTN_BATCH_SRC_U8_TABLE = 0, DCTN_BATCH_SRC_ROWS = 1 };
+enum { DCTN_BATCH_IDENTITY_ORDER = 1 };   /* `flags` of dctn_batch_draw */
+size_t dctn_batch_state_bytes(void);
+int dctn_batch_draw(const void* src, const void* table, const void* labels, void* x, void* y, void* indices, void* state,
+                    int64_t n, int64_t global_batch, int64_t local_batch, int64_t rank_offset, int64_t row_len, int width,
+                    int src_kind, int flags, int dtype, void* stream);
+int dctn_batch_gather(const void* src, const void* table, const void* labels, const void* sample_idx, void* x, void* y,
+                      void* indices, int64_t n, int64_t count, int64_t row_len, int width, int src_kind, int dtype,
+                      void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Tensor-network inner product of two stacks of EPS cores - replaces the contractions of
  * dctn/epses_composition.py:21-58 `inner_product` (Gram of the first pair of cores over their input legs:
  * dctn/eps.py:106-112 `contract_on_input_dims`; that matrix absorbed into every input leg of the next core:
