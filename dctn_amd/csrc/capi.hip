@@ -190,7 +190,7 @@ static int eps_fwd_family(int family, const void* x, const void* core, void* out
     case DCTN_EPS_FAMILY_BIGCORE_F32: return eps_fwd_bigcore(x, core, out, ws, ws_bytes, p, dtype, r.precision, st, keep);
     case DCTN_EPS_FAMILY_HALVES: return eps_fwd_halves(x, core, out, ws, ws_bytes, p, dtype, st, keep);
   }
-  return eps_fwd_generic(x, core, out, p, dtype, st);
+  return eps_fwd_generic(x, core, out, ws, ws_bytes, p, dtype, st);
 }
 
 // ---------------------------------------------------------------------------------------------- fused head

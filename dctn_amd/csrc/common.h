@@ -82,7 +82,8 @@ int eps_fill_params(EpsP& p, const int64_t x_strides[5], int C, int B, int H, in
                     int O, int policy = 0);
 
 // generic (any shape, f32/f64/bf16-storage) kernels — eps_generic.hip
-int eps_fwd_generic(const void* x, const void* core, void* out, EpsP p, int dtype, hipStream_t st);
+int eps_fwd_generic(const void* x, const void* core, void* out, void* ws, size_t ws_bytes, EpsP p, int dtype,
+                    hipStream_t st);
 size_t eps_bwd_generic_workspace(const EpsP& p, int dtype, int need_dx, int need_dcore);
 int eps_bwd_generic(const void* x, const void* core, const void* dY, void* dX, void* dCore,
                     void* ws, size_t ws_bytes, EpsP p, int dtype, hipStream_t st);

@@ -6,6 +6,8 @@
 // LO = Q^m <= 64): P[w,i] = Phi[w,hi] * Plo[w,lo].  Plo lives in a per-lane LDS column
 // ([entry][lane] layout: conflict-free), the core is read through wave-uniform (scalar) loads.
 // Nothing of size Wn x Q^n is ever written to HBM.
+// A launch that splits its work over grid.y keeps one partial result per slice in the workspace and
+// a fixed-order sum joins them (no float atomics): the same bits from run to run.
 //
 // These kernels are the exact reference-grade path (f64 for the reference's own tests, odd Q);
 // the MFMA kernels in eps_mfma.hip take over for the power-of-two-Q shape families.
@@ -65,7 +67,8 @@ __device__ __forceinline__ void build_plo(const EpsP& p, const A* xs, A* plo, in
 template <typename S, typename A, int OT>
 __global__ __launch_bounds__(DCTN_WAVE) void eps_fwd_generic_k(const S* __restrict__ x,
                                                                const S* __restrict__ core,
-                                                               S* __restrict__ out, EpsP p,
+                                                               S* __restrict__ out,
+                                                               A* __restrict__ part, EpsP p,
                                                                long long hi_per_slice) {
   extern __shared__ __align__(16) unsigned char smem[];
   A* xs = reinterpret_cast<A*>(smem);               // [N*Q][64]
@@ -79,7 +82,8 @@ __global__ __launch_bounds__(DCTN_WAVE) void eps_fwd_generic_k(const S* __restri
   build_plo<A>(p, xs, plo, tid);
 
   // gridDim.y > 1: the high half of the core rows is split over grid.y (few windows would leave
-  // most SIMDs idle behind one serial loop per wave); slices meet by atomic adds on a zeroed `out`
+  // most SIMDs idle behind one serial loop per wave); every slice stores its partial output in
+  // `part` [slice][Wn * O], and sum_slices_k adds the slices in a fixed order (no float atomics)
   const long long hi_begin = (long long)blockIdx.y * hi_per_slice;
   const long long hi_end = hi_begin + hi_per_slice < p.HI ? hi_begin + hi_per_slice : p.HI;
   for (int o0 = 0; o0 < p.O; o0 += OT) {
@@ -106,20 +110,18 @@ __global__ __launch_bounds__(DCTN_WAVE) void eps_fwd_generic_k(const S* __restri
 #pragma unroll
       for (int j = 0; j < OT; ++j)
         if (o0 + j < p.O) {
-          if constexpr (sizeof(S) == sizeof(A)) {
-            if (gridDim.y > 1) {
-              atomicAdd(reinterpret_cast<A*>(out) + w * p.O + o0 + j, acc[j]);
-              continue;
-            }
-          }
-          out[w * p.O + o0 + j] = (S)acc[j];
+          if (part)
+            part[((long long)blockIdx.y * p.Wn + w) * p.O + o0 + j] = acc[j];
+          else
+            out[w * p.O + o0 + j] = (S)acc[j];
         }
     }
   }
 }
 
 // ------------------------------------------------------------- backward: per-window d/d(factor)
-// Writes gx[(n*Q+q)][w] = d(sum_o out[w,o] dY[w,o]) / d x_n[w,q] to the workspace (coalesced);
+// Writes gx[(n*Q+q)][w] = d(sum_o out[w,o] dY[w,o]) / d x_n[w,q] to the workspace (coalesced), one
+// [N*Q][Wn] slice per grid.y (sum_slices_k adds them in a fixed order when there are several);
 // eps_gather_dx_k then sums, for every input pixel, the K*K windows that cover it (no atomics,
 // deterministic).
 template <typename S, typename A>
@@ -201,11 +203,8 @@ __global__ __launch_bounds__(DCTN_WAVE) void eps_bwd_dfactor_generic_k(
     }
   }
   if (valid) {
-    if (gridDim.y > 1) {
-      for (int e = 0; e < NQ; ++e) atomicAdd(&gxw[(long long)e * p.Wn + w], gx[e * DCTN_WAVE + tid]);
-    } else {
-      for (int e = 0; e < NQ; ++e) gxw[(long long)e * p.Wn + w] = gx[e * DCTN_WAVE + tid];
-    }
+    A* slice = gxw + (long long)blockIdx.y * NQ * p.Wn;
+    for (int e = 0; e < NQ; ++e) slice[(long long)e * p.Wn + w] = gx[e * DCTN_WAVE + tid];
   }
 }
 
@@ -252,7 +251,8 @@ namespace {
 // ------------------------------------------------------------------------- backward: dCore
 // dCore[i,o] = sum_w P[w,i] dY[w,o].  One lane owns one core row i (digits packed in 128 bits),
 // window features and dY are staged through LDS and read as broadcasts.  grid.y splits the
-// windows; partial sums are combined with float atomics into an A-typed accumulator.
+// windows; every chunk stores its partial sums as slice [blockIdx.y][R * O] of an A-typed buffer
+// (sum_slices_k adds the slices in a fixed order when there are several).
 constexpr int DC_WB = 32;  // windows staged per step
 
 template <typename S, typename A, int OT>
@@ -319,7 +319,7 @@ __global__ __launch_bounds__(DCTN_WAVE) void eps_bwd_dcore_generic_k(
     if (rvalid) {
 #pragma unroll
       for (int j = 0; j < OT; ++j)
-        if (o0 + j < p.O) atomicAdd(&dCoreAcc[row * p.O + o0 + j], acc[j]);
+        if (o0 + j < p.O) dCoreAcc[((long long)blockIdx.y * p.R + row) * p.O + o0 + j] = acc[j];
     }
   }
 }
@@ -333,6 +333,31 @@ __global__ void convert_k(const A* __restrict__ src, S* __restrict__ dst, long l
     dst[i] = (S)src[i];
 }
 template __global__ void convert_k<bf16_t, float>(const float*, bf16_t*, long long);
+
+// dst[i] = part[0][i] + part[1][i] + ... in this order: the join of the split launches above
+template <typename S, typename A>
+__global__ void sum_slices_k(const A* __restrict__ part, S* __restrict__ dst, long long n, int slices) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (long long)gridDim.x * blockDim.x) {
+    A acc = part[i];
+    for (int s = 1; s < slices; ++s) acc += part[(long long)s * n + i];
+    dst[i] = (S)acc;
+  }
+}
+
+template <typename S, typename A>
+static void sum_slices(const A* part, S* dst, long long n, int slices, hipStream_t st) {
+  const unsigned g = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+  hipLaunchKernelGGL((sum_slices_k<S, A>), dim3(g), dim3(256), 0, st, part, dst, n, slices);
+}
+
+// The split launches keep one partial result per slice in whatever the workspace has left, so the split is as fine as
+// that room allows and no finer: `want` slices of `one` bytes each in `room` bytes (1 = no split, nothing kept)
+static long long slices_that_fit(long long want, size_t one, const void* ws, size_t room) {
+  const long long fit = ws ? (long long)(room / one) : 0;
+  if (want > fit) want = fit;
+  return want < 2 ? 1 : want;
+}
 
 // ================================================================================== host side
 int eps_fill_params(EpsP& p, const int64_t xs[5], int C, int B, int H, int W, int Q, int K, int O, int policy) {
@@ -382,33 +407,40 @@ static long long hi_slices(const EpsP& p, unsigned window_blocks) {
 }
 
 template <typename S, typename A>
-static int fwd_launch(const void* x, const void* core, void* out, const EpsP& p, hipStream_t st) {
+static int fwd_launch(const void* x, const void* core, void* out, void* ws, size_t ws_bytes, const EpsP& p,
+                      hipStream_t st) {
   const size_t lds = fwd_lds(p, sizeof(A));
   if (lds > dctn_lds_wg_max()) return DCTN_ERR_UNSUPPORTED;
   const unsigned grid = (unsigned)((p.Wn + DCTN_WAVE - 1) / DCTN_WAVE);
-  const long long slices = sizeof(S) == sizeof(A) ? hi_slices(p, grid) : 1;
+  const long long n_out = p.Wn * p.O;
+  const long long slices = sizeof(S) == sizeof(A) ? slices_that_fit(hi_slices(p, grid), (size_t)n_out * sizeof(A), ws, ws_bytes) : 1;
   const long long hps = (p.HI + slices - 1) / slices;
-  const dim3 g2(grid, (unsigned)((p.HI + hps - 1) / hps));
+  const dim3 g2(grid, (unsigned)((p.HI + hps - 1) / hps));   // (g2.y <= slices)
+  A* part = g2.y > 1 ? (A*)ws : nullptr;
   if (!dctn_lds_optin(p.O <= 4 ? (const void*)eps_fwd_generic_k<S, A, 4> : (const void*)eps_fwd_generic_k<S, A, 8>, lds))
     return DCTN_ERR_UNSUPPORTED;
-  if (g2.y > 1 && dctn_zero_async(out, (size_t)p.Wn * p.O * sizeof(S), st) != DCTN_OK) return DCTN_ERR_LAUNCH;
   if (p.O <= 4) {
     hipLaunchKernelGGL((eps_fwd_generic_k<S, A, 4>), g2, dim3(DCTN_WAVE), lds, st,
-                       (const S*)x, (const S*)core, (S*)out, p, hps);
+                       (const S*)x, (const S*)core, (S*)out, part, p, hps);
   } else {
     hipLaunchKernelGGL((eps_fwd_generic_k<S, A, 8>), g2, dim3(DCTN_WAVE), lds, st,
-                       (const S*)x, (const S*)core, (S*)out, p, hps);
+                       (const S*)x, (const S*)core, (S*)out, part, p, hps);
   }
   DCTN_CHECK_LAUNCH();
+  if (part) {
+    sum_slices<S, A>(part, (S*)out, n_out, (int)g2.y, st);
+    DCTN_CHECK_LAUNCH();
+  }
   dctn_set_last_kernel("eps_fwd_generic");
   return DCTN_OK;
 }
 
-int eps_fwd_generic(const void* x, const void* core, void* out, EpsP p, int dtype, hipStream_t st) {
+int eps_fwd_generic(const void* x, const void* core, void* out, void* ws, size_t ws_bytes, EpsP p, int dtype,
+                    hipStream_t st) {
   switch (dtype) {
-    case DCTN_F32: return fwd_launch<float, float>(x, core, out, p, st);
-    case DCTN_F64: return fwd_launch<double, double>(x, core, out, p, st);
-    case DCTN_BF16: return fwd_launch<bf16_t, float>(x, core, out, p, st);
+    case DCTN_F32: return fwd_launch<float, float>(x, core, out, ws, ws_bytes, p, st);
+    case DCTN_F64: return fwd_launch<double, double>(x, core, out, ws, ws_bytes, p, st);
+    case DCTN_BF16: return fwd_launch<bf16_t, float>(x, core, out, ws, ws_bytes, p, st);
   }
   return DCTN_ERR_BAD_DTYPE;
 }
@@ -429,20 +461,28 @@ static int bwd_launch(const void* x, const void* core, const void* dY, void* dX,
   if (eps_bwd_generic_workspace(p, dtype, dX != nullptr, dCore != nullptr) > ws_bytes)
     return DCTN_ERR_WORKSPACE;
   unsigned char* wsp = (unsigned char*)ws;
+  // [gxw | the bf16 dCore accumulator | room]: what the query does not count is room for the partial results of the
+  // split launches, first dX's, then (stream order) dCore's
+  const size_t counted = eps_bwd_generic_workspace(p, dtype, dX != nullptr, dCore != nullptr);
+  unsigned char* room = ws ? wsp + counted : nullptr;
+  const size_t room_bytes = ws ? ws_bytes - counted : 0;
   if (dX) {
     const size_t lds = dfac_lds(p, sizeof(A));
     if (lds > dctn_lds_wg_max() || !dctn_lds_optin((const void*)eps_bwd_dfactor_generic_k<S, A>, lds)) return DCTN_ERR_UNSUPPORTED;
     A* gxw = (A*)wsp;
     wsp += align256((size_t)p.Wn * p.N * p.Q * sizeof(A));
     const unsigned grid = (unsigned)((p.Wn + DCTN_WAVE - 1) / DCTN_WAVE);
-    const long long slices = hi_slices(p, grid);
+    const long long n_gx = p.Wn * p.N * p.Q;
+    const long long slices = slices_that_fit(hi_slices(p, grid), (size_t)n_gx * sizeof(A), room, room_bytes);
     const long long hps = (p.HI + slices - 1) / slices;
-    const dim3 g3(grid, (unsigned)((p.HI + hps - 1) / hps));
-    if (g3.y > 1 && dctn_zero_async(gxw, (size_t)p.Wn * p.N * p.Q * sizeof(A), st) != DCTN_OK)
-      return DCTN_ERR_LAUNCH;
+    const dim3 g3(grid, (unsigned)((p.HI + hps - 1) / hps));   // (g3.y <= slices)
     hipLaunchKernelGGL((eps_bwd_dfactor_generic_k<S, A>), g3, dim3(DCTN_WAVE), lds, st,
-                       (const S*)x, (const S*)core, (const S*)dY, gxw, p, hps);
+                       (const S*)x, (const S*)core, (const S*)dY, g3.y > 1 ? (A*)room : gxw, p, hps);
     DCTN_CHECK_LAUNCH();
+    if (g3.y > 1) {
+      sum_slices<A, A>((const A*)room, gxw, n_gx, (int)g3.y, st);
+      DCTN_CHECK_LAUNCH();
+    }
     const long long total = (long long)p.C * p.B * p.H * p.W * p.Q;
     const unsigned g2 = (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
     hipLaunchKernelGGL((eps_gather_dx_k<S, A>), dim3(g2), dim3(256), 0, st, gxw, (S*)dX, p);
@@ -454,18 +494,19 @@ static int bwd_launch(const void* x, const void* core, const void* dY, void* dX,
     if (lds > dctn_lds_wg_max()) return DCTN_ERR_UNSUPPORTED;
     if (!dctn_lds_optin(p.O <= 4 ? (const void*)eps_bwd_dcore_generic_k<S, A, 4> : (const void*)eps_bwd_dcore_generic_k<S, A, 8>, lds))
       return dX ? DCTN_ERR_LAUNCH : DCTN_ERR_UNSUPPORTED;   // (dX is written by now: no fall-through)
-    A* acc = sizeof(S) == sizeof(A) ? (A*)dCore : (A*)wsp;
-    if (dctn_zero_async(acc, (size_t)p.R * p.O * sizeof(A), st) != DCTN_OK)
-      return DCTN_ERR_LAUNCH;
+    const long long n_core = p.R * p.O;
     const long long row_blocks = (p.R + DCTN_WAVE - 1) / DCTN_WAVE;
     long long chunks = 4096 / row_blocks;
     if (chunks < 1) chunks = 1;
     const long long max_chunks = (p.Wn + DC_WB - 1) / DC_WB;
     if (chunks > max_chunks) chunks = max_chunks;
     if (chunks > 65535) chunks = 65535;
+    chunks = slices_that_fit(chunks, (size_t)n_core * sizeof(A), room, room_bytes);
     long long wpb = (p.Wn + chunks - 1) / chunks;
     wpb = (wpb + DC_WB - 1) / DC_WB * DC_WB;
-    chunks = (p.Wn + wpb - 1) / wpb;
+    chunks = (p.Wn + wpb - 1) / wpb;   // (rounding wpb up: never more than fit)
+    // one chunk writes the result itself (bf16: its float32 form, converted below); several write their slices
+    A* acc = chunks > 1 ? (A*)room : sizeof(S) == sizeof(A) ? (A*)dCore : (A*)wsp;
     dim3 grid((unsigned)row_blocks, (unsigned)chunks);
     if (p.O <= 4) {
       hipLaunchKernelGGL((eps_bwd_dcore_generic_k<S, A, 4>), grid, dim3(DCTN_WAVE), lds, st,
@@ -475,10 +516,12 @@ static int bwd_launch(const void* x, const void* core, const void* dY, void* dX,
                          (const S*)x, (const S*)dY, acc, p, wpb);
     }
     DCTN_CHECK_LAUNCH();
-    if constexpr (sizeof(S) != sizeof(A)) {
-      const long long n = p.R * p.O;
-      const unsigned g = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-      hipLaunchKernelGGL((convert_k<S, A>), dim3(g), dim3(256), 0, st, (const A*)acc, (S*)dCore, n);
+    if (chunks > 1) {
+      sum_slices<S, A>((const A*)acc, (S*)dCore, n_core, (int)chunks, st);
+      DCTN_CHECK_LAUNCH();
+    } else if constexpr (sizeof(S) != sizeof(A)) {
+      const unsigned g = (unsigned)((n_core + 255) / 256 < 4096 ? (n_core + 255) / 256 : 4096);
+      hipLaunchKernelGGL((convert_k<S, A>), dim3(g), dim3(256), 0, st, (const A*)acc, (S*)dCore, n_core);
       DCTN_CHECK_LAUNCH();
     }
   }

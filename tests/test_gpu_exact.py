@@ -128,7 +128,7 @@ GENERIC_CASES = [c for c in eps_cases() if c[2] ** (c[1] * c[1] * c[0]) <= 2 ** 
 @pytest.mark.parametrize("case", GENERIC_CASES, ids=lambda c: "C%dK%dQ%dO%dB%d_%dx%d_%s%s" % (
     c[0], c[1], c[2], c[3], c[4], c[5], c[6], str(c[7]).split(".")[1], "_strided" if c[8] else ""))
 def test_eps_generic(case):
-    """eps_one_by_one: the generic kernels (DCTN_OPT_GENERIC_KERNELS), one lane per window, float atomics for dCore."""
+    """eps_one_by_one: the generic kernels (DCTN_OPT_GENERIC_KERNELS), one lane per window, split launches joined by fixed-order slice sums."""
     C, K, Q, O, B, H, W, dtype, strided = case
     core, x, dy = eps_operands(C, K, Q, O, B, H, W, dtype, seed=sum(case[:7]))
     run_eps(core, x, dy, dtype, strided=strided, fn=eps_one_by_one, fwd="eps_fwd_generic", bwd="eps_bwd_generic",
