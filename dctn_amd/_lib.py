@@ -28,7 +28,7 @@ SAVED, PARTIAL = 1, 2   # positive success codes (include/dctn_amd.h)
 SBS_MATRIX_CORE_SWEEP = 1 << 8   # OR-ed into the dtype argument of the dctn_convsbs_* calls
 SBS_WIDE_SWEEP = 1 << 9   # likewise: the backward on the wide family (convsbs_wide.hip) for any string it covers
 BATCH_SRC_U8_TABLE, BATCH_SRC_ROWS = 0, 1   # DCTN_BATCH_SRC_*: `src_kind` of dctn_batch_draw / dctn_batch_gather
-BATCH_IDENTITY_ORDER = 1                    # `flags` of dctn_batch_draw
+BATCH_IDENTITY_ORDER, BATCH_PAD_TAIL = 1, 2  # `flags` of dctn_batch_draw
 
 _DTYPE_CODE = {torch.float32: F32, torch.float64: F64, torch.bfloat16: BF16}
 

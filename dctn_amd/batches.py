@@ -96,6 +96,16 @@ def expected_indices(seed: int, k: int, n: int, batch_size: int, rank: int = 0, 
     return [_walk(first + j, n, b, K) for j in range(Bl)]
 
 
+def expected_padded_indices(k: int, n: int, batch_size: int, rank: int = 0, world: int = 1) -> List[int]:
+    """The sample numbers of draw ``k`` of the padded sequential form (`DeviceBatches.draw_padded_into`,
+    DCTN_BATCH_PAD_TAIL) for ``rank`` of ``world``: S = ceil(n / batch_size) batches a pass, positions
+    ``(k % S) * batch_size + rank * Bl + j`` for ``j < Bl = batch_size // world``, and -1 where the position is >= n
+    (padding: the slot's label is -100)."""
+    S, Bl = steps_per_epoch(n, batch_size, drop_last=False), local_batch(batch_size, rank, world)
+    first = (k % S) * batch_size + rank * Bl
+    return [pos if pos < n else -1 for pos in range(first, first + Bl)]
+
+
 def _new_state(seed: int, device: torch.device, batches_done: int = 0) -> Tensor:
     """The 16-byte device block {uint32 seed_lo, seed_hi, batches_done, ticket} as four int32 (same bits)."""
     assert L.lib().dctn_batch_state_bytes() == 16
@@ -138,6 +148,14 @@ class DeviceBatches:
     ``shuffle=False`` gives the identity order.  ``drop_last=False`` (with ``shuffle=False`` only: the form of the
     reference's validation and test loaders) makes every pass a sequential walk over ALL samples through
     `dctn_batch_gather`, the last batch short; such a pass is eager and does not touch the counter.
+
+    ``draw_padded_into(x, y, indices)`` (``shuffle=False`` sources) is the capturable form of that walk: every batch has
+    the full shape, ``padded_steps`` = ceil(n / batch_size) draws cover all samples once, and the slots past the last sample
+    are padding (label -100, index -1; `expected_padded_indices`).  It reads the SAME counter word as ``draw_into`` with a
+    different number of batches per pass, so a source used for padded passes is used for nothing else.  Its sharding differs
+    from the eager ``drop_last=False`` iteration: rank r takes slots ``r * Bl .. r * Bl + Bl - 1`` of every batch (of the
+    last one too, where a rank may get nothing but padding), whereas the eager iteration splits the short tail evenly; the
+    sums over all ranks are the same.
     """
 
     def __init__(self, images_u8: Tensor, labels: Tensor, batch_size: int, *, dtype: torch.dtype, seed: int,
@@ -200,6 +218,7 @@ class DeviceBatches:
         if shuffle and not drop_last:
             raise ValueError("drop_last=False is the sequential form: it needs shuffle=False")
         self.steps = steps_per_epoch(self.n, self.batch_size)             # S of the device counter: whole batches
+        self.padded_steps = steps_per_epoch(self.n, self.batch_size, drop_last=False)   # S of `draw_padded_into`
         self.local_batch = local_batch(self.batch_size, self.rank, self.world)
         _state_words(self.seed, 0)
 
@@ -240,15 +259,27 @@ class DeviceBatches:
             raise ValueError(f"a batch of {count} samples needs contiguous x {self.x_shape(count)} in {self.dtype} and "
                              f"int64 y, indices of shape ({count},)")
 
-    def draw_into(self, x: Tensor, y: Tensor, indices: Tensor) -> None:
-        """The next batch (this rank's shard of it) into caller-owned buffers: one launch, capturable."""
+    def _draw(self, x: Tensor, y: Tensor, indices: Tensor, flags: int) -> None:
         self._check_out(x, y, indices, self.local_batch)
         with torch.cuda.device(self.device):
             L.check(L.lib().dctn_batch_draw(
                 self.src.data_ptr(), None if self.table is None else self.table.data_ptr(), self.labels.data_ptr(),
                 x.data_ptr(), y.data_ptr(), indices.data_ptr(), self._state.data_ptr(), self.n, self.batch_size,
-                self.local_batch, self.rank * self.local_batch, self.row_len, self.width, self.kind,
-                0 if self.shuffle else L.BATCH_IDENTITY_ORDER, L.dtype_code(x), L.stream_ptr(self.device)), "batch draw")
+                self.local_batch, self.rank * self.local_batch, self.row_len, self.width, self.kind, flags,
+                L.dtype_code(x), L.stream_ptr(self.device)), "batch draw")
+
+    def draw_into(self, x: Tensor, y: Tensor, indices: Tensor) -> None:
+        """The next batch (this rank's shard of it) into caller-owned buffers: one launch, capturable."""
+        self._draw(x, y, indices, 0 if self.shuffle else L.BATCH_IDENTITY_ORDER)
+
+    def draw_padded_into(self, x: Tensor, y: Tensor, indices: Tensor) -> None:
+        """The next batch of the padded sequential walk (this rank's shard of it): one launch, capturable, never reads the
+        device.  ``padded_steps`` draws from a counter at 0 (mod ``padded_steps``) cover every sample once and leave the
+        counter there again; padding slots carry the label -100 and the index -1 (see the class docstring: the source is
+        then used for nothing else)."""
+        if self.shuffle:
+            raise ValueError("the padded pass is sequential: it needs a source built with shuffle=False")
+        self._draw(x, y, indices, L.BATCH_IDENTITY_ORDER | L.BATCH_PAD_TAIL)
 
     def draw(self) -> Tuple[Tensor, Tensor, Tensor]:
         out = self.empty_batch()
@@ -282,6 +313,10 @@ class DeviceBatches:
             lo, hi = first + count * self.rank // self.world, first + count * (self.rank + 1) // self.world
             if hi > lo:
                 yield self.gather(self._all[lo:hi])
+
+    def expected_padded_indices(self, k: int) -> List[int]:
+        """Host restatement: what draw ``k`` of the padded walk gives this rank (-1: padding)."""
+        return expected_padded_indices(k, self.n, self.batch_size, self.rank, self.world)
 
     def expected_indices(self, k: int) -> List[int]:
         """Host restatement: the sample numbers draw ``k`` gives this rank."""

@@ -76,12 +76,13 @@ __device__ __forceinline__ void batch_read_head(const BatchArgs& a, BatchHead& h
   const unsigned k0 = __hip_atomic_load(&a.state->seed_lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const unsigned k1 = __hip_atomic_load(&a.state->seed_hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const unsigned k = __hip_atomic_load(&a.state->batches_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const unsigned epoch = k / a.S;
+  const unsigned epoch = k / a.S;   // (the identity order, padded or not, uses neither the epoch nor the keys)
   unsigned w0[4], w1[4];
   philox4x32_10(0u, 0u, epoch, BATCH_TAG, k0, k1, w0);
   philox4x32_10(1u, 0u, epoch, BATCH_TAG, k0, k1, w1);
   head.K[0] = w0[0], head.K[1] = w0[1], head.K[2] = w0[2], head.K[3] = w0[3], head.K[4] = w1[0], head.K[5] = w1[1];
-  head.pos0 = (k % a.S) * a.G + a.offset;   // < S * G <= n < 2^31
+  // < S * G: at most n < 2^31, and with DCTN_BATCH_PAD_TAIL below n + G <= 2 n < 2^32, so neither this nor pos0 + j wraps
+  head.pos0 = (k % a.S) * a.G + a.offset;
   head.k = k;
 }
 
@@ -96,7 +97,7 @@ __device__ __forceinline__ void batch_take_ticket(const BatchArgs& a, unsigned k
   }
 }
 
-// the sample of slot j of this launch, wave-uniform
+// the sample of slot j of this launch, wave-uniform; under DCTN_BATCH_PAD_TAIL (identity order only) it may be >= n
 template <bool DRAW>
 __device__ __forceinline__ unsigned batch_sample(const BatchArgs& a, const unsigned (&K)[6], unsigned pos0, unsigned j) {
   if (!DRAW) return (unsigned)a.sample_idx[j];
@@ -106,6 +107,16 @@ __device__ __forceinline__ unsigned batch_sample(const BatchArgs& a, const unsig
     while (v >= a.n);
   }
   return v;
+}
+
+// DCTN_BATCH_PAD_TAIL (PAD, identity order only): a slot whose position s is >= n is padding.  It reads the row of sample
+// n - 1, so that x is fully written with finite values, and reports the label -100 (the score kernel's "skip this row")
+// and the index -1.  PAD is a template parameter and the unpadded statements are the ones the kernels had before it: the
+// instantiations without it - every training draw, every gather - compile to the instructions they compiled to then.
+template <bool PAD>
+__device__ __forceinline__ void batch_report(const BatchArgs& a, unsigned j, unsigned s, bool padding) {
+  if constexpr (PAD) a.y[j] = padding ? -100ll : a.labels[s], a.indices[j] = padding ? -1ll : (long long)s;
+  else a.y[j] = a.labels[s], a.indices[j] = (long long)s;
 }
 
 template <typename Tb, int Q> struct alignas((Q & (Q - 1)) == 0 ? (Q * sizeof(Tb) > 16 ? 16 : Q * sizeof(Tb)) : sizeof(Tb)) BatchEntry {
@@ -140,7 +151,7 @@ template <typename Tb, int N> struct BatchGroup {
 };
 
 // DCTN_BATCH_SRC_U8_TABLE: x[0, j, p, :] = table[src[s_j, p], :]
-template <typename S, int Q, bool DRAW>
+template <typename S, int Q, bool DRAW, bool PAD>
 __global__ __launch_bounds__(BATCH_THREADS) void batch_u8_k(BatchArgs a) {
   typedef typename BatchBits<S>::type Tb;
   __shared__ BatchEntry<Tb, Q> tab[256];
@@ -166,8 +177,10 @@ __global__ __launch_bounds__(BATCH_THREADS) void batch_u8_k(BatchArgs a) {
   // four pixels per 32-bit load: every row starts on a 4-byte boundary, and 4 Q elements of x on a store boundary
   const bool vec = P % 4u == 0u && (uintptr_t)src % 4u == 0u && (uintptr_t)x % BatchGroup<Tb, 4 * Q>::ALIGN == 0u;
   for (unsigned j = wave; j < a.Bl; j += gridDim.x * BATCH_WAVES) {
-    const unsigned s = batch_sample<DRAW>(a, K, pos0, j);
-    if (lane == 0) a.y[j] = a.labels[s], a.indices[j] = (long long)s;
+    const unsigned drawn = batch_sample<DRAW>(a, K, pos0, j);
+    const bool padding = PAD && drawn >= a.n;   // wave-uniform
+    const unsigned s = padding ? a.n - 1u : drawn;
+    if (lane == 0) batch_report<PAD>(a, j, s, padding);
     const unsigned char* row = src + (size_t)s * P;
     Tb* out = x + (size_t)j * P * Q;
     if (vec) {
@@ -205,7 +218,7 @@ __global__ __launch_bounds__(BATCH_THREADS) void batch_u8_k(BatchArgs a) {
 }
 
 // DCTN_BATCH_SRC_ROWS: x[c, j, :] = src[c, s_j, :]
-template <typename S, bool DRAW>
+template <typename S, bool DRAW, bool PAD>
 __global__ __launch_bounds__(BATCH_THREADS) void batch_rows_k(BatchArgs a) {
   typedef typename BatchBits<S>::type Tb;
   __shared__ BatchHead head;
@@ -225,8 +238,10 @@ __global__ __launch_bounds__(BATCH_THREADS) void batch_rows_k(BatchArgs a) {
   const size_t row_bytes = (size_t)R * sizeof(Tb);
   const bool vec = row_bytes % 16u == 0u && ((uintptr_t)src | (uintptr_t)x) % 16u == 0u;
   for (unsigned j = wave; j < a.Bl; j += gridDim.x * BATCH_WAVES) {
-    const unsigned s = batch_sample<DRAW>(a, K, pos0, j);
-    if (lane == 0) a.y[j] = a.labels[s], a.indices[j] = (long long)s;
+    const unsigned drawn = batch_sample<DRAW>(a, K, pos0, j);
+    const bool padding = PAD && drawn >= a.n;   // wave-uniform
+    const unsigned s = padding ? a.n - 1u : drawn;
+    if (lane == 0) batch_report<PAD>(a, j, s, padding);
     for (unsigned c = 0; c < C; ++c) {
       const Tb* in = src + ((size_t)c * a.n + s) * R;
       Tb* out = x + ((size_t)c * a.Bl + j) * R;
@@ -261,19 +276,27 @@ const char* const BATCH_NAMES[2][2][3] = {
      {"batch_gather_rows_f32", "batch_gather_rows_f64", "batch_gather_rows_bf16"}},
 };
 
-template <typename S, bool DRAW>
-void batch_launch_typed(const BatchArgs& a, int kind, dim3 g, hipStream_t st) {
+template <typename S, bool DRAW, bool PAD>
+void batch_launch_padded(const BatchArgs& a, int kind, dim3 g, hipStream_t st) {
   const dim3 b(BATCH_THREADS);
   if (kind == DCTN_BATCH_SRC_ROWS) {
-    hipLaunchKernelGGL((batch_rows_k<S, DRAW>), g, b, 0, st, a);
+    hipLaunchKernelGGL((batch_rows_k<S, DRAW, PAD>), g, b, 0, st, a);
     return;
   }
   switch (a.width) {
-    case 1: hipLaunchKernelGGL((batch_u8_k<S, 1, DRAW>), g, b, 0, st, a); break;
-    case 2: hipLaunchKernelGGL((batch_u8_k<S, 2, DRAW>), g, b, 0, st, a); break;
-    case 3: hipLaunchKernelGGL((batch_u8_k<S, 3, DRAW>), g, b, 0, st, a); break;
-    default: hipLaunchKernelGGL((batch_u8_k<S, 4, DRAW>), g, b, 0, st, a); break;
+    case 1: hipLaunchKernelGGL((batch_u8_k<S, 1, DRAW, PAD>), g, b, 0, st, a); break;
+    case 2: hipLaunchKernelGGL((batch_u8_k<S, 2, DRAW, PAD>), g, b, 0, st, a); break;
+    case 3: hipLaunchKernelGGL((batch_u8_k<S, 3, DRAW, PAD>), g, b, 0, st, a); break;
+    default: hipLaunchKernelGGL((batch_u8_k<S, 4, DRAW, PAD>), g, b, 0, st, a); break;
   }
+}
+
+template <typename S, bool DRAW>
+void batch_launch_typed(const BatchArgs& a, int kind, bool pad, dim3 g, hipStream_t st) {
+  if constexpr (DRAW) {   // a gather has no positions to pad
+    if (pad) return batch_launch_padded<S, true, true>(a, kind, g, st);
+  }
+  batch_launch_padded<S, DRAW, false>(a, kind, g, st);
 }
 
 // everything is decided here, on the host, before any launch
@@ -286,13 +309,15 @@ int batch_launch(BatchArgs a, int64_t n, int64_t G, int64_t count, int64_t offse
   if (n < 1 || n >= (int64_t)1 << 31 || count < 1 || count >= (int64_t)1 << 31) return DCTN_ERR_BAD_SHAPE;
   if (row_len < 1 || row_len >= (int64_t)1 << 31 || width < 1) return DCTN_ERR_BAD_SHAPE;
   if (DRAW && (G < 1 || G > n || offset < 0 || offset + count > G)) return DCTN_ERR_BAD_SHAPE;
-  if (DRAW && (flags & ~DCTN_BATCH_IDENTITY_ORDER)) return DCTN_ERR_BAD_SHAPE;
+  if (DRAW && (flags & ~(DCTN_BATCH_IDENTITY_ORDER | DCTN_BATCH_PAD_TAIL))) return DCTN_ERR_BAD_SHAPE;
+  if (DRAW && (flags & DCTN_BATCH_PAD_TAIL) && !(flags & DCTN_BATCH_IDENTITY_ORDER)) return DCTN_ERR_BAD_SHAPE;
   if (dtype != DCTN_F32 && dtype != DCTN_F64 && dtype != DCTN_BF16) return DCTN_ERR_BAD_DTYPE;
   if (width > 4) return DCTN_ERR_UNSUPPORTED;
+  const bool pad = DRAW && (flags & DCTN_BATCH_PAD_TAIL);
   a.n = (unsigned)n, a.Bl = (unsigned)count, a.row_len = (unsigned)row_len, a.width = (unsigned)width;
   if (DRAW) {
-    a.G = (unsigned)G, a.S = (unsigned)(n / G), a.offset = (unsigned)offset;
     a.identity = (flags & DCTN_BATCH_IDENTITY_ORDER) ? 1u : 0u;
+    a.G = (unsigned)G, a.S = (unsigned)(pad ? (n + G - 1) / G : n / G), a.offset = (unsigned)offset;
     a.bits = 2;
     while (a.bits < 31 && ((int64_t)1 << a.bits) < n) ++a.bits;
   }
@@ -301,9 +326,9 @@ int batch_launch(BatchArgs a, int64_t n, int64_t G, int64_t count, int64_t offse
   if (wgs > cap) wgs = cap;
   const dim3 g((unsigned)wgs);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == DCTN_F32) batch_launch_typed<float, DRAW>(a, kind, g, st);
-  else if (dtype == DCTN_F64) batch_launch_typed<double, DRAW>(a, kind, g, st);
-  else batch_launch_typed<bf16_t, DRAW>(a, kind, g, st);
+  if (dtype == DCTN_F32) batch_launch_typed<float, DRAW>(a, kind, pad, g, st);
+  else if (dtype == DCTN_F64) batch_launch_typed<double, DRAW>(a, kind, pad, g, st);
+  else batch_launch_typed<bf16_t, DRAW>(a, kind, pad, g, st);
   DCTN_CHECK_LAUNCH();
   dctn_set_last_kernel(BATCH_NAMES[DRAW ? 0 : 1][kind][dtype]);
   return DCTN_OK;

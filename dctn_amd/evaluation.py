@@ -3,7 +3,7 @@ sums reduced over the data-parallel ranks when a process group is up: every rank
 shard and all ranks return the same global numbers."""
 from __future__ import annotations
 
-from typing import Iterable, Tuple
+from typing import Any, Callable, Dict, Iterable, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -53,3 +53,99 @@ def score_fused(model, dl: Iterable, device) -> Tuple[float, float]:
                         "fused scoring")
     sum_loss, num_correct, num_samples = ddp.all_reduce_scalar_sums(acc[0], acc[1], acc[2])
     return float(sum_loss / num_samples), float(num_correct / num_samples)
+
+
+class GraphedScore:
+    """A whole scoring pass over ``src`` (a ``batches.DeviceBatches`` built with ``shuffle=False``) replayed from ONE
+    captured HIP graph of ONE batch: ``src.draw_padded_into`` -> ``model(x)`` -> `dctn_ce_score_accumulate` into three
+    float64 sums on the device, under ``torch.no_grad()`` with the model in eval mode.  A pass is ``src.padded_steps``
+    replays: the source's device counter does the walking, every batch has the full shape, and the rows past the last
+    sample are padding the score kernel skips (label -100).  The graph's size and capture time do not depend on the data
+    set.  Same numbers as `score_fused` fed the same padded batches, bit for bit.
+
+    The constructor runs ``warmup`` eager batches (kernel attributes, the allocator), puts the source's counter back to 0
+    with ``load_state_dict`` and captures; it restores ``model.training``, as every pass does.  ``src`` belongs to this
+    scorer alone (its counter is what the graph walks on).  The graph reads the LIVE parameters through their storage: it
+    holds no copy, so a pass scores the weights as they are when its replays run, and training replays enqueued behind
+    ``launch()`` do not change its result (stream order).  It touches neither the training source's counter, nor the
+    dropout state block (eval mode draws no mask), nor the optimizer.
+
+    One pass at a time: ``launch()`` assumes the counter at 0 (mod ``padded_steps``) - where the constructor and every
+    complete pass leave it - and zeroes the sums, so a second ``launch()`` before ``read()`` wipes what the first pass has
+    added so far and the next ``read()`` returns neither pass's score; any other draw from ``src`` shifts the walk
+    without notice.  Call ``read()`` after every ``launch()``.
+
+    ``launch()`` zeroes the sums and enqueues the replays; it never synchronises.  ``read()`` reduces the three sums over
+    the data-parallel ranks (`ddp.all_reduce_scalar_sums`, as `score_fused`) and returns ``(mean_ce, accuracy)``; the
+    integer ``rows`` and ``correct`` of the pass are attributes afterwards.  ``scorer()`` is ``launch()`` then ``read()``.
+    """
+
+    def __init__(self, model, src, warmup: int = 1):
+        from . import _lib as L
+
+        if src.shuffle:
+            raise ValueError("GraphedScore walks a sequential source: build it with shuffle=False")
+        assert warmup >= 1, "capture needs at least one eager batch first (kernel attributes, lazy initialisation)"
+        self.model, self.src, self._L = model, src, L
+        self.rows = self.correct = None
+        dev = src.device
+        self.x, self.y, self.indices = src.empty_batch()
+        self.acc = torch.zeros(3, dtype=torch.float64, device=dev)
+        was_training = model.training
+        model.eval()
+        try:
+            start = dict(src.state_dict(), batches_done=0)
+            side = torch.cuda.Stream(dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side), torch.no_grad():
+                for _ in range(warmup):
+                    self._one_batch()
+            torch.cuda.current_stream(dev).wait_stream(side)
+            torch.cuda.synchronize(dev)
+            src.load_state_dict(start)   # outside the capture: a pass starts at 0 (mod padded_steps)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.no_grad(), torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+                self._one_batch()
+        finally:
+            model.train(was_training)
+
+    def _one_batch(self) -> None:
+        L = self._L
+        self.src.draw_padded_into(self.x, self.y, self.indices)
+        out = self.model(self.x).contiguous()
+        dev = L.require_device(out, self.y, self.acc)
+        assert out.ndim == 2 and self.y.shape == (out.shape[0],)
+        with torch.cuda.device(dev):
+            L.check(L.lib().dctn_ce_score_accumulate(out.data_ptr(), self.y.data_ptr(), self.acc.data_ptr(), out.shape[0],
+                                                     out.shape[1], L.dtype_code(out), L.stream_ptr(dev)), "fused scoring")
+
+    def launch(self) -> None:
+        """Enqueues one pass on the current stream; does not wait for it."""
+        self.acc.zero_()
+        for _ in range(self.src.padded_steps):
+            self.graph.replay()
+
+    def read(self) -> Tuple[float, float]:
+        """``(mean_ce, accuracy)`` of the pass last launched (reads the device: it synchronises)."""
+        sum_loss, num_correct, num_samples = ddp.all_reduce_scalar_sums(self.acc[0], self.acc[1], self.acc[2])
+        self.rows, self.correct = int(round(float(num_samples))), int(round(float(num_correct)))
+        return float(sum_loss / num_samples), float(num_correct / num_samples)
+
+    def __call__(self) -> Tuple[float, float]:
+        self.launch()
+        return self.read()
+
+
+def make_evaluation_hook(train_scorer, val_scorer) -> Callable[[Dict[str, Any], Dict[str, Any]], None]:
+    """``f(st_x, st_it)`` that fills ``train_mean_ce``, ``train_acc``, ``val_mean_ce`` and ``val_acc`` - what
+    `training._checkpoint_tag`, the checkpointers and the early stopper read - from two scorers with ``launch()`` /
+    ``read()`` (`GraphedScore`); for ``at_iter_start=[every_n_iters_intervals(...)(hook), ...]`` of `training.train`.  Both
+    passes are enqueued before either is read."""
+
+    def hook(st_x, st_it) -> None:
+        train_scorer.launch()
+        val_scorer.launch()
+        st_it["train_mean_ce"], st_it["train_acc"] = train_scorer.read()
+        st_it["val_mean_ce"], st_it["val_acc"] = val_scorer.read()
+
+    return hook

@@ -523,6 +523,14 @@ int dctn_core_dropout_mask(void* const* mask, const int64_t* numel, int n_cores,
  * Batch k (the device counter) with global batch G and S = n / G batches per epoch (the remainder of an epoch is dropped):
  * epoch e = k / S; the launch of a rank whose shard starts at rank_offset takes positions (k % S) * G + rank_offset + j,
  * j < local_batch.  With DCTN_BATCH_IDENTITY_ORDER in `flags` the sample IS the position (a sequential pass).
+ * DCTN_BATCH_PAD_TAIL (version 504; only together with DCTN_BATCH_IDENTITY_ORDER) makes that pass cover ALL n samples with
+ * batches of one fixed shape: S = ceil(n / G), the positions are the same expression with this S, and a slot whose position
+ * is >= n is padding: its x row is the row of sample n - 1 (fully written, finite), y[j] = -100 (the label
+ * dctn_ce_score_accumulate and dctn_ce_loss_* skip) and indices[j] = -1.  Slots with a position below n are exactly what the
+ * identity order gives without the flag.  S draws that start at k = 0 (mod S) walk every sample once and leave the counter
+ * at 0 (mod S) again.  S * G exceeds n by up to G - 1; G <= n < 2^31 keeps every position below 2^32.  The counter word
+ * means a different S with and without the flag: one block serves one of the two forms.  The flag selects instantiations
+ * of their own (same kernel names): a draw without it runs code that holds no trace of it.
  *
  * dctn_batch_draw   : sample numbers from `state`; the launch draws batch k = batches_done as read at its start and
  *                     leaves k + 1.  It only enqueues and never reads the device on the host: a captured graph that holds
@@ -553,11 +561,16 @@ int dctn_core_dropout_mask(void* const* mask, const int64_t* numel, int n_cores,
  * touched; src, table, labels and sample_idx are never written; of the block only batches_done and ticket change.
  * Return codes, all decided on the host before any launch: DCTN_ERR_NULL; DCTN_ERR_BAD_SHAPE (n < 1, n >= 2^31,
  * global_batch > n or < 1, local_batch / count < 1, rank_offset + local_batch > global_batch, row_len or width < 1, an
- * unknown src_kind or flag); DCTN_ERR_BAD_DTYPE; DCTN_ERR_UNSUPPORTED (width > 4).  No workspace.
+ * unknown src_kind or flag, DCTN_BATCH_PAD_TAIL without DCTN_BATCH_IDENTITY_ORDER); DCTN_ERR_BAD_DTYPE;
+ * DCTN_ERR_UNSUPPORTED (width > 4).  No workspace.
  * dctn_last_kernel(): batch_{draw,gather}_{u8,rows}_{f32,f64,bf16}.
  * ------------------------------------------------------------------------------------------ */
 enum { DCTN_BATCH_SRC_U8_TABLE = 0, DCTN_BATCH_SRC_ROWS = 1 };
 enum { DCTN_BATCH_IDENTITY_ORDER = 1 };   /* `flags` of dctn_batch_draw */
+/* `flags` of dctn_batch_draw, version 504: with DCTN_BATCH_IDENTITY_ORDER only.  A macro beside the enum, not a member of
+ * it: tests/test_host_batches.py takes every `DCTN_BATCH_x = n` of this header for the complete list of the version 503
+ * constants; tests/test_host_eval_pass.py reads this line and holds dctn_amd/_lib.py to it. */
+#define DCTN_BATCH_PAD_TAIL 2
 size_t dctn_batch_state_bytes(void);
 int dctn_batch_draw(const void* src, const void* table, const void* labels, void* x, void* y, void* indices, void* state,
                     int64_t n, int64_t global_batch, int64_t local_batch, int64_t rank_offset, int64_t row_len, int width,
