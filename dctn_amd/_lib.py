@@ -74,6 +74,17 @@ SIGNATURES = {
                                   ctypes.c_float, ctypes.c_float, c_int, c_void]),
     "dctn_adam_l2_step_master": (c_int, [c_void] * 7 + [c_i64, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_float,
                                          ctypes.c_float, ctypes.c_float, c_void]),
+    "dctn_grad_guard_state_bytes": (c_size, []),
+    "dctn_grad_guard_num_partials": (c_int, [c_i64]),
+    "dctn_grad_guard_check": (c_int, [c_void, c_i64, c_int, c_void, c_void, c_void, c_void]),
+    "dctn_adam_l2_step_guarded": (c_int, [c_void] * 7 + [c_i64, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_float,
+                                          ctypes.c_float, ctypes.c_float, c_int, c_void]),
+    "dctn_adam_l2_step_master_guarded": (c_int, [c_void] * 8 + [c_i64, c_i64, ctypes.c_double, ctypes.c_double,
+                                                 ctypes.c_float, ctypes.c_float, ctypes.c_float, c_void]),
+    "dctn_sgd_l2_step_guarded": (c_int, [c_void] * 5 + [c_i64, c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                         c_int, c_int, c_void]),
+    "dctn_sgd_l2_step_master_guarded": (c_int, [c_void] * 6 + [c_i64, c_i64, ctypes.c_float, ctypes.c_float,
+                                                ctypes.c_float, c_int, c_void]),
     "dctn_ce_score_accumulate": (c_int, [c_void, c_void, c_void, c_i64, c_int, c_int, c_void]),
     "dctn_core_dropout_state_bytes": (c_size, []),
     "dctn_core_dropout_fwd": (c_int, [_PtrP, _PtrP, _I64P, c_int, c_void, c_void, c_void, c_int, c_void]),

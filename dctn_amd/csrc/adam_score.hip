@@ -7,6 +7,7 @@
 //                the bf16 cell only receives the rounded result and is never read.
 //   ce_score_k : adds one batch's {sum of cross-entropies, correct rows, rows} to three float64 values
 #include "common.h"
+#include "grad_guard.h"
 
 #include <cmath>
 
@@ -69,13 +70,35 @@ __device__ __forceinline__ void store4(bf16_t* p, const float (&x)[4]) {
 // Workgroups of 1024 threads, at most 256 of them: the ticket at the end is one atomic per workgroup on ONE address,
 // and those serialise at about 12 ns each (measured: 1024 workgroups of 256 threads took 17.7 us over 1.9 M
 // parameters where the same stream without a ticket, sgd_l2_k, takes 5.7 us).
-template <typename S, bool VEC, bool MASTER>
+__device__ __forceinline__ const GradGuardBlock* guard_of(const GradGuardBlock* g) { return g; }
+// the guarded step's gradient: one rounded float32 product, never contracted into the FMA that follows
+template <bool GUARD> __device__ __forceinline__ float clipped(float g, float coef) {
+  if constexpr (GUARD) return __fmul_rn(g, coef); else return g;
+}
+
+// GUARD: the step obeys a gradient guard's decision (grad_guard.hip, launched in front of this kernel).  Lane 0 of every
+// workgroup reads `halted` and `coef` from the guard block before anything else.  Halted: the workgroup returns at once
+// - it writes no parameter, master value, moment or sq_sum slot and draws no ticket, so steps_done does not advance.
+// Otherwise every gradient is replaced by ONE rounded float32 product g * coef (a bf16 gradient is widened first and
+// not rounded back) in front of adam_elem: the clip applies to the gradient as it stands in the buffer, and weight
+// decay and the 2 * l2 * w term come after it.  coef == 1 leaves g's bits, so an unclipped guarded step is the
+// unguarded one.  The guard block is a trailing parameter PACK, empty in the unguarded instantiations, and everything
+// else of it is behind `if constexpr`: those compile to what they did.
+template <typename S, bool VEC, bool MASTER, typename... G>
 __global__ __launch_bounds__(1024) void adam_l2_k(S* __restrict__ w, float* __restrict__ wm, const S* __restrict__ g,
                                                  float* __restrict__ ea, float* __restrict__ eas,
                                                  float* __restrict__ sq_sum, AdamState* __restrict__ state, long long n,
-                                                 long long n_reg, AdamCoef k) {
+                                                 long long n_reg, AdamCoef k, G... guard_block) {
+  constexpr bool GUARD = sizeof...(G) == 1;   // G = {const GradGuardBlock*}; empty: the unguarded kernel, parameter for parameter
   __shared__ float red[16];
-  __shared__ float scale[2];
+  __shared__ float scale[GUARD ? 4 : 2];
+  if constexpr (GUARD) {
+    if (threadIdx.x == 0) {
+      const GradGuardBlock* guard = guard_of(guard_block...);
+      scale[2] = __hip_atomic_load(&guard->halted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ? 1.f : 0.f;
+      scale[3] = __hip_atomic_load(&guard->coef, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
   // lane 0 of every workgroup reads the step count and the learning rate BEFORE it takes the workgroup's ticket below;
   // the one write of the launch to steps_done happens after the last ticket is drawn, so no workgroup can see the new
   // value
@@ -91,6 +114,11 @@ __global__ __launch_bounds__(1024) void adam_l2_k(S* __restrict__ w, float* __re
   }
   __syncthreads();
   const float step = scale[0], bc2_sqrt = scale[1];
+  float coef = 1.f;
+  if constexpr (GUARD) {
+    if (scale[2] != 0.f) return;   // the whole workgroup, before any store and before the ticket
+    coef = scale[3];
+  }
   float part = 0.f;
   const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, nthr = (long long)gridDim.x * blockDim.x;
   const long long n_vec = VEC ? (n & ~3LL) : 0;
@@ -100,6 +128,8 @@ __global__ __launch_bounds__(1024) void adam_l2_k(S* __restrict__ w, float* __re
       if (MASTER) load4(wm + i, wi); else load4(w + i, wi);
       load4(g + i, gi), load4(ea + i, mi), load4(eas + i, vi);
 #pragma unroll
+      for (int e = 0; e < 4; ++e) gi[e] = clipped<GUARD>(gi[e], coef);
+#pragma unroll
       for (int e = 0; e < 4; ++e) wi[e] = adam_elem(wi[e], gi[e], mi[e], vi[e], i + e < n_reg, k, step, bc2_sqrt, part);
       store4(ea + i, mi), store4(eas + i, vi), store4(w + i, wi);
       if (MASTER) store4(wm + i, wi);
@@ -107,7 +137,8 @@ __global__ __launch_bounds__(1024) void adam_l2_k(S* __restrict__ w, float* __re
   }
   for (long long i = n_vec + tid; i < n; i += nthr) {
     float m = ea[i], v = eas[i];
-    const float wi = adam_elem(MASTER ? wm[i] : (float)w[i], (float)g[i], m, v, i < n_reg, k, step, bc2_sqrt, part);
+    const float wi = adam_elem(MASTER ? wm[i] : (float)w[i], clipped<GUARD>((float)g[i], coef), m, v, i < n_reg, k, step,
+                               bc2_sqrt, part);
     w[i] = (S)wi;
     if (MASTER) wm[i] = wi;
     ea[i] = m, eas[i] = v;
@@ -210,10 +241,11 @@ int dctn_adam_l2_num_partials(int64_t n) { return n < 1 ? 0 : (int)adam_blocks_f
 
 // master == nullptr: the parameters are updated in their own dtype; otherwise they are bf16, written only, and the step
 // runs on the float32 `master`
+// guarded: the step obeys the guard block `guard` (dctn_grad_guard_check ran in front of it on the same stream)
 static int adam_launch(void* master, void* params, const void* grads, void* exp_avg, void* exp_avg_sq, void* sq_sum,
                        void* state, int64_t n, int64_t n_reg, double beta1, double beta2, float eps, float weight_decay,
-                       float l2, int dtype, void* stream) {
-  if (!params || !grads || !exp_avg || !exp_avg_sq || !state) return DCTN_ERR_NULL;
+                       float l2, int dtype, void* stream, bool guarded = false, const void* guard = nullptr) {
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !state || (guarded && !guard)) return DCTN_ERR_NULL;
   if (n < 1 || n_reg < 0 || n_reg > n) return DCTN_ERR_BAD_SHAPE;
   if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return DCTN_ERR_BAD_SHAPE;   // torch raises ValueError
   if (dtype != DCTN_F32 && dtype != DCTN_BF16) return DCTN_ERR_BAD_DTYPE;
@@ -230,7 +262,19 @@ static int adam_launch(void* master, void* params, const void* grads, void* exp_
 #define DCTN_ADAM_LAUNCH(S, VEC, MASTER)                                                                            \
   hipLaunchKernelGGL((adam_l2_k<S, VEC, MASTER>), g, b, 0, st, (S*)params, (float*)master, (const S*)grads,        \
                      (float*)exp_avg, (float*)exp_avg_sq, (float*)sq_sum, sp, (long long)n, (long long)n_reg, k)
-  if (master) {
+#define DCTN_ADAM_LAUNCH_GUARDED(S, VEC, MASTER)                                                                    \
+  hipLaunchKernelGGL((adam_l2_k<S, VEC, MASTER, const GradGuardBlock*>), g, b, 0, st, (S*)params, (float*)master,   \
+                     (const S*)grads, (float*)exp_avg, (float*)exp_avg_sq, (float*)sq_sum, sp, (long long)n,        \
+                     (long long)n_reg, k, (const GradGuardBlock*)guard)
+  if (guarded) {
+    if (master) {
+      if (vec) DCTN_ADAM_LAUNCH_GUARDED(bf16_t, true, true); else DCTN_ADAM_LAUNCH_GUARDED(bf16_t, false, true);
+    } else if (dtype == DCTN_F32) {
+      if (vec) DCTN_ADAM_LAUNCH_GUARDED(float, true, false); else DCTN_ADAM_LAUNCH_GUARDED(float, false, false);
+    } else {
+      if (vec) DCTN_ADAM_LAUNCH_GUARDED(bf16_t, true, false); else DCTN_ADAM_LAUNCH_GUARDED(bf16_t, false, false);
+    }
+  } else if (master) {
     if (vec) DCTN_ADAM_LAUNCH(bf16_t, true, true); else DCTN_ADAM_LAUNCH(bf16_t, false, true);
   } else if (dtype == DCTN_F32) {
     if (vec) DCTN_ADAM_LAUNCH(float, true, false); else DCTN_ADAM_LAUNCH(float, false, false);
@@ -238,6 +282,7 @@ static int adam_launch(void* master, void* params, const void* grads, void* exp_
     if (vec) DCTN_ADAM_LAUNCH(bf16_t, true, false); else DCTN_ADAM_LAUNCH(bf16_t, false, false);
   }
 #undef DCTN_ADAM_LAUNCH
+#undef DCTN_ADAM_LAUNCH_GUARDED
   DCTN_CHECK_LAUNCH();
   return DCTN_OK;
 }
@@ -255,6 +300,21 @@ int dctn_adam_l2_step_master(void* master, void* params, const void* grads, void
   if (!master) return DCTN_ERR_NULL;
   return adam_launch(master, params, grads, exp_avg, exp_avg_sq, sq_sum, state, n, n_reg, beta1, beta2, eps,
                      weight_decay, l2, DCTN_BF16, stream);
+}
+
+int dctn_adam_l2_step_guarded(void* params, const void* grads, void* exp_avg, void* exp_avg_sq, void* sq_sum, void* state,
+                              const void* guard, int64_t n, int64_t n_reg, double beta1, double beta2, float eps,
+                              float weight_decay, float l2, int dtype, void* stream) {
+  return adam_launch(nullptr, params, grads, exp_avg, exp_avg_sq, sq_sum, state, n, n_reg, beta1, beta2, eps,
+                     weight_decay, l2, dtype, stream, true, guard);
+}
+
+int dctn_adam_l2_step_master_guarded(void* master, void* params, const void* grads, void* exp_avg, void* exp_avg_sq,
+                                     void* sq_sum, void* state, const void* guard, int64_t n, int64_t n_reg,
+                                     double beta1, double beta2, float eps, float weight_decay, float l2, void* stream) {
+  if (!master) return DCTN_ERR_NULL;
+  return adam_launch(master, params, grads, exp_avg, exp_avg_sq, sq_sum, state, n, n_reg, beta1, beta2, eps,
+                     weight_decay, l2, DCTN_BF16, stream, true, guard);
 }
 
 int dctn_ce_score_accumulate(const void* logits, const void* labels, void* acc, int64_t B, int C, int dtype,

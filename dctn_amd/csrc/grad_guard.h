@@ -1,0 +1,15 @@
+// The gradient guard's device block (include/dctn_amd.h documents this layout: it is part of the ABI).  grad_guard.hip
+// writes it; the guarded forms of adam_l2_k (adam_score.hip) and sgd_l2_k (train_tail.hip) read `halted` and `coef`.
+#pragma once
+
+struct GradGuardBlock {
+  float max_norm;     // clip threshold, +inf = never clip; the host writes it
+  float last_norm;    // norm seen by the last launch (may be inf / NaN)
+  unsigned halted;    // latch: 1 once a non-finite launch was seen; only the host clears it
+  int bad_step;       // `seen` at the launch that set the latch, -1 before
+  unsigned seen;      // launches so far
+  unsigned clipped;   // launches whose coefficient was below 1
+  unsigned ticket;    // 0 between launches
+  float coef;         // decision for the step that follows: the gradient multiplier (0 when the step is not applied)
+};
+static_assert(sizeof(GradGuardBlock) == 32, "the guard block is 32 bytes (include/dctn_amd.h)");

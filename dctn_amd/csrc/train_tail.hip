@@ -13,6 +13,7 @@
 //                into the parameter's cell).  MASTER form (bf16 parameters): the step runs on a float32 master
 //                copy, which is read and written; the bf16 cell only receives the rounded result
 #include "common.h"
+#include "grad_guard.h"
 
 namespace {
 
@@ -112,16 +113,42 @@ __device__ __forceinline__ float sgd_elem(float wi, float gi, float* __restrict_
 
 // MASTER (S = bf16_t): the weight comes from and goes back to the float32 array `wm`; `w` gets its bf16 rounding and is
 // not read, and `wm` and the sq_sum slots are the float instantiation's bits.  Without MASTER `wm` is unused (null).
-template <typename S, bool MASTER>
+__device__ __forceinline__ const GradGuardBlock* guard_of(const GradGuardBlock* g) { return g; }
+// the guarded step's gradient: one rounded float32 product, never contracted into the FMA that follows
+template <bool GUARD> __device__ __forceinline__ float clipped(float g, float coef) {
+  if constexpr (GUARD) return __fmul_rn(g, coef); else return g;
+}
+
+// GUARD: the step obeys a gradient guard's decision (grad_guard.hip, launched in front of this kernel), as
+// adam_l2_k's guarded form does: lane 0 of every workgroup reads `halted` and `coef` before anything else; halted, the
+// workgroup returns at once and writes no parameter, master value, momentum or sq_sum slot; otherwise every gradient is
+// replaced by ONE rounded float32 product g * coef in front of sgd_elem (the 2 * l2 * w term comes after the clip).
+// The guard block is a trailing parameter PACK, empty in the unguarded instantiations, and the rest is behind
+// `if constexpr`: those compile to what they did.
+template <typename S, bool MASTER, typename... G>
 __global__ __launch_bounds__(256) void sgd_l2_k(S* __restrict__ w, float* __restrict__ wm, const S* __restrict__ g,
                                                 float* __restrict__ buf, float* __restrict__ sq_sum, long long n,
-                                                long long n_reg, float lr, float momentum, float l2, int first_step) {
+                                                long long n_reg, float lr, float momentum, float l2, int first_step,
+                                                G... guard_block) {
+  constexpr bool GUARD = sizeof...(G) == 1;   // G = {const GradGuardBlock*}; empty: the unguarded kernel, parameter for parameter
   __shared__ float red[4];
+  float coef = 1.f;
+  if constexpr (GUARD) {
+    __shared__ float decision[2];
+    if (threadIdx.x == 0) {
+      const GradGuardBlock* guard = guard_of(guard_block...);
+      decision[0] = __hip_atomic_load(&guard->halted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ? 1.f : 0.f;
+      decision[1] = __hip_atomic_load(&guard->coef, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (decision[0] != 0.f) return;   // the whole workgroup, before any store
+    coef = decision[1];
+  }
   float part = 0.f;
   const float two_l2 = 2.f * l2;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const float wi = sgd_elem(MASTER ? wm[i] : (float)w[i], (float)g[i], buf + i, i < n_reg, lr, momentum, two_l2,
-                              first_step, part);
+    const float wi = sgd_elem(MASTER ? wm[i] : (float)w[i], clipped<GUARD>((float)g[i], coef), buf + i, i < n_reg, lr,
+                              momentum, two_l2, first_step, part);
     w[i] = (S)wi;
     if (MASTER) wm[i] = wi;
   }
@@ -194,14 +221,23 @@ int dctn_ce_loss_bwd(const void* logits, const void* labels, const void* dloss, 
 int dctn_sgd_l2_num_partials(int64_t n) { return n < 1 ? 0 : (int)blocks_for(n); }
 
 // master == nullptr: the parameters are updated in their own dtype; otherwise they are bf16, written only
+// guarded: the step obeys the guard block `guard` (dctn_grad_guard_check ran in front of it on the same stream)
 static int sgd_launch(void* master, void* params, const void* grads, void* momentum_buf, void* sq_sum, int64_t n,
-                      int64_t n_reg, float lr, float momentum, float l2, int first_step, int dtype, void* stream) {
-  if (!params || !grads || !momentum_buf) return DCTN_ERR_NULL;
+                      int64_t n_reg, float lr, float momentum, float l2, int first_step, int dtype, void* stream,
+                      bool guarded = false, const void* guard = nullptr) {
+  if (!params || !grads || !momentum_buf || (guarded && !guard)) return DCTN_ERR_NULL;
   if (n < 1 || n_reg < 0 || n_reg > n) return DCTN_ERR_BAD_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   if (dtype != DCTN_F32 && dtype != DCTN_BF16) return DCTN_ERR_BAD_DTYPE;
   const dim3 g(blocks_for(n)), b(256);
-  if (master)
+  const GradGuardBlock* gp = (const GradGuardBlock*)guard;
+  if (guarded && master)
+    hipLaunchKernelGGL((sgd_l2_k<bf16_t, true, const GradGuardBlock*>), g, b, 0, st, (bf16_t*)params, (float*)master, (const bf16_t*)grads, (float*)momentum_buf, (float*)sq_sum, (long long)n, (long long)n_reg, lr, momentum, l2, first_step, gp);
+  else if (guarded && dtype == DCTN_F32)
+    hipLaunchKernelGGL((sgd_l2_k<float, false, const GradGuardBlock*>), g, b, 0, st, (float*)params, (float*)nullptr, (const float*)grads, (float*)momentum_buf, (float*)sq_sum, (long long)n, (long long)n_reg, lr, momentum, l2, first_step, gp);
+  else if (guarded)
+    hipLaunchKernelGGL((sgd_l2_k<bf16_t, false, const GradGuardBlock*>), g, b, 0, st, (bf16_t*)params, (float*)nullptr, (const bf16_t*)grads, (float*)momentum_buf, (float*)sq_sum, (long long)n, (long long)n_reg, lr, momentum, l2, first_step, gp);
+  else if (master)
     hipLaunchKernelGGL((sgd_l2_k<bf16_t, true>), g, b, 0, st, (bf16_t*)params, (float*)master, (const bf16_t*)grads, (float*)momentum_buf, (float*)sq_sum, (long long)n, (long long)n_reg, lr, momentum, l2, first_step);
   else if (dtype == DCTN_F32)
     hipLaunchKernelGGL((sgd_l2_k<float, false>), g, b, 0, st, (float*)params, (float*)nullptr, (const float*)grads, (float*)momentum_buf, (float*)sq_sum, (long long)n, (long long)n_reg, lr, momentum, l2, first_step);
@@ -220,6 +256,21 @@ int dctn_sgd_l2_step_master(void* master, void* params, const void* grads, void*
                             int64_t n, int64_t n_reg, float lr, float momentum, float l2, int first_step, void* stream) {
   if (!master) return DCTN_ERR_NULL;
   return sgd_launch(master, params, grads, momentum_buf, sq_sum, n, n_reg, lr, momentum, l2, first_step, DCTN_BF16, stream);
+}
+
+int dctn_sgd_l2_step_guarded(void* params, const void* grads, void* momentum_buf, void* sq_sum, const void* guard,
+                             int64_t n, int64_t n_reg, float lr, float momentum, float l2, int first_step, int dtype,
+                             void* stream) {
+  return sgd_launch(nullptr, params, grads, momentum_buf, sq_sum, n, n_reg, lr, momentum, l2, first_step, dtype, stream,
+                    true, guard);
+}
+
+int dctn_sgd_l2_step_master_guarded(void* master, void* params, const void* grads, void* momentum_buf, void* sq_sum,
+                                    const void* guard, int64_t n, int64_t n_reg, float lr, float momentum, float l2,
+                                    int first_step, void* stream) {
+  if (!master) return DCTN_ERR_NULL;
+  return sgd_launch(master, params, grads, momentum_buf, sq_sum, n, n_reg, lr, momentum, l2, first_step, DCTN_BF16,
+                    stream, true, guard);
 }
 
 }  // extern "C"

@@ -83,6 +83,15 @@ class GraphedTrainStep:
     shapes), and the returned dictionary gains ``"indices"``, the sample numbers of the batch (a static buffer like the
     others).  The warm-up iterations consume real draws and are real training steps, as they already are on the example
     batch: after construction the source stands at batch ``warmup``.
+
+    A gradient guard needs no argument here: the step captures whatever ``optimizer.step()`` launches, so with
+    ``FlatAdam(..., guard=GradGuard(dev, max_norm))`` the check and the guarded step kernel are two nodes of the one
+    graph, or of the optimizer's graph ``g_opt`` in the split form, where the check then sees the all-reduced
+    gradients.  The host still reads nothing between replays.  Once the guard has halted, replays go on running
+    forward and backward but the optimizer writes nothing; with a ``batch_source`` the source and the dropout
+    counter go on advancing meanwhile.  The guard counts its checks from the first warm-up iteration, as the source
+    counts its draws, so (both fresh at construction) ``batch_source.expected_indices(guard.read()["bad_step"])`` names
+    the batch that set the latch.  ``guard.max_norm`` may be assigned and ``guard.reset()`` called between replays.
     """
 
     def __init__(self, model: torch.nn.Module, example_x: Optional[Tensor], example_y: Optional[Tensor],
@@ -254,6 +263,121 @@ def fused_cross_entropy(logits: Tensor, labels: Tensor) -> Tensor:
 fused_cross_entropy.accepts_low_precision = True   # train_step / GraphedTrainStep skip their float32 cast
 
 
+class GradGuard:
+    """The device-side gradient guard: a non-finite halt and global norm clipping that a captured iteration carries
+    with it (`dctn_grad_guard_check`, include/dctn_amd.h).  Pass one to ``FlatAdam(..., guard=g)`` or
+    ``FlatSGD(..., guard=g)``: ``step()`` then launches the check in front of the guarded step kernel.
+
+    The check forms the squared norm of the flat gradient buffer in float64 and leaves a decision in a 32-byte DEVICE
+    block {max_norm, last_norm, halted, bad_step, seen, clipped, ticket, coef} that the step kernel obeys:
+
+    - a non-finite value anywhere in the gradients (or in the optional loss scalar) sets the latch ``halted`` and
+      records ``bad_step`` = the number of checks that ran before this one; the step is NOT applied, and neither is any
+      later one until ``reset()`` - parameters, moments, master copy and step count stay as the last good step left
+      them.  This is the reference's stop-on-NaN-loss hook without a host read per iteration;
+    - otherwise the gradients are multiplied by ``coef = min(1, max_norm / (norm + 1e-6))``,
+      ``torch.nn.utils.clip_grad_norm_``'s coefficient, as one rounded float32 product per element.  The clip applies to
+      the gradient as it stands in the buffer (after the all-reduce; a regulariser that went through ``reg_fn`` and
+      autograd is in the buffer and is clipped with it); ``weight_decay * w`` and the kernel's fused ``2 * l2 * w`` come
+      after it - ``clip_grad_norm_`` followed by ``Adam(weight_decay=...)``.  ``max_norm=None`` (+inf) never clips, and
+      a step whose ``coef`` is 1 is, bit for bit, the unguarded step.
+
+    ``max_norm`` may be assigned at any time outside a capture (a tiny asynchronous device write, as ``FlatAdam.lr``):
+    replays of an already captured graph follow it.  ``read()`` returns the block as a dictionary and synchronises;
+    nothing else here does.  ``state_dict()`` / ``load_state_dict()`` carry the block.
+    """
+
+    FIELDS = ("max_norm", "last_norm", "halted", "bad_step", "seen", "clipped", "ticket", "coef")
+    _FLOATS = (0, 1, 7)
+
+    def __init__(self, device, max_norm: Optional[float] = None):
+        self.device = torch.device(device)
+        lib = L.lib()
+        assert lib.dctn_grad_guard_state_bytes() == 32
+        self._block = torch.zeros(8, dtype=torch.int32, device=self.device)
+        # one float64 slot per workgroup of the check; the grid never exceeds what the largest n asks for
+        self._partials = torch.empty(lib.dctn_grad_guard_num_partials(1 << 62), dtype=torch.float64, device=self.device)
+        self._cells = self._block.view(torch.float32)
+        self._max_norm = float("nan")
+        self._write(dict(max_norm=float("inf") if max_norm is None else float(max_norm), last_norm=0.0, halted=0,
+                         bad_step=-1, seen=0, clipped=0, ticket=0, coef=0.0))
+
+    def _write(self, values: Dict[str, Any]) -> None:
+        host = torch.zeros(8, dtype=torch.int32)
+        for i, name in enumerate(self.FIELDS):
+            if i in self._FLOATS:
+                host.view(torch.float32)[i] = float(values[name])
+            else:
+                host[i] = int(values[name])
+        self._max_norm = float(values["max_norm"])
+        with torch.no_grad():
+            self._block.copy_(host)
+
+    @property
+    def max_norm(self) -> float:
+        return self._max_norm
+
+    @max_norm.setter
+    def max_norm(self, value: Optional[float]) -> None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("GradGuard.max_norm cannot be assigned during a graph capture: the captured check reads "
+                               "the threshold from the device, assign it between replays")
+        self._max_norm = float("inf") if value is None else float(value)
+        with torch.cuda.device(self.device):
+            self._cells[0:1].fill_(self._max_norm)
+
+    def check(self, grads: Tensor, loss: Optional[Tensor] = None) -> None:
+        """Launches the check over the flat gradient buffer ``grads`` (and the float32 device scalar ``loss``)."""
+        if loss is not None and (loss.dtype != torch.float32 or loss.numel() != 1 or loss.device != grads.device):
+            raise TypeError("GradGuard: the loss must be a float32 scalar on the gradients' device")
+        L.check(L.lib().dctn_grad_guard_check(grads.data_ptr(), grads.numel(), L.dtype_code(grads),
+                                              None if loss is None else loss.data_ptr(), self._partials.data_ptr(),
+                                              self._block.data_ptr(), L.stream_ptr(grads.device)), "gradient guard")
+
+    def read(self) -> Dict[str, Any]:
+        """The block as a dictionary (synchronises)."""
+        host = self._block.cpu()
+        floats = host.view(torch.float32)
+        return {name: (float(floats[i]) if i in self._FLOATS else int(host[i])) for i, name in enumerate(self.FIELDS)}
+
+    @property
+    def halted(self) -> bool:
+        """Whether the latch is set (read from the device: synchronises)."""
+        return bool(self._block[2].item())
+
+    def reset(self, counters: bool = False) -> None:
+        """Clears the latch and ``bad_step`` (asynchronous; not during a capture): the next step is applied again.
+        ``counters=True`` also zeroes ``seen`` and ``clipped``, so that ``bad_step`` counts from here."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("GradGuard.reset() during a graph capture would become a node of that graph")
+        with torch.no_grad():
+            self._block[2:3].zero_()
+            self._block[3:4].fill_(-1)
+            if counters:
+                self._block[4:6].zero_()
+
+    def state_dict(self) -> Dict[str, Any]:
+        return self.read()
+
+    def load_state_dict(self, state: Dict[str, Any]) -> None:
+        self._write({**state, "ticket": 0})
+
+    @staticmethod
+    def decide(total_sq: float, max_norm: float, halted_before: bool = False, loss: Optional[float] = None):
+        """The kernel's decision on the host, in the kernel's number formats: ``(apply, coef, norm)`` for a float64 sum
+        of squares ``total_sq``, a float32 threshold and an optional loss value."""
+        import math
+
+        total = torch.tensor(float(total_sq), dtype=torch.float64)
+        norm = total.sqrt().to(torch.float32)
+        finite = math.isfinite(float(total_sq)) and (loss is None or math.isfinite(float(loss)))
+        if halted_before or not finite:
+            return False, 0.0, float(norm)
+        threshold = torch.tensor(float(max_norm), dtype=torch.float32).double()
+        coef = (threshold / (norm.double() + 1e-6)).to(torch.float32)
+        return True, min(1.0, float(coef)), float(norm)
+
+
 class _FlatOptimizer:
     """What FlatSGD and FlatAdam share: the parameters moved into ONE flat buffer (their ``.data`` become views of it,
     in the order regularised + others), the gradients read in place when they already sit back to back in that
@@ -264,7 +388,12 @@ class _FlatOptimizer:
     by exact widening) that the step kernel updates; the bfloat16 parameters then only receive its rounding.  With
     float32 parameters the option changes nothing and ``master`` is None."""
 
-    def __init__(self, regularised, others, num_partials: Callable[[int], int], master_weights: bool = False):
+    def __init__(self, regularised, others, num_partials: Callable[[int], int], master_weights: bool = False,
+                 guard: Optional["GradGuard"] = None, guard_loss=None):
+        # guard: a GradGuard whose check runs in front of every step; guard_loss: the float32 device scalar the check
+        # looks at beside the gradients, or a callable that returns it (the loss tensor of a training loop is a new one
+        # every iteration)
+        self.guard, self.guard_loss = guard, guard_loss
         self.reg_params = [p for p in regularised]
         self.params = self.reg_params + [p for p in others]
         assert self.params and len({p.dtype for p in self.params}) == 1 and len({p.device for p in self.params}) == 1
@@ -331,6 +460,12 @@ class _FlatOptimizer:
                   out=self.flat_grad)
         return self.flat_grad
 
+    def _run_guard(self, g: Tensor) -> int:
+        """Launches the guard's check over the gradients; returns the block's address for the guarded step."""
+        loss = self.guard_loss() if callable(self.guard_loss) else self.guard_loss
+        self.guard.check(g, loss)
+        return self.guard._block.data_ptr()
+
     def reg_value(self) -> Tensor:
         """l2 * sum of squared Frobenius norms of the regularised parameters, as of the last step."""
         return self.sq_sum.sum() * self.l2
@@ -354,11 +489,15 @@ class FlatSGD(_FlatOptimizer):
     (`dctn_sgd_l2_step_master`); an update below half an ulp of the bfloat16 value is then kept instead of rounded
     away.  ``state_dict()`` / ``load_state_dict()`` carry the momentum buffer, the step count, the hyper-parameters
     and the master copy.
+
+    ``guard`` (a `GradGuard`) / ``guard_loss``: ``step()`` launches the guard's check and then the guarded kernel
+    (`dctn_sgd_l2_step_guarded`): gradients clipped to ``guard.max_norm`` in front of the ``2 * l2 * w`` term, and no
+    write at all once the guard has halted.  Without a guard ``step()`` makes the calls it always made.
     """
 
     def __init__(self, regularised, others=(), lr: float = 1e-3, momentum: float = 0.0, l2: float = 0.0,
-                 master_weights: bool = False):
-        super().__init__(regularised, others, L.lib().dctn_sgd_l2_num_partials, master_weights)
+                 master_weights: bool = False, guard: Optional["GradGuard"] = None, guard_loss=None):
+        super().__init__(regularised, others, L.lib().dctn_sgd_l2_num_partials, master_weights, guard, guard_loss)
         self.lr, self.momentum, self.l2 = float(lr), float(momentum), float(l2)
         self.buf = torch.zeros(self.n, dtype=torch.float32, device=self.flat.device)
         self._steps = 0
@@ -368,6 +507,24 @@ class FlatSGD(_FlatOptimizer):
         g = self._grads()
         dev = self.flat.device
         first = 1 if self._steps == 0 else 0
+        if self.guard is not None:
+            # `first` is the host's count of launches, and the host does not know whether the guard let a launch
+            # through.  A skipped step 0 leaves the momentum buffer at its zeros, and the next launch, with first = 0,
+            # forms momentum * 0 + g = g: the update a first step makes.
+            block = self._run_guard(g)
+            if self.master is not None:
+                L.check(L.lib().dctn_sgd_l2_step_master_guarded(self.master.data_ptr(), self.flat.data_ptr(),
+                                                                g.data_ptr(), self.buf.data_ptr(), self.sq_sum.data_ptr(),
+                                                                block, self.n, self.n_reg, self.lr, self.momentum,
+                                                                self.l2, first, L.stream_ptr(dev)),
+                        "guarded fused SGD step (master weights)")
+            else:
+                L.check(L.lib().dctn_sgd_l2_step_guarded(self.flat.data_ptr(), g.data_ptr(), self.buf.data_ptr(),
+                                                         self.sq_sum.data_ptr(), block, self.n, self.n_reg, self.lr,
+                                                         self.momentum, self.l2, first, L.dtype_code(self.flat),
+                                                         L.stream_ptr(dev)), "guarded fused SGD step")
+            self._steps += 1
+            return
         if self.master is not None:
             L.check(L.lib().dctn_sgd_l2_step_master(self.master.data_ptr(), self.flat.data_ptr(), g.data_ptr(),
                                                     self.buf.data_ptr(), self.sq_sum.data_ptr(), self.n, self.n_reg,
@@ -414,11 +571,21 @@ class FlatAdam(_FlatOptimizer):
     bfloat16 weight whose Adam step (about ``lr``) is below half an ulp of its value does not move at all.  The
     master follows, bit for bit, what FlatAdam does on float32 parameters given the same gradients.  Call
     ``refresh_master()`` after writing the parameters from outside.
+
+    ``guard`` (a `GradGuard`) / ``guard_loss`` (a float32 device scalar, or a callable returning one): ``step()``
+    launches the guard's check over the gradients and then the guarded kernel (`dctn_adam_l2_step_guarded`, two
+    launches instead of one).  The gradients are clipped to ``guard.max_norm`` as they stand in the buffer - after the
+    all-reduce, in front of ``weight_decay * w`` and the fused ``2 * l2 * w``: ``clip_grad_norm_`` followed by
+    ``Adam(weight_decay=...)``; a regulariser passed through ``reg_fn`` is in the buffer and is clipped with it.  Once
+    the guard has halted, a step writes nothing: parameters, ``m``, ``v``, ``master`` and ``t`` stay as they are.  The
+    guard's state is not part of this optimizer's ``state_dict()``; save ``guard.state_dict()`` beside it.  Without a
+    guard ``step()`` makes the calls it always made.
     """
 
     def __init__(self, regularised, others=(), lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0, l2: float = 0.0, master_weights: bool = False):
-        super().__init__(regularised, others, L.lib().dctn_adam_l2_num_partials, master_weights)
+                 weight_decay: float = 0.0, l2: float = 0.0, master_weights: bool = False,
+                 guard: Optional["GradGuard"] = None, guard_loss=None):
+        super().__init__(regularised, others, L.lib().dctn_adam_l2_num_partials, master_weights, guard, guard_loss)
         if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0 and lr >= 0.0 and eps >= 0.0 and weight_decay >= 0.0):
             raise ValueError(f"invalid Adam hyper-parameters: lr={lr} betas={betas} eps={eps} weight_decay={weight_decay}")
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
@@ -455,6 +622,24 @@ class FlatAdam(_FlatOptimizer):
     def step(self) -> None:
         g = self._grads()
         dev = self.flat.device
+        if self.guard is not None:
+            block = self._run_guard(g)
+            if self.master is not None:
+                L.check(L.lib().dctn_adam_l2_step_master_guarded(self.master.data_ptr(), self.flat.data_ptr(),
+                                                                 g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                                                                 self.sq_sum.data_ptr(), self._state.data_ptr(), block,
+                                                                 self.n, self.n_reg, self.betas[0], self.betas[1],
+                                                                 self.eps, self.weight_decay, self.l2,
+                                                                 L.stream_ptr(dev)),
+                        "guarded fused Adam step (master weights)")
+            else:
+                L.check(L.lib().dctn_adam_l2_step_guarded(self.flat.data_ptr(), g.data_ptr(), self.m.data_ptr(),
+                                                          self.v.data_ptr(), self.sq_sum.data_ptr(),
+                                                          self._state.data_ptr(), block, self.n, self.n_reg,
+                                                          self.betas[0], self.betas[1], self.eps, self.weight_decay,
+                                                          self.l2, L.dtype_code(self.flat), L.stream_ptr(dev)),
+                        "guarded fused Adam step")
+            return
         if self.master is not None:
             L.check(L.lib().dctn_adam_l2_step_master(self.master.data_ptr(), self.flat.data_ptr(), g.data_ptr(),
                                                      self.m.data_ptr(), self.v.data_ptr(), self.sq_sum.data_ptr(),
@@ -721,6 +906,59 @@ class _StopOnNonFiniteLoss:
 
 def make_stopper_on_nan_loss(dir: str, set_breakpoint: bool) -> Callable[[StX, StIt], None]:
     return _StopOnNonFiniteLoss(dir, set_breakpoint)
+
+
+class _StopOnDeviceHalt:
+    """Hook for the ``after_back`` list of a run whose optimizer carries a `GradGuard`: every ``every`` calls it reads
+    the guard's block (the only synchronisation it makes) and, when the latch is set, raises the stop flag and writes
+    the artefact `_StopOnNonFiniteLoss` writes - ``dir/nan_loss_stop`` (``nan_loss_stop_rank<r>`` with several ranks)
+    holding the model's state_dict and whatever of ``x``, ``y``, ``indices``, ``output`` the iteration's dictionary
+    has - with ``bad_step`` and ``last_norm`` in the model file's name and the whole block in ``guard.pth``.  The
+    parameters it saves are those of the last good step: the guard kept the optimizer from applying any later one.
+    The batch in ``st_it`` is the current one, up to ``every`` iterations after the one that set the latch;
+    ``bad_step`` names that one."""
+
+    DUMPED = _StopOnNonFiniteLoss.DUMPED
+
+    def __init__(self, dir: str, guard: "GradGuard", every: int):
+        assert every >= 1
+        self.dir, self.guard, self.every = dir, guard, int(every)
+        self._calls = 0
+
+    def _target(self) -> str:
+        leaf = "nan_loss_stop" if _world() == 1 else f"nan_loss_stop_rank{dist.get_rank()}"
+        return os.path.join(self.dir, leaf)
+
+    def __call__(self, st_x: StX, st_it: StIt) -> None:
+        self._calls += 1
+        if self._calls % self.every != 0:
+            return
+        state = self.guard.read()
+        if not state["halted"]:
+            return
+        log = getLogger(__name__)
+        log.warning(f"Stopping: the gradient guard halted at its check number {state['bad_step']} "
+                    f"(last gradient norm {state['last_norm']})")
+        st_it["stop"] = True
+        target = self._target()
+        if os.path.exists(target):
+            log.error(f"subdir={target!r} already exists")
+            return
+        os.mkdir(target)
+        tag = f"nitd={st_it['num_iters_done']}"
+        if "loss" in st_it and "reg_term" in st_it:
+            loss, reg_term = (float(torch.as_tensor(st_it[k]).detach()) for k in ("loss", "reg_term"))
+            tag += f"_loss={loss:.3f}_reg_term={reg_term:.3f}"
+        tag += f"_bad_step={state['bad_step']}_last_norm={state['last_norm']:.3e}"
+        torch.save(st_x["model"].state_dict(), os.path.join(target, f"model_{tag}.pth"))
+        torch.save(state, os.path.join(target, "guard.pth"))
+        for key in self.DUMPED:
+            if key in st_it:
+                torch.save(st_it[key], os.path.join(target, key + ".pth"))
+
+
+def make_stopper_on_device_halt(dir: str, guard: "GradGuard", every: int = 1) -> Callable[[StX, StIt], None]:
+    return _StopOnDeviceHalt(dir, guard, every)
 
 
 def log_parameters_stats(st_x: StX, st_it: StIt) -> None:

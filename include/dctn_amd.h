@@ -441,6 +441,57 @@ int dctn_adam_l2_step_master(void* master, void* params, const void* grads, void
                              float weight_decay, float l2, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Gradient guard (version 505; reference: the stop-on-NaN-loss hook every run installs, new_runner.py:544, and
+ * torch.nn.utils.clip_grad_norm_): ONE launch in front of the optimizer step forms the squared norm of the flat gradient
+ * buffer and leaves a decision on the DEVICE that the guarded step kernels obey - the host reads nothing per iteration,
+ * and a captured graph that holds the two launches halts and clips on its own.
+ *
+ * dctn_grad_guard_check : grads (n values, DCTN_F32 / DCTN_BF16) are summed as g*g in FLOAT64 (the square of a float32
+ *   value cannot overflow a double, so the sum is non-finite exactly when some element is); one partial sum per workgroup
+ *   is STORED into `partials` (dctn_grad_guard_num_partials of n float64 slots, OVERWRITTEN, nothing of their previous
+ *   content is used), and the workgroup that finishes last adds them in one fixed order: the same bits from run to run.
+ *   No workgroup waits for another.  loss_or_null: optional float32 device scalar; a non-finite loss counts like a
+ *   non-finite gradient.  `guard`: dctn_grad_guard_state_bytes = 32 bytes, 16-byte aligned, laid out as
+ *     float  max_norm    clip threshold; +inf = never clip.  The caller writes it, in stream order between launches
+ *     float  last_norm   (float)sqrt(sum) of the last launch (may be inf / NaN)
+ *     uint32 halted      latch: 1 once a launch saw a non-finite sum or loss; ONLY the caller clears it
+ *     int32  bad_step    value of `seen` at the launch that set the latch; -1 before
+ *     uint32 seen        launches so far (this launch adds 1)
+ *     uint32 clipped     launches whose coefficient was below 1
+ *     uint32 ticket      0 between launches (workgroups count themselves out on it; the last one resets it)
+ *     float  coef        the decision for the step that follows: its gradient multiplier
+ *   The caller creates the block once: {max_norm, 0, 0, -1, 0, 0, 0, 0}.  With apply = the latch was clear before this
+ *   launch, and sum and loss are finite:
+ *     apply     : coef = min(1, (float)((double)max_norm / ((double)last_norm + 1e-6)))   (clip_grad_norm_'s coefficient)
+ *     otherwise : coef = 0, the latch is set, and bad_step is written if the latch was clear
+ *
+ * The guarded steps (the `guard` argument follows `state` / `sq_sum`; everything else as the unguarded entry points,
+ * which are unchanged): every workgroup reads `halted` and `coef` first.  Halted: the launch writes NOTHING - no
+ * parameter, master value, moment, momentum or sq_sum slot, and the Adam step count does not advance.  Otherwise each
+ * gradient is replaced by one rounded float32 product g * coef (a bf16 gradient is widened first and not rounded back)
+ * in front of the step's arithmetic: the clip applies to the gradient as it stands in the buffer; weight_decay * w and
+ * 2 * l2 * w are added after it - clip_grad_norm_ followed by Adam(weight_decay) / SGD.  With coef = 1 the results are,
+ * bit for bit, the unguarded step's.  dctn_grad_guard_check must run before every guarded step, on the same stream.
+ * Return codes: DCTN_ERR_NULL, DCTN_ERR_BAD_SHAPE (n < 1, ...), DCTN_ERR_BAD_DTYPE as the unguarded steps.
+ * ------------------------------------------------------------------------------------------ */
+size_t dctn_grad_guard_state_bytes(void);
+int dctn_grad_guard_num_partials(int64_t n);
+int dctn_grad_guard_check(const void* grads, int64_t n, int dtype, const void* loss_or_null, void* partials, void* guard,
+                          void* stream);
+int dctn_adam_l2_step_guarded(void* params, const void* grads, void* exp_avg, void* exp_avg_sq, void* sq_sum, void* state,
+                              const void* guard, int64_t n, int64_t n_reg, double beta1, double beta2, float eps,
+                              float weight_decay, float l2, int dtype, void* stream);
+int dctn_adam_l2_step_master_guarded(void* master, void* params, const void* grads, void* exp_avg, void* exp_avg_sq,
+                                     void* sq_sum, void* state, const void* guard, int64_t n, int64_t n_reg,
+                                     double beta1, double beta2, float eps, float weight_decay, float l2, void* stream);
+int dctn_sgd_l2_step_guarded(void* params, const void* grads, void* momentum_buf, void* sq_sum, const void* guard,
+                             int64_t n, int64_t n_reg, float lr, float momentum, float l2, int first_step, int dtype,
+                             void* stream);
+int dctn_sgd_l2_step_master_guarded(void* master, void* params, const void* grads, void* momentum_buf, void* sq_sum,
+                                    const void* guard, int64_t n, int64_t n_reg, float lr, float momentum, float l2,
+                                    int first_step, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Scoring (reference: dctn/evaluation.py:7-22): one launch per batch ADDS to acc = three float64 values
  * {sum of the rows' cross-entropies, number of correct rows, number of rows}.  logits (B, C) contiguous, DCTN_F32 /
  * DCTN_BF16; labels int64.  Per row a max-shifted log-sum-exp with float32 exponentials; the row's sum, its
