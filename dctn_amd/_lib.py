@@ -29,6 +29,9 @@ SBS_MATRIX_CORE_SWEEP = 1 << 8   # OR-ed into the dtype argument of the dctn_con
 SBS_WIDE_SWEEP = 1 << 9   # likewise: the backward on the wide family (convsbs_wide.hip) for any string it covers
 BATCH_SRC_U8_TABLE, BATCH_SRC_ROWS = 0, 1   # DCTN_BATCH_SRC_*: `src_kind` of dctn_batch_draw / dctn_batch_gather
 BATCH_IDENTITY_ORDER, BATCH_PAD_TAIL = 1, 2  # `flags` of dctn_batch_draw
+# Python side only: the source kind of `DeviceBatches.from_colour`, which goes through dctn_batch_draw_cols /
+# dctn_batch_gather_cols (entry points of their own: the C `src_kind` stays 0 / 1)
+BATCH_SRC_COLOUR = 2
 
 _DTYPE_CODE = {torch.float32: F32, torch.float64: F64, torch.bfloat16: BF16}
 
@@ -93,6 +96,8 @@ SIGNATURES = {
     "dctn_batch_state_bytes": (c_size, []),
     "dctn_batch_draw": (c_int, [c_void] * 7 + [c_i64] * 5 + [c_int] * 4 + [c_void]),
     "dctn_batch_gather": (c_int, [c_void] * 7 + [c_i64] * 3 + [c_int] * 3 + [c_void]),
+    "dctn_batch_draw_cols": (c_int, [c_void] * 7 + [c_i64] * 5 + [c_int] * 4 + [c_void]),
+    "dctn_batch_gather_cols": (c_int, [c_void] * 7 + [c_i64] * 3 + [c_int] * 3 + [c_void]),
     "dctn_window_stats": (c_int, [c_void, _I64x5, c_void] + [c_int] * 6 + [c_int, c_void]),
     "dctn_phi_window_stats": (c_int, [c_void, c_void, c_int, c_int, c_int, c_int, c_void]),
     "dctn_phi_expand": (c_int, [c_void, c_void, c_i64, ctypes.c_float, c_int, c_void]),

@@ -1,8 +1,10 @@
-"""Batches drawn on the device (dctn_amd/csrc/batch_source.hip): the input side of the reference's ``train(dl, ...)``.
+"""Batches drawn on the device (dctn_amd/csrc/batch_source.hip, colour_source.hip): the input side of the reference's
+``train(dl, ...)``.
 
 The reference makes a batch with ``__getitem__`` per sample, ``collate_quantum``, pinning and a copy
 (dctn/dataset_loading.py:69-70, 282-286, 319-325).  Here the whole data set lives on the device - the raw uint8
-intensities, or an already-expanded feature tensor - and ONE launch picks the samples of a batch, applies the feature map
+intensities, the raw interleaved colour bytes (`DeviceBatches.from_colour`), or an already-expanded feature tensor - and
+ONE launch picks the samples of a batch, applies the feature map
 and the scale (a 256-row table), casts to the model dtype and advances a device counter.  The epoch order is a pure
 function of (seed, epoch, position) - a 6-round Feistel network with cycle walking, keyed by the Philox4x32-10 of
 `dropout` - so nothing of the size of the data set is shuffled or stored, every rank that holds the same 16-byte block
@@ -128,6 +130,67 @@ def feature_table(phi: Sequence[Callable[[Tensor], Tensor]], scale: float, dtype
     return (scale * torch.stack(tuple(f(u) for f in phi), dim=1)).to(dtype).contiguous()
 
 
+def _per_channel(value, channels: int, what: str) -> Tuple[float, ...]:
+    out = (float(value),) * channels if isinstance(value, (int, float)) else tuple(float(v) for v in value)
+    if len(out) != channels:
+        raise ValueError(f"{what} needs one value per channel ({channels}), got {len(out)}")
+    return out
+
+
+def colour_table(channels: int, *, nu, mean: Optional[Tensor] = None, std: Optional[Tensor] = None,
+                 constant_channel: Optional[float] = None, dtype: torch.dtype) -> Tensor:
+    """(W, 256), W = ``channels`` (+ 1 with a constant channel): row c holds what the reference's colour pipeline
+    (dataset_loading.py:349-375) gives for each of the 256 byte values in channel c, cast to ``dtype``.  Every value of
+    that pipeline is a function of one byte and its channel, so the table IS the pipeline: it is built on the CPU with
+    the reference's own ops in the reference's order on a (256, channels) float32 tensor -
+    ``arange(256, uint8).float().div(255)`` (``to_tensor``), in-place ``-= mean`` and ``/= std`` with float64 (channels,)
+    tensors when given (both or neither), the concatenated column ``constant_channel * ones``, in-place
+    ``*= torch.tensor(nu)`` where ``nu`` gets ``(1.0,)`` appended when a constant channel is added - and indexing it with
+    the bytes gives the bits of the expanded tensor.  ``nu``: one value per channel, or one number for all of them.  Row
+    ``channels`` (the constant channel) holds one value 256 times."""
+    channels = int(channels)
+    width = channels + (constant_channel is not None)
+    if not 1 <= channels <= MAX_WIDTH or width > MAX_WIDTH:
+        raise NotImplementedError(f"one launch writes 1 .. {MAX_WIDTH} columns, got {channels} channels"
+                                  + (" and a constant one" if constant_channel is not None else ""))
+    if (mean is None) != (std is None):
+        raise ValueError("centring and scaling go together: give both mean and std, or neither")
+    L.dtype_code(torch.empty(0, dtype=dtype))
+    nu = _per_channel(nu, channels, "nu")
+    t = torch.arange(256, dtype=torch.uint8).float().div(255).unsqueeze(1).repeat(1, channels)
+    if mean is not None:
+        mean, std = (torch.as_tensor(v, dtype=torch.float64).cpu().reshape(-1) for v in (mean, std))
+        if mean.shape != (channels,) or std.shape != (channels,):
+            raise ValueError(f"mean and std need one value per channel ({channels})")
+        t -= mean
+        t /= std
+    if constant_channel is not None:
+        t = torch.cat((t, constant_channel * torch.ones_like(t[:, :1])), dim=1)
+        nu = nu + (1.0,)
+    t *= torch.tensor(nu)
+    return t.to(dtype).t().contiguous()
+
+
+def channel_moments(images_u8: Tensor) -> Tuple[Tensor, Tensor]:
+    """``(mean, std)`` of ``images_u8 / 255`` per channel (the last dimension), float64 (channels,) on the input's device,
+    population std: what dataset_loading.py:351-352 computes from the expanded training tensor, here from a 256-bin
+    histogram of each channel, so nothing of the data set's size is expanded.  It agrees with
+    ``x.double().mean(...)`` / ``x.double().std(..., unbiased=False)`` to rounding (a few float64 ulps), NOT bit for bit: for
+    bit parity with a given reference run pass that run's own logged mean and std to `colour_table` / ``from_colour``."""
+    if images_u8.dtype != torch.uint8 or images_u8.ndim < 2:
+        raise TypeError(f"channel_moments takes (..., channels) uint8 bytes, got {images_u8.dtype}, {tuple(images_u8.shape)}")
+    C = images_u8.shape[-1]
+    flat = images_u8.reshape(-1, C)
+    if flat.shape[0] < 1:
+        raise ValueError("channel_moments needs at least one pixel")
+    counts = torch.stack([torch.bincount(flat[:, c].int(), minlength=256) for c in range(C)]).double()   # (C, 256)
+    values = torch.arange(256, dtype=torch.uint8).float().div(255).double().to(counts.device)   # to_tensor's float32 values
+    total = float(flat.shape[0])
+    mean = (counts * values).sum(dim=1) / total
+    var = (counts * (values.unsqueeze(0) - mean.unsqueeze(1)) ** 2).sum(dim=1) / total
+    return mean, var.sqrt()
+
+
 class DeviceBatches:
     """``(x, y, indices)`` batches of a data set that lives on the device, in place of the reference's train ``DataLoader``.
 
@@ -136,7 +199,8 @@ class DeviceBatches:
     to ``torch.distributed``'s when a process group is up, else 0 / 1; when they default, rank 0's 16-byte block is
     broadcast, so every rank draws the same global batch whatever seed it was given).  ``x`` comes out as
     (1, Bl, height, width, len(phi)) in ``dtype``: ``scale * phi(intensity / 255)`` evaluated with the reference's own
-    float32 ops once per intensity (`feature_table`), then cast.  `from_features` takes a tensor that is already expanded.
+    float32 ops once per intensity (`feature_table`), then cast.  `from_colour` takes raw (n, height, width, channels)
+    colour bytes and one 256-row table per channel (`colour_table`); `from_features` takes a tensor that is already expanded.
     CPU inputs are moved to the device once, here; without a GPU the constructor raises.
 
     ``draw_into(x, y, indices)`` enqueues one launch into caller-owned buffers and never reads the device: it can be
@@ -183,8 +247,8 @@ class DeviceBatches:
                       drop_last: bool = True, rank: Optional[int] = None,
                       world: Optional[int] = None) -> "DeviceBatches":
         """A source over features that are already expanded: ``x_full`` (channels, samples, ...) in the model dtype,
-        channels <= 4 (colour, constant-channel or normalised variants, whose values no 256-row table holds).  ``x`` comes
-        out as (channels, Bl, ...): a row copy."""
+        channels <= 4 (whatever no 256-row table per channel holds: augmented or otherwise pre-computed features; raw
+        colour bytes go through `from_colour`).  ``x`` comes out as (channels, Bl, ...): a row copy."""
         self = cls.__new__(cls)
         if x_full.ndim < 2:
             raise TypeError(f"from_features takes (channels, samples, ...) features, got {tuple(x_full.shape)}")
@@ -199,6 +263,35 @@ class DeviceBatches:
         self.table = None
         self.row_len, self.width = max(1, x_full[0, 0].numel()), C
         self.x_shape = lambda count: (C, count) + rest
+        self._finish(labels, dev)
+        return self
+
+    @classmethod
+    def from_colour(cls, images_u8: Tensor, labels: Tensor, batch_size: int, *, dtype: torch.dtype, seed: int, nu,
+                    mean: Optional[Tensor] = None, std: Optional[Tensor] = None,
+                    constant_channel: Optional[float] = None, shuffle: bool = True, drop_last: bool = True,
+                    rank: Optional[int] = None, world: Optional[int] = None, device=None) -> "DeviceBatches":
+        """A source over raw colour images: ``images_u8`` (n, height, width, channels) uint8 with the channels interleaved
+        (what ``torchvision.datasets.CIFAR10.data`` holds; for YCbCr the caller converts the bytes on the host first),
+        channels <= 4.  ``x`` comes out as (1, Bl, height, width, Wout), Wout = channels (+ 1 with ``constant_channel``):
+        the reference's colour pipeline (dataset_loading.py:331-389 - ``to_tensor``, the per-channel ``mean`` / ``std``,
+        the constant channel, the per-channel ``nu``) evaluated once per byte value and channel (`colour_table`), then
+        cast.  `channel_moments` gives ``mean`` and ``std`` of a training split from its bytes.  The data set stays on the
+        device as its bytes: 45 000 x 32 x 32 x 3 is 138 MB, against 737 MB expanded to float32 with a constant channel."""
+        self = cls.__new__(cls)
+        if images_u8.dtype != torch.uint8 or images_u8.ndim != 4:
+            raise TypeError("from_colour takes (samples, height, width, channels) uint8 bytes; float-valued sources go "
+                            f"through DeviceBatches.from_features (got {images_u8.dtype}, {tuple(images_u8.shape)})")
+        n, H, W, C = images_u8.shape
+        table = colour_table(C, nu=nu, mean=mean, std=std, constant_channel=constant_channel, dtype=dtype)
+        Wout = table.shape[0]
+        self._plan(n, labels, batch_size, seed, shuffle, drop_last, rank, world)
+        dev = self._device(device, images_u8)
+        self.kind, self.dtype = L.BATCH_SRC_COLOUR, dtype
+        self.src = images_u8.to(dev).contiguous()
+        self.table = table.to(dev)
+        self.row_len, self.channels, self.width = H * W, C, Wout
+        self.x_shape = lambda count: (1, count, H, W, Wout)
         self._finish(labels, dev)
         return self
 
@@ -262,6 +355,13 @@ class DeviceBatches:
     def _draw(self, x: Tensor, y: Tensor, indices: Tensor, flags: int) -> None:
         self._check_out(x, y, indices, self.local_batch)
         with torch.cuda.device(self.device):
+            if self.kind == L.BATCH_SRC_COLOUR:
+                L.check(L.lib().dctn_batch_draw_cols(
+                    self.src.data_ptr(), self.table.data_ptr(), self.labels.data_ptr(), x.data_ptr(), y.data_ptr(),
+                    indices.data_ptr(), self._state.data_ptr(), self.n, self.batch_size, self.local_batch,
+                    self.rank * self.local_batch, self.row_len, self.channels, self.width, flags, L.dtype_code(x),
+                    L.stream_ptr(self.device)), "colour batch draw")
+                return
             L.check(L.lib().dctn_batch_draw(
                 self.src.data_ptr(), None if self.table is None else self.table.data_ptr(), self.labels.data_ptr(),
                 x.data_ptr(), y.data_ptr(), indices.data_ptr(), self._state.data_ptr(), self.n, self.batch_size,
@@ -295,6 +395,12 @@ class DeviceBatches:
         idx = sample_idx.contiguous()
         x, y, indices = self.empty_batch(idx.numel())
         with torch.cuda.device(self.device):
+            if self.kind == L.BATCH_SRC_COLOUR:
+                L.check(L.lib().dctn_batch_gather_cols(
+                    self.src.data_ptr(), self.table.data_ptr(), self.labels.data_ptr(), idx.data_ptr(), x.data_ptr(),
+                    y.data_ptr(), indices.data_ptr(), self.n, idx.numel(), self.row_len, self.channels, self.width,
+                    L.dtype_code(x), L.stream_ptr(self.device)), "colour batch gather")
+                return x, y, indices
             L.check(L.lib().dctn_batch_gather(
                 self.src.data_ptr(), None if self.table is None else self.table.data_ptr(), self.labels.data_ptr(),
                 idx.data_ptr(), x.data_ptr(), y.data_ptr(), indices.data_ptr(), self.n, idx.numel(), self.row_len,

@@ -630,6 +630,35 @@ int dctn_batch_gather(const void* src, const void* table, const void* labels, co
                       void* indices, int64_t n, int64_t count, int64_t row_len, int width, int src_kind, int dtype,
                       void* stream);
 
+/* Raw colour images (version 506; reference: get_cifar10_colored_data_loaders, dctn/dataset_loading.py:331-389 -
+ * to_tensor, the optional per-channel centring and scaling, the optional constant channel, the per-channel nu).  Every
+ * value of that pipeline is a function of one byte and its channel, so one 256-row table per channel holds them all
+ * (dctn_amd/batches.py `colour_table`).  A third source form with entry points of its own; `src_kind` above keeps its two
+ * values.
+ *   src   = (n, P, C) uint8, the channels interleaved (what torchvision's CIFAR10 `.data` holds), P = pixels,
+ *           C = src_channels;
+ *   table = (W, 256) values of `dtype`, W = width: row c is channel c's table;
+ *   x     = (1, local_batch, P, W):  x[0, j, p, c] = table[c][src[s_j, p, c]]  for c < C,
+ *                                    x[0, j, p, c] = table[c][0]               for C <= c < W (the constant channel).
+ * 1 <= C <= 4 and W = C or C + 1 with W <= 4.  The byte offset of a row is 64-bit: n * P * C may pass 4 GiB.
+ * The workgroup stages the table in LDS, planar as it is given.  A lane moves four pixels per step - C 32-bit loads, 4 W
+ * elements in 16-byte stores (8-byte ones for bf16 with odd W) - when P % 4 == 0, src is 4-byte aligned and x is aligned
+ * to that store width; pixel by pixel otherwise.  Same results either way.
+ * dctn_batch_draw_cols / dctn_batch_gather_cols are dctn_batch_draw / dctn_batch_gather in everything else: the order
+ * definition, the 16-byte `state` block and how a draw advances it, both flags (padding slots read sample n - 1 and
+ * report the label -100 and the index -1), sharding by rank_offset, y and indices, the buffer contract (x, y, indices
+ * fully overwritten, nothing else written but batches_done and ticket) and the return-code rules: DCTN_ERR_NULL (any
+ * pointer; the table is always needed); DCTN_ERR_BAD_SHAPE (as above, with pixels, src_channels or width < 1);
+ * DCTN_ERR_BAD_DTYPE; DCTN_ERR_UNSUPPORTED (src_channels > 4, width > 4, width < src_channels,
+ * width > src_channels + 1).  No workspace.
+ * dctn_last_kernel(): colour_{draw,gather}_{f32,f64,bf16}. */
+int dctn_batch_draw_cols(const void* src, const void* table, const void* labels, void* x, void* y, void* indices,
+                         void* state, int64_t n, int64_t global_batch, int64_t local_batch, int64_t rank_offset,
+                         int64_t pixels, int src_channels, int width, int flags, int dtype, void* stream);
+int dctn_batch_gather_cols(const void* src, const void* table, const void* labels, const void* sample_idx, void* x, void* y,
+                           void* indices, int64_t n, int64_t count, int64_t pixels, int src_channels, int width, int dtype,
+                           void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Tensor-network inner product of two stacks of EPS cores - replaces the contractions of
  * dctn/epses_composition.py:21-58 `inner_product` (Gram of the first pair of cores over their input legs:
