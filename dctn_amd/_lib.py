@@ -32,10 +32,12 @@ BATCH_IDENTITY_ORDER, BATCH_PAD_TAIL = 1, 2  # `flags` of dctn_batch_draw
 # Python side only: the source kind of `DeviceBatches.from_colour`, which goes through dctn_batch_draw_cols /
 # dctn_batch_gather_cols (entry points of their own: the C `src_kind` stays 0 / 1)
 BATCH_SRC_COLOUR = 2
+AUG_HFLIP = 1   # DCTN_AUG_HFLIP: `aug_flags` of dctn_batch_draw_aug / dctn_batch_draw_cols_aug
 
 _DTYPE_CODE = {torch.float32: F32, torch.float64: F64, torch.bfloat16: BF16}
 
 c_int, c_i64, c_void, c_size = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t
+c_u32 = ctypes.c_uint32
 _I64x5 = ctypes.POINTER(c_i64)
 _I64P = ctypes.POINTER(c_i64)
 _IntP = ctypes.POINTER(c_int)
@@ -98,6 +100,8 @@ SIGNATURES = {
     "dctn_batch_gather": (c_int, [c_void] * 7 + [c_i64] * 3 + [c_int] * 3 + [c_void]),
     "dctn_batch_draw_cols": (c_int, [c_void] * 7 + [c_i64] * 5 + [c_int] * 4 + [c_void]),
     "dctn_batch_gather_cols": (c_int, [c_void] * 7 + [c_i64] * 3 + [c_int] * 3 + [c_void]),
+    "dctn_batch_draw_aug": (c_int, [c_void] * 7 + [c_i64] * 6 + [c_int] * 5 + [c_u32, c_void]),
+    "dctn_batch_draw_cols_aug": (c_int, [c_void] * 7 + [c_i64] * 6 + [c_int] * 6 + [c_u32, c_void]),
     "dctn_window_stats": (c_int, [c_void, _I64x5, c_void] + [c_int] * 6 + [c_int, c_void]),
     "dctn_phi_window_stats": (c_int, [c_void, c_void, c_int, c_int, c_int, c_int, c_void]),
     "dctn_phi_expand": (c_int, [c_void, c_void, c_i64, ctypes.c_float, c_int, c_void]),

@@ -11,10 +11,16 @@ function of (seed, epoch, position) - a 6-round Feistel network with cycle walki
 draws its shard of the same global batch, a resumed run repeats its batches from ``{"seed", "batches_done"}``, and a
 captured graph that holds the launch draws batch k, k + 1, ... on its replays.  include/dctn_amd.h holds the normative
 definition; `round_keys`, `order_at` and `expected_indices` restate it in plain Python.
+
+`Augment` adds a random shift (pad and crop) and a horizontal flip to the two byte-resident sources
+(dctn_amd/csrc/augment_source.hip).  Both act on the bytes, inside the same one launch, and their parameters are a pure
+function of (seed, epoch, global position) as the order is: no new state, the same batch on every sharding, the same
+augmentations after a resume, other ones on every replay of a captured graph.  `augment_params`, `augment_bytes` and
+`DeviceBatches.expected_augment` restate the definition of include/dctn_amd.h.
 """
 from __future__ import annotations
 
-from typing import Callable, Dict, Iterator, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, Iterator, List, Optional, Sequence, Tuple, Union
 
 import torch
 import torch.distributed as dist
@@ -26,6 +32,9 @@ from .window_stats import φ_cos_sin_squared_1
 
 TAG = 0x53485546   # counter word c3 of the round keys; dropout's c3 is a core number below 8
 MAX_WIDTH = 4      # table columns / channels of one launch (include/dctn_amd.h)
+AUG_TAG = 0x41554731            # counter word c3 of a slot's augmentation parameters (DCTN_AUG_TAG)
+AUG_MAX_SHIFT = (1 << 15) - 1   # the largest max_shift
+AUG_MAX_SAMPLE_BYTES = 13 * 1024   # an augmented launch keeps a sample's bytes (rounded up to 16) in a wave's LDS region
 
 
 def round_keys(seed: int, epoch: int) -> Tuple[int, ...]:
@@ -106,6 +115,74 @@ def expected_padded_indices(k: int, n: int, batch_size: int, rank: int = 0, worl
     S, Bl = steps_per_epoch(n, batch_size, drop_last=False), local_batch(batch_size, rank, world)
     first = (k % S) * batch_size + rank * Bl
     return [pos if pos < n else -1 for pos in range(first, first + Bl)]
+
+
+class Augment:
+    """What an augmented source does to the bytes of every drawn sample, before the table lookup: a shift by
+    (dy, dx), each uniform in [-max_shift, max_shift] (pad the image by ``max_shift`` with ``fill`` on every side and crop
+    a window of the image's size: ``RandomCrop(padding=max_shift, fill)`` in distribution), then with ``hflip`` a
+    horizontal flip with probability 1/2.  ``fill`` is a BYTE value, 0 .. 255, one for all source channels or one per
+    channel: after per-channel centring, ``round(255 * mean_c)`` is about 0 in the model's units.  Validated here, without
+    a device.  One ``max_shift`` serves both axes."""
+
+    def __init__(self, max_shift: int = 0, hflip: bool = False, fill: Union[int, Sequence[int]] = 0):
+        if isinstance(max_shift, bool) or not isinstance(max_shift, int) or not 0 <= max_shift <= AUG_MAX_SHIFT:
+            raise ValueError(f"max_shift is an integer in [0, {AUG_MAX_SHIFT}], got {max_shift!r}")
+        if not isinstance(hflip, bool):
+            raise ValueError(f"hflip is a bool, got {hflip!r}")
+        values = tuple(fill) if isinstance(fill, (tuple, list)) else (fill,)
+        if not 1 <= len(values) <= MAX_WIDTH or any(isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 255
+                                                    for v in values):
+            raise ValueError(f"fill is one byte value (0 .. 255) or one per source channel (at most {MAX_WIDTH}), got {fill!r}")
+        self.max_shift, self.hflip = max_shift, hflip
+        self.fill = values if isinstance(fill, (tuple, list)) else values[0]
+
+    @property
+    def flags(self) -> int:
+        return L.AUG_HFLIP if self.hflip else 0
+
+    def fill_bytes(self, channels: int) -> Tuple[int, ...]:
+        """One fill byte per source channel."""
+        if isinstance(self.fill, int):
+            return (self.fill,) * channels
+        if len(self.fill) != channels:
+            raise ValueError(f"fill needs one byte per source channel ({channels}), got {len(self.fill)}")
+        return self.fill
+
+    def packed_fill(self, channels: int) -> int:
+        """The 32-bit `fill` argument: channel c in bits 8 c .. 8 c + 7."""
+        return sum(v << (8 * c) for c, v in enumerate(self.fill_bytes(channels)))
+
+    def __repr__(self) -> str:
+        return f"Augment(max_shift={self.max_shift}, hflip={self.hflip}, fill={self.fill})"
+
+
+def augment_params(seed: int, epoch: int, position: int, max_shift: int, hflip: bool) -> Tuple[int, int, int]:
+    """``(dy, dx, flip)`` of the slot at GLOBAL position ``position`` of epoch ``epoch``: the words of
+    Philox4x32-10(counter (position, 0, epoch, AUG_TAG), key (seed_lo, seed_hi)), the first two mapped onto
+    [-max_shift, max_shift] by multiply-high, the top bit of the third the flip."""
+    w = philox4x32_10((position, 0, epoch, AUG_TAG), (seed & _MASK32, (seed >> 32) & _MASK32))
+    span = 2 * max_shift + 1
+    return ((w[0] * span >> 32) - max_shift, (w[1] * span >> 32) - max_shift, w[2] >> 31 if hflip else 0)
+
+
+def augment_bytes(images_u8: Tensor, params: Sequence[Tuple[int, int, int]], fill=0) -> Tensor:
+    """The augmentation on CPU bytes: ``images_u8`` (count, H, Wd) or (count, H, Wd, C) uint8, one ``(dy, dx, flip)`` per
+    image, ``fill`` one byte value or one per channel.  ``out[i, h, w] = images_u8[i, h + dy, wf + dx]`` with
+    ``wf = Wd - 1 - w`` when flipped, else ``w``, where that lies inside the image, and the fill elsewhere."""
+    if images_u8.dtype != torch.uint8 or images_u8.ndim not in (3, 4) or len(params) != images_u8.shape[0]:
+        raise ValueError("augment_bytes takes (count, H, Wd[, C]) uint8 images and one (dy, dx, flip) per image")
+    H, Wd = images_u8.shape[1], images_u8.shape[2]
+    channels = 1 if images_u8.ndim == 3 else images_u8.shape[3]
+    fills = torch.tensor(Augment(fill=fill).fill_bytes(channels), dtype=torch.uint8)
+    out = (fills[0] if images_u8.ndim == 3 else fills).expand(images_u8.shape).clone()
+    for i, (dy, dx, flip) in enumerate(params):
+        h0, h1, w0, w1 = max(0, -dy), min(H, H - dy), max(0, -dx), min(Wd, Wd - dx)   # where the source covers the window
+        if h0 < h1 and w0 < w1:
+            out[i, h0:h1, w0:w1] = images_u8[i, h0 + dy : h1 + dy, w0 + dx : w1 + dx]
+        if flip:
+            out[i] = out[i].flip(1)
+    return out
 
 
 def _new_state(seed: int, device: torch.device, batches_done: int = 0) -> Tensor:
@@ -220,12 +297,21 @@ class DeviceBatches:
     from the eager ``drop_last=False`` iteration: rank r takes slots ``r * Bl .. r * Bl + Bl - 1`` of every batch (of the
     last one too, where a rank may get nothing but padding), whereas the eager iteration splits the short tail evenly; the
     sums over all ranks are the same.
+
+    ``augment=Augment(...)`` (the uint8 and the colour sources; not `from_features`, whose rows have no height or width)
+    makes ``draw_into`` / ``draw`` - and with them ``GraphedTrainStep(batch_source=...)``, ``train(dl=...)`` and
+    ``batches_forever`` - shift and flip every sample's bytes inside the same launch (`augment_params`,
+    `expected_augment`, `augment_bytes`).  ``gather`` stays unaugmented, ``draw_padded_into`` raises and
+    ``drop_last=False`` is refused: evaluation is not augmented.  It takes a second source over the same bytes with
+    ``augment=None``: a constructor does not copy a tensor that is already on the device, so building both from one
+    device tensor (``train_src.src``, ``train_src.labels``) shares the data set.  ``state_dict`` is unchanged, and a loaded
+    state repeats the augmentations with the batches.
     """
 
     def __init__(self, images_u8: Tensor, labels: Tensor, batch_size: int, *, dtype: torch.dtype, seed: int,
                  scale: float = 1.0, phi: Sequence[Callable[[Tensor], Tensor]] = φ_cos_sin_squared_1,
                  shuffle: bool = True, drop_last: bool = True, rank: Optional[int] = None,
-                 world: Optional[int] = None, device=None):
+                 world: Optional[int] = None, device=None, augment: Optional[Augment] = None):
         if images_u8.dtype != torch.uint8 or images_u8.ndim != 3:
             raise TypeError("DeviceBatches takes (samples, height, width) uint8 intensities; float-valued sources go "
                             f"through DeviceBatches.from_features (got {images_u8.dtype}, {tuple(images_u8.shape)})")
@@ -234,6 +320,7 @@ class DeviceBatches:
         L.dtype_code(torch.empty(0, dtype=dtype))
         n, H, W = images_u8.shape
         self._plan(n, labels, batch_size, seed, shuffle, drop_last, rank, world)
+        self._plan_augment(augment, H, W, 1)
         dev = self._device(device, images_u8)
         self.kind, self.dtype = L.BATCH_SRC_U8_TABLE, dtype
         self.src = images_u8.to(dev).contiguous()
@@ -257,6 +344,7 @@ class DeviceBatches:
         L.dtype_code(x_full)
         C, n, rest = x_full.shape[0], x_full.shape[1], tuple(x_full.shape[2:])
         self._plan(n, labels, batch_size, seed, shuffle, drop_last, rank, world)
+        self.augment = None
         dev = self._device(None, x_full)
         self.kind, self.dtype = L.BATCH_SRC_ROWS, x_full.dtype
         self.src = x_full.to(dev).contiguous()
@@ -270,7 +358,8 @@ class DeviceBatches:
     def from_colour(cls, images_u8: Tensor, labels: Tensor, batch_size: int, *, dtype: torch.dtype, seed: int, nu,
                     mean: Optional[Tensor] = None, std: Optional[Tensor] = None,
                     constant_channel: Optional[float] = None, shuffle: bool = True, drop_last: bool = True,
-                    rank: Optional[int] = None, world: Optional[int] = None, device=None) -> "DeviceBatches":
+                    rank: Optional[int] = None, world: Optional[int] = None, device=None,
+                    augment: Optional[Augment] = None) -> "DeviceBatches":
         """A source over raw colour images: ``images_u8`` (n, height, width, channels) uint8 with the channels interleaved
         (what ``torchvision.datasets.CIFAR10.data`` holds; for YCbCr the caller converts the bytes on the host first),
         channels <= 4.  ``x`` comes out as (1, Bl, height, width, Wout), Wout = channels (+ 1 with ``constant_channel``):
@@ -286,6 +375,7 @@ class DeviceBatches:
         table = colour_table(C, nu=nu, mean=mean, std=std, constant_channel=constant_channel, dtype=dtype)
         Wout = table.shape[0]
         self._plan(n, labels, batch_size, seed, shuffle, drop_last, rank, world)
+        self._plan_augment(augment, H, W, C)
         dev = self._device(device, images_u8)
         self.kind, self.dtype = L.BATCH_SRC_COLOUR, dtype
         self.src = images_u8.to(dev).contiguous()
@@ -314,6 +404,20 @@ class DeviceBatches:
         self.padded_steps = steps_per_epoch(self.n, self.batch_size, drop_last=False)   # S of `draw_padded_into`
         self.local_batch = local_batch(self.batch_size, self.rank, self.world)
         _state_words(self.seed, 0)
+
+    def _plan_augment(self, augment: Optional[Augment], H: int, Wd: int, channels: int) -> None:
+        """The augmentation's own errors, before the device as well; `_plan` has run."""
+        self.augment, self.height, self.width_px = augment, int(H), int(Wd)
+        if augment is None:
+            return
+        if not isinstance(augment, Augment):
+            raise TypeError(f"augment takes an Augment, got {type(augment).__name__}")
+        if not self.drop_last:
+            raise ValueError("drop_last=False is the evaluation form, which is not augmented: build that source with augment=None")
+        self._fill = augment.packed_fill(channels)
+        if -(-H * Wd * channels // 16) * 16 > AUG_MAX_SAMPLE_BYTES:
+            raise NotImplementedError(f"an augmented draw keeps a sample's bytes in LDS: at most {AUG_MAX_SAMPLE_BYTES} "
+                                      f"bytes, got {H} x {Wd} x {channels}")
 
     @staticmethod
     def _device(device, tensor: Tensor) -> torch.device:
@@ -355,6 +459,18 @@ class DeviceBatches:
     def _draw(self, x: Tensor, y: Tensor, indices: Tensor, flags: int) -> None:
         self._check_out(x, y, indices, self.local_batch)
         with torch.cuda.device(self.device):
+            if self.augment is not None:
+                head = (self.src.data_ptr(), self.table.data_ptr(), self.labels.data_ptr(), x.data_ptr(), y.data_ptr(),
+                        indices.data_ptr(), self._state.data_ptr(), self.n, self.batch_size, self.local_batch,
+                        self.rank * self.local_batch, self.height, self.width_px)
+                tail = (flags, L.dtype_code(x), self.augment.max_shift, self.augment.flags, self._fill,
+                        L.stream_ptr(self.device))
+                if self.kind == L.BATCH_SRC_COLOUR:
+                    L.check(L.lib().dctn_batch_draw_cols_aug(*head, self.channels, self.width, *tail),
+                            "augmented colour batch draw")
+                else:
+                    L.check(L.lib().dctn_batch_draw_aug(*head, self.width, *tail), "augmented batch draw")
+                return
             if self.kind == L.BATCH_SRC_COLOUR:
                 L.check(L.lib().dctn_batch_draw_cols(
                     self.src.data_ptr(), self.table.data_ptr(), self.labels.data_ptr(), x.data_ptr(), y.data_ptr(),
@@ -369,7 +485,8 @@ class DeviceBatches:
                 L.dtype_code(x), L.stream_ptr(self.device)), "batch draw")
 
     def draw_into(self, x: Tensor, y: Tensor, indices: Tensor) -> None:
-        """The next batch (this rank's shard of it) into caller-owned buffers: one launch, capturable."""
+        """The next batch (this rank's shard of it) into caller-owned buffers: one launch, capturable.  With ``augment``
+        the launch shifts and flips the samples' bytes (`expected_augment`)."""
         self._draw(x, y, indices, 0 if self.shuffle else L.BATCH_IDENTITY_ORDER)
 
     def draw_padded_into(self, x: Tensor, y: Tensor, indices: Tensor) -> None:
@@ -379,6 +496,8 @@ class DeviceBatches:
         then used for nothing else)."""
         if self.shuffle:
             raise ValueError("the padded pass is sequential: it needs a source built with shuffle=False")
+        if self.augment is not None:
+            raise ValueError("the padded pass is an evaluation pass, which is not augmented: use a source with augment=None")
         self._draw(x, y, indices, L.BATCH_IDENTITY_ORDER | L.BATCH_PAD_TAIL)
 
     def draw(self) -> Tuple[Tensor, Tensor, Tensor]:
@@ -388,7 +507,7 @@ class DeviceBatches:
 
     def gather(self, sample_idx: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
         """The batch made of the given samples (a device int64 vector, every entry in [0, n): not checked).  Reads no
-        state."""
+        state.  Never augmented."""
         L.require_device(sample_idx, self.src)
         if sample_idx.dtype != torch.int64 or sample_idx.ndim != 1 or sample_idx.numel() < 1:
             raise ValueError("gather takes a non-empty int64 vector of sample numbers")
@@ -427,6 +546,14 @@ class DeviceBatches:
     def expected_indices(self, k: int) -> List[int]:
         """Host restatement: the sample numbers draw ``k`` gives this rank."""
         return expected_indices(self.seed, k, self.n, self.batch_size, self.rank, self.world, self.shuffle)
+
+    def expected_augment(self, k: int) -> List[Tuple[int, int, int]]:
+        """Host restatement: ``(dy, dx, flip)`` of this rank's slots of draw ``k`` (all (0, 0, 0) without ``augment``)."""
+        if self.augment is None:
+            return [(0, 0, 0)] * self.local_batch
+        first = (k % self.steps) * self.batch_size + self.rank * self.local_batch
+        return [augment_params(self.seed, k // self.steps, first + j, self.augment.max_shift, self.augment.hflip)
+                for j in range(self.local_batch)]
 
     # ---------------------------------------------------------------------------------------------- resume
     def state_dict(self) -> Dict[str, int]:

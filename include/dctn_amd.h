@@ -659,6 +659,53 @@ int dctn_batch_gather_cols(const void* src, const void* table, const void* label
                            void* indices, int64_t n, int64_t count, int64_t pixels, int src_channels, int width, int dtype,
                            void* stream);
 
+/* On-device augmentation of the two byte-resident sources (version 507): a random shift (pad and crop) and a horizontal
+ * flip of the BYTES of every drawn sample, before the table lookup.  The reference has no augmentation (its README notes
+ * that the model overfits CIFAR-10); these are torchvision's RandomCrop(padding = m, fill) and RandomHorizontalFlip in
+ * distribution.
+ *
+ * Definition (normative; dctn_amd/batches.py `augment_params` / `augment_bytes` restate it in Python).  k is the batch
+ * counter read at the launch's start, S = n / G the batches per epoch, e = k / S the epoch.  Slot j of the launch has the
+ * GLOBAL position g = (k % S) * G + rank_offset + j - the position the order definition above maps to the sample s_j
+ * (with DCTN_BATCH_IDENTITY_ORDER s_j = g).  The parameters of the slot:
+ *   w = Philox4x32-10(counter (g, 0, e, DCTN_AUG_TAG), key (seed & 0xFFFFFFFF, seed >> 32)), DCTN_AUG_TAG = 0x41554731
+ *       (disjoint from the order's 0x53485546 and from dropout's c3 < 8);
+ *   with m = max_shift:  dy = (int)(((uint64)w[0] * (2 m + 1)) >> 32) - m,  dx the same expression on w[1],
+ *                        flip = (aug_flags & DCTN_AUG_HFLIP) ? w[2] >> 31 : 0.
+ * Output for image height H = height, width Wd = width_px, wf = flip ? Wd - 1 - w : w:
+ *   grey   (dctn_batch_draw_aug):       x[0, j, h, w, :] = table[b, :]
+ *   colour (dctn_batch_draw_cols_aug):  x[0, j, h, w, c] = table[c][b_c] for c < C, table[C][0] for the constant column
+ * where b (b_c) is the source byte of sample s_j at row h + dy, column wf + dx (channel c) when that lies inside the
+ * image, and the fill byte otherwise: one fill byte per source channel, packed in `fill` with channel c in bits
+ * 8 c .. 8 c + 7.  This equals padding the byte image by m with the fill on every side, cropping an H x Wd window at
+ * (m + dy, m + dx), flipping it horizontally, and then applying the unaugmented per-byte pipeline; the fill is in the
+ * byte domain so that the result is bit for bit "augment the bytes, then expand".  The parameters depend on the global
+ * position, never on the rank or the number of ranks: the global batch does not depend on how it is sharded.  y, indices,
+ * the `state` block, the ticket and the counter advance are those of the unaugmented draw; there is no new device state,
+ * so {"seed", "batches_done"} repeats the augmentations too, and a captured launch augments every replay differently.
+ * The 32-bit words are mapped by multiply-high: the bias of a value is below 2^-32 * (2 m + 1).
+ *
+ * Arguments: those of dctn_batch_draw (without src_kind: the source is the uint8 one) and dctn_batch_draw_cols, with
+ * row_len / pixels replaced by height, width_px, and max_shift, aug_flags, fill added.  src = (n, H, Wd) or
+ * (n, H, Wd, C) uint8; x = (1, local_batch, H, Wd, width).  `flags` accepts DCTN_BATCH_IDENTITY_ORDER only: an evaluation
+ * pass is not augmented, so DCTN_BATCH_PAD_TAIL is DCTN_ERR_BAD_SHAPE like an unknown bit.  There is no augmented gather.
+ * Return codes, decided on the host before any launch, in this order: DCTN_ERR_NULL; DCTN_ERR_BAD_SHAPE (the rules of the
+ * unaugmented draws with height, width_px or their product outside [1, 2^31); max_shift < 0 or >= 2^15; an unknown bit
+ * in aug_flags; fill bits above the source channels); DCTN_ERR_BAD_DTYPE; DCTN_ERR_UNSUPPORTED (the width rules of the
+ * unaugmented draws; a sample of more than 13 KiB, H * Wd * C rounded up to 16 bytes: a wave keeps its sample in LDS -
+ * 64 x 64 x 3 fits).  Buffer contract as above; no workspace.
+ * dctn_last_kernel(): aug_draw_{u8,cols}_{f32,f64,bf16}. */
+#define DCTN_AUG_TAG 0x41554731u
+enum { DCTN_AUG_HFLIP = 1 };   /* `aug_flags` */
+int dctn_batch_draw_aug(const void* src, const void* table, const void* labels, void* x, void* y, void* indices, void* state,
+                        int64_t n, int64_t global_batch, int64_t local_batch, int64_t rank_offset, int64_t height,
+                        int64_t width_px, int width, int flags, int dtype, int max_shift, int aug_flags, uint32_t fill,
+                        void* stream);
+int dctn_batch_draw_cols_aug(const void* src, const void* table, const void* labels, void* x, void* y, void* indices,
+                             void* state, int64_t n, int64_t global_batch, int64_t local_batch, int64_t rank_offset,
+                             int64_t height, int64_t width_px, int src_channels, int width, int flags, int dtype,
+                             int max_shift, int aug_flags, uint32_t fill, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Tensor-network inner product of two stacks of EPS cores - replaces the contractions of
  * dctn/epses_composition.py:21-58 `inner_product` (Gram of the first pair of cores over their input legs:
