@@ -12,6 +12,19 @@ template <> struct AccOf<double> { typedef double type; };
 
 #define DCTN_WAVE 64
 
+// Store policy of the two buffers a register-family EPS step hands from one kernel to the next (eps_mfma.hip,
+// eps_q2f32.hip): the `aux` operand of their 16-byte buffer stores.  0 = plain (the line stays dirty in the XCD's L2
+// until the write-back at the end of the kernel), 16 = sc1, 17 = sc0 sc1 (written through, the line is dropped: the
+// next kernel reads it from the memory side).  Build-time switches of the comparison in DESIGN 4.1.
+//   DCTN_WT_FEATURES: the forward's feature buffer (blocked4 block store in bf16, the 16-byte row store in float32)
+//   DCTN_WT_TILES:    the dCore kernels' partial tiles
+#ifndef DCTN_WT_FEATURES
+#define DCTN_WT_FEATURES 16
+#endif
+#ifndef DCTN_WT_TILES
+#define DCTN_WT_TILES 0
+#endif
+
 // The device's geometry, asked once per process (capi.hip); gfx950 defaults when the runtime cannot say
 struct DctnDev { int cus; int lds; };   // CUs, LDS bytes per CU
 const DctnDev& dctn_dev();

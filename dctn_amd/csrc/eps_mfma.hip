@@ -1088,7 +1088,7 @@ __global__ __launch_bounds__(64 * HEADT_WAVES) void eps_fwd_head_q2reg_t_k(const
         for (int i = 0; i < HEADT_GS; ++i) r[i] = i < ng ? *reinterpret_cast<const unsigned*>(ftile + i * LP + f) : 0u;
         const u32x4 q = u32x4{__builtin_amdgcn_perm(r[1], r[0], 0x05040100u), __builtin_amdgcn_perm(r[3], r[2], 0x05040100u),
                               __builtin_amdgcn_perm(r[1], r[0], 0x07060302u), __builtin_amdgcn_perm(r[3], r[2], 0x07060302u)};
-        __builtin_amdgcn_raw_buffer_store_b128(q, rs_o, (unsigned)f * 8u, sob, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(q, rs_o, (unsigned)f * 8u, sob, DCTN_WT_FEATURES);
       }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -1566,11 +1566,16 @@ __global__ __launch_bounds__(64 * (BWD_WAVES + DWROLE)) void eps_bwd_dcore_q2reg
         big[(wv * MT + t) * 1024 + row * 32 + r] = acc[t][0][v];
       }
     __syncthreads();
-    for (int e = tid; e < MT * 1024; e += 64 * BWD_WAVES) {
-      float sum = 0.f;
+    // thread t sums elements 4 t .. 4 t + 3 (each in wave order k = 0 .. 7) and stores them as one 16-byte store whose
+    // policy is DCTN_WT_TILES; MT = 2: every dCore thread once, MT = 1: the first half of them
+    typedef __attribute__((ext_vector_type(4))) float f32x4v;
+    const __amdgpu_buffer_rsrc_t rs_t = make_rsrc(dst, (unsigned)(MT * 1024 * sizeof(float)));
+    for (int e = 4 * tid; e < MT * 1024; e += 4 * 64 * BWD_WAVES) {
+      f32x4v sum = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int k = 0; k < BWD_WAVES; ++k) sum += big[k * MT * 1024 + e];
-      dst[e] = sum;   // [t][row][col] = row-major (MT * 32) x 32
+      for (int k = 0; k < BWD_WAVES; ++k) sum += *reinterpret_cast<const f32x4v*>(big + k * MT * 1024 + e);
+      // [t][row][col] = row-major (MT * 32) x 32
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, sum), rs_t, (unsigned)e * 4u, 0, DCTN_WT_TILES);
     }
   } else {
 #pragma unroll

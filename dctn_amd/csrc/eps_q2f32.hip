@@ -348,7 +348,7 @@ __global__ __launch_bounds__(64 * QF_WAVES) void eps_fwd_q2f32_k(const float* __
       if (p.ovec) {   // (lanes without a position: out of range, nothing stored)
         if constexpr (OP == 4)
           __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(res[0]), __float_as_uint(res[1]), __float_as_uint(res[2]),
-                                                       __float_as_uint(res[3])}, rs_o, voff_o, soff_o, 0);
+                                                       __float_as_uint(res[3])}, rs_o, voff_o, soff_o, DCTN_WT_FEATURES);
         else
           __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(res[0]), __float_as_uint(res[1])}, rs_o, voff_o, soff_o, 0);
       } else {
@@ -627,11 +627,13 @@ __global__ __launch_bounds__(64 * QF_WAVES) void eps_bwd_q2f32_k(const float* __
       dsm[(wv * MT + t) * 1024 + row * 32 + r] = acc[t][v];
     }
   __syncthreads();
-  for (int e = tid; e < MT * 1024; e += 64 * QF_WAVES) {
-    float sum = 0.f;
+  // thread t sums elements 4 t .. 4 t + 3 (each in wave order) and stores them as one 16-byte store (DCTN_WT_TILES)
+  const __amdgpu_buffer_rsrc_t rs_t = q2_make_rsrc(dst, (unsigned)(MT * 1024 * sizeof(float)));
+  for (int e = 4 * tid; e < MT * 1024; e += 4 * 64 * QF_WAVES) {
+    f32x4 sum = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int k = 0; k < QF_WAVES; ++k) sum += dsm[k * MT * 1024 + e];
-    dst[e] = sum;
+    for (int k = 0; k < QF_WAVES; ++k) sum += *reinterpret_cast<const f32x4*>(dsm + k * MT * 1024 + e);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, sum), rs_t, (unsigned)e * 4u, 0, DCTN_WT_TILES);
   }
 }
 
