@@ -102,6 +102,10 @@ SIGNATURES = {
     "dctn_batch_gather_cols": (c_int, [c_void] * 7 + [c_i64] * 3 + [c_int] * 3 + [c_void]),
     "dctn_batch_draw_aug": (c_int, [c_void] * 7 + [c_i64] * 6 + [c_int] * 5 + [c_u32, c_void]),
     "dctn_batch_draw_cols_aug": (c_int, [c_void] * 7 + [c_i64] * 6 + [c_int] * 6 + [c_u32, c_void]),
+    "dctn_state_max_regions": (c_int, []),
+    "dctn_state_arena_bytes": (c_size, [_I64P, c_int]),
+    "dctn_state_gather": (c_int, [_PtrP, _I64P, c_int, c_void, c_size, c_void, c_void]),
+    "dctn_state_scatter": (c_int, [c_void, _PtrP, _I64P, c_int, c_void, c_void]),
     "dctn_window_stats": (c_int, [c_void, _I64x5, c_void] + [c_int] * 6 + [c_int, c_void]),
     "dctn_phi_window_stats": (c_int, [c_void, c_void, c_int, c_int, c_int, c_int, c_void]),
     "dctn_phi_expand": (c_int, [c_void, c_void, c_i64, ctypes.c_float, c_int, c_void]),

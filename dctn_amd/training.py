@@ -693,13 +693,17 @@ def batches_forever(dl: Iterable) -> Iterator[Any]:
 
 
 def train(dl, model, optimizer, dev, loss_fn, reg_fn, reg_coeff: float, at_iter_start, after_back,
-          after_param_upd) -> Tuple[StX, StIt]:
+          after_param_upd, first_iter: int = 0) -> Tuple[StX, StIt]:
     """The loop of dctn/training.py:23-84.  ``dl`` yields ``(x, y, indices)`` (this rank's shard under
     ``torch.distributed``); ``loss_fn(output, y)`` and ``reg_fn(st_x, st_it)`` return 0-dim tensors; the three
     hook lists hold callables ``f(st_x, st_it)`` run at the start of an iteration, after ``backward()`` (the
     gradients they see are already averaged over the ranks) and after ``optimizer.step()``.  A hook stops
     the loop by setting ``st_it["stop"]``; with several ranks the flag is OR-ed over them so that all
-    leave in the same iteration.  Returns the two state dictionaries of the last iteration."""
+    leave in the same iteration.  Returns the two state dictionaries of the last iteration.
+
+    ``first_iter``: ``num_iters_done`` counts from it, so the schedules of the hooks and the checkpoint names of a run
+    resumed from a snapshot (`checkpoint.RunState.load`, whose extras hold the last finished iteration) continue where
+    the saved run stood.  The default, 0, is a run from the start."""
     st_x: StX = dict(model=model.to(dev), optimizer=optimizer, loss_fn=loss_fn, reg_fn=reg_fn, reg_coeff=reg_coeff,
                      at_iter_start=list(at_iter_start), after_back=list(after_back),
                      after_param_upd=list(after_param_upd), dev=dev)
@@ -722,7 +726,7 @@ def train(dl, model, optimizer, dev, loss_fn, reg_fn, reg_coeff: float, at_iter_
         for hook in tuple(st_x[key]):   # a hook may remove itself
             hook(st_x, st_it)
 
-    for count, (x, y, indices) in enumerate(batches_forever(dl)):
+    for count, (x, y, indices) in enumerate(batches_forever(dl), int(first_iter)):
         st_it = dict(num_iters_done=count, x=x.to(dev), y=y.to(dev), indices=indices.to(dev), stop=False)
         run_hooks("at_iter_start")
         st_x["model"].train()

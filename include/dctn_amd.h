@@ -707,6 +707,48 @@ int dctn_batch_draw_cols_aug(const void* src, const void* table, const void* lab
                              int max_shift, int aug_flags, uint32_t fill, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Whole-run snapshots (version 508; the reference's runner only has --load-model-state): everything a training run keeps
+ * on the device - the flat parameter buffer, the moments, the float32 master copy and the 16- / 32-byte state blocks of
+ * the optimizer, the gradient guard, the dropout and the batch source - gathered into ONE contiguous arena by one launch
+ * at one point of the stream, and put back in place by one launch.  dctn_amd/checkpoint.py is the host side.
+ *
+ * Layout (normative).  Region r of a call (r = its index in the pointer array) has bytes[r] >= 1 bytes and starts in the
+ * arena at the sum of the earlier lengths, each rounded up to a multiple of 16; the arena's size is that sum over all
+ * regions, which the arena-size query returns (0 for a NULL table, a count outside 1 .. 16 or a length < 1).  The
+ * gather writes every byte of the arena: the bytes between a region's end and the next multiple of 16 are ZERO.
+ *
+ * Digest (normative; dctn_amd/checkpoint.py `digest` restates it in Python).  A region's bytes, zero-padded to a multiple
+ * of 16, read as little-endian uint32 words w_0 .. w_(m-1):  s1 = sum of w_i,  s2 = sum of (i + 1) * w_i,  both mod 2^64.
+ * Integer sums: every summation order gives the same bits.  `digests` receives {uint64 s1, uint64 s2} per region, 16
+ * bytes each, in table order.  The gather digests what it READ from the regions, the scatter what it READ from the arena
+ * (the region's bytes there; the arena's padding does not enter), so a host that recomputes the digest of the bytes it
+ * received, or sent, checks the whole way.
+ *
+ * Arguments.  srcs / dsts: HOST array of n_regions device pointers, each a multiple of 4 (DCTN_ERR_UNSUPPORTED otherwise:
+ * a bf16 view at an odd element); a region whose address is a multiple of 16 moves in 16-byte accesses, any other in
+ * dwords; the last bytes[r] % 4 bytes move as a short and / or a byte, and no access reaches past a region's last byte.
+ * bytes: HOST array of the lengths.  1 <= n_regions <= 16 as the max-regions query returns (more:
+ * DCTN_ERR_UNSUPPORTED; the caller makes several calls).  arena: device, 16-byte aligned; arena_bytes must be exactly the
+ * padded sum (DCTN_ERR_BAD_SHAPE).  digests: device, 8-byte aligned, 16 * n_regions bytes.  Regions must not overlap
+ * each other or the arena.  The table travels by value in the kernel argument: the calls read no host memory after they
+ * return and no device memory on the host, they only enqueue (a zeroing launch for the digest cells, then the one copy
+ * launch: the cells are summed with 64-bit vector atomics, no workgroup waits for another) and can be captured.
+ *
+ * Buffer contract.  gather: the arena (all arena_bytes) and the 16 * n_regions digest bytes are fully OVERWRITTEN,
+ * whatever they held; the regions are only read.  scatter: every byte of every region and the digest bytes are
+ * OVERWRITTEN, nothing past a region's last byte is written, the arena is only read.  Nothing else is touched.  No
+ * workspace.  Return codes, decided on the host before any launch: DCTN_ERR_NULL (table, an entry, arena, digests);
+ * DCTN_ERR_BAD_SHAPE (n_regions < 1, a length < 1, arena_bytes off); DCTN_ERR_UNSUPPORTED (n_regions > 16, alignment).
+ * These launches do not report to dctn_last_kernel.
+ * ------------------------------------------------------------------------------------------ */
+int dctn_state_max_regions(void);
+size_t dctn_state_arena_bytes(const int64_t* bytes, int n_regions);
+int dctn_state_gather(const void* const* srcs, const int64_t* bytes, int n_regions, void* arena, size_t arena_bytes,
+                      void* digests, void* stream);
+int dctn_state_scatter(const void* arena, void* const* dsts, const int64_t* bytes, int n_regions, void* digests,
+                       void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Tensor-network inner product of two stacks of EPS cores - replaces the contractions of
  * dctn/epses_composition.py:21-58 `inner_product` (Gram of the first pair of cores over their input legs:
  * dctn/eps.py:106-112 `contract_on_input_dims`; that matrix absorbed into every input leg of the next core:
