@@ -25,6 +25,23 @@ template <> struct AccOf<double> { typedef double type; };
 #define DCTN_WT_TILES 0
 #endif
 
+// Build-time switches of the fused bf16 head forward's prologue and step loop (eps_fwd_head_q2reg_t_k, eps_mfma.hip), one
+// per item of the comparison in DESIGN 4.1; none of them touches a floating-point operation.  1 = on, 0 = the form before; the defaults are what won its own A/B.
+//   DCTN_FWD_ARGS_ONCE:    every kernel argument is read in the one scalar round at entry and kept in registers
+//   DCTN_FWD_EARLY_WINDOW: the first group's step counter is set in front of the barrier that publishes the core (one
+//                          workgroup barrier fewer), a wave's first window goes out behind the core's loads
+//   DCTN_FWD_POS_TABLE:    a step reads its lane's offsets from a table in LDS that the workgroup fills once, and splits
+//                          its ticket into (sample, position group) by a multiply-shift
+#ifndef DCTN_FWD_ARGS_ONCE
+#define DCTN_FWD_ARGS_ONCE 0   // built and measured: it does not beat its twin (NOTEBOOK round 13)
+#endif
+#ifndef DCTN_FWD_EARLY_WINDOW
+#define DCTN_FWD_EARLY_WINDOW 1
+#endif
+#ifndef DCTN_FWD_POS_TABLE
+#define DCTN_FWD_POS_TABLE 1
+#endif
+
 // The device's geometry, asked once per process (capi.hip); gfx950 defaults when the runtime cannot say
 struct DctnDev { int cus; int lds; };   // CUs, LDS bytes per CU
 const DctnDev& dctn_dev();

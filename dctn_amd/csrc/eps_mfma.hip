@@ -158,6 +158,7 @@ struct MfmaP {
   int ncb;                      //   chunk blocks (8 sample chunks each) of the grouped wave mapping
   int skew;                     //   grouped mapping: the first half of a block's waves takes spc + skew samples each, the second spc - skew
   int opts;                     // DCTN_OPT_* flags of the call
+  unsigned npg_rcp;             // ceil(2^16 / npg): ticket / npg = (ticket * npg_rcp) >> 16 (exact below 2^16 / npg)
 #ifdef DCTN_STAMPS
   unsigned long long* stamps;   // diagnostic build only (tools/stamp_cfg2.hip): per-workgroup phase time stamps
 #endif
@@ -886,16 +887,36 @@ __global__ __launch_bounds__(64 * HEADT_WAVES) void eps_fwd_head_q2reg_t_k(const
                                                                            const bf16_t* __restrict__ hw,
                                                                            const bf16_t* __restrict__ bias,
                                                                            bf16_t* __restrict__ out,
-                                                                           bf16_t* __restrict__ logits, MfmaP p) {
+                                                                           bf16_t* __restrict__ logits, MfmaP p_in) {
   typedef bf16_t S;
   typedef __attribute__((ext_vector_type(4))) float f32x4v;
   constexpr int N = N0 + N1, A = 1 << N0, BN = 1 << N1, KS = A / 16, MT = BN * OP / 32;
   constexpr int LOGO = ilog2(OP);
   constexpr int TOT = A * BN * OP;
   static_assert(OP % 2 == 0 && TOT % 4 == 0, "outputs are handled as bf16 pairs");
+#if DCTN_FWD_ARGS_ONCE
+  // Every argument the kernel uses, read in the scalar round at entry: the empty statement needs them all in registers
+  // here, so no load of the argument block is left behind a barrier, on the way to the first window (they came in four
+  // dependent rounds, the last one behind the barrier that publishes the core)
+  MfmaP p = p_in;
+  asm volatile("" ::"s"(x), "s"(core), "s"(hw), "s"(bias), "s"(out), "s"(logits), "s"(p.B), "s"(p.O), "s"(p.Wo), "s"(p.P),
+               "s"(p.npg), "s"(p.spc), "s"(p.rowoffb[0]), "s"(p.rowoffb[1]), "s"(p.rowoffb[2]), "s"(p.rowoffb[ROWS - 1]),
+               "s"(p.s1b), "s"(p.s2b), "s"(p.s3b), "s"(p.x_bytes), "s"(p.o_bytes), "s"(p.o_s1b), "s"(p.div_wo.M),
+               "s"(p.div_wo.s1), "s"(p.div_wo.s2), "s"(p.Cout), "s"(p.hw_rowb), "s"(p.hw_bytes), "s"(p.npg_rcp));
+#else
+  const MfmaP& p = p_in;
+#endif
   __shared__ __attribute__((aligned(16))) bf16_t cs[TOT];
   __shared__ float hsum[HEADT_WAVES][HEADT_GS][16];
   __shared__ unsigned step_ctr;
+#if DCTN_FWD_POS_TABLE
+  // per (position group, lane): {byte offset of the window in a sample of x, byte offset of the position's features in a
+  // sample's row of the tile and of `out`}; lanes without a position and the whole row npg (the row of a dead ticket):
+  // {past x, POS_NONE}
+  static_assert((HEAD_FWD_MAXPG + 1) * 64 <= 64 * HEADT_WAVES, "one table entry per thread");
+  __shared__ u32x2 pos_tab[(HEAD_FWD_MAXPG + 1) * 64];
+#endif
+  constexpr unsigned POS_NONE = 0x80000000u;   // as an offset into `out` it is past every extent (o_bytes < 2^31)
   extern __shared__ __attribute__((aligned(16))) short ftile[];   // [HEADT_GS][LP]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -908,6 +929,29 @@ __global__ __launch_bounds__(64 * HEADT_WAVES) void eps_fwd_head_q2reg_t_k(const
   // group's last barrier.  Its load goes out BEHIND the core's first loads and in front of their LDS stores: a wave's
   // loads return in order, so it neither holds the core back nor waits for a round trip of its own.
   float bias_v = 0.f;
+  // offsets of window position `pos`: into a sample of x (past x without a position), and into a sample's feature row
+  auto lane_at = [&](int pos, unsigned& voff_x, unsigned& toff) {
+    const bool valid = pos < p.P;
+    const unsigned pu = (unsigned)(valid ? pos : p.P - 1);
+    const unsigned ho = fdiv(pu, p.div_wo), wo = pu - ho * (unsigned)p.Wo;
+    voff_x = valid ? ho * p.s2b + wo * p.s3b : p.x_bytes;
+    toff = valid ? pu * (unsigned)(OP * 2) : POS_NONE;
+  };
+  // a wave's first step of a group is the static ticket wv: its sample and its lane's offsets, without the table (the
+  // first group's goes out before the table is published)
+  auto first_ticket = [&](int nsteps, int& s, unsigned& voff_x, unsigned& toff) {
+    const int sq = (int)(((unsigned)wv * p.npg_rcp) >> 16), pg = wv - sq * p.npg;
+    const bool live = wv < nsteps;
+    s = live ? sq : 0;
+    lane_at(live ? pg * 64 + lane : p.P, voff_x, toff);
+  };
+  const int ng0 = b0 + HEADT_GS < b1 ? HEADT_GS : b1 - b0, nsteps0 = ng0 * p.npg;
+  int s;
+  unsigned voff_x, toff;
+  RawWindow<S, N, true, ROWS> raw;
+#if DCTN_FWD_EARLY_WINDOW
+  if (tid == 0) step_ctr = 2 * HEADT_WAVES;   // the first group's: published by the barrier below
+#endif
   // core -> LDS in fragment order (as eps_fwd_q2reg_k): 4 elements per thread and batch, the loads of a batch in flight together
   for (int e0 = 0; e0 < TOT; e0 += 4 * 64 * HEADT_WAVES) {
     S tmp[4];
@@ -917,6 +961,20 @@ __global__ __launch_bounds__(64 * HEADT_WAVES) void eps_fwd_head_q2reg_t_k(const
       tmp[i] = core[(long long)ab * p.O + (o < p.O ? o : 0)];
     }
     if (e0 == 0 && wv == 0) bias_v = (float)bias[(lane & 15) < p.Cout ? (lane & 15) : 0];
+#if DCTN_FWD_EARLY_WINDOW
+    // the wave's first window of the first group (a static ticket) goes out behind the core's loads as well
+    if (e0 == 0) {
+      first_ticket(nsteps0, s, voff_x, toff);
+      issue_window<S, N, true, ROWS>(rs_x, voff_x, (unsigned)(b0 + s) * p.s1b, p, raw);
+    }
+#endif
+#if DCTN_FWD_POS_TABLE
+    if (e0 == 0 && tid < (p.npg + 1) * 64) {   // the table: arithmetic while the loads above are in flight
+      unsigned vx, t;
+      lane_at(tid, vx, t);
+      pos_tab[tid] = u32x2{vx, t};
+    }
+#endif
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int e = e0 + tid + i * 64 * HEADT_WAVES, o = e % OP, ab = e / OP, bb = ab % BN, aa = ab / BN;
@@ -938,14 +996,6 @@ __global__ __launch_bounds__(64 * HEADT_WAVES) void eps_fwd_head_q2reg_t_k(const
       cf[t][s] = *reinterpret_cast<const bf16x8*>(&cs[((t * KS + s) * 64 + lane) * 8]);
   DCTN_STAMP(p, 1);
 
-  auto lane_at = [&](int pg, bool live, unsigned& voff_x, unsigned& voff_o, int& pos) {
-    pos = pg * 64 + lane;
-    const bool valid = live && pos < p.P;
-    const unsigned pu = (unsigned)(pos < p.P ? pos : p.P - 1);
-    const unsigned ho = fdiv(pu, p.div_wo), wo = pu - ho * (unsigned)p.Wo;
-    voff_x = valid ? ho * p.s2b + wo * p.s3b : p.x_bytes;
-    voff_o = valid ? pu * (unsigned)(OP * 2) : p.o_bytes;
-  };
   auto draw = [&]() {
     unsigned v = 0;
     if (lane == 0) v = __hip_atomic_fetch_add(&step_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -955,33 +1005,45 @@ __global__ __launch_bounds__(64 * HEADT_WAVES) void eps_fwd_head_q2reg_t_k(const
   for (int g0 = b0; g0 < b1; g0 += HEADT_GS) {
     const int ng = g0 + HEADT_GS < b1 ? HEADT_GS : b1 - g0;
     const int nsteps = ng * p.npg;
-    if (tid == 0) step_ctr = 2 * HEADT_WAVES;   // steps 0 .. 31 are dealt: wave w starts with w and w + 16
-    __syncthreads();
+    // ticket -> sample of the group and the lane's offsets; a dead ticket (past the group's steps): sample 0, no position
+    auto locate = [&](int ticket, int& s, unsigned& voff_x, unsigned& toff) {
+      const bool live = ticket < nsteps;
+#if DCTN_FWD_POS_TABLE
+      const int sq = (int)(((unsigned)ticket * p.npg_rcp) >> 16), pg = ticket - sq * p.npg;
+      s = live ? sq : 0;
+      const u32x2 e = pos_tab[(live ? pg : p.npg) * 64 + lane];
+      voff_x = e.x;
+      toff = e.y;
+#else
+      const int sq = ticket / p.npg, pg = ticket - sq * p.npg;
+      s = live ? sq : 0;
+      lane_at(live ? pg * 64 + lane : p.P, voff_x, toff);
+#endif
+    };
+    // (built and dropped in round 11: the first window sent in FRONT of the core staging, and at the end of the group
+    //  before for later groups: the core fragments came 0.17 us later, the step was 0.16 us slower - NOTEBOOK, "critical
+    //  path of cfg2".  DCTN_FWD_EARLY_WINDOW sends the first group's BEHIND the core's loads, in the prologue above.)
+    if (!DCTN_FWD_EARLY_WINDOW || g0 != b0) {
+      if (tid == 0) step_ctr = 2 * HEADT_WAVES;   // steps 0 .. 31 are dealt: wave w starts with w and w + 16
+      __syncthreads();
+      first_ticket(nsteps, s, voff_x, toff);
+      issue_window<S, N, true, ROWS>(rs_x, voff_x, (unsigned)(g0 + s) * p.s1b, p, raw);
+    }
     int cur = wv, nxt = wv + HEADT_WAVES;
-    int s = cur / p.npg, pg = cur - s * p.npg, pos;
-    unsigned voff_x, voff_o;
-    lane_at(pg, cur < nsteps, voff_x, voff_o, pos);
-    RawWindow<S, N, true, ROWS> raw;
-    // (built and dropped: this first window - a static ticket - sent in front of the core staging, and at the end of
-    //  the group before for later groups: 122 VGPRs, no scratch; in the stamps the core fragments came 0.17 us later,
-    //  the first step was done 0.18 us earlier and the step was 0.16 us SLOWER - NOTEBOOK, "critical path of cfg2")
-    issue_window<S, N, true, ROWS>(rs_x, voff_x, (unsigned)(g0 + (cur < nsteps ? s : 0)) * p.s1b, p, raw);
 #ifdef DCTN_STAMPS
     bool first_step = true;
 #endif
     while (cur < nsteps) {
       float xv[N][2];
       unpack_window<S, N, true, ROWS>(raw, xv);
-      const unsigned vo = voff_o, so = (unsigned)(g0 + s) * p.o_s1b;
-      short* trow = ftile + s * LP + (pos < p.P ? pos : 0) * OP;
-      const bool tvalid = pos < p.P;
+      const unsigned vo = toff, so = (unsigned)(g0 + s) * p.o_s1b;
+      const bool tvalid = toff != POS_NONE;
+      short* trow = reinterpret_cast<short*>(reinterpret_cast<char*>(ftile + s * LP) + toff);   // used under tvalid only
       {  // the wave's next step: its window goes out before this step's arithmetic (past the last step every lane is out
          // of range: zeros, no control flow around the loads); and the ticket of the step after it
         cur = nxt;
-        s = cur / p.npg;
-        pg = cur - s * p.npg;
-        lane_at(pg, cur < nsteps, voff_x, voff_o, pos);
-        issue_window<S, N, true, ROWS>(rs_x, voff_x, (unsigned)(g0 + (cur < nsteps ? s : 0)) * p.s1b, p, raw);
+        locate(cur, s, voff_x, toff);
+        issue_window<S, N, true, ROWS>(rs_x, voff_x, (unsigned)(g0 + s) * p.s1b, p, raw);
         nxt = draw();
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -2120,6 +2182,7 @@ void fill_mp(MfmaP& m, const EpsP& p, const void* x, int dtype) {
   m.C = p.C; m.B = p.B; m.K = p.K; m.O = p.O; m.Ho = p.Ho; m.Wo = p.Wo;
   m.P = p.Ho * p.Wo;
   m.npg = (m.P + 63) / 64;
+  m.npg_rcp = (65536u + (unsigned)m.npg - 1u) / (unsigned)m.npg;   // exact for tickets below 2^16 / npg
   m.spc = 1; m.nchunks = p.B;
   m.o_s1b = (unsigned)((long long)m.P * p.O * esz);
   m.o_bytes = (unsigned)(p.Wn * p.O * esz);
