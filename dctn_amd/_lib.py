@@ -32,6 +32,7 @@ BATCH_IDENTITY_ORDER, BATCH_PAD_TAIL = 1, 2  # `flags` of dctn_batch_draw
 # Python side only: the source kind of `DeviceBatches.from_colour`, which goes through dctn_batch_draw_cols /
 # dctn_batch_gather_cols (entry points of their own: the C `src_kind` stays 0 / 1)
 BATCH_SRC_COLOUR = 2
+TRACE_HAS_REG, TRACE_HAS_GUARD, TRACE_HAS_ADAM, TRACE_HAS_SOURCE = 1, 2, 4, 8   # DCTN_TRACE_HAS_*: a record's `present`
 AUG_HFLIP = 1   # DCTN_AUG_HFLIP: `aug_flags` of dctn_batch_draw_aug / dctn_batch_draw_cols_aug
 
 _DTYPE_CODE = {torch.float32: F32, torch.float64: F64, torch.bfloat16: BF16}
@@ -90,6 +91,9 @@ SIGNATURES = {
                                          c_int, c_int, c_void]),
     "dctn_sgd_l2_step_master_guarded": (c_int, [c_void] * 6 + [c_i64, c_i64, ctypes.c_float, ctypes.c_float,
                                                 ctypes.c_float, c_int, c_void]),
+    "dctn_step_trace_head_bytes": (c_size, []),
+    "dctn_step_trace_record_bytes": (c_size, []),
+    "dctn_step_trace_record": (c_int, [c_void] * 9 + [c_int, c_i64, c_int, c_int, c_void]),
     "dctn_ce_score_accumulate": (c_int, [c_void, c_void, c_void, c_i64, c_int, c_int, c_void]),
     "dctn_core_dropout_state_bytes": (c_size, []),
     "dctn_core_dropout_fwd": (c_int, [_PtrP, _PtrP, _I64P, c_int, c_void, c_void, c_void, c_int, c_void]),

@@ -253,7 +253,7 @@ class Snapshot:
         return path
 
 
-def _tensor_regions(model, optimizer, batch_source, guard):
+def _tensor_regions(model, optimizer, batch_source, guard, trace=None):
     """``(regions, model entries, optimizer kind)``: the named device tensors of a run, in file order."""
     from . import training
 
@@ -294,6 +294,9 @@ def _tensor_regions(model, optimizer, batch_source, guard):
         regions.append(("guard.block", guard._block))
     if batch_source is not None:
         regions.append(("batch_source.state", batch_source._state))
+    if trace is not None:
+        regions.append(("trace.head", trace._head))
+        regions.append(("trace.ring", trace._ring))
     return regions, entries, kind
 
 
@@ -302,8 +305,10 @@ class RunState:
     moments (or the momentum buffer), the master copy, the 16-byte step block and ``sq_sum``; every entry of the model's
     state_dict that does not live in the flat buffer (the buffer ``p``; without an optimizer every parameter) as a region
     of its own; ``model._dropout_state`` when the fused dropout is on; ``guard._block`` (``guard`` defaults to the
-    optimizer's); ``batch_source._state``.  The host scalars travel in the manifest: the hyper-parameters and ``lr``,
-    `FlatSGD`'s step count, the source's ``n`` / ``batch_size`` / ``seed``, ``guard.max_norm``.
+    optimizer's); ``batch_source._state``; with ``trace`` (a `training.StepTrace`) its head and ring as ``trace.head`` /
+    ``trace.ring``, so that a resumed run continues its ``seq`` (without the argument the region list is unchanged).  The
+    host scalars travel in the manifest: the hyper-parameters and ``lr``, `FlatSGD`'s step count, the source's ``n`` /
+    ``batch_size`` / ``seed``, ``guard.max_norm``.
 
     ``snapshot(extras)`` never blocks the host: it enqueues the gather on the current stream (one launch per 16 regions)
     and the copy of arena and digests to pinned memory on a side stream behind an event; the next ``snapshot()`` makes the
@@ -311,11 +316,12 @@ class RunState:
     dtypes, shapes and digests on the host before it writes anything, then uploads and scatters in place and sets the
     host mirrors; it returns the extras.  Every region must start at a multiple of 4 bytes (NotImplementedError)."""
 
-    def __init__(self, model: torch.nn.Module, optimizer=None, *, batch_source=None, guard=None):
+    def __init__(self, model: torch.nn.Module, optimizer=None, *, batch_source=None, guard=None, trace=None):
         if guard is None:
             guard = getattr(optimizer, "guard", None)
         self.model, self.optimizer, self.batch_source, self.guard = model, optimizer, batch_source, guard
-        regions, self._model_entries, self._kind = _tensor_regions(model, optimizer, batch_source, guard)
+        self.trace = trace
+        regions, self._model_entries, self._kind = _tensor_regions(model, optimizer, batch_source, guard, trace)
         if not regions:
             raise ValueError("RunState: nothing to save")
         self.device = L.require_device(*(t for _, t in regions))
@@ -443,6 +449,10 @@ class RunState:
                 raise RuntimeError(f"{path}: region {r['name']!r} was damaged on its way to the device: the scatter read "
                                    f"the digest {(int(s1), int(s2))}, the manifest says {(r['s1'], r['s2'])}")
         self._set_host_mirrors(manifest["host"])
+        if self.trace is not None:   # head and ring came back with their regions: the records before the head count as read
+            head = next(r for r in manifest["regions"] if r["name"] == "trace.head")
+            done = int(arena[head["offset"]: head["offset"] + 4].view("<u4")[0])
+            self.trace._last_read, self.trace.lost = done, 0
         return manifest["extras"]
 
     def _set_host_mirrors(self, host: Dict[str, Any]) -> None:

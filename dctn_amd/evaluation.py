@@ -62,6 +62,9 @@ class GraphedScore:
     replays: the source's device counter does the walking, every batch has the full shape, and the rows past the last
     sample are padding the score kernel skips (label -100).  The graph's size and capture time do not depend on the data
     set.  Same numbers as `score_fused` fed the same padded batches, bit for bit.
+    ``GraphedScore.with_batches_per_launch(model, src, k)`` (k must divide ``src.padded_steps``: ValueError) captures k
+    batches back to back, so a pass is ``padded_steps / k`` launches; the batches are added to the three sums in the same
+    order, so the sums are those of the per-batch form, bit for bit.
 
     The constructor runs ``warmup`` eager batches (kernel attributes, the allocator), puts the source's counter back to 0
     with ``load_state_dict`` and captures; it restores ``model.training``, as every pass does.  ``src`` belongs to this
@@ -81,10 +84,25 @@ class GraphedScore:
     """
 
     def __init__(self, model, src, warmup: int = 1):
+        self._build(model, src, warmup, 1)
+
+    @classmethod
+    def with_batches_per_launch(cls, model, src, batches_per_launch: int, warmup: int = 1) -> "GraphedScore":
+        """A scorer whose graph holds ``batches_per_launch`` batches (the constructor's form holds one)."""
+        self = cls.__new__(cls)
+        self._build(model, src, warmup, batches_per_launch)
+        return self
+
+    def _build(self, model, src, warmup: int, batches_per_launch: int) -> None:
         from . import _lib as L
 
         if src.shuffle:
             raise ValueError("GraphedScore walks a sequential source: build it with shuffle=False")
+        k = int(batches_per_launch)
+        if k != batches_per_launch or k < 1 or src.padded_steps % k != 0:
+            raise ValueError(f"batches_per_launch must divide the source's padded_steps ({src.padded_steps}), got "
+                             f"{batches_per_launch!r}: a pass is a whole number of launches")
+        self.batches_per_launch = k
         assert warmup >= 1, "capture needs at least one eager batch first (kernel attributes, lazy initialisation)"
         self.model, self.src, self._L = model, src, L
         self.rows = self.correct = None
@@ -105,7 +123,8 @@ class GraphedScore:
             src.load_state_dict(start)   # outside the capture: a pass starts at 0 (mod padded_steps)
             self.graph = torch.cuda.CUDAGraph()
             with torch.no_grad(), torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                self._one_batch()
+                for _ in range(k):   # back to back on the one capture stream: a single chain
+                    self._one_batch()
         finally:
             model.train(was_training)
 
@@ -122,7 +141,7 @@ class GraphedScore:
     def launch(self) -> None:
         """Enqueues one pass on the current stream; does not wait for it."""
         self.acc.zero_()
-        for _ in range(self.src.padded_steps):
+        for _ in range(self.src.padded_steps // self.batches_per_launch):
             self.graph.replay()
 
     def read(self) -> Tuple[float, float]:

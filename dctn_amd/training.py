@@ -92,15 +92,46 @@ class GraphedTrainStep:
     counter go on advancing meanwhile.  The guard counts its checks from the first warm-up iteration, as the source
     counts its draws, so (both fresh at construction) ``batch_source.expected_indices(guard.read()["bad_step"])`` names
     the batch that set the latch.  ``guard.max_norm`` may be assigned and ``guard.reset()`` called between replays.
+
+    ``trace`` (a `StepTrace`): every iteration - the warm-up ones too, as they advance every other counter - ends with
+    ``trace.record(...)`` behind ``optimizer.step()`` (in the split data-parallel form at the end of the optimizer's
+    graph ``g_opt``): one 64-byte record per iteration in a ring on the device, holding the loss, the rows of the batch and
+    how many were classified correctly, the guard's norm / coefficient / latch, Adam's step count and rate and the
+    source's counter.  ``trace.read()`` fetches the records whenever the host likes.  In a data-parallel run every rank
+    records its own shard's loss and counts.
+
+    ``iters_per_launch=K`` > 1: the one graph holds K whole iterations back to back (draw, forward, loss, backward, the
+    in-graph all-reduce if there is one, optimizer step, trace record) as a single chain of nodes, and one call runs K
+    iterations for one graph launch from the host.  It needs a ``batch_source`` (ValueError) and, with a reducer, the
+    all-reduce inside the graph (ValueError naming ``graph_allreduce``: the split form cannot work).  The call returns
+    the LAST iteration's static buffers and ``"iters"`` = K (a step of one iteration per launch returns the keys it always
+    returned; ``step.iters_per_launch`` holds K either way); what the inner iterations saw is in the trace.  The graph's
+    memory pool does not grow K-fold: the allocator gives the blocks an iteration has freed to the next one.  The
+    host's settings - ``optimizer.lr = ...``, ``guard.max_norm = ...``, ``guard.reset()`` - are device writes in stream
+    order BETWEEN launches: they take effect at a launch boundary, for all K iterations of the next launch.  Once the
+    guard halts inside a launch, the rest of that launch runs forward and backward and applies nothing, as replays do.
+    With the defaults (K = 1, no trace) the captured graph is exactly what it was without these arguments.
     """
 
     def __init__(self, model: torch.nn.Module, example_x: Optional[Tensor], example_y: Optional[Tensor],
                  loss_fn: Callable[[Tensor, Tensor], Tensor], optimizer: torch.optim.Optimizer,
                  reg_fn: Optional[Callable[[torch.nn.Module], Tensor]] = None, reg_coeff: float = 0.0,
                  reducer: Optional[ddp.FlatGradAllReducer] = None, warmup: int = 3,
-                 graph_allreduce: Optional[bool] = None, batch_source=None):
+                 graph_allreduce: Optional[bool] = None, *, iters_per_launch: int = 1, trace=None, batch_source=None):
         self.model, self.optimizer, self.reducer = model, optimizer, reducer
         self.batch_source = batch_source
+        K = int(iters_per_launch)
+        if K != iters_per_launch or K < 1:
+            raise ValueError(f"iters_per_launch must be an integer >= 1, got {iters_per_launch!r}")
+        self.iters_per_launch, self.trace = K, trace
+        if K > 1:
+            if batch_source is None:
+                raise ValueError("iters_per_launch > 1 needs a batch_source: the inner iterations of a launch draw their "
+                                 "own batches, the host cannot hand them in")
+            if reducer is not None and (reducer.world > 1 or not reducer.skip_single_rank) and graph_allreduce is False:
+                raise ValueError("iters_per_launch > 1 needs the gradient all-reduce inside the graph: graph_allreduce=False "
+                                 "(forward + backward graph, eager all-reduce, optimizer graph) cannot run K iterations in "
+                                 "one launch")
         if batch_source is None:
             self.x, self.y = example_x.clone(), example_y.clone()
         else:
@@ -115,6 +146,10 @@ class GraphedTrainStep:
                                                  dtype=some.dtype, local_rank=dev.index)
                 graph_allreduce = ddp.all_ranks_agree(ok, dev)
         graph_allreduce = bool(graph_allreduce) and reduces
+        if K > 1 and reduces and not graph_allreduce:
+            raise ValueError("iters_per_launch > 1 needs the gradient all-reduce inside the graph, and the capture probe "
+                             "said no on this machine (graph_allreduce): use iters_per_launch=1, or a reducer whose "
+                             "all-reduce is a plain kernel launch (algorithm='direct') with graph_allreduce=True")
         split = reduces
 
         def fwd_bwd():
@@ -134,16 +169,34 @@ class GraphedTrainStep:
             total.backward(unit_seed(dev, total.dtype))
             return out, loss, reg
 
+        def record(out, loss, reg):   # the iteration's last launch; nothing at all without a trace
+            if trace is not None:
+                trace.record(out, self.y, loss, reg=None if reg is no_reg else reg,
+                             guard=getattr(optimizer, "guard", None), optimizer=optimizer, batch_source=batch_source)
+
+        def iterations():   # K whole iterations back to back on the one capture stream: a single chain, no forks
+            last = None
+            for _ in range(K):
+                del last   # the iteration before is over: its buffers go back to the graph's pool before the next one asks
+                last = fwd_bwd()
+                if reduces:
+                    reducer()
+                optimizer.step()
+                record(*last)
+            return last
+
         no_reg = torch.zeros((), dtype=torch.float32, device=dev)
         assert warmup >= 1, "capture needs at least one eager iteration first (lazy optimizer state, kernel attributes)"
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             for _ in range(warmup):
-                fwd_bwd()
+                last = fwd_bwd()
                 if split:
                     reducer()
                 optimizer.step()
+                record(*last)
+                del last   # nothing of a warm-up iteration (its autograd graph) is alive when the capture begins
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         self.g_opt = None
@@ -152,9 +205,7 @@ class GraphedTrainStep:
             try:   # the whole iteration, collective included, as one graph
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    self.out, self.loss, self.reg = fwd_bwd()
-                    reducer()
-                    optimizer.step()
+                    self.out, self.loss, self.reg = iterations()
                 self.g_main, self.allreduce_in_graph, split = g, True, False
                 return
             except Exception as e:
@@ -163,13 +214,15 @@ class GraphedTrainStep:
                                    "graph_allreduce=False") from e
         self.g_main = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_main, capture_error_mode="thread_local"):
-            self.out, self.loss, self.reg = fwd_bwd()
-            if not split:
-                optimizer.step()
+            if split:   # (K == 1: checked above)
+                self.out, self.loss, self.reg = fwd_bwd()
+            else:
+                self.out, self.loss, self.reg = iterations()
         if split:
             self.g_opt = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.g_opt, capture_error_mode="thread_local"):
                 optimizer.step()
+                record(self.out, self.loss, self.reg)
 
     def __call__(self, x: Optional[Tensor] = None, y: Optional[Tensor] = None) -> Dict[str, Tensor]:
         if self.batch_source is not None:
@@ -189,6 +242,8 @@ class GraphedTrainStep:
         result = {"output": self.out, "loss": self.loss, "reg_term": self.reg}
         if self.batch_source is not None:
             result["indices"] = self.indices
+        if self.iters_per_launch > 1:   # (one iteration per launch returns the keys it always returned)
+            result["iters"] = self.iters_per_launch
         return result
 
 
@@ -376,6 +431,120 @@ class GradGuard:
         threshold = torch.tensor(float(max_norm), dtype=torch.float32).double()
         coef = (threshold / (norm.double() + 1e-6)).to(torch.float32)
         return True, min(1.0, float(coef)), float(norm)
+
+
+class StepTrace:
+    """The device-side step trace (`dctn_step_trace_record`, include/dctn_amd.h): a 16-byte head {records_done, ...} and a
+    ring of ``capacity`` 64-byte records on the device.  ``record(...)`` enqueues ONE launch that writes the next slot and
+    advances the head - it reads nothing on the host, so it can be captured, and replays fill consecutive slots
+    (``GraphedTrainStep(..., trace=...)`` ends every iteration with it).  ``read()`` copies head and ring in stream order
+    and returns the records not yet returned as a numpy structured array (`StepTrace.RECORD`) ordered by ``seq``;
+    ``lost`` is then the number of records that were overwritten before they were read (the ring holds the last
+    ``capacity``).  ``capacity`` may be any number >= 1.  ``state_dict()`` / ``load_state_dict()`` carry the head, so a
+    resumed run continues its ``seq`` (`checkpoint.RunState(..., trace=...)` carries head and ring in place).
+
+    Fields of a record: ``seq``; ``present`` (bits `PRESENT`: which of reg / guard / adam / source were given; an absent
+    block's fields are 0); ``loss`` and ``reg`` (the float32 scalars' bits); ``rows`` (labels other than -100) and
+    ``correct`` (label = lowest index of the row's maximum; `dctn_ce_score_accumulate`'s rules); ``grad_norm``, ``coef``,
+    ``halted``, ``bad_step`` (the guard's block after this iteration's check); ``opt_steps_done``, ``lr`` (`FlatAdam`'s
+    block after the step); ``batches_done`` (the source's counter after the iteration's draw)."""
+
+    RECORD = None   # the numpy dtype of a record, set below the class (64 bytes)
+    PRESENT = {"reg": L.TRACE_HAS_REG, "guard": L.TRACE_HAS_GUARD, "adam": L.TRACE_HAS_ADAM, "source": L.TRACE_HAS_SOURCE}
+
+    def __init__(self, device, capacity: int = 4096):
+        if int(capacity) != capacity or capacity < 1:
+            raise ValueError(f"StepTrace: capacity must be an integer >= 1, got {capacity!r}")
+        self.device, self.capacity = torch.device(device), int(capacity)
+        lib = L.lib()
+        assert lib.dctn_step_trace_head_bytes() == 16 and lib.dctn_step_trace_record_bytes() == 64
+        self._head = torch.zeros(4, dtype=torch.int32, device=self.device)
+        self._ring = torch.zeros(16 * self.capacity, dtype=torch.int32, device=self.device)
+        self._last_read = 0   # records returned so far = the seq the next read() starts at
+        self.lost = 0
+
+    def record(self, logits: Tensor, labels: Tensor, loss: Tensor, reg: Optional[Tensor] = None,
+               guard: Optional["GradGuard"] = None, optimizer=None, batch_source=None) -> None:
+        """Enqueues the launch on the current stream.  ``logits`` (B, C) float32 / bfloat16, ``labels`` int64, ``loss`` and
+        ``reg`` float32 device scalars (a ``reg`` of another dtype is cast first: one more launch).  The Adam block is
+        taken from a `FlatAdam`; a `FlatSGD` (or any other optimizer) has no device block and passes none."""
+        dev = L.require_device(logits, labels, loss)
+        if logits.ndim != 2 or labels.shape != (logits.shape[0],) or labels.dtype != torch.int64:
+            raise TypeError("StepTrace.record: logits (batch, classes) and int64 labels (batch,)")
+        if loss.dtype != torch.float32 or loss.numel() != 1:
+            raise TypeError("StepTrace.record: the loss must be a float32 scalar on the logits' device")
+        if not (logits.is_contiguous() and labels.is_contiguous()):
+            raise TypeError("StepTrace.record: logits and labels must be contiguous (a copy here would be a launch per step)")
+        if reg is not None:
+            if reg.numel() != 1:
+                raise TypeError("StepTrace.record: reg must be a scalar")
+            reg = reg.detach().to(device=dev, dtype=torch.float32)
+        adam = getattr(optimizer, "_state", None) if isinstance(optimizer, FlatAdam) else None
+        L.check(L.lib().dctn_step_trace_record(
+            logits.data_ptr(), labels.data_ptr(), loss.data_ptr(), None if reg is None else reg.data_ptr(),
+            None if guard is None else guard._block.data_ptr(), None if adam is None else adam.data_ptr(),
+            None if batch_source is None else batch_source._state.data_ptr(), self._head.data_ptr(),
+            self._ring.data_ptr(), self.capacity, logits.shape[0], logits.shape[1], L.dtype_code(logits),
+            L.stream_ptr(dev)), "step trace")
+
+    @staticmethod
+    def decode(head_bytes, ring_bytes, capacity: int, last_read: int):
+        """The slot arithmetic on the host: ``(records, lost, records_done)`` for the bytes of a head and a ring.  The ring
+        holds the records ``seq`` in [max(0, done - capacity), done), record ``seq`` in slot ``seq % capacity``; returned
+        are those with ``seq >= last_read``, in order; ``lost`` = how many records between ``last_read`` and the window's
+        start are gone.  A ``last_read`` past ``done`` (the head was put back to an earlier state) returns nothing."""
+        import numpy as np
+
+        capacity, last_read = int(capacity), int(last_read)
+        if capacity < 1 or last_read < 0:
+            raise ValueError(f"StepTrace.decode: capacity >= 1 and last_read >= 0, got {capacity}, {last_read}")
+        head = np.frombuffer(bytes(head_bytes), dtype="<u4")
+        ring = np.frombuffer(bytes(ring_bytes), dtype=StepTrace.RECORD)
+        if head.size != 4 or ring.size != capacity:
+            raise ValueError(f"StepTrace.decode: a head of 16 bytes and a ring of {capacity} records of 64 bytes, got "
+                             f"{len(bytes(head_bytes))} and {len(bytes(ring_bytes))} bytes")
+        done = int(head[0])
+        start = max(0, done - capacity)
+        lost = max(0, start - last_read)
+        seqs = np.arange(max(start, last_read), done, dtype=np.int64)
+        records = ring[seqs % capacity].copy()
+        if records.size and not np.array_equal(records["seq"].astype(np.int64), seqs):
+            raise RuntimeError("StepTrace.decode: the ring's records do not carry the sequence numbers the head implies "
+                               "(head and ring were not read at one point of the stream)")
+        return records, lost, done
+
+    def read(self):
+        """The records not yet returned, ordered by ``seq`` (copies head and ring in stream order: it synchronises)."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("StepTrace.read() copies to the host: not during a graph capture")
+        both = torch.cat((self._head, self._ring)).cpu().numpy()   # one copy kernel, one transfer: one point of the stream
+        records, self.lost, done = self.decode(both[:4].tobytes(), both[4:].tobytes(), self.capacity, self._last_read)
+        self._last_read = done
+        return records
+
+    def state_dict(self) -> Dict[str, Any]:
+        words = [int(v) & 0xFFFFFFFF for v in self._head.cpu().tolist()]
+        return {"records_done": words[0], "capacity": self.capacity}
+
+    def load_state_dict(self, state: Dict[str, Any]) -> None:
+        """Puts the head back (in place: a captured graph keeps its pointer); the records before it count as read."""
+        done = int(state["records_done"]) & 0xFFFFFFFF
+        host = torch.tensor([done - (1 << 32) if done >= 1 << 31 else done, 0, 0, 0], dtype=torch.int32)
+        with torch.no_grad():
+            self._head.copy_(host)
+        self._last_read, self.lost = done, 0
+
+
+def _trace_record_dtype():
+    import numpy as np
+
+    return np.dtype([("seq", "<u4"), ("present", "<u4"), ("loss", "<f4"), ("reg", "<f4"), ("rows", "<i4"),
+                     ("correct", "<i4"), ("grad_norm", "<f4"), ("coef", "<f4"), ("halted", "<u4"), ("bad_step", "<i4"),
+                     ("opt_steps_done", "<i4"), ("lr", "<f4"), ("batches_done", "<u4"), ("pad", "<u4", (3,))])
+
+
+StepTrace.RECORD = _trace_record_dtype()
+assert StepTrace.RECORD.itemsize == 64
 
 
 class _FlatOptimizer:
@@ -747,6 +916,70 @@ def train(dl, model, optimizer, dev, loss_fn, reg_fn, reg_coeff: float, at_iter_
         if st_it["stop"]:
             break
     return st_x, st_it
+
+
+def train_graphed(step: "GraphedTrainStep", n_iters: int, after_launch=(), first_iter: int = 0) -> Tuple[StX, StIt]:
+    """The replay-loop counterpart of `train` for a `GraphedTrainStep` built with a ``batch_source``: calls ``step()``
+    until ``n_iters`` iterations are done (a launch runs ``step.iters_per_launch`` = K of them, so the last launch may
+    overshoot ``n_iters`` by up to K - 1), and after each launch runs the hooks ``f(st_x, st_it)`` of ``after_launch``.
+    ``st_it`` holds what the launch returned (``output``, ``loss``, ``reg_term``, ``indices``: the static buffers of its
+    LAST iteration), ``stop`` and ``num_iters_done`` = the number of the last finished iteration, counted from
+    ``first_iter`` as `train` counts (a run resumed from a snapshot passes ``extras["num_iters_done"] + 1``); ``st_x`` holds
+    ``model``, ``optimizer``, ``step`` and ``dev``.  A hook stops the loop by setting ``st_it["stop"]``; with several
+    ranks the flag is OR-ed over them, as in `train`.  Returns the two dictionaries of the last launch.
+
+    `checkpoint.RunCheckpointer`, `make_stopper_on_device_halt`, `evaluation.make_evaluation_hook` and
+    `make_trace_logger` work unchanged as such hooks.  Hooks run at launch boundaries only and ``num_iters_done``
+    advances by K between two calls, so the period of a hook gated with `every_n_iters_intervals` should be a multiple
+    of K - any other period never (or irregularly) coincides with a launch boundary."""
+    if step.batch_source is None:
+        raise ValueError("train_graphed drives a GraphedTrainStep that draws its own batches: build it with a batch_source")
+    K = int(step.iters_per_launch)
+    dev = step.x.device
+    st_x: StX = dict(model=step.model, optimizer=step.optimizer, step=step, dev=dev, after_launch=list(after_launch))
+    st_it: StIt = {}
+    world = _world()
+    done = 0
+    while done < int(n_iters):
+        out = step()
+        done += K
+        st_it = dict(out, num_iters_done=int(first_iter) + done - 1, stop=False)
+        for hook in tuple(st_x["after_launch"]):   # a hook may remove itself
+            hook(st_x, st_it)
+        if world > 1:
+            flag = torch.tensor([1.0 if st_it["stop"] else 0.0], device=dev)
+            dist.all_reduce(flag, op=dist.ReduceOp.MAX)
+            st_it["stop"] = bool(flag.item() > 0)
+        if st_it["stop"]:
+            break
+    return st_x, st_it
+
+
+class _TraceLogger:
+    """Hook for `train_graphed`: every ``every`` calls (launches) it reads the trace - the one synchronisation it makes -
+    and hands ``sink`` the new records (a `StepTrace.RECORD` array, possibly empty) and the number lost since the last
+    read."""
+
+    def __init__(self, trace: "StepTrace", every: int, sink: Callable[..., None]):
+        assert every >= 1
+        self.trace, self.every, self.sink = trace, int(every), sink
+        self._calls = 0
+
+    def __call__(self, st_x: StX, st_it: StIt) -> None:
+        self._calls += 1
+        if self._calls % self.every == 0:
+            self.flush()
+
+    def flush(self) -> None:
+        """Reads now (call it when the loop ends, for the launches after the last multiple of ``every``)."""
+        records = self.trace.read()
+        self.sink(records, self.trace.lost)
+
+
+def make_trace_logger(trace: "StepTrace", every: int, sink: Callable[..., None]) -> Callable[[StX, StIt], None]:
+    """``sink(records, lost)`` is called every ``every`` launches with the records written since the last call.  Choose
+    ``trace.capacity >= every * iters_per_launch`` and nothing is lost."""
+    return _TraceLogger(trace, every, sink)
 
 
 def every_n_iters_intervals(*intervals):

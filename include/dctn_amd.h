@@ -505,6 +505,57 @@ int dctn_ce_score_accumulate(const void* logits, const void* labels, void* acc, 
                              void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Step trace (version 509): ONE launch at the end of a training iteration writes one 64-byte record into a ring on the
+ * DEVICE and advances a device counter, so that a captured graph which holds the launch - once, or K times for K
+ * iterations per graph launch - fills consecutive slots on its replays and the host reads nothing per iteration.
+ *
+ * `head`: dctn_step_trace_head_bytes() = 16 bytes, 16-byte aligned, laid out as
+ *   uint32 records_done   records written so far; the launch reads seq = records_done and leaves records_done + 1
+ *   uint32 ticket         0 (the launch is one workgroup and draws no ticket; the word is kept for a split form)
+ *   uint32 reserved[2]    0
+ * The caller zeroes it once and may read or write it in stream order between launches.
+ * `ring`: capacity records of dctn_step_trace_record_bytes() = 64 bytes, 16-byte aligned; capacity >= 1 may be any
+ * number, not only a power of two.  The launch writes slot seq % capacity.  (seq is 32 bits: when it wraps, the slot jumps
+ * for a capacity that is no power of two.)
+ *
+ * Record (little-endian, EVERY byte of the 64 written by every launch; a field whose block is absent is 0):
+ *   offset  0  uint32 seq
+ *           4  uint32 present         DCTN_TRACE_HAS_REG | _GUARD | _ADAM | _SOURCE: which optional blocks were given
+ *           8  float  loss            the bits of loss[0] (float32 device scalar)
+ *          12  float  reg             the bits of reg_or_null[0] (float32 device scalar)
+ *          16  int32  rows            rows of the batch whose label is not -100
+ *          20  int32  correct         of those, the rows whose label equals the LOWEST index among the row's maxima
+ *          24  float  grad_norm       guard block: last_norm   } the block of dctn_grad_guard_check (32 bytes) as it
+ *          28  float  coef            guard block: coef        } stands when the launch runs: placed after the
+ *          32  uint32 halted          guard block: halted      } optimizer step, it shows this iteration's check
+ *          36  int32  bad_step        guard block: bad_step    }
+ *          40  int32  opt_steps_done  Adam block (16 bytes, dctn_adam_l2_step): steps_done, after the step
+ *          44  float  lr              Adam block: lr
+ *          48  uint32 batches_done    batch source block (16 bytes, dctn_batch_draw): batches_done as read (after the
+ *                                     iteration's draw: the number of this batch + 1)
+ *          52  12 bytes of zero
+ * rows / correct follow dctn_ce_score_accumulate's rules exactly: logits (B, C) contiguous, DCTN_F32 / DCTN_BF16, labels
+ * int64; rows labelled -100 are skipped; any other label outside [0, C) counts as a wrong row; the maximum of a row is
+ * taken with fmaxf, so a NaN logit is never the maximum and a row of nothing but NaN is a wrong row.  Integer counts: the
+ * record is the same bits from run to run.
+ *
+ * Buffer contract: `head` (records_done) and the one addressed slot are written, with vector stores; nothing else is.
+ * Logits, labels, loss, reg and the three state blocks are only read.  No workgroup waits for another.  The call
+ * allocates nothing and synchronises nothing: it only enqueues and can be captured.  Return codes, decided on the host
+ * before any launch: DCTN_ERR_NULL (logits, labels, loss, head, ring); DCTN_ERR_BAD_SHAPE (B < 1, C < 1, capacity < 1);
+ * DCTN_ERR_BAD_DTYPE.  No workspace.  This launch does not report to dctn_last_kernel.
+ * ------------------------------------------------------------------------------------------ */
+#define DCTN_TRACE_HAS_REG 1
+#define DCTN_TRACE_HAS_GUARD 2
+#define DCTN_TRACE_HAS_ADAM 4
+#define DCTN_TRACE_HAS_SOURCE 8
+size_t dctn_step_trace_head_bytes(void);
+size_t dctn_step_trace_record_bytes(void);
+int dctn_step_trace_record(const void* logits, const void* labels, const void* loss, const void* reg_or_null,
+                           const void* guard_or_null, const void* adam_state_or_null, const void* batch_state_or_null,
+                           void* head, void* ring, int capacity, int64_t B, int C, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Component dropout of the EPS cores (version 502; reference: dctn/eps_plus_linear.py:139-143, `mask * core / p` with
  * mask ~ Bernoulli(p) per component of every core): ONE launch each way for all cores of a model, and a mask that is
  * stored nowhere - a pure function of (seed, draw, core number, element index).
