@@ -56,7 +56,7 @@ class _StringPlan:
     int arrays of the C-ABI, output size.  Rebuilding them on every call was a third of the host time of a small
     layer's forward."""
 
-    __slots__ = ("n", "shape_tuples", "outs", "bonds", "ph", "pw", "max_h", "max_w", "out_total", "C", "q", "ws",
+    __slots__ = ("n", "shape_tuples", "outs", "bonds", "ph", "pw", "max_h", "max_w", "out_total", "C", "q", "ws", "saved",
                  "outs_list", "bonds_list", "ph_list", "pw_list", "many_ok")
 
     def __init__(self, spec: SBSSpecString):
@@ -75,6 +75,7 @@ class _StringPlan:
         self.out_total = spec.out_total_quantum_dim_size
         self.C, self.q = spec.in_num_channels, spec.in_quantum_dim_size
         self.ws = {}   # (B, H, W, dtype code, backward) -> workspace bytes
+        self.saved = {}   # (B, H, W, dtype code) -> bytes of the saved forward states
         self.many_ok = {}   # ((B, H, W), partner plans) -> workspace bytes of the several-strings-per-launch path (0: unsupported)
 
 
@@ -88,34 +89,54 @@ def _plan(spec: SBSSpecString) -> _StringPlan:
     return plan
 
 
-def _workspace_bytes(plan: _StringPlan, B: int, H: int, W: int, code: int, backward: int) -> int:
-    """backward: 0 forward scratch, 1 backward scratch, 2 the forward states a training forward leaves for the backward
-    (0 bytes: this string's backward recomputes them)."""
+def _workspace_bytes(plan: _StringPlan, B: int, H: int, W: int, code: int, backward: bool) -> int:
+    """Scratch of the forward or of the backward."""
     key = (B, H, W, code, backward)
     nbytes = plan.ws.get(key)
     if nbytes is None:
-        if backward == 2:
-            nbytes = L.lib().dctn_convsbs_saved_states_bytes(plan.n, plan.outs, plan.bonds, plan.C, B, H, W, plan.q, plan.ph,
-                                                             plan.pw, code)
-        else:
-            nbytes = L.lib().dctn_convsbs_workspace_bytes(plan.n, plan.outs, plan.bonds, plan.C, B, H, W, plan.q,
-                                                          plan.ph, plan.pw, code, backward)
-        plan.ws[key] = nbytes
+        nbytes = plan.ws[key] = L.lib().dctn_convsbs_workspace_bytes(plan.n, plan.outs, plan.bonds, plan.C, B, H, W, plan.q,
+                                                                     plan.ph, plan.pw, code, int(backward))
     return nbytes
+
+
+def _saved_states_bytes(plan: _StringPlan, B: int, H: int, W: int, code: int) -> int:
+    """The forward states a training forward leaves for the backward (0 bytes: this string's backward recomputes them)."""
+    key = (B, H, W, code)
+    nbytes = plan.saved.get(key)
+    if nbytes is None:
+        nbytes = plan.saved[key] = L.lib().dctn_convsbs_saved_states_bytes(plan.n, plan.outs, plan.bonds, plan.C, B, H, W,
+                                                                           plan.q, plan.ph, plan.pw, code)
+    return nbytes
+
+
+def _core_grad_views(cores) -> list:
+    """The gradients of a string's cores as views of ONE flat buffer: the library zero-fills it with a single launch, and a
+    data-parallel reducer can all-reduce it in place."""
+    flat = torch.empty(sum(c.numel() for c in cores), dtype=cores[0].dtype, device=cores[0].device)
+    views, off = [], 0
+    for c in cores:
+        views.append(flat[off : off + c.numel()].view_as(c))
+        off += c.numel()
+    return views
+
+
+def _wanted(ctx, d_x, d_cores) -> tuple:
+    """What a backward returns: dX, nothing for the spec, and of the core gradients those that were asked for."""
+    needs = ctx.needs_input_grad[2:]
+    return (d_x, None, *(dc if need else None for dc, need in zip(d_cores or [None] * len(needs), needs)))
 
 
 _sbs_flags = 0
 
 
-class matrix_core_sweep:
-    """``with matrix_core_sweep(): ...`` - strings whose bonds are all <= 4 run on the matrix-core sweep
-    (convsbs_mfma.hip) instead of the register-resident sweep (convsbs_reg.hip) that is their default: the tests use it
-    to hold both kernel families against the same expected values on the same strings (`DCTN_SBS_MATRIX_CORE_SWEEP`)."""
+class _sbs_flag:
+    """``with <flag>(): ...`` sets one bit of the flags every ConvSBS call carries beside its dtype code."""
+    flag = 0
 
     def __enter__(self):
         global _sbs_flags
         self._saved = _sbs_flags
-        _sbs_flags |= L.SBS_MATRIX_CORE_SWEEP
+        _sbs_flags |= self.flag
         return self
 
     def __exit__(self, *exc):
@@ -124,22 +145,19 @@ class matrix_core_sweep:
         return False
 
 
-class wide_sweep:
+class matrix_core_sweep(_sbs_flag):
+    """``with matrix_core_sweep(): ...`` - strings whose bonds are all <= 4 run on the matrix-core sweep
+    (convsbs_mfma.hip) instead of the register-resident sweep (convsbs_reg.hip) that is their default: the tests use it
+    to hold both kernel families against the same expected values on the same strings (`DCTN_SBS_MATRIX_CORE_SWEEP`)."""
+    flag = L.SBS_MATRIX_CORE_SWEEP
+
+
+class wide_sweep(_sbs_flag):
     """``with wide_sweep(): ...`` - the backward of every string runs on the wide family (convsbs_wide.hip), the one
     strings whose core gradients do not fit one workgroup's LDS fall to, instead of the family that is their default: the
     tests hold it against the generic sweep and the expected values on strings both take (`DCTN_SBS_WIDE_SWEEP`).  The forward is
     unchanged, and the strings of a layer go one by one."""
-
-    def __enter__(self):
-        global _sbs_flags
-        self._saved = _sbs_flags
-        _sbs_flags |= L.SBS_WIDE_SWEEP
-        return self
-
-    def __exit__(self, *exc):
-        global _sbs_flags
-        _sbs_flags = self._saved
-        return False
+    flag = L.SBS_WIDE_SWEEP
 
 
 class _ConvSBSFunction(torch.autograd.Function):
@@ -162,13 +180,13 @@ class _ConvSBSFunction(torch.autograd.Function):
         code = L.dtype_code(x) | _sbs_flags
         # a forward that will be differentiated leaves its forward states (a buffer of its own, alive until the backward)
         # instead of having the backward's first quarter recompute them
-        saved_bytes = _workspace_bytes(plan, B, H, W, code, 2) if any(ctx.needs_input_grad) else 0
+        saved_bytes = _saved_states_bytes(plan, B, H, W, code) if any(ctx.needs_input_grad) else 0
         if saved_bytes > 0:
             states = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
             ws = states
         else:
             states = None
-            ws = L.workspace(_workspace_bytes(plan, B, H, W, code, 0), dev)
+            ws = L.workspace(_workspace_bytes(plan, B, H, W, code, False), dev)
         rc = L.check(
             L.lib().dctn_convsbs_fwd(x.data_ptr(), L.strides5(x), L.ptr_array(cores_c), out.data_ptr(), n,
                                      plan.outs, plan.bonds, plan.ph, plan.pw, C, B, H, W, q, ws.data_ptr(), ws.numel(), code,
@@ -197,16 +215,8 @@ class _ConvSBSFunction(torch.autograd.Function):
         need_dcores = any(ctx.needs_input_grad[2:])
         g = d_out.contiguous()
         d_x = torch.empty((C, B, H, W, q), dtype=x.dtype, device=dev) if need_dx else None
-        d_cores = None
-        if need_dcores:
-            # one flat buffer for the gradients of all cores of the string: the library zero-fills it with a single
-            # launch, and a data-parallel reducer can all-reduce it in place
-            flat = torch.empty(sum(c.numel() for c in cores_c), dtype=cores_c[0].dtype, device=dev)
-            d_cores, off = [], 0
-            for c in cores_c:
-                d_cores.append(flat[off : off + c.numel()].view_as(c))
-                off += c.numel()
-        ws = L.workspace(_workspace_bytes(plan, B, H, W, code, 1), dev)
+        d_cores = _core_grad_views(cores_c) if need_dcores else None
+        ws = L.workspace(_workspace_bytes(plan, B, H, W, code, True), dev)
         L.check(
             L.lib().dctn_convsbs_bwd_saved(
                 x.data_ptr(), L.strides5(x), L.ptr_array(cores_c), g.data_ptr(),
@@ -216,10 +226,7 @@ class _ConvSBSFunction(torch.autograd.Function):
                 L.stream_ptr(dev)),
             "ConvSBS backward",
         )
-        grads = [None] * n if d_cores is None else [
-            dc if need else None for dc, need in zip(d_cores, ctx.needs_input_grad[2:])
-        ]
-        return (d_x, None, *grads)
+        return _wanted(ctx, d_x, d_cores)
 
 
 class _ManyConvSBSFunction(torch.autograd.Function):
@@ -284,18 +291,8 @@ class _ManyConvSBSFunction(torch.autograd.Function):
             gs.append(torch.zeros((B, H - p.max_h, W - p.max_w, p.out_total), dtype=x.dtype, device=dev) if g is None
                       else g.contiguous())
         d_x = torch.empty((C, B, H, W, q), dtype=x.dtype, device=dev) if need_dx else None
-        d_cores = None
-        if need_dcores:
-            # one flat buffer per string (what a single string's backward produces too: a per-string reducer all-reduces in place)
-            d_cores, k = [], 0
-            for p in plans:
-                cs = cores_c[k : k + n]
-                flat = torch.empty(sum(c.numel() for c in cs), dtype=x.dtype, device=dev)
-                off = 0
-                for c in cs:
-                    d_cores.append(flat[off : off + c.numel()].view_as(c))
-                    off += c.numel()
-                k += n
+        # one flat buffer per string (what a single string's backward produces too: a per-string reducer all-reduces in place)
+        d_cores = [v for k in range(0, ns * n, n) for v in _core_grad_views(cores_c[k : k + n])] if need_dcores else None
         outs_arr, bonds_arr, ph_arr, pw_arr = _many_arrays(plans)
         nbytes = L.lib().dctn_convsbs_many_workspace_bytes(ns, n, outs_arr, bonds_arr, C, B, H, W, q, ph_arr, pw_arr, L.F32)
         ws = L.workspace(nbytes, dev)
@@ -306,10 +303,7 @@ class _ManyConvSBSFunction(torch.autograd.Function):
                 ws.data_ptr(), ws.numel(), L.F32, L.stream_ptr(dev)),
             "ManyConvSBS backward",
         )
-        grads = [None] * (ns * n) if d_cores is None else [
-            dc if need else None for dc, need in zip(d_cores, ctx.needs_input_grad[2:])
-        ]
-        return (d_x, None, *grads)
+        return _wanted(ctx, d_x, d_cores)
 
 
 def _many_arrays(plans):

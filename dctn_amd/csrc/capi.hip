@@ -89,8 +89,6 @@ int dctn_zero_async(void* ptr, size_t bytes, hipStream_t st) {
 
 static bool dtype_ok(int dtype) { return dtype == DCTN_F32 || dtype == DCTN_F64 || dtype == DCTN_BF16; }
 
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // the EpsP of a query: no tensor, so the strides of a contiguous-like dummy
 static bool eps_query_params(EpsP& p, int C, int B, int H, int W, int Q, int K, int O, int policy) {
   const int64_t dummy[5] = {0, 0, 0, 0, 1};
@@ -475,6 +473,168 @@ int dctn_eps_bwd_saved(const void* x, const int64_t x_strides[5], const void* co
   if (!saved) return DCTN_ERR_NULL;
   return eps_bwd_impl(x, x_strides, core, dY, saved, saved_bytes, dX, dCore, workspace, workspace_bytes, C, B, H, W, Q, K,
                       O, dtype, policy, stream);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------- ConvSBS routing
+// Every entry point walks its families top to bottom (DESIGN.md "ConvSBS routing"): DCTN_ERR_UNSUPPORTED = nothing written, ask the next.
+// bonds 5..16 go to the band family, except that under DCTN_SBS_MATRIX_CORE_SWEEP bonds up to 8 stay on the matrix-core
+// sweep (the tests hold both against the oracle)
+static bool band_family_first(const SbsShape& sh, int dtype_flags) {
+  int largest = 0;
+  for (int c = 0; c < sh.n; ++c) largest = sh.bond_sizes[c] > largest ? sh.bond_sizes[c] : largest;
+  return !((dtype_flags & DCTN_SBS_MATRIX_CORE_SWEEP) && largest <= 8);
+}
+
+constexpr int SBS_FLAGS = DCTN_SBS_MATRIX_CORE_SWEEP | DCTN_SBS_WIDE_SWEEP;
+
+extern "C" {
+
+size_t dctn_convsbs_workspace_bytes(int n_cores, const int* out_sizes, const int* bond_sizes, int C, int B, int H, int W, int q,
+                                    const int* pos_h, const int* pos_w, int dtype_flags, int backward) {
+  const int dtype = dtype_flags & DCTN_DTYPE_MASK;   // (the query covers every family: flags only select among them)
+  if (!out_sizes || !bond_sizes || !pos_h || !pos_w) return 0;
+  const SbsShape sh{n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype};
+  if (convsbs_check_shape(sh, nullptr) != DCTN_OK) return 0;
+  if (!backward) return 256;
+  bool fits = false;
+  size_t m = std::max({convsbs_bwd_generic_workspace(sh, &fits), convsbs_reg_bwd_workspace(sh), convsbs_band_bwd_workspace(sh)});
+  // the wide family: where the generic sweep's LDS plan declines the string, or where the flag forces it
+  if ((dtype_flags & DCTN_SBS_WIDE_SWEEP) || !fits) m = std::max(m, convsbs_wide_bwd_workspace(sh));
+  return m + 256;
+}
+
+size_t dctn_convsbs_saved_states_bytes(int n_cores, const int* out_sizes, const int* bond_sizes, int C, int B, int H,
+                                       int W, int q, const int* pos_h, const int* pos_w, int dtype_flags) {
+  if (!out_sizes || !bond_sizes || !pos_h || !pos_w) return 0;
+  return convsbs_saved_states_bytes({n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype_flags & DCTN_DTYPE_MASK});
+}
+
+int dctn_convsbs_fwd(const void* x, const int64_t x_strides[5], const void* const* cores, void* out, int n_cores,
+                     const int* out_sizes, const int* bond_sizes, const int* pos_h, const int* pos_w, int C, int B, int H, int W,
+                     int q, void* workspace, size_t workspace_bytes, int dtype_flags, void* stream) {
+  if (!x || !x_strides || !cores || !out || !out_sizes || !bond_sizes || !pos_h || !pos_w) return DCTN_ERR_NULL;
+  if (dtype_flags & ~(DCTN_DTYPE_MASK | SBS_FLAGS)) return DCTN_ERR_UNSUPPORTED;
+  const SbsShape sh{n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype_flags & DCTN_DTYPE_MASK};
+  int rc = convsbs_check_shape(sh, cores);
+  if (rc != DCTN_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  // a workspace of dctn_convsbs_saved_states_bytes(...) bytes: the forward leaves its states there for
+  // dctn_convsbs_bwd_saved (a training forward); anything smaller: plain forward
+  // small bonds: the register-resident sweep (keeps nothing: its backward recomputes the chain in registers)
+  if (!(dtype_flags & DCTN_SBS_MATRIX_CORE_SWEEP)) {
+    rc = convsbs_fwd_reg(x, x_strides, cores, out, sh, st);
+    if (rc != DCTN_ERR_UNSUPPORTED) return rc;
+  }
+  // bonds 5..16: the band family's forward (nothing kept: its backward recomputes the chain in registers)
+  if (band_family_first(sh, dtype_flags)) {
+    rc = convsbs_fwd_band(x, x_strides, cores, out, sh, st);
+    if (rc != DCTN_ERR_UNSUPPORTED) return rc;
+  }
+  const size_t sb = convsbs_saved_states_bytes(sh);
+  float* save = (sb > 0 && workspace && workspace_bytes >= sb) ? (float*)workspace : nullptr;
+  rc = convsbs_fwd_mfma(x, x_strides, cores, out, sh, st, save);
+  // the caller learns whether the states were WRITTEN: only the matrix-core sweep writes them, and it can still decline
+  // a string the size query accepted (its LDS plan); the generic sweep below leaves the buffer untouched
+  if (rc == DCTN_OK) return save ? DCTN_SAVED : DCTN_OK;
+  if (rc != DCTN_ERR_UNSUPPORTED) return rc;
+  return convsbs_fwd_generic(x, x_strides, cores, out, sh, st);
+}
+
+int dctn_convsbs_bwd(const void* x, const int64_t x_strides[5], const void* const* cores, const void* dY, void* dX,
+                     void* const* dCores, int n_cores, const int* out_sizes, const int* bond_sizes, const int* pos_h,
+                     const int* pos_w, int C, int B, int H, int W, int q, void* workspace, size_t workspace_bytes,
+                     int dtype_flags, void* stream) {
+  return dctn_convsbs_bwd_saved(x, x_strides, cores, dY, dX, dCores, n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H,
+                                W, q, workspace, workspace_bytes, nullptr, 0, dtype_flags, stream);
+}
+
+int dctn_convsbs_bwd_saved(const void* x, const int64_t x_strides[5], const void* const* cores, const void* dY, void* dX,
+                           void* const* dCores, int n_cores, const int* out_sizes, const int* bond_sizes, const int* pos_h,
+                           const int* pos_w, int C, int B, int H, int W, int q, void* workspace, size_t workspace_bytes,
+                           const void* saved_states, size_t saved_states_bytes, int dtype_flags, void* stream) {
+  if (!x || !x_strides || !cores || !dY || !out_sizes || !bond_sizes || !pos_h || !pos_w) return DCTN_ERR_NULL;
+  if (dtype_flags & ~(DCTN_DTYPE_MASK | SBS_FLAGS)) return DCTN_ERR_UNSUPPORTED;
+  const SbsShape sh{n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype_flags & DCTN_DTYPE_MASK};
+  if (saved_states) {   // only what the forward of this very shape can have written
+    const size_t sb = convsbs_saved_states_bytes(sh);
+    if (sb == 0 || saved_states_bytes < sb) saved_states = nullptr;
+  }
+  if (!dX && !dCores) return DCTN_OK;
+  int rc = convsbs_check_shape(sh, cores);
+  if (rc != DCTN_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype_flags & DCTN_SBS_WIDE_SWEEP) {   // forced: the wide family for every string it covers
+    rc = convsbs_bwd_wide(x, x_strides, cores, dY, dX, dCores, sh, st, workspace, workspace_bytes);
+    if (rc != DCTN_ERR_UNSUPPORTED) return rc;
+  }
+  if (sh.dtype == DCTN_F32 && band_family_first(sh, dtype_flags)) {   // (true whenever the register family is tried)
+    for (int c = 0; dCores && c < n_cores; ++c)
+      if (!dCores[c]) return DCTN_ERR_NULL;
+    if (!(dtype_flags & DCTN_SBS_MATRIX_CORE_SWEEP)) {
+      rc = convsbs_bwd_reg(x, x_strides, cores, dY, dX, (float* const*)dCores, sh, st, workspace, workspace_bytes);
+      if (rc != DCTN_ERR_UNSUPPORTED) return rc;
+    }
+    // bonds 5..16: the band-owning backward (recomputes the chain; no saved states, no helper launches)
+    rc = convsbs_bwd_band(x, x_strides, cores, dY, dX, (float* const*)dCores, sh, st, workspace, workspace_bytes);
+    if (rc != DCTN_ERR_UNSUPPORTED) return rc;
+  }
+  // the generic sweep's plan declines only for its LDS, before it writes anything: the wide family takes those strings
+  SbsBwdPlan plan;
+  rc = convsbs_bwd_generic_plan(plan, sh, dCores, workspace, workspace_bytes, st);
+  if (rc == DCTN_ERR_UNSUPPORTED) return convsbs_bwd_wide(x, x_strides, cores, dY, dX, dCores, sh, st, workspace, workspace_bytes);
+  if (rc != DCTN_OK) return rc;
+  // float32 strings of the matrix-core family: its sweep, in the planned workspace with the accumulators already zero
+  // (a dX-only backward stays on the generic sweep)
+  if (sh.dtype == DCTN_F32 && dCores) {
+    rc = convsbs_bwd_mfma(x, x_strides, cores, dY, (float*)plan.states, dX ? (float*)plan.gxw : nullptr, (float* const*)dCores,
+                          sh, st, plan.partials, plan.partial_bytes, (const float*)saved_states);
+    if (rc == DCTN_OK) return dX ? convsbs_gather_dx(sh, plan.gxw, dX, st) : DCTN_OK;
+    if (rc != DCTN_ERR_UNSUPPORTED) return rc;
+  }
+  return convsbs_bwd_generic_run(plan, x, x_strides, cores, dY, dX, dCores, sh, st);
+}
+
+// ---- several strings of one layer (ManyConvSBS, dctn/conv_sbs.py:314-370) in one launch each way
+size_t dctn_convsbs_many_workspace_bytes(int n_strings, int n_cores, const int* out_sizes, const int* bond_sizes, int C, int B,
+                                         int H, int W, int q, const int* pos_h, const int* pos_w, int dtype) {
+  if (!out_sizes || !bond_sizes || !pos_h || !pos_w) return 0;
+  const SbsShape sh{n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype & DCTN_DTYPE_MASK};
+  const size_t a = convsbs_many_reg_bwd_workspace(n_strings, sh);
+  return a > 0 ? a : convsbs_many_band_bwd_workspace(n_strings, sh);
+}
+
+int dctn_convsbs_many_fwd(const void* x, const int64_t x_strides[5], const void* const* cores, void* const* outs,
+                          int n_strings, int n_cores, const int* out_sizes, const int* bond_sizes, const int* pos_h,
+                          const int* pos_w, int C, int B, int H, int W, int q, int dtype, void* stream) {
+  if (!x || !x_strides || !cores || !outs || !out_sizes || !bond_sizes || !pos_h || !pos_w) return DCTN_ERR_NULL;
+  if (n_strings < 1 || n_cores < 1) return DCTN_ERR_BAD_SHAPE;
+  if (dtype & ~DCTN_DTYPE_MASK) return DCTN_ERR_UNSUPPORTED;
+  for (int i = 0; i < n_strings * n_cores; ++i)
+    if (!cores[i]) return DCTN_ERR_NULL;
+  const SbsShape sh{n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype};
+  const int rc = convsbs_many_fwd_reg(x, x_strides, cores, outs, n_strings, sh, (hipStream_t)stream);
+  if (rc != DCTN_ERR_UNSUPPORTED) return rc;
+  return convsbs_many_fwd_band(x, x_strides, cores, outs, n_strings, sh, (hipStream_t)stream);
+}
+
+int dctn_convsbs_many_bwd(const void* x, const int64_t x_strides[5], const void* const* cores, const void* const* dYs, void* dX,
+                          void* const* dCores, int n_strings, int n_cores, const int* out_sizes, const int* bond_sizes,
+                          const int* pos_h, const int* pos_w, int C, int B, int H, int W, int q, void* workspace,
+                          size_t workspace_bytes, int dtype, void* stream) {
+  if (!x || !x_strides || !cores || !dYs || !out_sizes || !bond_sizes || !pos_h || !pos_w) return DCTN_ERR_NULL;
+  if (n_strings < 1 || n_cores < 1) return DCTN_ERR_BAD_SHAPE;
+  if (dtype & ~DCTN_DTYPE_MASK) return DCTN_ERR_UNSUPPORTED;
+  if (!dX && !dCores) return DCTN_OK;
+  for (int i = 0; i < n_strings * n_cores; ++i)
+    if (!cores[i] || (dCores && !dCores[i])) return DCTN_ERR_NULL;
+  const SbsShape sh{n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype};
+  const int rc = convsbs_many_bwd_reg(x, x_strides, cores, dYs, dX, (float* const*)dCores, n_strings, sh, (hipStream_t)stream,
+                                      workspace, workspace_bytes);
+  if (rc != DCTN_ERR_UNSUPPORTED) return rc;
+  return convsbs_many_bwd_band(x, x_strides, cores, dYs, dX, (float* const*)dCores, n_strings, sh, (hipStream_t)stream, workspace,
+                               workspace_bytes);
 }
 
 }  // extern "C"

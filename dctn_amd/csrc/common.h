@@ -74,6 +74,10 @@ static inline long long ipow_ll(long long b, int e) {
 static inline size_t dtype_size(int dtype) {
   return dtype == DCTN_F64 ? 8 : (dtype == DCTN_F32 ? 4 : 2);
 }
+// bytes of the type a dtype accumulates in: bf16 storage accumulates in float32
+static inline size_t acc_size(int dtype) { return dtype == DCTN_F64 ? 8 : 4; }
+
+static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 template <typename T>
 __device__ __forceinline__ T wave_reduce_sum(T v) {
@@ -213,7 +217,27 @@ static inline SbsShape sbs_string(SbsShape many, int i) {
   return many;
 }
 
+// Generic sweep (any string, f32 / f64 / bf16 storage) — convsbs_generic.hip
+// the shape checks every entry point makes before it asks a family (cores optional: every pointer non-NULL)
+int convsbs_check_shape(const SbsShape& sh, const void* const* cores);
+int convsbs_fwd_generic(const void* x, const int64_t xs[5], const void* const* cores, void* out, const SbsShape& sh, hipStream_t st);
+// The backward in two calls.  The plan checks the workspace, plans the LDS and opts the kernel in (DCTN_ERR_UNSUPPORTED:
+// nothing written, the wide family takes the string), carves the workspace and zero-fills the accumulators; the run is the
+// sweep, the dX gather and the bf16 conversion.  Between the two the entry point tries the matrix-core backward.
+// states [element][window] | gxw: per-window d/d(pixel features) [n C q][windows] | acc: bf16 storage's float32 accumulators |
+// partials: the matrix-core backward's records (NULL: the tail is too short for partial_bytes)
+struct SbsBwdPlan { void *states, *gxw; unsigned char* acc; float* partials; size_t partial_bytes; };
+size_t convsbs_bwd_generic_workspace(const SbsShape& sh, bool* lds_fits = nullptr);   // lds_fits: the plan's LDS answer with core gradients
+int convsbs_bwd_generic_plan(SbsBwdPlan& pl, const SbsShape& sh, void* const* dCores, void* ws, size_t ws_bytes, hipStream_t st);
+int convsbs_bwd_generic_run(const SbsBwdPlan& pl, const void* x, const int64_t xs[5], const void* const* cores,
+                            const void* dY, void* dX, void* const* dCores, const SbsShape& sh, hipStream_t st);
+// dX from per-window gradients in the gxw layout: every family that writes them gathers here
+int convsbs_gather_dx(const SbsShape& sh, const void* gxw, void* dX, hipStream_t st);
+
 // MFMA ConvSBS sweep (open chain, uniform bond) — convsbs_mfma.hip
+// its share of the generic backward's workspace: state elements per window (0: bonds outside the family), bytes of its records
+long long convsbs_mfma_state_elems(const SbsShape& sh);
+size_t convsbs_mfma_partial_bytes(const SbsShape& sh);
 // save_states (optional): room of convsbs_saved_states_bytes(...) for the forward states a following backward takes over
 size_t convsbs_saved_states_bytes(const SbsShape& sh);
 int convsbs_fwd_mfma(const void* x, const int64_t xs[5], const void* const* cores, void* out, const SbsShape& sh,
@@ -232,13 +256,11 @@ int convsbs_bwd_band(const void* x, const int64_t xs[5], const void* const* core
                      float* const* dcores, const SbsShape& sh, hipStream_t st, void* ws, size_t ws_bytes);
 // Wide backward for strings whose core gradients do not fit one workgroup's LDS (any bond, f32 / f64 / bf16 storage) -
 // convsbs_wide.hip.  GEMMs over HBM buffers of window chunks, fixed-order partial records, no atomics.  The per-window input
-// gradients land at the START of `ws` in the generic sweep's gxw layout ([n C q][windows]; the caller gathers dX from them
-// when need_dx).  convsbs_wide_bwd_workspace: 0 = outside the family.
+// gradients land at the START of `ws` in the generic sweep's gxw layout ([n C q][windows]; dX, when wanted, is gathered
+// from them by convsbs_gather_dx).  convsbs_wide_bwd_workspace: 0 = outside the family.
 size_t convsbs_wide_bwd_workspace(const SbsShape& sh);
-int convsbs_bwd_wide(const void* x, const int64_t xs[5], const void* const* cores, const void* dY, int need_dx,
+int convsbs_bwd_wide(const void* x, const int64_t xs[5], const void* const* cores, const void* dY, void* dX,
                      void* const* dcores, const SbsShape& sh, hipStream_t st, void* ws, size_t ws_bytes);
-// room for the per-workgroup partial-gradient records of the MFMA backward (deterministic dCore)
-constexpr int SBS_MAX_PARTIAL_RECORDS = 2048;
 
 // Register-resident sweep for small bonds (every bond <= 4, float32 open chains, at most one two-valued core,
 // q^C <= 4) - convsbs_reg.hip.  The backward writes dX itself (no per-window gradients, no gather launch) and needs

@@ -1158,8 +1158,6 @@ int bd_plan(BdPlan& pl, const int64_t xs[5], const void* const* cores, const Sbs
   return DCTN_OK;
 }
 
-size_t bd_align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
 
 bool convsbs_band_covers(const SbsShape& sh) {
@@ -1174,7 +1172,7 @@ size_t convsbs_band_bwd_workspace(const SbsShape& sh) {
 #ifdef DCTN_STAMPS
   extra = (size_t)pl.nwg * 2 * 32 * sizeof(long long);
 #endif
-  return bd_align256(pl.records_bytes) + bd_align256(pl.side_bytes) + 256 + extra;
+  return align256(pl.records_bytes) + align256(pl.side_bytes) + 256 + extra;
 }
 
 int convsbs_bwd_band(const void* x, const int64_t xs[5], const void* const* cores, const void* dY, void* dX,
@@ -1183,14 +1181,14 @@ int convsbs_bwd_band(const void* x, const int64_t xs[5], const void* const* core
   const int rc = bd_plan(pl, xs, cores, sh);
   if (rc != DCTN_OK) return rc;
   if (!dX && !dcores) return DCTN_OK;
-  const size_t need = bd_align256(pl.records_bytes) + bd_align256(pl.side_bytes);
+  const size_t need = align256(pl.records_bytes) + align256(pl.side_bytes);
   if (!ws || ws_bytes < need) return DCTN_ERR_WORKSPACE;
   BdP& p = pl.p;
   p.x = (const float*)x;
   p.dY = (const float*)dY;
   p.dX = (float*)dX;
   p.records = dcores ? (float*)ws : nullptr;
-  p.side = (float*)((unsigned char*)ws + bd_align256(pl.records_bytes));
+  p.side = (float*)((unsigned char*)ws + align256(pl.records_bytes));
   p.stamps = nullptr;
 #ifdef DCTN_STAMPS
   if (ws_bytes >= need + (size_t)pl.nwg * 2 * 32 * sizeof(long long)) p.stamps = (long long*)((unsigned char*)ws + need);
@@ -1298,8 +1296,8 @@ size_t convsbs_many_band_bwd_workspace(int ns, const SbsShape& sh) {
   BdPlan pl[BD_MANY];
   if (bd_plan_many(pl, ns, nullptr, nullptr, sh) != DCTN_OK) return 0;
   size_t tot = 256;
-  for (int s2 = 0; s2 < ns; ++s2) tot += bd_align256(pl[s2].records_bytes) + bd_align256(pl[s2].side_bytes);
-  tot += (size_t)(ns - 1) * bd_align256((size_t)sh.C * sh.B * sh.H * sh.W * sh.q * sizeof(float));   // the other strings' shares of dX
+  for (int s2 = 0; s2 < ns; ++s2) tot += align256(pl[s2].records_bytes) + align256(pl[s2].side_bytes);
+  tot += (size_t)(ns - 1) * align256((size_t)sh.C * sh.B * sh.H * sh.W * sh.q * sizeof(float));   // the other strings' shares of dX
   return tot;
 }
 
@@ -1367,14 +1365,14 @@ int convsbs_many_bwd_band(const void* x, const int64_t xs[5], const void* const*
     p.x = (const float*)x;
     p.dY = (const float*)dYs[s2];
     p.records = dcores ? (float*)cur : nullptr;
-    cur += bd_align256(pl[s2].records_bytes);
+    cur += align256(pl[s2].records_bytes);
     p.side = (float*)cur;
-    cur += bd_align256(pl[s2].side_bytes);
+    cur += align256(pl[s2].side_bytes);
     if (!dX) p.dX = nullptr;
     else if (s2 == 0) p.dX = (float*)dX;
     else {
       p.dX = (float*)cur;
-      cur += bd_align256((size_t)sh.C * sh.B * sh.H * sh.W * sh.q * sizeof(float));
+      cur += align256((size_t)sh.C * sh.B * sh.H * sh.W * sh.q * sizeof(float));
     }
     p.stamps = nullptr;
     pp.s[s2] = p;

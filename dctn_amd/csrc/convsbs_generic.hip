@@ -328,10 +328,12 @@ int fill(SbsP& p, const int64_t xs[5], const SbsShape& sh, const void* const* co
   p.oacc[sh.n] = (int)oacc;
   p.st_off[sh.n] = off;
   p.cmax = 0;
+  p.core_off[0] = 0;
   for (int c = 0; c < sh.n; ++c) {
     const long long e = (long long)p.o[c] * p.bl[c] * p.br[c] * p.qc;
     if (e > (1 << 20)) return DCTN_ERR_UNSUPPORTED;
     if ((int)e > p.cmax) p.cmax = (int)e;
+    p.core_off[c + 1] = p.core_off[c] + e;
   }
   p.Otot = (int)oacc;
   p.vmax = vmax;
@@ -343,188 +345,7 @@ int fill(SbsP& p, const int64_t xs[5], const SbsShape& sh, const void* const* co
   return DCTN_OK;
 }
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-long long core_elems(const SbsP& p, int c) {
-  return (long long)p.o[c] * p.bl[c] * p.br[c] * p.qc;
-}
-
-template <typename S, typename A>
-int fwd_launch(const void* x, void* out, SbsP& p, hipStream_t st) {
-  const size_t per_col = ((size_t)2 * p.vmax + p.qc + p.Otot) * sizeof(A);
-  p.cs = DCTN_WAVE;
-  while (p.cs > 1 && per_col * p.cs > dctn_lds_wg_max()) p.cs >>= 1;
-  const size_t lds = per_col * p.cs;
-  if (lds > dctn_lds_wg_max() || !dctn_lds_optin((const void*)convsbs_fwd_generic_k<S, A>, lds)) return DCTN_ERR_UNSUPPORTED;
-  p.cst = p.cs;
-  const unsigned grid = (unsigned)((p.Wn + p.cs - 1) / p.cs);
-  hipLaunchKernelGGL((convsbs_fwd_generic_k<S, A>), dim3(grid), dim3(DCTN_WAVE), lds, st,
-                     (const S*)x, (S*)out, p);
-  DCTN_CHECK_LAUNCH();
-  dctn_set_last_kernel("convsbs_fwd_generic");
-  return DCTN_OK;
-}
-
-// State elements per window of the workspace's first region: the generic sweep's own need, or what a slice of the MFMA
-// sweep stores (at most two states of the PADDED bond per core) when that is more - a padded bond (6 -> 8) or a ring
-// (whose generic states are counted differently) would otherwise let the MFMA states run into the feature-gradient
-// region behind them, which ring / many-output slices accumulate across launches.
-long long state_elems(const SbsP& p) {
-  long long need = p.st_off[p.n];
-  int bmax = 1;
-  for (int c = 0; c < p.n; ++c) bmax = p.bl[c] > bmax ? p.bl[c] : bmax;
-  if (bmax <= 16) {
-    const int rpad = bmax <= 4 ? 4 : bmax <= 8 ? 8 : 16;
-    const long long mfma = (long long)p.n * 2 * rpad;
-    if (mfma > need) need = mfma;
-  }
-  return need;
-}
-
-size_t bwd_ws(const SbsP& p, int dtype) {
-  const size_t asz = dtype == DCTN_F64 ? 8 : 4;
-  size_t total = align256((size_t)state_elems(p) * p.Wn * asz);      // forward states
-  total += align256((size_t)p.n * p.C * p.q * p.Wn * asz);           // per-window d/d(pixel features)
-  if (dtype == DCTN_BF16)
-    for (int c = 0; c < p.n; ++c) total += align256((size_t)core_elems(p, c) * asz);
-  if (dtype == DCTN_F32) {   // per-workgroup partial gradients of the MFMA backward (fixed-order reduce instead of atomics)
-    size_t ce = 0;
-    for (int c = 0; c < p.n; ++c) ce += (size_t)core_elems(p, c);
-    total += align256((size_t)SBS_MAX_PARTIAL_RECORDS * ce * sizeof(float));
-  }
-  return total;
-}
-
-template <typename S, typename A>
-int bwd_launch(const void* x, const void* dY, void* dX, void* const* dCores, void* ws, size_t ws_bytes, SbsP& p,
-               const SbsShape& sh, hipStream_t st, const void* saved) {
-  const int dtype = sh.dtype;
-  if (!ws || bwd_ws(p, dtype) > ws_bytes) return DCTN_ERR_WORKSPACE;
-  p.core_off[0] = 0;
-  for (int c = 0; c < p.n; ++c) p.core_off[c + 1] = p.core_off[c] + core_elems(p, c);
-  const int need_dcore_lds = dCores != nullptr;
-  const size_t acc_bytes = need_dcore_lds ? (size_t)p.core_off[p.n] * sizeof(A) : 0;
-  if (acc_bytes > dctn_lds_wg_max() / 2) return DCTN_ERR_UNSUPPORTED;
-  const size_t per_col = ((size_t)3 * p.vmax + 2 * p.qc + p.Otot) * sizeof(A);
-  p.cs = DCTN_WAVE;
-  while (p.cs > 1 && per_col * (p.cs + 1) + acc_bytes > dctn_lds_wg_max()) p.cs >>= 1;
-  int waves = 1;  // several waves share one dCore accumulator when every wave has its 64 columns
-  if (p.cs == DCTN_WAVE && acc_bytes >= 4096)  // small strings: more, smaller workgroups win
-    while (waves < 4 && per_col * (2 * waves * DCTN_WAVE + 1) + acc_bytes <= dctn_lds_wg_max()) waves *= 2;
-  const int csb = waves * p.cs;
-  p.cst = csb + 1;
-  const size_t lds = per_col * p.cst + acc_bytes;
-  if (lds > dctn_lds_wg_max() || !dctn_lds_optin((const void*)convsbs_bwd_generic_k<S, A>, lds)) return DCTN_ERR_UNSUPPORTED;
-  unsigned char* wsp = (unsigned char*)ws;
-  A* states = (A*)wsp;
-  wsp += align256((size_t)state_elems(p) * p.Wn * sizeof(A));
-  A* gxw = (A*)wsp;
-  wsp += align256((size_t)p.n * p.C * p.q * p.Wn * sizeof(A));
-  const int need_dcore = dCores != nullptr;
-  if (need_dcore) {
-    for (int c = 0; c < p.n; ++c) {
-      if (!dCores[c]) return DCTN_ERR_NULL;
-      if constexpr (sizeof(S) == sizeof(A)) {
-        p.dcore[c] = dCores[c];
-      } else {
-        p.dcore[c] = wsp;
-        wsp += align256((size_t)core_elems(p, c) * sizeof(A));
-      }
-    }
-    // the accumulators start from zero: ONE fill when they sit back to back (the Python wrapper allocates the
-    // gradients of a string as one flat buffer; nine separate fills were 30 us of a 200 us backward), else one each
-    bool flat = true;
-    size_t total = 0;
-    for (int c = 0; c < p.n; ++c) {
-      if (c > 0 && (unsigned char*)p.dcore[c] != (unsigned char*)p.dcore[0] + total) flat = false;
-      total += (size_t)core_elems(p, c) * sizeof(A);
-    }
-    if (flat) {
-      if (dctn_zero_async(p.dcore[0], total, st) != DCTN_OK) return DCTN_ERR_LAUNCH;
-    } else {
-      for (int c = 0; c < p.n; ++c)
-        if (dctn_zero_async(p.dcore[c], (size_t)core_elems(p, c) * sizeof(A), st) != DCTN_OK)
-          return DCTN_ERR_LAUNCH;
-    }
-  }
-  if constexpr (sizeof(S) == 4 && sizeof(A) == 4) {
-    // float32 strings of the MFMA family: register-resident sweep on the matrix cores
-    if (need_dcore) {
-      size_t ce = 0;
-      for (int c = 0; c < p.n; ++c) ce += (size_t)core_elems(p, c);
-      const size_t pbytes = (size_t)SBS_MAX_PARTIAL_RECORDS * ce * sizeof(float);
-      float* partials = ((size_t)((unsigned char*)ws + ws_bytes - wsp) >= pbytes) ? (float*)wsp : nullptr;
-      const int rcm = convsbs_bwd_mfma(x, (const int64_t*)p.s, (const void* const*)p.core, dY, (float*)states,
-                                       dX ? (float*)gxw : nullptr, (float* const*)p.dcore, sh, st, partials, pbytes, (const float*)saved);
-      if (rcm == DCTN_OK) {
-        if (dX) {
-          const long long total = (long long)p.C * p.B * p.H * p.W * p.q;
-          const unsigned g2 = (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-          hipLaunchKernelGGL((convsbs_gather_dx_k<S, A>), dim3(g2), dim3(256), 0, st, gxw, (S*)dX, p);
-          DCTN_CHECK_LAUNCH();
-        }
-        return DCTN_OK;
-      }
-      if (rcm != DCTN_ERR_UNSUPPORTED) return rcm;
-    }
-  }
-  const long long ngroups = (p.Wn + csb - 1) / csb;
-  // persistent workgroups: as many as can be resident (LDS-limited), at most one per window group
-  long long grid = dctn_resident_wgs(lds, 1, 8);
-  if (grid > ngroups) grid = ngroups;
-  hipLaunchKernelGGL((convsbs_bwd_generic_k<S, A>), dim3((unsigned)grid), dim3(DCTN_WAVE * waves), lds, st,
-                     (const S*)x, (const S*)dY, states, gxw, p, dX != nullptr, need_dcore, ngroups);
-  DCTN_CHECK_LAUNCH();
-  if (dX) {
-    const long long total = (long long)p.C * p.B * p.H * p.W * p.q;
-    const unsigned g2 = (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL((convsbs_gather_dx_k<S, A>), dim3(g2), dim3(256), 0, st, gxw, (S*)dX, p);
-    DCTN_CHECK_LAUNCH();
-  }
-  if constexpr (sizeof(S) != sizeof(A)) {
-    if (need_dcore)
-      for (int c = 0; c < p.n; ++c) {
-        const long long ne = core_elems(p, c);
-        hipLaunchKernelGGL((convert_sbs_k<S, A>), dim3((unsigned)((ne + 255) / 256)), dim3(256), 0,
-                           st, (const A*)p.dcore[c], (S*)dCores[c], ne);
-        DCTN_CHECK_LAUNCH();
-      }
-  }
-  dctn_set_last_kernel("convsbs_bwd_generic");
-  return DCTN_OK;
-}
-
-// Whether the LDS plan of bwd_launch takes the string when it computes core gradients (the same arithmetic as its two
-// checks; the runtime's opt-in aside): strings it declines fall to the wide family, whose workspace the query then adds.
-bool generic_bwd_fits(const SbsP& p, size_t asz) {
-  long long ce = 0;
-  for (int c = 0; c < p.n; ++c) ce += core_elems(p, c);
-  const size_t acc_bytes = (size_t)ce * asz;
-  if (acc_bytes > dctn_lds_wg_max() / 2) return false;
-  const size_t per_col = ((size_t)3 * p.vmax + 2 * p.qc + p.Otot) * asz;
-  int cs = DCTN_WAVE;
-  while (cs > 1 && per_col * (cs + 1) + acc_bytes > dctn_lds_wg_max()) cs >>= 1;
-  return per_col * (cs + 1) + acc_bytes <= dctn_lds_wg_max();
-}
-
-// The wide family (convsbs_wide.hip) writes the per-window input gradients at the start of the workspace; dX is gathered
-// from them by the generic sweep's own kernel.
-template <typename S, typename A>
-int wide_launch(const void* x, const void* dY, void* dX, void* const* dCores, void* ws, size_t ws_bytes, SbsP& p,
-                const SbsShape& sh, hipStream_t st) {
-  const int dtype = sh.dtype;
-  const int rc = convsbs_bwd_wide(x, (const int64_t*)p.s, (const void* const*)p.core, dY, dX != nullptr, dCores, sh, st, ws, ws_bytes);
-  if (rc != DCTN_OK) return rc;
-  if (dX) {
-    const long long total = (long long)p.C * p.B * p.H * p.W * p.q;
-    const unsigned g2 = (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL((convsbs_gather_dx_k<S, A>), dim3(g2), dim3(256), 0, st, (const A*)ws, (S*)dX, p);
-    DCTN_CHECK_LAUNCH();
-  }
-  dctn_set_last_kernel(dtype == DCTN_F64 ? "convsbs_bwd_wide_f64" : dtype == DCTN_BF16 ? "convsbs_bwd_wide_bf16"
-                                                                                    : "convsbs_bwd_wide_f32");
-  return DCTN_OK;
-}
+long long core_elems(const SbsP& p, int c) { return p.core_off[c + 1] - p.core_off[c]; }
 
 // f(S(), A()) with the storage and accumulator types of a dtype code
 template <typename F>
@@ -537,172 +358,167 @@ int with_types(int dtype, F f) {
   return DCTN_ERR_BAD_DTYPE;
 }
 
-// bonds 5..16 go to the band family, except that under DCTN_SBS_MATRIX_CORE_SWEEP bonds up to 8 stay on the matrix-core
-// sweep (the tests hold both against the oracle)
-bool band_family_first(const SbsShape& sh, int dtype_flags) {
-  int largest = 0;
-  for (int c = 0; c < sh.n; ++c) largest = sh.bond_sizes[c] > largest ? sh.bond_sizes[c] : largest;
-  return !((dtype_flags & DCTN_SBS_MATRIX_CORE_SWEEP) && largest <= 8);
+// The backward workspace, region by region in this order (bytes, each a multiple of 256): forward states
+// [element][window] | per-window d/d(pixel features) | bf16 storage: the float32 accumulators of the cores, one aligned row
+// each | float32: the matrix-core backward's per-workgroup records (fixed-order reduce instead of atomics)
+struct BwdLayout { size_t states, gxw, acc, partials, total; };
+BwdLayout bwd_layout(const SbsP& p, const SbsShape& sh) {
+  const size_t asz = acc_size(sh.dtype);
+  // State elements per window: the generic sweep's own need, or the matrix-core sweep's when that is more - a padded bond
+  // (6 -> 8) or a ring (whose generic states are counted differently) would otherwise let its states run into the
+  // feature-gradient region behind them, which ring / many-output slices accumulate across launches.
+  const long long own = p.st_off[p.n], mfma = convsbs_mfma_state_elems(sh);
+  BwdLayout L;
+  L.states = align256((size_t)(mfma > own ? mfma : own) * p.Wn * asz);
+  L.gxw = align256((size_t)p.n * p.C * p.q * p.Wn * asz);
+  L.acc = 0;
+  if (sh.dtype == DCTN_BF16)
+    for (int c = 0; c < p.n; ++c) L.acc += align256((size_t)core_elems(p, c) * asz);
+  L.partials = align256(convsbs_mfma_partial_bytes(sh));
+  L.total = L.states + L.gxw + L.acc + L.partials;
+  return L;
 }
 
-constexpr int SBS_FLAGS = DCTN_SBS_MATRIX_CORE_SWEEP | DCTN_SBS_WIDE_SWEEP;
+// The backward's LDS plan: sets p.cs, p.cst; lds == 0: no fit; several waves share one dCore accumulator when each has its 64 columns
+struct BwdLds { size_t lds; int waves; };
+BwdLds bwd_lds_plan(SbsP& p, size_t asz, bool need_dcore) {
+  const size_t acc_bytes = need_dcore ? (size_t)p.core_off[p.n] * asz : 0;
+  if (acc_bytes > dctn_lds_wg_max() / 2) return {0, 0};
+  const size_t per_col = ((size_t)3 * p.vmax + 2 * p.qc + p.Otot) * asz;
+  p.cs = DCTN_WAVE;
+  while (p.cs > 1 && per_col * (p.cs + 1) + acc_bytes > dctn_lds_wg_max()) p.cs >>= 1;
+  int waves = 1;
+  if (p.cs == DCTN_WAVE && acc_bytes >= 4096)  // small strings: more, smaller workgroups win
+    while (waves < 4 && per_col * (2 * waves * DCTN_WAVE + 1) + acc_bytes <= dctn_lds_wg_max()) waves *= 2;
+  p.cst = waves * p.cs + 1;
+  const size_t lds = per_col * p.cst + acc_bytes;
+  return {lds > dctn_lds_wg_max() ? 0 : lds, waves};
+}
+
+// the A-typed accumulators of the cores: the gradients themselves, or (bf16 storage) their rows in the workspace
+template <typename S, typename A>
+void set_accumulators(SbsP& p, void* const* dCores, unsigned char* acc) {
+  for (int c = 0; c < p.n; ++c) {
+    p.dcore[c] = sizeof(S) == sizeof(A) ? dCores[c] : acc;
+    acc += align256((size_t)core_elems(p, c) * sizeof(A));
+  }
+}
 
 }  // namespace
 
-extern "C" {
+// (the launchers below stand in the order in which they first use their kernels: the device code keeps it)
+int convsbs_check_shape(const SbsShape& sh, const void* const* cores) {
+  SbsP p;
+  return fill(p, nullptr, sh, cores);
+}
 
-size_t dctn_convsbs_workspace_bytes(int n_cores, const int* out_sizes, const int* bond_sizes,
-                                    int C, int B, int H, int W, int q, const int* pos_h,
-                                    const int* pos_w, int dtype_flags, int backward) {
-  const int dtype = dtype_flags & DCTN_DTYPE_MASK;   // (the query covers every family: flags only select among them)
-  if (!out_sizes || !bond_sizes || !pos_h || !pos_w) return 0;
-  const SbsShape sh{n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype};
+int convsbs_fwd_generic(const void* x, const int64_t xs[5], const void* const* cores, void* out, const SbsShape& sh, hipStream_t st) {
+  return with_types(sh.dtype, [&](auto s, auto a) -> int {
+    using S = decltype(s); using A = decltype(a);
+    SbsP p;
+    const int rc = fill(p, xs, sh, cores);
+    if (rc != DCTN_OK) return rc;
+    const size_t per_col = ((size_t)2 * p.vmax + p.qc + p.Otot) * sizeof(A);
+    p.cs = DCTN_WAVE;
+    while (p.cs > 1 && per_col * p.cs > dctn_lds_wg_max()) p.cs >>= 1;
+    const size_t lds = per_col * p.cs;
+    if (lds > dctn_lds_wg_max() || !dctn_lds_optin((const void*)convsbs_fwd_generic_k<S, A>, lds)) return DCTN_ERR_UNSUPPORTED;
+    p.cst = p.cs;
+    const unsigned grid = (unsigned)((p.Wn + p.cs - 1) / p.cs);
+    hipLaunchKernelGGL((convsbs_fwd_generic_k<S, A>), dim3(grid), dim3(DCTN_WAVE), lds, st, (const S*)x, (S*)out, p);
+    DCTN_CHECK_LAUNCH();
+    dctn_set_last_kernel("convsbs_fwd_generic");
+    return DCTN_OK;
+  });
+}
+
+int convsbs_gather_dx(const SbsShape& sh, const void* gxw, void* dX, hipStream_t st) {
+  return with_types(sh.dtype, [&](auto s, auto a) -> int {
+    using S = decltype(s); using A = decltype(a);
+    SbsP p;
+    const int rc = fill(p, nullptr, sh);
+    if (rc != DCTN_OK) return rc;
+    const long long total = (long long)p.C * p.B * p.H * p.W * p.q;
+    const unsigned g2 = (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    hipLaunchKernelGGL((convsbs_gather_dx_k<S, A>), dim3(g2), dim3(256), 0, st, (const A*)gxw, (S*)dX, p);
+    DCTN_CHECK_LAUNCH();
+    return DCTN_OK;
+  });
+}
+
+size_t convsbs_bwd_generic_workspace(const SbsShape& sh, bool* lds_fits) {
   SbsP p;
   if (fill(p, nullptr, sh) != DCTN_OK) return 0;
-  if (!backward) return 256;
-  const size_t a = bwd_ws(p, dtype), b = convsbs_reg_bwd_workspace(sh), c = convsbs_band_bwd_workspace(sh);
-  size_t m = a > b ? a : b;
-  m = m > c ? m : c;
-  // the wide family: where the generic sweep's LDS plan declines the string, or where the flag forces it
-  if ((dtype_flags & DCTN_SBS_WIDE_SWEEP) || !generic_bwd_fits(p, dtype == DCTN_F64 ? 8 : 4)) {
-    const size_t w = convsbs_wide_bwd_workspace(sh);
-    m = m > w ? m : w;
-  }
-  return m + 256;
+  if (lds_fits) *lds_fits = bwd_lds_plan(p, acc_size(sh.dtype), true).lds != 0;
+  return bwd_layout(p, sh).total;
 }
 
-size_t dctn_convsbs_saved_states_bytes(int n_cores, const int* out_sizes, const int* bond_sizes, int C, int B, int H,
-                                       int W, int q, const int* pos_h, const int* pos_w, int dtype_flags) {
-  if (!out_sizes || !bond_sizes || !pos_h || !pos_w) return 0;
-  return convsbs_saved_states_bytes({n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype_flags & DCTN_DTYPE_MASK});
-}
-
-int dctn_convsbs_fwd(const void* x, const int64_t x_strides[5], const void* const* cores,
-                     void* out, int n_cores, const int* out_sizes, const int* bond_sizes,
-                     const int* pos_h, const int* pos_w, int C, int B, int H, int W, int q,
-                     void* workspace, size_t workspace_bytes, int dtype_flags, void* stream) {
-  if (!x || !x_strides || !cores || !out || !out_sizes || !bond_sizes || !pos_h || !pos_w)
-    return DCTN_ERR_NULL;
-  if (dtype_flags & ~(DCTN_DTYPE_MASK | SBS_FLAGS)) return DCTN_ERR_UNSUPPORTED;
-  const SbsShape sh{n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype_flags & DCTN_DTYPE_MASK};
-  SbsP p;
-  int rc = fill(p, x_strides, sh, cores);
-  if (rc != DCTN_OK) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  // a workspace of dctn_convsbs_saved_states_bytes(...) bytes: the forward leaves its states there for
-  // dctn_convsbs_bwd_saved (a training forward); anything smaller: plain forward
-  // small bonds: the register-resident sweep (keeps nothing: its backward recomputes the chain in registers)
-  if (!(dtype_flags & DCTN_SBS_MATRIX_CORE_SWEEP)) {
-    rc = convsbs_fwd_reg(x, x_strides, cores, out, sh, st);
-    if (rc != DCTN_ERR_UNSUPPORTED) return rc;
-  }
-  // bonds 5..16: the band family's forward (nothing kept: its backward recomputes the chain in registers)
-  if (band_family_first(sh, dtype_flags)) {
-    rc = convsbs_fwd_band(x, x_strides, cores, out, sh, st);
-    if (rc != DCTN_ERR_UNSUPPORTED) return rc;
-  }
-  const size_t sb = convsbs_saved_states_bytes(sh);
-  float* save = (sb > 0 && workspace && workspace_bytes >= sb) ? (float*)workspace : nullptr;
-  rc = convsbs_fwd_mfma(x, x_strides, cores, out, sh, st, save);
-  // the caller learns whether the states were WRITTEN: only the matrix-core sweep writes them, and it can still decline
-  // a string the size query accepted (its LDS plan); the generic sweep below leaves the buffer untouched
-  if (rc == DCTN_OK) return save ? DCTN_SAVED : DCTN_OK;
-  if (rc != DCTN_ERR_UNSUPPORTED) return rc;
-  return with_types(sh.dtype, [&](auto s, auto a) { return fwd_launch<decltype(s), decltype(a)>(x, out, p, st); });
-}
-
-int dctn_convsbs_bwd(const void* x, const int64_t x_strides[5], const void* const* cores,
-                     const void* dY, void* dX, void* const* dCores, int n_cores,
-                     const int* out_sizes, const int* bond_sizes, const int* pos_h,
-                     const int* pos_w, int C, int B, int H, int W, int q, void* workspace,
-                     size_t workspace_bytes, int dtype_flags, void* stream) {
-  return dctn_convsbs_bwd_saved(x, x_strides, cores, dY, dX, dCores, n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H,
-                                W, q, workspace, workspace_bytes, nullptr, 0, dtype_flags, stream);
-}
-
-int dctn_convsbs_bwd_saved(const void* x, const int64_t x_strides[5], const void* const* cores,
-                           const void* dY, void* dX, void* const* dCores, int n_cores,
-                           const int* out_sizes, const int* bond_sizes, const int* pos_h,
-                           const int* pos_w, int C, int B, int H, int W, int q, void* workspace,
-                           size_t workspace_bytes, const void* saved_states, size_t saved_states_bytes, int dtype_flags,
-                           void* stream) {
-  if (!x || !x_strides || !cores || !dY || !out_sizes || !bond_sizes || !pos_h || !pos_w)
-    return DCTN_ERR_NULL;
-  if (dtype_flags & ~(DCTN_DTYPE_MASK | SBS_FLAGS)) return DCTN_ERR_UNSUPPORTED;
-  const SbsShape sh{n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype_flags & DCTN_DTYPE_MASK};
-  if (saved_states) {   // only what the forward of this very shape can have written
-    const size_t sb = convsbs_saved_states_bytes(sh);
-    if (sb == 0 || saved_states_bytes < sb) saved_states = nullptr;
-  }
-  if (!dX && !dCores) return DCTN_OK;
-  SbsP p;
-  int rc = fill(p, x_strides, sh, cores);
-  if (rc != DCTN_OK) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  const auto wide = [&](auto s, auto a) {
-    return wide_launch<decltype(s), decltype(a)>(x, dY, dX, dCores, workspace, workspace_bytes, p, sh, st);
-  };
-  if (dtype_flags & DCTN_SBS_WIDE_SWEEP) {   // forced: the wide family for every string it covers
-    rc = with_types(sh.dtype, wide);
-    if (rc != DCTN_ERR_UNSUPPORTED) return rc;
-  }
-  if (sh.dtype == DCTN_F32 && band_family_first(sh, dtype_flags)) {   // (true whenever the register family is tried)
-    for (int c = 0; dCores && c < n_cores; ++c)
+// (declines - DCTN_ERR_UNSUPPORTED - only in its LDS plan, before anything is written)
+int convsbs_bwd_generic_plan(SbsBwdPlan& pl, const SbsShape& sh, void* const* dCores, void* ws, size_t ws_bytes, hipStream_t st) {
+  return with_types(sh.dtype, [&](auto s, auto a) -> int {
+    using S = decltype(s); using A = decltype(a);
+    SbsP p;
+    const int rc = fill(p, nullptr, sh);
+    if (rc != DCTN_OK) return rc;
+    const BwdLayout L = bwd_layout(p, sh);
+    if (!ws || L.total > ws_bytes) return DCTN_ERR_WORKSPACE;
+    const size_t lds = bwd_lds_plan(p, sizeof(A), dCores != nullptr).lds;
+    if (!lds || !dctn_lds_optin((const void*)convsbs_bwd_generic_k<S, A>, lds)) return DCTN_ERR_UNSUPPORTED;
+    pl.states = ws;
+    pl.gxw = (unsigned char*)ws + L.states;
+    pl.acc = (unsigned char*)pl.gxw + L.gxw;
+    // the matrix-core backward's records; a tail too short for them is no error: that sweep then uses its other reduction
+    unsigned char* tail = pl.acc + L.acc;
+    pl.partial_bytes = convsbs_mfma_partial_bytes(sh);
+    pl.partials = (size_t)((unsigned char*)ws + ws_bytes - tail) >= pl.partial_bytes ? (float*)tail : nullptr;
+    if (!dCores) return DCTN_OK;
+    for (int c = 0; c < p.n; ++c)
       if (!dCores[c]) return DCTN_ERR_NULL;
-    if (!(dtype_flags & DCTN_SBS_MATRIX_CORE_SWEEP)) {
-      rc = convsbs_bwd_reg(x, x_strides, cores, dY, dX, (float* const*)dCores, sh, st, workspace, workspace_bytes);
-      if (rc != DCTN_ERR_UNSUPPORTED) return rc;
+    set_accumulators<S, A>(p, dCores, pl.acc);
+    // the accumulators start from zero: ONE fill when they sit back to back (the Python wrapper allocates the
+    // gradients of a string as one flat buffer; nine separate fills were 30 us of a 200 us backward), else one each
+    bool flat = true;
+    size_t total = 0;
+    for (int c = 0; c < p.n; ++c) {
+      if (c > 0 && (unsigned char*)p.dcore[c] != (unsigned char*)p.dcore[0] + total) flat = false;
+      total += (size_t)core_elems(p, c) * sizeof(A);
     }
-    // bonds 5..16: the band-owning backward (recomputes the chain; no saved states, no helper launches)
-    rc = convsbs_bwd_band(x, x_strides, cores, dY, dX, (float* const*)dCores, sh, st, workspace, workspace_bytes);
-    if (rc != DCTN_ERR_UNSUPPORTED) return rc;
-  }
-  // the generic sweep declines only in its LDS plan, before it writes anything: the wide family takes those strings
-  rc = with_types(sh.dtype, [&](auto s, auto a) {
-    return bwd_launch<decltype(s), decltype(a)>(x, dY, dX, dCores, workspace, workspace_bytes, p, sh, st, saved_states);
+    if (flat) return dctn_zero_async(p.dcore[0], total, st) != DCTN_OK ? DCTN_ERR_LAUNCH : DCTN_OK;
+    for (int c = 0; c < p.n; ++c)
+      if (dctn_zero_async(p.dcore[c], (size_t)core_elems(p, c) * sizeof(A), st) != DCTN_OK) return DCTN_ERR_LAUNCH;
+    return DCTN_OK;
   });
-  return rc != DCTN_ERR_UNSUPPORTED ? rc : with_types(sh.dtype, wide);
 }
 
-// ---- several strings of one layer (ManyConvSBS, dctn/conv_sbs.py:314-370) in one launch each way
-size_t dctn_convsbs_many_workspace_bytes(int n_strings, int n_cores, const int* out_sizes, const int* bond_sizes, int C, int B,
-                                         int H, int W, int q, const int* pos_h, const int* pos_w, int dtype) {
-  if (!out_sizes || !bond_sizes || !pos_h || !pos_w) return 0;
-  const SbsShape sh{n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype & DCTN_DTYPE_MASK};
-  const size_t a = convsbs_many_reg_bwd_workspace(n_strings, sh);
-  return a > 0 ? a : convsbs_many_band_bwd_workspace(n_strings, sh);
+int convsbs_bwd_generic_run(const SbsBwdPlan& pl, const void* x, const int64_t xs[5], const void* const* cores,
+                            const void* dY, void* dX, void* const* dCores, const SbsShape& sh, hipStream_t st) {
+  return with_types(sh.dtype, [&](auto s, auto a) -> int {
+    using S = decltype(s); using A = decltype(a);
+    SbsP p;
+    int rc = fill(p, xs, sh, cores);
+    if (rc != DCTN_OK) return rc;
+    const int need_dcore = dCores != nullptr;
+    const BwdLds lp = bwd_lds_plan(p, sizeof(A), need_dcore);
+    if (need_dcore) set_accumulators<S, A>(p, dCores, pl.acc);
+    const int csb = p.cst - 1;
+    const long long ngroups = (p.Wn + csb - 1) / csb;
+    // persistent workgroups: as many as can be resident (LDS-limited), at most one per window group
+    long long grid = dctn_resident_wgs(lp.lds, 1, 8);
+    if (grid > ngroups) grid = ngroups;
+    hipLaunchKernelGGL((convsbs_bwd_generic_k<S, A>), dim3((unsigned)grid), dim3(DCTN_WAVE * lp.waves), lp.lds, st,
+                       (const S*)x, (const S*)dY, (A*)pl.states, (A*)pl.gxw, p, dX != nullptr, need_dcore, ngroups);
+    DCTN_CHECK_LAUNCH();
+    if (dX && (rc = convsbs_gather_dx(sh, pl.gxw, dX, st)) != DCTN_OK) return rc;
+    if constexpr (sizeof(S) != sizeof(A)) {
+      for (int c = 0; need_dcore && c < p.n; ++c) {
+        const long long ne = core_elems(p, c);
+        hipLaunchKernelGGL((convert_sbs_k<S, A>), dim3((unsigned)((ne + 255) / 256)), dim3(256), 0,
+                           st, (const A*)p.dcore[c], (S*)dCores[c], ne);
+        DCTN_CHECK_LAUNCH();
+      }
+    }
+    dctn_set_last_kernel("convsbs_bwd_generic");
+    return DCTN_OK;
+  });
 }
 
-int dctn_convsbs_many_fwd(const void* x, const int64_t x_strides[5], const void* const* cores, void* const* outs,
-                          int n_strings, int n_cores, const int* out_sizes, const int* bond_sizes, const int* pos_h,
-                          const int* pos_w, int C, int B, int H, int W, int q, int dtype, void* stream) {
-  if (!x || !x_strides || !cores || !outs || !out_sizes || !bond_sizes || !pos_h || !pos_w) return DCTN_ERR_NULL;
-  if (n_strings < 1 || n_cores < 1) return DCTN_ERR_BAD_SHAPE;
-  if (dtype & ~DCTN_DTYPE_MASK) return DCTN_ERR_UNSUPPORTED;
-  for (int i = 0; i < n_strings * n_cores; ++i)
-    if (!cores[i]) return DCTN_ERR_NULL;
-  const SbsShape sh{n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype};
-  const int rc = convsbs_many_fwd_reg(x, x_strides, cores, outs, n_strings, sh, (hipStream_t)stream);
-  if (rc != DCTN_ERR_UNSUPPORTED) return rc;
-  return convsbs_many_fwd_band(x, x_strides, cores, outs, n_strings, sh, (hipStream_t)stream);
-}
-
-int dctn_convsbs_many_bwd(const void* x, const int64_t x_strides[5], const void* const* cores, const void* const* dYs, void* dX,
-                          void* const* dCores, int n_strings, int n_cores, const int* out_sizes, const int* bond_sizes,
-                          const int* pos_h, const int* pos_w, int C, int B, int H, int W, int q, void* workspace,
-                          size_t workspace_bytes, int dtype, void* stream) {
-  if (!x || !x_strides || !cores || !dYs || !out_sizes || !bond_sizes || !pos_h || !pos_w) return DCTN_ERR_NULL;
-  if (n_strings < 1 || n_cores < 1) return DCTN_ERR_BAD_SHAPE;
-  if (dtype & ~DCTN_DTYPE_MASK) return DCTN_ERR_UNSUPPORTED;
-  if (!dX && !dCores) return DCTN_OK;
-  for (int i = 0; i < n_strings * n_cores; ++i)
-    if (!cores[i] || (dCores && !dCores[i])) return DCTN_ERR_NULL;
-  const SbsShape sh{n_cores, out_sizes, bond_sizes, pos_h, pos_w, C, B, H, W, q, dtype};
-  const int rc = convsbs_many_bwd_reg(x, x_strides, cores, dYs, dX, (float* const*)dCores, n_strings, sh, (hipStream_t)stream,
-                                      workspace, workspace_bytes);
-  if (rc != DCTN_ERR_UNSUPPORTED) return rc;
-  return convsbs_many_bwd_band(x, x_strides, cores, dYs, dX, (float* const*)dCores, n_strings, sh, (hipStream_t)stream, workspace,
-                               workspace_bytes);
-}
-
-}  // extern "C"

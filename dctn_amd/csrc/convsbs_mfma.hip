@@ -1383,6 +1383,19 @@ struct SbsSlice {   // one launch of a string that runs in slices (many-valued c
   int sliced, obase, ostride, accum, out_accum, last_stride, ostep;
 };
 
+// Element offsets per window of the input states of cores 1 .. n-1: what a saving forward stores and the backward's sweep
+// writes and reads.  Returns their total.
+static long long sbsm_state_offsets(SbsMP& p, int n, int R) {
+  long long so = 0;
+  int oacc = 1;
+  for (int c = 0; c < n; ++c) {
+    p.st_off[c] = so;
+    if (c >= 1) so += (long long)oacc * R;
+    oacc *= p.o[c];
+  }
+  return p.st_off[n] = so;
+}
+
 static int convsbs_fwd_mfma_one(const void* x, const int64_t xs[5], const void* const* cores, void* out, const SbsShape& sh,
                                 hipStream_t st, const SbsSlice& sl, float* save) {
   SbsMP p;
@@ -1391,14 +1404,7 @@ static int convsbs_fwd_mfma_one(const void* x, const int64_t xs[5], const void* 
   if (rcf != DCTN_OK) return rcf;
   if (sl.sliced) { p.ostride = sl.ostride; p.obase = sl.obase; p.ostep = sl.ostep; p.out_accum = sl.out_accum; p.last_stride = sl.last_stride; }
   if (save && !sl.sliced && R <= 16) {   // input states of cores 1 .. n-1 for the backward (same offsets as its own sweep)
-    long long so = 0;
-    int oacc = 1;
-    for (int c = 0; c < sh.n; ++c) {
-      p.st_off[c] = so;
-      if (c >= 1) so += (long long)oacc * R;
-      oacc *= p.o[c];
-    }
-    p.st_off[sh.n] = so;
+    sbsm_state_offsets(p, sh.n, R);
     p.save = save;
   }
   const size_t lds = (size_t)off * sizeof(float);
@@ -1527,13 +1533,22 @@ size_t convsbs_saved_states_bytes(const SbsShape& sh) {
   const void* none[SBSM_MAXC] = {};
   if (sbsm_fill(p, R, off, dummy, none, sh) != DCTN_OK || R > 16) return 0;
   if (R < 8) return 0;   // bond <= 4: storing costs the forward what the backward saves (80 -> 83 us at the cfg4 shape)
-  long long so = 0;
-  int oacc = 1;
-  for (int c = 0; c < sh.n; ++c) {
-    if (c >= 1) so += (long long)oacc * R;
-    oacc *= p.o[c];
-  }
-  return (size_t)so * (size_t)p.Wn * sizeof(float);
+  return (size_t)sbsm_state_offsets(p, sh.n, R) * (size_t)p.Wn * sizeof(float);
+}
+
+// What a slice of the backward stores per window: at most two states of the padded bond per core
+long long convsbs_mfma_state_elems(const SbsShape& sh) {
+  int bmax = 1;
+  for (int c = 0; c < sh.n; ++c) bmax = sh.bond_sizes[c] > bmax ? sh.bond_sizes[c] : bmax;
+  return bmax > 16 ? 0 : (long long)sh.n * 2 * (bmax <= 4 ? 4 : bmax <= 8 ? 8 : 16);
+}
+
+// room for the per-workgroup partial-gradient records of the backward (deterministic dCore): one record is every core
+constexpr int SBS_MAX_PARTIAL_RECORDS = 2048;
+size_t convsbs_mfma_partial_bytes(const SbsShape& sh) {
+  size_t ce = 0;
+  for (int c = 0; c < sh.n; ++c) ce += (size_t)sh.out_sizes[c] * sh.bond_sizes[c] * sh.bond_sizes[(c + 1) % sh.n];
+  return sh.dtype != DCTN_F32 ? 0 : (size_t)SBS_MAX_PARTIAL_RECORDS * ce * (size_t)ipow_ll(sh.q, sh.C) * sizeof(float);
 }
 
 int convsbs_fwd_mfma(const void* x, const int64_t xs[5], const void* const* cores, void* out, const SbsShape& sh,
@@ -1563,15 +1578,8 @@ static int convsbs_bwd_mfma_one(const void* x, const int64_t xs[5], const void* 
   // the training forward's stored states replace this launch's forward sweep (whole strings only: a slice has its own)
   const bool use_saved = saved != nullptr && !sl.sliced;
   if (use_saved) states = const_cast<float*>(saved);
-  long long so = 0;
-  int oacc = 1;
-  for (int c = 0; c < sh.n; ++c) {
-    p.st_off[c] = so;
-    if (c >= 1) so += (long long)oacc * R;
-    oacc *= p.o[c];
-    p.dcore[c] = dcores[c];
-  }
-  p.st_off[sh.n] = so;
+  sbsm_state_offsets(p, sh.n, R);
+  for (int c = 0; c < sh.n; ++c) p.dcore[c] = dcores[c];
   {
     // second version (16x16x4 tiles): its own LDS plan - two packs of every middle core, the accumulators in
     // accumulator layout, the per-wave feature slices and transposition tiles
@@ -1660,19 +1668,12 @@ static int convsbs_bwd_mfma_one(const void* x, const int64_t xs[5], const void* 
   for (int c = 1; c < sh.n; ++c) full_tiles = full_tiles && sh.bond_sizes[c] == R;
   if (sl.sliced || !full_tiles || use_saved) return DCTN_ERR_UNSUPPORTED;   // (slices, padded bonds, saved states: second version only)
   p.ngroups = (p.Wn + 31) / 32;
-  so = 0;
-  oacc = 1;
-  int dacc = off;
+  int dacc = off;   // (the state offsets and the accumulators stand as set above)
   for (int c = 0; c < sh.n; ++c) {
-    p.st_off[c] = so;
-    if (c >= 1) so += (long long)oacc * R;
-    oacc *= p.o[c];
     p.dacc_off[c] = dacc;
     const int L = c == 0 ? 1 : R, Rr = c == sh.n - 1 ? 1 : R;
     dacc += p.o[c] * L * Rr * p.qc;
-    p.dcore[c] = dcores[c];
   }
-  p.st_off[sh.n] = so;
   p.dacc_off[sh.n] = dacc;
   const size_t lds = (size_t)(dacc + 1) * sizeof(float);
   if (lds > dctn_lds_wg_max()) return DCTN_ERR_UNSUPPORTED;

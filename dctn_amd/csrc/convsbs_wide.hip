@@ -48,8 +48,6 @@ struct WideLayout {
   size_t gxw, acc, part, v, f, t, g0, g1, df, total;
 };
 
-size_t wd_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 int wide_fill(WideP& p, const SbsShape& sh) {
   if (sh.n < 1 || sh.n > WIDE_MAXC || sh.C < 1 || sh.B < 1 || sh.q < 1) return DCTN_ERR_UNSUPPORTED;
   int max_h = 0, max_w = 0;
@@ -96,7 +94,7 @@ int wide_fill(WideP& p, const SbsShape& sh) {
 }
 
 WideLayout wide_layout(const WideP& p, int dtype) {
-  const size_t asz = dtype == DCTN_F64 ? 8 : 4;
+  const size_t asz = acc_size(dtype);
   WideLayout L;
   // per window of a chunk: the states of every core, features, T / dT, two state gradients, feature gradients
   const size_t per_win = ((size_t)p.st_off[p.n] + 2 * (size_t)p.qc + (size_t)p.emax + 2 * (size_t)p.gmax) * asz;
@@ -109,15 +107,15 @@ WideLayout wide_layout(const WideP& p, int dtype) {
   long long sp = (L.wc + 511) / 512;
   L.splits = (int)(sp < WIDE_MAX_SPLITS ? sp : WIDE_MAX_SPLITS);
   size_t off = 0;
-  L.gxw = off; off += wd_align((size_t)p.n * p.C * p.q * p.Wn * asz);
-  L.acc = off; if (dtype == DCTN_BF16) off += wd_align((size_t)p.cetot * sizeof(float));
-  L.part = off; off += wd_align((size_t)L.splits * p.cemax * asz);
-  L.v = off; off += wd_align((size_t)p.st_off[p.n] * L.wc * asz);
-  L.f = off; off += wd_align((size_t)p.qc * L.wc * asz);
-  L.t = off; off += wd_align((size_t)p.emax * L.wc * asz);
-  L.g0 = off; off += wd_align((size_t)p.gmax * L.wc * asz);
-  L.g1 = off; off += wd_align((size_t)p.gmax * L.wc * asz);
-  L.df = off; off += wd_align((size_t)p.qc * L.wc * asz);
+  L.gxw = off; off += align256((size_t)p.n * p.C * p.q * p.Wn * asz);
+  L.acc = off; if (dtype == DCTN_BF16) off += align256((size_t)p.cetot * sizeof(float));
+  L.part = off; off += align256((size_t)L.splits * p.cemax * asz);
+  L.v = off; off += align256((size_t)p.st_off[p.n] * L.wc * asz);
+  L.f = off; off += align256((size_t)p.qc * L.wc * asz);
+  L.t = off; off += align256((size_t)p.emax * L.wc * asz);
+  L.g0 = off; off += align256((size_t)p.gmax * L.wc * asz);
+  L.g1 = off; off += align256((size_t)p.gmax * L.wc * asz);
+  L.df = off; off += align256((size_t)p.qc * L.wc * asz);
   L.total = off;
   return L;
 }
@@ -494,25 +492,32 @@ size_t convsbs_wide_bwd_workspace(const SbsShape& sh) {
   return wide_layout(p, sh.dtype).total;
 }
 
-int convsbs_bwd_wide(const void* x, const int64_t xs[5], const void* const* cores, const void* dY, int need_dx,
+int convsbs_bwd_wide(const void* x, const int64_t xs[5], const void* const* cores, const void* dY, void* dX,
                      void* const* dcores, const SbsShape& sh, hipStream_t st, void* ws, size_t ws_bytes) {
+  const int dtype = sh.dtype;
+  if (dtype != DCTN_F32 && dtype != DCTN_F64 && dtype != DCTN_BF16) return DCTN_ERR_BAD_DTYPE;
   WideP p;
-  const int rc = wide_fill(p, sh);
+  int rc = wide_fill(p, sh);
   if (rc != DCTN_OK) return rc;
   for (int i = 0; i < 5; ++i) p.s[i] = xs[i];
   // the family's only LDS is the GEMM tiles (static): a device whose workgroups get less declines before any write
-  const size_t tile_lds = (size_t)16 * (64 + 4 + 64 + 4) * (sh.dtype == DCTN_F64 ? 8 : 4);
-  const size_t tile_lds_narrow = (size_t)16 * (256 + 4 + 16 + 4) * (sh.dtype == DCTN_F64 ? 8 : 4);
+  const size_t tile_lds = (size_t)16 * (64 + 4 + 64 + 4) * acc_size(dtype);
+  const size_t tile_lds_narrow = (size_t)16 * (256 + 4 + 16 + 4) * acc_size(dtype);
   if ((tile_lds > tile_lds_narrow ? tile_lds : tile_lds_narrow) > (size_t)dctn_lds_wg_max()) return DCTN_ERR_UNSUPPORTED;
-  const WideLayout L = wide_layout(p, sh.dtype);
+  const WideLayout L = wide_layout(p, dtype);
   if (!ws || ws_bytes < L.total) return DCTN_ERR_WORKSPACE;
   for (int c = 0; c < sh.n; ++c)
     if (!cores[c] || (dcores && !dcores[c])) return DCTN_ERR_NULL;
   unsigned char* w = (unsigned char*)ws;
-  switch (sh.dtype) {
-    case DCTN_F32: return wide_run<float, float>(x, cores, dY, need_dx, dcores, w, p, L, st);
-    case DCTN_F64: return wide_run<double, double>(x, cores, dY, need_dx, dcores, w, p, L, st);
-    case DCTN_BF16: return wide_run<bf16_t, float>(x, cores, dY, need_dx, dcores, w, p, L, st);
+  switch (dtype) {
+    case DCTN_F32: rc = wide_run<float, float>(x, cores, dY, dX != nullptr, dcores, w, p, L, st); break;
+    case DCTN_F64: rc = wide_run<double, double>(x, cores, dY, dX != nullptr, dcores, w, p, L, st); break;
+    case DCTN_BF16: rc = wide_run<bf16_t, float>(x, cores, dY, dX != nullptr, dcores, w, p, L, st); break;
   }
-  return DCTN_ERR_BAD_DTYPE;
+  // dX: gathered from the per-window input gradients at the start of the workspace, as the generic sweep's is
+  if (rc == DCTN_OK && dX) rc = convsbs_gather_dx(sh, ws, dX, st);
+  if (rc != DCTN_OK) return rc;
+  dctn_set_last_kernel(dtype == DCTN_F64 ? "convsbs_bwd_wide_f64" : dtype == DCTN_BF16 ? "convsbs_bwd_wide_bf16"
+                                                                                    : "convsbs_bwd_wide_f32");
+  return DCTN_OK;
 }

@@ -445,10 +445,8 @@ int eps_fwd_generic(const void* x, const void* core, void* out, void* ws, size_t
   return DCTN_ERR_BAD_DTYPE;
 }
 
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 size_t eps_bwd_generic_workspace(const EpsP& p, int dtype, int need_dx, int need_dcore) {
-  const size_t asz = dtype == DCTN_F64 ? 8 : 4;
+  const size_t asz = acc_size(dtype);
   size_t total = 0;
   if (need_dx) total += align256((size_t)p.Wn * p.N * p.Q * asz);
   if (need_dcore && dtype == DCTN_BF16) total += align256((size_t)p.R * p.O * asz);

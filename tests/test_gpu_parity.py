@@ -312,12 +312,21 @@ def test_convsbs_vs_oracle_mnist_snake(r, q, C, B, HW):
         assert close(c.grad, gc, torch.float32)
 
 
+# (rows, cols, bond) -> the kernels of a forward whose workspace is one byte short and of the backward handed that buffer
+# (the sixteen-bond strings: the matrix-core backward's LDS plan declines them, the generic sweep recomputes)
+SHORT_WORKSPACE_KERNELS = {
+    (2, 5, 8): ("convsbs_fwd_mfma_f32", "convsbs_bwd_mfma_f32"),
+    (5, 5, 16): ("convsbs_fwd_mfma_f32", "convsbs_bwd_generic"),
+    (4, 6, 16): ("convsbs_fwd_mfma_f32", "convsbs_bwd_generic"),
+}
+
+
 def test_convsbs_forward_reports_whether_it_wrote_the_saved_states():
     """`dctn_convsbs_fwd` returns DCTN_SAVED only when the matrix-core sweep wrote the forward states; a string the size
     query accepts but the sweep's LDS plan declines (bond 16, long strings) runs the generic forward, the buffer stays
     uninitialised and must never reach `dctn_convsbs_bwd_saved` - checked with a poisoned allocator and the oracle."""
     lib = _lib.lib()
-    seen = set()
+    seen, shorts = set(), {}
     for rows, cols, r, q in ((2, 5, 8, 2), (5, 5, 16, 2), (4, 6, 16, 2)):   # (ten cores and more: outside the band family)
         pos = [(h, w if h % 2 == 0 else cols - 1 - w) for h in range(rows) for w in range(cols)]   # boustrophedon snake
         n = len(pos)
@@ -345,6 +354,24 @@ def test_convsbs_forward_reports_whether_it_wrote_the_saved_states():
             assert dctn_amd.last_kernel() == "convsbs_fwd_mfma_f32" and not bool((states == 0xFF).all())
         else:
             assert dctn_amd.last_kernel() == "convsbs_fwd_generic" and bool((states == 0xFF).all())   # untouched
+        # a workspace one byte short of the query's answer: a plain forward (OK, not SAVED; nothing written), and a backward
+        # handed that buffer drops it silently and recomputes the states (checked against the oracle below)
+        states.fill_(0xFF)
+        rc = lib.dctn_convsbs_fwd(x.data_ptr(), _lib.strides5(x), _lib.ptr_array(cores_c), out.data_ptr(), n, plan_args[1],
+                                  plan_args[2], plan_args[8], plan_args[9], 1, B, HW, HW, q, states.data_ptr(), nstates - 1,
+                                  _lib.F32, _lib.stream_ptr(DEV))
+        torch.cuda.synchronize()
+        assert rc == 0 and bool((states == 0xFF).all()), (rows, cols, r, rc)
+        short_fwd = dctn_amd.last_kernel()
+        dy_s, dx_s = torch.randn_like(out), torch.empty_like(x)
+        dc_s = [torch.empty_like(c) for c in cores_c]
+        ws = _lib.workspace(lib.dctn_convsbs_workspace_bytes(*plan_args, 1), DEV)
+        _lib.check(lib.dctn_convsbs_bwd_saved(x.data_ptr(), _lib.strides5(x), _lib.ptr_array(cores_c), dy_s.data_ptr(),
+                                              dx_s.data_ptr(), _lib.ptr_array(dc_s), n, plan_args[1], plan_args[2], plan_args[8],
+                                              plan_args[9], 1, B, HW, HW, q, ws.data_ptr(), ws.numel(), states.data_ptr(),
+                                              nstates - 1, _lib.F32, _lib.stream_ptr(DEV)), "backward, short saved states")
+        torch.cuda.synchronize()
+        short = (short_fwd, dctn_amd.last_kernel(), out.clone(), dy_s, dx_s, dc_s)
         del states
         with guarded(fill=0xFF) as arena:   # what the module allocates (the states, of exactly the queried size) is poisoned
             y = m(x)
@@ -358,6 +385,12 @@ def test_convsbs_forward_reports_whether_it_wrote_the_saved_states():
         assert close(x.grad, gr[0], torch.float32)
         for c, gc in zip(m.cores, gr[1:]):
             assert close(c.grad, gc, torch.float32)
+        short_fwd, short_bwd, y_s, dy_s, dx_s, dc_s = short
+        shorts[(rows, cols, r)] = (short_fwd, short_bwd)
+        gs = R.grads(lambda xx, *cc: R.convsbs_forward(cc, pos, xx), [x.detach().cpu().double()] + cores64, dy_s.cpu().double())
+        assert close(y_s, want, torch.float32) and close(dx_s, gs[0], torch.float32)
+        assert all(close(g, w, torch.float32) for g, w in zip(dc_s, gs[1:]))
+    assert shorts == SHORT_WORKSPACE_KERNELS, shorts
     assert _lib.SAVED in seen   # (whether a string is declined depends on the LDS plan; the ten-core bond-8 snake always saves)
 
 
