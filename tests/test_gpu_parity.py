@@ -996,11 +996,13 @@ def test_logmatmulexp_fold16_factored_mfma_and_exact_fallback():
         assert float((got[wdw] - gm[wdw]).abs().max() / scale) < 2e-4, wdw
 
 
-@pytest.mark.parametrize("nb,T,Rr,I", [(1, 256, 256, 256), (3, 100, 70, 130), (2, 64, 16, 64), (5, 33, 40, 65)])
+@pytest.mark.parametrize("nb,T,Rr,I", [(1, 256, 256, 256), (3, 100, 70, 130), (2, 64, 16, 64), (5, 33, 40, 65), (64, 100, 100, 100)])
 def test_logmatmulexp_factored_gemm_and_exact_fallback(nb, T, Rr, I):
     """float32 products that are not tiny: exp -> MFMA GEMM -> log.  Ragged tiles, -inf rows / columns,
     dynamic ranges the factorisation cannot hold (output tiles / batch elements redone by the direct
-    kernels) — torch.logsumexp semantics throughout."""
+    kernels) — torch.logsumexp semantics throughout.  The last set is the only one whose 64 x 64 tiles fill the chip
+    (2 x 2 ragged tiles x 64 batch elements, forward, dA and dB alike): the 2 x 2-wave workgroup shape of the GEMM in all
+    three modes (tests/test_host_small_device.py restates the rule)."""
     from dctn_amd.logmatmulexp import logmatmulexp_batched
     torch.manual_seed(nb * 1000 + T)
     a, b = torch.randn(nb, T, Rr) * 3, torch.randn(nb, Rr, I) * 3
@@ -1046,6 +1048,58 @@ def test_logmatmulexp_factored_gemm_and_exact_fallback(nb, T, Rr, I):
     a2[0, 9, 4] = float("nan")
     y2 = logmatmulexp_batched(a2.to(DEV), bd.detach()).cpu()
     assert torch.isnan(y2[0, 9]).all() and int(torch.isnan(y2).sum()) == I
+
+
+def _lme_ref(aa, bb):
+    return torch.logsumexp(aa.unsqueeze(3) + bb.unsqueeze(1), dim=2)
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+def test_logmatmulexp_batched_left_operand_broadcast(dtype):
+    """(1, 4, 6) x (5, 6, 3) on the direct kernels: the LEFT operand is shared by the batch, so its gradient is a sum over
+    the batch inside lme_bwd_dA_k (the right operand's broadcast is in test_logmatmulexp_fold_and_batched)."""
+    torch.manual_seed(46)
+    a, b = torch.randn(1, 4, 6, dtype=dtype), torch.randn(5, 6, 3, dtype=dtype)
+    ad, bd = a.to(DEV).requires_grad_(True), b.to(DEV).requires_grad_(True)
+    y = logmatmulexp_batched(ad, bd)
+    assert dctn_amd.last_kernel() == "logmatmulexp_fwd" and y.shape == (5, 4, 3)
+    assert close(y, _lme_ref(a.double(), b.double()), dtype)
+    dy = torch.randn(5, 4, 3, dtype=dtype)
+    y.backward(dy.to(DEV))
+    assert dctn_amd.last_kernel() == "logmatmulexp_bwd"
+    ga, gb = R.grads(_lme_ref, [a.double(), b.double()], dy.double())
+    assert ad.grad.shape == (1, 4, 6) and close(ad.grad, ga, dtype) and close(bd.grad, gb, dtype)
+
+
+def test_logmatmulexp_bf16_storage():
+    """bf16 tensors on the direct kernels (float32 arithmetic, one rounding per stored value): the batched product and the
+    fold at D = 7, L = 3, against the float64 oracle on the bf16-rounded inputs; `mag` is the same sum over the absolute
+    terms (the forward's terms are positive: its own magnitude)."""
+    torch.manual_seed(47)
+    a, b = (torch.randn(5, 4, 6) * 0.5).bfloat16(), (torch.randn(5, 6, 3) * 0.5).bfloat16()
+    dy = torch.randn(5, 4, 3).bfloat16()
+    ad, bd = a.to(DEV).requires_grad_(True), b.to(DEV).requires_grad_(True)
+    y = logmatmulexp_batched(ad, bd)
+    assert dctn_amd.last_kernel() == "logmatmulexp_fwd" and y.dtype == torch.bfloat16
+    want = _lme_ref(a.double(), b.double())
+    assert bf16_close(y, want, want.abs())
+    y.backward(dy.to(DEV))
+    assert dctn_amd.last_kernel() == "logmatmulexp_bwd"
+    ga, gb = R.grads(_lme_ref, [a.double(), b.double()], dy.double())
+    ma, mb = R.grads(_lme_ref, [a.double(), b.double()], dy.double().abs())
+    assert bf16_close(ad.grad, ga, ma) and bf16_close(bd.grad, gb, mb)
+    m = (torch.randn(9, 3, 7, 7) * 0.5).bfloat16()
+    md = m.to(DEV).requires_grad_(True)
+    yf = logmatmulexp_fold(md)
+    assert dctn_amd.last_kernel() == "logmatmulexp_fold_fwd" and yf.dtype == torch.bfloat16
+    wf = R.logmatmulexp_fold_batched(m.double())
+    assert bf16_close(yf, wf, wf.abs())
+    dyf = torch.randn(9, 7, 7).bfloat16()
+    yf.backward(dyf.to(DEV))
+    assert dctn_amd.last_kernel() == "logmatmulexp_fold_bwd"
+    (gm,) = R.grads(R.logmatmulexp_fold_batched, [m.double()], dyf.double())
+    (mm,) = R.grads(R.logmatmulexp_fold_batched, [m.double()], dyf.double().abs())
+    assert bf16_close(md.grad, gm, mm)
 
 
 # ------------------------------------------------------------------ window statistics (SURVEY 8(f) f3)
