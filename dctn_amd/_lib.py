@@ -91,6 +91,11 @@ SIGNATURES = {
                                          c_int, c_int, c_void]),
     "dctn_sgd_l2_step_master_guarded": (c_int, [c_void] * 6 + [c_i64, c_i64, ctypes.c_float, ctypes.c_float,
                                                 ctypes.c_float, c_int, c_void]),
+    "dctn_lr_schedule_bytes": (c_size, []),
+    "dctn_lr_schedule_value": (c_int, [c_void, c_i64, ctypes.POINTER(ctypes.c_float)]),
+    "dctn_adam_l2_step_scheduled": (c_int, [c_void] * 9 + [c_i64, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_float,
+                                            ctypes.c_float, ctypes.c_float, c_int, c_void]),
+    "dctn_sgd_l2_step_scheduled": (c_int, [c_void] * 8 + [c_i64, c_i64, ctypes.c_float, ctypes.c_float, c_int, c_void]),
     "dctn_step_trace_head_bytes": (c_size, []),
     "dctn_step_trace_record_bytes": (c_size, []),
     "dctn_step_trace_record": (c_int, [c_void] * 9 + [c_int, c_i64, c_int, c_int, c_void]),

@@ -273,7 +273,11 @@ def _tensor_regions(model, optimizer, batch_source, guard, trace=None):
             regions.append((f"optimizer.{name}", getattr(optimizer, name)))
         if optimizer.master is not None:
             regions.append(("optimizer.master", optimizer.master))
-        if isinstance(optimizer, training.FlatAdam):
+        # a scheduled optimizer: the schedule's block, and in front of the step block so that a file and a run that
+        # disagree about the schedule differ at this entry first
+        if getattr(optimizer, "schedule", None) is not None:
+            regions.append(("optimizer.schedule", optimizer.schedule._block))
+        if getattr(optimizer, "_state", None) is not None:   # FlatAdam; a FlatSGD with a schedule
             regions.append(("optimizer.state", optimizer._state))
         regions.append(("optimizer.sq_sum", optimizer.sq_sum))
     entries = []
@@ -302,7 +306,10 @@ def _tensor_regions(model, optimizer, batch_source, guard, trace=None):
 
 class RunState:
     """The device state of a training run as named regions: with a `FlatAdam` / `FlatSGD` its flat parameter buffer, the
-    moments (or the momentum buffer), the master copy, the 16-byte step block and ``sq_sum``; every entry of the model's
+    moments (or the momentum buffer), the master copy, the 16-byte step block and ``sq_sum``; with an `LRSchedule` on the
+    optimizer the schedule's block as ``optimizer.schedule`` (and the step block of a scheduled `FlatSGD` as
+    ``optimizer.state``; a file and a run that disagree about the schedule are refused at that entry, and runs without a
+    schedule keep their region lists and their files); every entry of the model's
     state_dict that does not live in the flat buffer (the buffer ``p``; without an optimizer every parameter) as a region
     of its own; ``model._dropout_state`` when the fused dropout is on; ``guard._block`` (``guard`` defaults to the
     optimizer's); ``batch_source._state``; with ``trace`` (a `training.StepTrace`) its head and ring as ``trace.head`` /
@@ -371,11 +378,12 @@ class RunState:
         host: Dict[str, Any] = {}
         opt = self.optimizer
         if opt is not None:
+            # (`_lr`: the host copy; with a schedule the rate is in the blocks, and reading `lr` would synchronise)
             if self._kind == "FlatAdam":
-                host["optimizer"] = dict(kind=self._kind, lr=opt.lr, betas=list(opt.betas), eps=opt.eps,
+                host["optimizer"] = dict(kind=self._kind, lr=opt._lr, betas=list(opt.betas), eps=opt.eps,
                                          weight_decay=opt.weight_decay, l2=opt.l2)
             else:
-                host["optimizer"] = dict(kind=self._kind, lr=opt.lr, momentum=opt.momentum, l2=opt.l2, steps=opt._steps)
+                host["optimizer"] = dict(kind=self._kind, lr=opt._lr, momentum=opt.momentum, l2=opt.l2, steps=opt._steps)
         if self.batch_source is not None:
             src = self.batch_source
             host["batch_source"] = dict(n=src.n, batch_size=src.batch_size, seed=src.seed)
@@ -449,6 +457,9 @@ class RunState:
                 raise RuntimeError(f"{path}: region {r['name']!r} was damaged on its way to the device: the scatter read "
                                    f"the digest {(int(s1), int(s2))}, the manifest says {(r['s1'], r['s2'])}")
         self._set_host_mirrors(manifest["host"])
+        if getattr(self.optimizer, "schedule", None) is not None:   # the block came back: the host copy of the table follows
+            block = next(r for r in manifest["regions"] if r["name"] == "optimizer.schedule")
+            self.optimizer.schedule._mirror_block(arena[block["offset"]: block["offset"] + block["bytes"]].view("<i4"))
         if self.trace is not None:   # head and ring came back with their regions: the records before the head count as read
             head = next(r for r in manifest["regions"] if r["name"] == "trace.head")
             done = int(arena[head["offset"]: head["offset"] + 4].view("<u4")[0])
@@ -464,7 +475,7 @@ class RunState:
                 opt.betas, opt.eps = (float(saved["betas"][0]), float(saved["betas"][1])), float(saved["eps"])
                 opt.weight_decay, opt.l2 = float(saved["weight_decay"]), float(saved["l2"])
             else:
-                opt.lr, opt.momentum, opt.l2 = float(saved["lr"]), float(saved["momentum"]), float(saved["l2"])
+                opt._lr, opt.momentum, opt.l2 = float(saved["lr"]), float(saved["momentum"]), float(saved["l2"])
                 opt._steps = int(saved["steps"])
         if self.guard is not None:
             self.guard._max_norm = float(host["guard"]["max_norm"])

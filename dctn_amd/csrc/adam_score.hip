@@ -8,6 +8,7 @@
 //   ce_score_k : adds one batch's {sum of cross-entropies, correct rows, rows} to three float64 values
 #include "common.h"
 #include "grad_guard.h"
+#include "lr_schedule.h"
 
 #include <cmath>
 
@@ -70,7 +71,6 @@ __device__ __forceinline__ void store4(bf16_t* p, const float (&x)[4]) {
 // Workgroups of 1024 threads, at most 256 of them: the ticket at the end is one atomic per workgroup on ONE address,
 // and those serialise at about 12 ns each (measured: 1024 workgroups of 256 threads took 17.7 us over 1.9 M
 // parameters where the same stream without a ticket, sgd_l2_k, takes 5.7 us).
-__device__ __forceinline__ const GradGuardBlock* guard_of(const GradGuardBlock* g) { return g; }
 // the guarded step's gradient: one rounded float32 product, never contracted into the FMA that follows
 template <bool GUARD> __device__ __forceinline__ float clipped(float g, float coef) {
   if constexpr (GUARD) return __fmul_rn(g, coef); else return g;
@@ -84,17 +84,25 @@ template <bool GUARD> __device__ __forceinline__ float clipped(float g, float co
 // decay and the 2 * l2 * w term come after it.  coef == 1 leaves g's bits, so an unclipped guarded step is the
 // unguarded one.  The guard block is a trailing parameter PACK, empty in the unguarded instantiations, and everything
 // else of it is behind `if constexpr`: those compile to what they did.
+// SCHED (the pack also holds a const LrScheduleBlock*): the rate is not read from state->lr but evaluated from the
+// schedule block at step steps_done (lr_schedule.h).  Wave 0 loads the table, one knot per lane, together with
+// steps_done - no load of it depends on another, so the table adds no memory round trip in front of the element loop -
+// finds the segment with a ballot, and lane 0 publishes step and bc2_sqrt as in the other forms.  The workgroup that
+// draws the last ticket writes the rate it used to state->lr beside steps_done: the block reports the rate of the step
+// just taken.  A halted guarded step returns before the ticket, so the schedule holds its place with steps_done.
 template <typename S, bool VEC, bool MASTER, typename... G>
 __global__ __launch_bounds__(1024) void adam_l2_k(S* __restrict__ w, float* __restrict__ wm, const S* __restrict__ g,
                                                  float* __restrict__ ea, float* __restrict__ eas,
                                                  float* __restrict__ sq_sum, AdamState* __restrict__ state, long long n,
                                                  long long n_reg, AdamCoef k, G... guard_block) {
-  constexpr bool GUARD = sizeof...(G) == 1;   // G = {const GradGuardBlock*}; empty: the unguarded kernel, parameter for parameter
+  // G holds a const GradGuardBlock* (GUARD), a const LrScheduleBlock* (SCHED), both in that order, or nothing: the plain
+  // kernel, parameter for parameter
+  constexpr bool GUARD = pack_has_v<const GradGuardBlock*, G...>, SCHED = pack_has_v<const LrScheduleBlock*, G...>;
   __shared__ float red[16];
   __shared__ float scale[GUARD ? 4 : 2];
   if constexpr (GUARD) {
     if (threadIdx.x == 0) {
-      const GradGuardBlock* guard = guard_of(guard_block...);
+      const GradGuardBlock* guard = pack_get<const GradGuardBlock*>(guard_block...);
       scale[2] = __hip_atomic_load(&guard->halted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ? 1.f : 0.f;
       scale[3] = __hip_atomic_load(&guard->coef, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -103,9 +111,19 @@ __global__ __launch_bounds__(1024) void adam_l2_k(S* __restrict__ w, float* __re
   // the one write of the launch to steps_done happens after the last ticket is drawn, so no workgroup can see the new
   // value
   int t = 0;
+  float lr = 0.f;
+  if constexpr (SCHED) {
+    if (threadIdx.x < 64) {   // wave 0, every lane: the ballot needs them all
+      const LrScheduleLane knot = lr_schedule_lane_load(pack_get<const LrScheduleBlock*>(guard_block...), threadIdx.x);
+      t = __hip_atomic_load(&state->steps_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
+      lr = lr_schedule_wave_value(knot, threadIdx.x, t - 1);
+    }
+  }
   if (threadIdx.x == 0) {
-    t = __hip_atomic_load(&state->steps_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
-    const float lr = __hip_atomic_load(&state->lr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (!SCHED) {
+      t = __hip_atomic_load(&state->steps_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
+      lr = __hip_atomic_load(&state->lr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     // The two bias corrections in float64, once per workgroup, rounded once - what torch's host arithmetic gives.  In
     // float32 the difference 1 - beta2^t cancels: at t = 1 it is 0.001 with the absolute error of 0.999, a relative
     // 6e-5 in every update of the first steps.  (From t itself, not as running products, which drift.)
@@ -159,6 +177,7 @@ __global__ __launch_bounds__(1024) void adam_l2_k(S* __restrict__ w, float* __re
     const unsigned drawn = __hip_atomic_fetch_add(&state->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (drawn == gridDim.x - 1) {   // plain vector stores; the next launch starts from ticket 0 again
       state->steps_done = t;
+      if constexpr (SCHED) state->lr = lr;   // the rate this step used (no workgroup of a scheduled launch reads it)
       state->ticket = 0u;
     }
   }
@@ -168,6 +187,19 @@ unsigned adam_blocks_for(long long n) {   // one vector access of every lane per
   long long b = (n + 4095) / 4096;
   if (b > 256) b = 256;
   return (unsigned)(b < 1 ? 1 : b);
+}
+
+// the scheduled forms: one launcher for every pack, the vector or the scalar kernel by alignment
+template <typename S, bool MASTER, typename... G>
+void adam_launch_pack(bool vec, dim3 g, dim3 b, hipStream_t st, void* params, void* master, const void* grads,
+                      void* exp_avg, void* exp_avg_sq, void* sq_sum, AdamState* sp, long long n, long long n_reg,
+                      const AdamCoef& k, G... pack) {
+  if (vec)
+    hipLaunchKernelGGL((adam_l2_k<S, true, MASTER, G...>), g, b, 0, st, (S*)params, (float*)master, (const S*)grads,
+                       (float*)exp_avg, (float*)exp_avg_sq, (float*)sq_sum, sp, n, n_reg, k, pack...);
+  else
+    hipLaunchKernelGGL((adam_l2_k<S, false, MASTER, G...>), g, b, 0, st, (S*)params, (float*)master, (const S*)grads,
+                       (float*)exp_avg, (float*)exp_avg_sq, (float*)sq_sum, sp, n, n_reg, k, pack...);
 }
 
 __device__ __forceinline__ float ld_f32(const float* p) { return *p; }
@@ -242,10 +274,13 @@ int dctn_adam_l2_num_partials(int64_t n) { return n < 1 ? 0 : (int)adam_blocks_f
 // master == nullptr: the parameters are updated in their own dtype; otherwise they are bf16, written only, and the step
 // runs on the float32 `master`
 // guarded: the step obeys the guard block `guard` (dctn_grad_guard_check ran in front of it on the same stream)
+// scheduled: the rate comes from the schedule block `schedule`, not from state->lr
 static int adam_launch(void* master, void* params, const void* grads, void* exp_avg, void* exp_avg_sq, void* sq_sum,
                        void* state, int64_t n, int64_t n_reg, double beta1, double beta2, float eps, float weight_decay,
-                       float l2, int dtype, void* stream, bool guarded = false, const void* guard = nullptr) {
-  if (!params || !grads || !exp_avg || !exp_avg_sq || !state || (guarded && !guard)) return DCTN_ERR_NULL;
+                       float l2, int dtype, void* stream, bool guarded = false, const void* guard = nullptr,
+                       bool scheduled = false, const void* schedule = nullptr) {
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !state || (guarded && !guard) || (scheduled && !schedule))
+    return DCTN_ERR_NULL;
   if (n < 1 || n_reg < 0 || n_reg > n) return DCTN_ERR_BAD_SHAPE;
   if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return DCTN_ERR_BAD_SHAPE;   // torch raises ValueError
   if (dtype != DCTN_F32 && dtype != DCTN_BF16) return DCTN_ERR_BAD_DTYPE;
@@ -266,7 +301,19 @@ static int adam_launch(void* master, void* params, const void* grads, void* exp_
   hipLaunchKernelGGL((adam_l2_k<S, VEC, MASTER, const GradGuardBlock*>), g, b, 0, st, (S*)params, (float*)master,   \
                      (const S*)grads, (float*)exp_avg, (float*)exp_avg_sq, (float*)sq_sum, sp, (long long)n,        \
                      (long long)n_reg, k, (const GradGuardBlock*)guard)
-  if (guarded) {
+  if (scheduled) {
+    const LrScheduleBlock* sched = (const LrScheduleBlock*)schedule;
+    const GradGuardBlock* gp = (const GradGuardBlock*)guard;
+#define DCTN_ADAM_ARGS vec, g, b, st, params, master, grads, exp_avg, exp_avg_sq, sq_sum, sp, (long long)n, (long long)n_reg, k
+    if (master) {
+      if (guarded) adam_launch_pack<bf16_t, true>(DCTN_ADAM_ARGS, gp, sched); else adam_launch_pack<bf16_t, true>(DCTN_ADAM_ARGS, sched);
+    } else if (dtype == DCTN_F32) {
+      if (guarded) adam_launch_pack<float, false>(DCTN_ADAM_ARGS, gp, sched); else adam_launch_pack<float, false>(DCTN_ADAM_ARGS, sched);
+    } else {
+      if (guarded) adam_launch_pack<bf16_t, false>(DCTN_ADAM_ARGS, gp, sched); else adam_launch_pack<bf16_t, false>(DCTN_ADAM_ARGS, sched);
+    }
+#undef DCTN_ADAM_ARGS
+  } else if (guarded) {
     if (master) {
       if (vec) DCTN_ADAM_LAUNCH_GUARDED(bf16_t, true, true); else DCTN_ADAM_LAUNCH_GUARDED(bf16_t, false, true);
     } else if (dtype == DCTN_F32) {
@@ -315,6 +362,32 @@ int dctn_adam_l2_step_master_guarded(void* master, void* params, const void* gra
   if (!master) return DCTN_ERR_NULL;
   return adam_launch(master, params, grads, exp_avg, exp_avg_sq, sq_sum, state, n, n_reg, beta1, beta2, eps,
                      weight_decay, l2, DCTN_BF16, stream, true, guard);
+}
+
+int dctn_adam_l2_step_scheduled(void* master_or_null, void* params, const void* grads, void* exp_avg, void* exp_avg_sq,
+                                void* sq_sum, void* state, const void* guard_or_null, const void* schedule, int64_t n,
+                                int64_t n_reg, double beta1, double beta2, float eps, float weight_decay, float l2,
+                                int dtype, void* stream) {
+  if (!schedule) return DCTN_ERR_NULL;
+  if (master_or_null && dtype != DCTN_BF16) return DCTN_ERR_BAD_DTYPE;   // a master copy goes with bf16 parameters
+  return adam_launch(master_or_null, params, grads, exp_avg, exp_avg_sq, sq_sum, state, n, n_reg, beta1, beta2, eps,
+                     weight_decay, l2, dtype, stream, guard_or_null != nullptr, guard_or_null, true, schedule);
+}
+
+size_t dctn_lr_schedule_bytes(void) { return sizeof(LrScheduleBlock); }
+
+// Host only: validates a HOST copy of the block and evaluates it with the function the kernels run
+int dctn_lr_schedule_value(const void* host_block, int64_t step, float* out) {
+  if (!host_block || !out) return DCTN_ERR_NULL;
+  const LrScheduleBlock& b = *(const LrScheduleBlock*)host_block;
+  if (step < 0 || b.n_knots < 1 || b.n_knots > DCTN_LR_MAX_KNOTS) return DCTN_ERR_BAD_SHAPE;
+  if (!(std::isfinite(b.scale) && b.scale >= 0.f)) return DCTN_ERR_BAD_SHAPE;
+  for (int i = 0; i < b.n_knots; ++i) {
+    if (b.k[i] < 0 || (i > 0 && b.k[i] <= b.k[i - 1])) return DCTN_ERR_BAD_SHAPE;
+    if (!(std::isfinite(b.lr[i]) && b.lr[i] >= 0.f)) return DCTN_ERR_BAD_SHAPE;
+  }
+  *out = lr_schedule_value_host(b, (long long)step);
+  return DCTN_OK;
 }
 
 int dctn_ce_score_accumulate(const void* logits, const void* labels, void* acc, int64_t B, int C, int dtype,

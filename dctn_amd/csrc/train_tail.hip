@@ -14,6 +14,7 @@
 //                copy, which is read and written; the bf16 cell only receives the rounded result
 #include "common.h"
 #include "grad_guard.h"
+#include "lr_schedule.h"
 
 namespace {
 
@@ -113,7 +114,6 @@ __device__ __forceinline__ float sgd_elem(float wi, float gi, float* __restrict_
 
 // MASTER (S = bf16_t): the weight comes from and goes back to the float32 array `wm`; `w` gets its bf16 rounding and is
 // not read, and `wm` and the sq_sum slots are the float instantiation's bits.  Without MASTER `wm` is unused (null).
-__device__ __forceinline__ const GradGuardBlock* guard_of(const GradGuardBlock* g) { return g; }
 // the guarded step's gradient: one rounded float32 product, never contracted into the FMA that follows
 template <bool GUARD> __device__ __forceinline__ float clipped(float g, float coef) {
   if constexpr (GUARD) return __fmul_rn(g, coef); else return g;
@@ -125,18 +125,49 @@ template <bool GUARD> __device__ __forceinline__ float clipped(float g, float co
 // replaced by ONE rounded float32 product g * coef in front of sgd_elem (the 2 * l2 * w term comes after the clip).
 // The guard block is a trailing parameter PACK, empty in the unguarded instantiations, and the rest is behind
 // `if constexpr`: those compile to what they did.
+// SCHED (the pack also holds a StepStateBlock* and a const LrScheduleBlock*): the launch arguments `lr` and `first_step`
+// are not used.  The 16-byte step block is adam_l2_k's, with the same ticket: wave 0 loads steps_done and the table, one
+// knot per lane, finds the segment with a ballot (lr_schedule.h) and publishes the rate and first_step = (steps_done
+// == 0) through LDS, together with the guard's decision when there is one; the workgroup that draws the last ticket
+// writes steps_done + 1 and the rate it used.  A halted guarded step returns before the ticket: steps_done stays, and
+// the schedule holds its place.
 template <typename S, bool MASTER, typename... G>
 __global__ __launch_bounds__(256) void sgd_l2_k(S* __restrict__ w, float* __restrict__ wm, const S* __restrict__ g,
                                                 float* __restrict__ buf, float* __restrict__ sq_sum, long long n,
                                                 long long n_reg, float lr, float momentum, float l2, int first_step,
                                                 G... guard_block) {
-  constexpr bool GUARD = sizeof...(G) == 1;   // G = {const GradGuardBlock*}; empty: the unguarded kernel, parameter for parameter
+  // G holds a const GradGuardBlock* (GUARD), a StepStateBlock* and a const LrScheduleBlock* (SCHED), all three in that
+  // order, or nothing: the plain kernel, parameter for parameter
+  constexpr bool GUARD = pack_has_v<const GradGuardBlock*, G...>, SCHED = pack_has_v<const LrScheduleBlock*, G...>;
   __shared__ float red[4];
   float coef = 1.f;
-  if constexpr (GUARD) {
+  int steps_done = 0;
+  if constexpr (SCHED) {
+    __shared__ float published[4];   // rate, first_step, halted, coef
+    if (threadIdx.x < 64) {   // wave 0, every lane: the ballot needs them all
+      const LrScheduleLane knot = lr_schedule_lane_load(pack_get<const LrScheduleBlock*>(guard_block...), threadIdx.x);
+      steps_done = __hip_atomic_load(&pack_get<StepStateBlock*>(guard_block...)->steps_done, __ATOMIC_RELAXED,
+                                     __HIP_MEMORY_SCOPE_AGENT);
+      const float rate = lr_schedule_wave_value(knot, threadIdx.x, steps_done);
+      if (threadIdx.x == 0) {
+        published[0] = rate, published[1] = steps_done == 0 ? 1.f : 0.f;
+        if constexpr (GUARD) {
+          const GradGuardBlock* guard = pack_get<const GradGuardBlock*>(guard_block...);
+          published[2] = __hip_atomic_load(&guard->halted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ? 1.f : 0.f;
+          published[3] = __hip_atomic_load(&guard->coef, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
+    }
+    __syncthreads();
+    if constexpr (GUARD) {
+      if (published[2] != 0.f) return;   // the whole workgroup, before any store and before the ticket
+      coef = published[3];
+    }
+    lr = published[0], first_step = published[1] != 0.f ? 1 : 0;
+  } else if constexpr (GUARD) {
     __shared__ float decision[2];
     if (threadIdx.x == 0) {
-      const GradGuardBlock* guard = guard_of(guard_block...);
+      const GradGuardBlock* guard = pack_get<const GradGuardBlock*>(guard_block...);
       decision[0] = __hip_atomic_load(&guard->halted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ? 1.f : 0.f;
       decision[1] = __hip_atomic_load(&guard->coef, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -158,12 +189,35 @@ __global__ __launch_bounds__(256) void sgd_l2_k(S* __restrict__ w, float* __rest
   // one slot per workgroup, stored (not accumulated): no fill before the kernel, no atomics, a fixed summation order;
   // the caller adds the dctn_sgd_l2_num_partials(n) slots when it wants the regulariser's value
   if (threadIdx.x == 0 && sq_sum) sq_sum[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  if constexpr (SCHED) {
+    if (threadIdx.x == 0) {
+      // The ticket of adam_l2_k: it orders every workgroup's read of steps_done before the last workgroup's write of it.
+      // The wait makes sure this lane's load of steps_done has returned before the ticket is drawn.
+      StepStateBlock* state = pack_get<StepStateBlock*>(guard_block...);
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      const unsigned drawn = __hip_atomic_fetch_add(&state->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (drawn == gridDim.x - 1) {   // plain vector stores; the next launch starts from ticket 0 again
+        state->steps_done = steps_done + 1;
+        state->lr = lr;
+        state->ticket = 0u;
+      }
+    }
+  }
 }
 
 unsigned blocks_for(long long n) {
   long long b = (n + 255) / 256;
   if (b > 1024) b = 1024;
   return (unsigned)(b < 1 ? 1 : b);
+}
+
+// the scheduled forms: rate and first_step come from the device (the launch arguments are zeros)
+template <typename S, bool MASTER, typename... G>
+void sgd_launch_pack(dim3 g, dim3 b, hipStream_t st, void* params, void* master, const void* grads,
+                            void* momentum_buf, void* sq_sum, long long n, long long n_reg, float momentum, float l2,
+                            G... pack) {
+  hipLaunchKernelGGL((sgd_l2_k<S, MASTER, G...>), g, b, 0, st, (S*)params, (float*)master, (const S*)grads,
+                     (float*)momentum_buf, (float*)sq_sum, n, n_reg, 0.f, momentum, l2, 0, pack...);
 }
 
 }  // namespace
@@ -243,6 +297,30 @@ static int sgd_launch(void* master, void* params, const void* grads, void* momen
     hipLaunchKernelGGL((sgd_l2_k<float, false>), g, b, 0, st, (float*)params, (float*)nullptr, (const float*)grads, (float*)momentum_buf, (float*)sq_sum, (long long)n, (long long)n_reg, lr, momentum, l2, first_step);
   else
     hipLaunchKernelGGL((sgd_l2_k<bf16_t, false>), g, b, 0, st, (bf16_t*)params, (float*)nullptr, (const bf16_t*)grads, (float*)momentum_buf, (float*)sq_sum, (long long)n, (long long)n_reg, lr, momentum, l2, first_step);
+  DCTN_CHECK_LAUNCH();
+  return DCTN_OK;
+}
+
+int dctn_sgd_l2_step_scheduled(void* master_or_null, void* params, const void* grads, void* momentum_buf, void* sq_sum,
+                               void* state, const void* guard_or_null, const void* schedule, int64_t n, int64_t n_reg,
+                               float momentum, float l2, int dtype, void* stream) {
+  if (!params || !grads || !momentum_buf || !state || !schedule) return DCTN_ERR_NULL;
+  if (n < 1 || n_reg < 0 || n_reg > n) return DCTN_ERR_BAD_SHAPE;
+  if ((dtype != DCTN_F32 && dtype != DCTN_BF16) || (master_or_null && dtype != DCTN_BF16)) return DCTN_ERR_BAD_DTYPE;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 g(blocks_for(n)), b(256);
+  const GradGuardBlock* gp = (const GradGuardBlock*)guard_or_null;
+  StepStateBlock* sp = (StepStateBlock*)state;
+  const LrScheduleBlock* sched = (const LrScheduleBlock*)schedule;
+#define DCTN_SGD_ARGS g, b, st, params, master_or_null, grads, momentum_buf, sq_sum, (long long)n, (long long)n_reg, momentum, l2
+  if (master_or_null) {
+    if (gp) sgd_launch_pack<bf16_t, true>(DCTN_SGD_ARGS, gp, sp, sched); else sgd_launch_pack<bf16_t, true>(DCTN_SGD_ARGS, sp, sched);
+  } else if (dtype == DCTN_F32) {
+    if (gp) sgd_launch_pack<float, false>(DCTN_SGD_ARGS, gp, sp, sched); else sgd_launch_pack<float, false>(DCTN_SGD_ARGS, sp, sched);
+  } else {
+    if (gp) sgd_launch_pack<bf16_t, false>(DCTN_SGD_ARGS, gp, sp, sched); else sgd_launch_pack<bf16_t, false>(DCTN_SGD_ARGS, sp, sched);
+  }
+#undef DCTN_SGD_ARGS
   DCTN_CHECK_LAUNCH();
   return DCTN_OK;
 }

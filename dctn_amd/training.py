@@ -467,7 +467,8 @@ class StepTrace:
                guard: Optional["GradGuard"] = None, optimizer=None, batch_source=None) -> None:
         """Enqueues the launch on the current stream.  ``logits`` (B, C) float32 / bfloat16, ``labels`` int64, ``loss`` and
         ``reg`` float32 device scalars (a ``reg`` of another dtype is cast first: one more launch).  The Adam block is
-        taken from a `FlatAdam`; a `FlatSGD` (or any other optimizer) has no device block and passes none."""
+        taken from a `FlatAdam`, or from a `FlatSGD` with a schedule (the same layout); a `FlatSGD` without one (or any
+        other optimizer) has no device block and passes none."""
         dev = L.require_device(logits, labels, loss)
         if logits.ndim != 2 or labels.shape != (logits.shape[0],) or labels.dtype != torch.int64:
             raise TypeError("StepTrace.record: logits (batch, classes) and int64 labels (batch,)")
@@ -479,7 +480,8 @@ class StepTrace:
             if reg.numel() != 1:
                 raise TypeError("StepTrace.record: reg must be a scalar")
             reg = reg.detach().to(device=dev, dtype=torch.float32)
-        adam = getattr(optimizer, "_state", None) if isinstance(optimizer, FlatAdam) else None
+        # (a FlatSGD has the block only with a schedule: the same 16 bytes)
+        adam = getattr(optimizer, "_state", None) if isinstance(optimizer, (FlatAdam, FlatSGD)) else None
         L.check(L.lib().dctn_step_trace_record(
             logits.data_ptr(), labels.data_ptr(), loss.data_ptr(), None if reg is None else reg.data_ptr(),
             None if guard is None else guard._block.data_ptr(), None if adam is None else adam.data_ptr(),
@@ -547,6 +549,225 @@ StepTrace.RECORD = _trace_record_dtype()
 assert StepTrace.RECORD.itemsize == 64
 
 
+class LRSchedule:
+    """A learning-rate schedule that lives on the device (`dctn_adam_l2_step_scheduled` / `dctn_sgd_l2_step_scheduled`,
+    include/dctn_amd.h): a table of at most 64 knots ``(step, lr)`` in a 784-byte DEVICE block that the optimizer launch
+    itself evaluates at the device step count.  Pass one to ``FlatAdam(..., schedule=s)`` or ``FlatSGD(..., schedule=s)``:
+    every replay of a captured step, and each of the K iterations of ``GraphedTrainStep(iters_per_launch=K)``, then
+    steps with its own rate - no host write, no further graph node.
+
+    The step index ``s`` is the 0-based index of the step being taken (the first step uses the value at 0, as
+    ``torch.optim.lr_scheduler.LambdaLR``).  The value is ``lr[0]`` in front of the first knot, ``lr[n-1]`` from the last
+    knot on, ``lr[i]`` on a segment with ``hold[i]`` set, and otherwise linear between the two knots around ``s``: one
+    float64 division, multiplication and addition, rounded to float32, then one float32 product with ``scale``.
+    ``value(step)`` is that arithmetic in numpy, bit for bit what the kernel uses (and what `dctn_lr_schedule_value`
+    returns on the host).  A step the gradient guard skipped does not count: the schedule holds its place with the
+    optimizer's step count.
+
+    ``hold``: one flag per knot (None: every segment linear).  ``set(knots, hold)`` rewrites the table in place and
+    ``scale`` may be assigned, both between launches only (RuntimeError during a capture, as ``FlatAdam.lr``): replays of
+    an already captured graph follow them.  ``device`` may be "cpu" for host-side use of the table; an optimizer takes a
+    schedule on its own device only.  ``state_dict()`` / ``load_state_dict()`` carry the table and the scale.
+    """
+
+    MAX_KNOTS = 64
+    WORDS = 196   # 784 bytes: n_knots, scale, reserved[2], k[64], lr[64], hold[64]
+
+    def __init__(self, device, knots, hold=None):
+        self.device = torch.device(device)
+        self._k, self._lr, self._hold = self._validated(knots, hold)
+        self._scale = 1.0
+        self._block = torch.zeros(self.WORDS, dtype=torch.int32, device=self.device)
+        self._scale_cell = self._block.view(torch.float32)[1:2]
+        self._upload()
+
+    # ---------------------------------------------------------------------------------------- host arithmetic
+    @classmethod
+    def _validated(cls, knots, hold):
+        import math
+
+        import numpy as np
+
+        knots = [tuple(pair) for pair in knots]
+        if not 1 <= len(knots) <= cls.MAX_KNOTS:
+            raise ValueError(f"LRSchedule: 1 to {cls.MAX_KNOTS} knots, got {len(knots)}")
+        ks, lrs = [], []
+        for step, lr in knots:
+            if int(step) != step or not 0 <= int(step) < 1 << 31:
+                raise ValueError(f"LRSchedule: a knot's step is an integer in [0, 2^31), got {step!r}")
+            if ks and int(step) <= ks[-1]:
+                raise ValueError(f"LRSchedule: the knots' steps must increase strictly, got {ks[-1]} then {step}")
+            with np.errstate(over="ignore"):
+                rate = float(np.float32(lr))   # the table holds float32 values
+            if not (math.isfinite(rate) and rate >= 0.0):
+                raise ValueError(f"LRSchedule: a rate must be finite (in float32) and >= 0, got {lr!r}")
+            ks.append(int(step))
+            lrs.append(rate)
+        if hold is None:
+            holds = [0] * len(ks)
+        else:
+            holds = [1 if h else 0 for h in hold]
+            if len(holds) != len(ks):
+                raise ValueError(f"LRSchedule: one hold flag per knot: {len(holds)} flags, {len(ks)} knots")
+        return ks, lrs, holds
+
+    @staticmethod
+    def _validated_scale(scale) -> float:
+        import math
+
+        import numpy as np
+
+        with np.errstate(over="ignore"):
+            value = float(np.float32(scale))
+        if not (math.isfinite(value) and value >= 0.0):
+            raise ValueError(f"LRSchedule: the scale must be finite (in float32) and >= 0, got {scale!r}")
+        return value
+
+    @staticmethod
+    def evaluate(k, lr, hold, scale, step) -> float:
+        """The value at ``step`` of the table (``k``, ``lr``, ``hold``) times ``scale``, in the kernel's number formats."""
+        import bisect
+
+        import numpy as np
+
+        s, n = int(step), len(k)
+        reached = bisect.bisect_right(k, s)   # knots with k <= s
+        i = max(reached, 1) - 1
+        value = np.float32(lr[i])
+        if 0 < reached < n and not hold[i]:
+            a, b = np.float64(np.float32(lr[i])), np.float64(np.float32(lr[i + 1]))
+            frac = np.float64(s - k[i]) / np.float64(k[i + 1] - k[i])
+            rise = (b - a) * frac
+            value = np.float32(a + rise)
+        return float(np.float32(value * np.float32(scale)))
+
+    def value(self, step: int) -> float:
+        """The rate of the step with 0-based index ``step``, scale applied: the kernel's bits."""
+        return self.evaluate(self._k, self._lr, self._hold, self._scale, step)
+
+    def host_block(self):
+        """The 784 bytes of the block as a numpy int32 array of 196 words (what `dctn_lr_schedule_value` takes)."""
+        import numpy as np
+
+        words = np.zeros(self.WORDS, dtype=np.int32)
+        n = len(self._k)
+        words[0] = n
+        words.view(np.float32)[1] = self._scale
+        words[4: 4 + n] = self._k
+        words.view(np.float32)[68: 68 + n] = self._lr
+        words[132: 132 + n] = self._hold
+        return words
+
+    @classmethod
+    def decode(cls, words):
+        """``(knots, hold, scale)`` of a block given as 196 int32 words (or its 784 bytes)."""
+        import numpy as np
+
+        words = np.frombuffer(bytes(words), dtype="<i4") if not isinstance(words, np.ndarray) else words.view("<i4").reshape(-1)
+        if words.size != cls.WORDS:
+            raise ValueError(f"LRSchedule.decode: a block has {cls.WORDS * 4} bytes, got {words.size * 4}")
+        n = int(words[0])
+        if not 1 <= n <= cls.MAX_KNOTS:
+            raise ValueError(f"LRSchedule.decode: n_knots = {n}")
+        floats = words.view(np.float32)
+        knots = [(int(words[4 + i]), float(floats[68 + i])) for i in range(n)]
+        return knots, [int(words[132 + i] != 0) for i in range(n)], float(floats[1])
+
+    # ---------------------------------------------------------------------------------------- the device block
+    def _upload(self) -> None:
+        with torch.no_grad():
+            self._block.copy_(torch.from_numpy(self.host_block()))
+
+    def _no_capture(self, what: str) -> None:
+        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"LRSchedule.{what} during a graph capture: the captured step reads the table from the "
+                               "device, change it between replays")
+
+    def set(self, knots, hold=None) -> None:
+        """Rewrites the table in place (the scale stays): the next launch, a replay included, follows it."""
+        self._no_capture("set()")
+        self._k, self._lr, self._hold = self._validated(knots, hold)
+        self._upload()
+
+    @property
+    def scale(self) -> float:
+        return self._scale
+
+    @scale.setter
+    def scale(self, value: float) -> None:
+        self._no_capture("scale cannot be assigned")
+        self._scale = self._validated_scale(value)
+        if self.device.type == "cuda":
+            with torch.cuda.device(self.device):
+                self._scale_cell.fill_(self._scale)
+        else:
+            self._scale_cell.fill_(self._scale)
+
+    @property
+    def knots(self):
+        return list(zip(self._k, self._lr))
+
+    @property
+    def hold(self):
+        return list(self._hold)
+
+    def state_dict(self) -> Dict[str, Any]:
+        return {"knots": [[k, lr] for k, lr in zip(self._k, self._lr)], "hold": list(self._hold), "scale": self._scale}
+
+    def load_state_dict(self, state: Dict[str, Any]) -> None:
+        self._no_capture("load_state_dict()")
+        scale = self._validated_scale(state["scale"])
+        self._k, self._lr, self._hold = self._validated(state["knots"], state["hold"])
+        self._scale = scale
+        self._upload()
+
+    def _mirror_block(self, words) -> None:
+        """Sets the host copy from the block's bytes (`checkpoint.RunState.load` put the block itself back)."""
+        knots, hold, scale = self.decode(words)
+        self._k, self._lr, self._hold = self._validated(knots, hold)
+        self._scale = self._validated_scale(scale)
+
+    # ---------------------------------------------------------------------------------------- builders
+    @classmethod
+    def constant(cls, device, lr: float) -> "LRSchedule":
+        return cls(device, [(0, lr)])
+
+    @classmethod
+    def warmup(cls, device, peak: float, warmup_steps: int, start: float = 0.0) -> "LRSchedule":
+        """Linear from ``start`` at step 0 to ``peak`` at step ``warmup_steps``, then constant."""
+        if int(warmup_steps) < 1:
+            return cls.constant(device, peak)
+        return cls(device, [(0, start), (int(warmup_steps), peak)])
+
+    @classmethod
+    def warmup_cosine(cls, device, peak: float, warmup_steps: int, total_steps: int, final: float = 0.0) -> "LRSchedule":
+        """Linear from 0 to ``peak`` over ``warmup_steps``, then half a cosine from ``peak`` down to ``final`` at
+        ``total_steps`` (constant after it), the cosine sampled on the knots the warm-up leaves free - 63 of them, 64
+        without a warm-up, fewer when the decay has fewer steps - with linear pieces between them."""
+        import math
+
+        warm, total = max(int(warmup_steps), 0), int(total_steps)
+        if total <= warm:
+            raise ValueError(f"LRSchedule.warmup_cosine: total_steps ({total_steps}) must exceed warmup_steps ({warmup_steps})")
+        free = cls.MAX_KNOTS - (1 if warm > 0 else 0)
+        m = min(free, total - warm + 1)   # sample points, both ends included; >= 2
+        steps = [warm + (j * (total - warm)) // (m - 1) for j in range(m)]   # strictly increasing: m - 1 <= total - warm
+        knots = [(0, 0.0)] if warm > 0 else []
+        for s in steps:
+            knots.append((s, final + (peak - final) * 0.5 * (1.0 + math.cos(math.pi * (s - warm) / (total - warm)))))
+        knots[-1] = (total, final)   # cos(pi) in floating point is -1 exactly, but say it
+        return cls(device, knots)
+
+    @classmethod
+    def milestones(cls, device, lr: float, milestones: Sequence[int], gamma: float) -> "LRSchedule":
+        """``torch.optim.lr_scheduler.MultiStepLR``: ``lr * gamma^j`` from the j-th milestone on, held in between."""
+        marks = [int(m) for m in milestones]
+        if any(m < 1 for m in marks):
+            raise ValueError(f"LRSchedule.milestones: milestones are steps >= 1, got {list(milestones)}")
+        knots = [(0, lr)] + [(m, lr * gamma ** (j + 1)) for j, m in enumerate(marks)]
+        return cls(device, knots, hold=[1] * len(knots))
+
+
 class _FlatOptimizer:
     """What FlatSGD and FlatAdam share: the parameters moved into ONE flat buffer (their ``.data`` become views of it,
     in the order regularised + others), the gradients read in place when they already sit back to back in that
@@ -558,11 +779,15 @@ class _FlatOptimizer:
     float32 parameters the option changes nothing and ``master`` is None."""
 
     def __init__(self, regularised, others, num_partials: Callable[[int], int], master_weights: bool = False,
-                 guard: Optional["GradGuard"] = None, guard_loss=None):
+                 guard: Optional["GradGuard"] = None, guard_loss=None, schedule: Optional["LRSchedule"] = None):
         # guard: a GradGuard whose check runs in front of every step; guard_loss: the float32 device scalar the check
         # looks at beside the gradients, or a callable that returns it (the loss tensor of a training loop is a new one
         # every iteration)
+        # schedule: an LRSchedule whose block the step kernel evaluates at the device step count
         self.guard, self.guard_loss = guard, guard_loss
+        if schedule is not None and not isinstance(schedule, LRSchedule):
+            raise TypeError(f"schedule must be an LRSchedule, got {type(schedule).__name__}")
+        self.schedule = schedule
         self.reg_params = [p for p in regularised]
         self.params = self.reg_params + [p for p in others]
         assert self.params and len({p.dtype for p in self.params}) == 1 and len({p.device for p in self.params}) == 1
@@ -583,6 +808,17 @@ class _FlatOptimizer:
         self.master: Optional[Tensor] = None
         if master_weights and ref.dtype == torch.bfloat16:
             self.master = self.flat.to(torch.float32)
+        if schedule is not None and schedule.device != self.flat.device:
+            raise ValueError(f"the schedule's block is on {schedule.device}, the parameters on {self.flat.device}")
+
+    def _scheduled_lr(self) -> float:
+        """``schedule.value(t)``, scale applied: the rate of the next step (reads the step count from the device)."""
+        return self.schedule.value(self.t)
+
+    def _refuse_lr(self):
+        raise RuntimeError(f"{type(self).__name__}.lr cannot be assigned with a schedule: the step kernel evaluates the "
+                           "schedule's table on the device; change the table with schedule.set(...) or multiply every "
+                           "rate with schedule.scale = ...")
 
     def refresh_master(self) -> None:
         """Rebuilds the float32 master copy from the current bfloat16 parameters (nothing to do without one).  Call it
@@ -635,6 +871,14 @@ class _FlatOptimizer:
         self.guard.check(g, loss)
         return self.guard._block.data_ptr()
 
+    def _put_step_block(self, steps: int) -> None:
+        """Writes the 16-byte step block of a scheduled optimizer: ``steps`` taken, the rate of the last of them."""
+        host = torch.zeros(4, dtype=torch.int32)
+        host[0] = int(steps)
+        host.view(torch.float32)[1] = self.schedule.value(steps - 1) if steps > 0 else 0.0
+        with torch.no_grad():
+            self._state.copy_(host)
+
     def reg_value(self) -> Tensor:
         """l2 * sum of squared Frobenius norms of the regularised parameters, as of the last step."""
         return self.sq_sum.sum() * self.l2
@@ -662,19 +906,63 @@ class FlatSGD(_FlatOptimizer):
     ``guard`` (a `GradGuard`) / ``guard_loss``: ``step()`` launches the guard's check and then the guarded kernel
     (`dctn_sgd_l2_step_guarded`): gradients clipped to ``guard.max_norm`` in front of the ``2 * l2 * w`` term, and no
     write at all once the guard has halted.  Without a guard ``step()`` makes the calls it always made.
+
+    ``schedule`` (an `LRSchedule`): ``step()`` launches `dctn_sgd_l2_step_scheduled` (behind the guard's check when there
+    is a guard).  The optimizer then owns a 16-byte DEVICE block {steps_done, lr, ticket, reserved} - `FlatAdam`'s - that
+    the launch advances: the rate is the schedule's value at ``steps_done`` and the first step is ``steps_done == 0``,
+    both read on the device, so a captured step changes its rate from replay to replay (without a schedule a captured
+    step replays the ``lr`` and ``first_step`` it was captured with).  ``opt.lr`` returns ``schedule.value(opt.t)``;
+    assigning it raises RuntimeError (``schedule.set`` / ``schedule.scale`` change the rate); the ``lr`` argument is
+    not used.  The schedule object is fixed for the life of a captured graph; its table and scale may change between
+    replays.  ``opt.t`` and ``state_dict()["steps"]`` are read from the block.  Without a schedule ``step()`` makes
+    the calls it always made.
     """
 
     def __init__(self, regularised, others=(), lr: float = 1e-3, momentum: float = 0.0, l2: float = 0.0,
-                 master_weights: bool = False, guard: Optional["GradGuard"] = None, guard_loss=None):
-        super().__init__(regularised, others, L.lib().dctn_sgd_l2_num_partials, master_weights, guard, guard_loss)
-        self.lr, self.momentum, self.l2 = float(lr), float(momentum), float(l2)
+                 master_weights: bool = False, guard: Optional["GradGuard"] = None, guard_loss=None, *,
+                 schedule: Optional["LRSchedule"] = None):
+        super().__init__(regularised, others, L.lib().dctn_sgd_l2_num_partials, master_weights, guard, guard_loss,
+                         schedule)
+        self._lr, self.momentum, self.l2 = float(lr), float(momentum), float(l2)
         self.buf = torch.zeros(self.n, dtype=torch.float32, device=self.flat.device)
         self._steps = 0
+        # with a schedule: {int32 steps_done, float32 lr, uint32 ticket, uint32 reserved}, FlatAdam's block
+        self._state: Optional[Tensor] = None
+        if schedule is not None:
+            assert L.lib().dctn_adam_state_bytes() == 16 and L.lib().dctn_lr_schedule_bytes() == 4 * LRSchedule.WORDS
+            self._state = torch.zeros(4, dtype=torch.int32, device=self.flat.device)
+
+    @property
+    def lr(self) -> float:
+        """Without a schedule the rate the next launch gets; with one, ``schedule.value(t)`` (reads the device)."""
+        return self._lr if self.schedule is None else self._scheduled_lr()
+
+    @lr.setter
+    def lr(self, value: float) -> None:
+        if self.schedule is not None:
+            self._refuse_lr()
+        self._lr = float(value)
+
+    @property
+    def t(self) -> int:
+        """Number of steps taken: with a schedule read from the device block (it synchronises; steps the guard skipped
+        do not count), otherwise the host's count of launches."""
+        return self._steps if self._state is None else int(self._state[0].item())
 
     @torch.no_grad()
     def step(self) -> None:
         g = self._grads()
         dev = self.flat.device
+        if self.schedule is not None:
+            block = self._run_guard(g) if self.guard is not None else None
+            L.check(L.lib().dctn_sgd_l2_step_scheduled(None if self.master is None else self.master.data_ptr(),
+                                                       self.flat.data_ptr(), g.data_ptr(), self.buf.data_ptr(),
+                                                       self.sq_sum.data_ptr(), self._state.data_ptr(), block,
+                                                       self.schedule._block.data_ptr(), self.n, self.n_reg,
+                                                       self.momentum, self.l2, L.dtype_code(self.flat),
+                                                       L.stream_ptr(dev)), "scheduled fused SGD step")
+            self._steps += 1
+            return
         first = 1 if self._steps == 0 else 0
         if self.guard is not None:
             # `first` is the host's count of launches, and the host does not know whether the guard let a launch
@@ -707,7 +995,7 @@ class FlatSGD(_FlatOptimizer):
 
     def state_dict(self) -> Dict[str, Any]:
         """Everything a resumed run needs besides the parameters themselves (those are the model's state_dict)."""
-        state = {"steps": self._steps, "lr": self.lr, "momentum": self.momentum, "l2": self.l2, "buf": self.buf.clone()}
+        state = {"steps": self.t, "lr": self.lr, "momentum": self.momentum, "l2": self.l2, "buf": self.buf.clone()}
         if self.master is not None:
             state["master"] = self.master.clone()
         return state
@@ -715,10 +1003,14 @@ class FlatSGD(_FlatOptimizer):
     def load_state_dict(self, state: Dict[str, Any]) -> None:
         if state["buf"].numel() != self.n:
             raise ValueError(f"optimizer state holds {state['buf'].numel()} values, the parameters {self.n}")
-        self.lr, self.momentum, self.l2 = float(state["lr"]), float(state["momentum"]), float(state["l2"])
+        self.momentum, self.l2 = float(state["momentum"]), float(state["l2"])
         with torch.no_grad():
             self.buf.copy_(state["buf"].reshape(-1))
         self._steps = int(state["steps"])
+        if self.schedule is None:
+            self.lr = float(state["lr"])
+        else:   # the block as the scheduled kernel would have left it: the count, and the rate of the last step
+            self._put_step_block(self._steps)
         self._load_master(state)
 
 
@@ -749,12 +1041,24 @@ class FlatAdam(_FlatOptimizer):
     the guard has halted, a step writes nothing: parameters, ``m``, ``v``, ``master`` and ``t`` stay as they are.  The
     guard's state is not part of this optimizer's ``state_dict()``; save ``guard.state_dict()`` beside it.  Without a
     guard ``step()`` makes the calls it always made.
+
+    ``schedule`` (an `LRSchedule`): ``step()`` launches `dctn_adam_l2_step_scheduled` (behind the guard's check when
+    there is a guard): the kernel evaluates the schedule's table at the device step count instead of reading the
+    block's rate, and leaves the rate it used in the block, so `StepTrace` records the rate of every iteration.  Every
+    replay of a captured step, and each of the K iterations of one launch, gets its own rate with no host write.
+    ``opt.lr`` returns ``schedule.value(opt.t)`` (it reads the device); assigning it raises RuntimeError
+    (``schedule.set`` / ``schedule.scale`` change the rate); the ``lr`` argument is not used.  A step the guard skipped
+    does not advance ``t``, so the schedule holds its place.  The schedule object is fixed for the life of a captured
+    graph; its table and scale may change between replays.  The schedule's state is not part of ``state_dict()``; save
+    ``schedule.state_dict()`` beside it (`checkpoint.RunState` carries its block).  Without a schedule ``step()``
+    makes the calls it always made.
     """
 
     def __init__(self, regularised, others=(), lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, l2: float = 0.0, master_weights: bool = False,
-                 guard: Optional["GradGuard"] = None, guard_loss=None):
-        super().__init__(regularised, others, L.lib().dctn_adam_l2_num_partials, master_weights, guard, guard_loss)
+                 guard: Optional["GradGuard"] = None, guard_loss=None, *, schedule: Optional["LRSchedule"] = None):
+        super().__init__(regularised, others, L.lib().dctn_adam_l2_num_partials, master_weights, guard, guard_loss,
+                         schedule)
         if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0 and lr >= 0.0 and eps >= 0.0 and weight_decay >= 0.0):
             raise ValueError(f"invalid Adam hyper-parameters: lr={lr} betas={betas} eps={eps} weight_decay={weight_decay}")
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
@@ -767,14 +1071,21 @@ class FlatAdam(_FlatOptimizer):
         self._state = torch.zeros(4, dtype=torch.int32, device=dev)
         self._lr_cell = self._state.view(torch.float32)[1:2]
         self._lr = float("nan")
-        self.lr = lr
+        if schedule is None:
+            self.lr = lr
+        else:   # the block's rate cell is the kernel's to write: the rate of the step just taken
+            self._lr = float(lr)
+            assert L.lib().dctn_lr_schedule_bytes() == 4 * LRSchedule.WORDS
 
     @property
     def lr(self) -> float:
-        return self._lr
+        """Without a schedule the host copy of the rate; with one, ``schedule.value(t)`` (reads the device)."""
+        return self._lr if self.schedule is None else self._scheduled_lr()
 
     @lr.setter
     def lr(self, value: float) -> None:
+        if self.schedule is not None:
+            self._refuse_lr()
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("FlatAdam.lr cannot be assigned during a graph capture: the captured step reads the "
                                "rate from the device, assign it between replays")
@@ -791,6 +1102,16 @@ class FlatAdam(_FlatOptimizer):
     def step(self) -> None:
         g = self._grads()
         dev = self.flat.device
+        if self.schedule is not None:
+            block = self._run_guard(g) if self.guard is not None else None
+            L.check(L.lib().dctn_adam_l2_step_scheduled(None if self.master is None else self.master.data_ptr(),
+                                                        self.flat.data_ptr(), g.data_ptr(), self.m.data_ptr(),
+                                                        self.v.data_ptr(), self.sq_sum.data_ptr(),
+                                                        self._state.data_ptr(), block, self.schedule._block.data_ptr(),
+                                                        self.n, self.n_reg, self.betas[0], self.betas[1], self.eps,
+                                                        self.weight_decay, self.l2, L.dtype_code(self.flat),
+                                                        L.stream_ptr(dev)), "scheduled fused Adam step")
+            return
         if self.guard is not None:
             block = self._run_guard(g)
             if self.master is not None:
@@ -823,7 +1144,7 @@ class FlatAdam(_FlatOptimizer):
 
     def state_dict(self) -> Dict[str, Any]:
         """Everything a resumed run needs besides the parameters themselves (those are the model's state_dict)."""
-        state = {"t": self.t, "lr": self._lr, "m": self.m.clone(), "v": self.v.clone(), "betas": self.betas,
+        state = {"t": self.t, "lr": self.lr, "m": self.m.clone(), "v": self.v.clone(), "betas": self.betas,
                  "eps": self.eps, "weight_decay": self.weight_decay, "l2": self.l2}
         if self.master is not None:
             state["master"] = self.master.clone()
@@ -839,7 +1160,10 @@ class FlatAdam(_FlatOptimizer):
             self.v.copy_(state["v"].reshape(-1))
             self._state.zero_()
             self._state[0] = int(state["t"])
-        self.lr = state["lr"]
+        if self.schedule is None:
+            self.lr = state["lr"]
+        else:
+            self._put_step_block(int(state["t"]))
         self._load_master(state)
 
 
@@ -1196,6 +1520,41 @@ class _StopOnDeviceHalt:
 
 def make_stopper_on_device_halt(dir: str, guard: "GradGuard", every: int = 1) -> Callable[[StX, StIt], None]:
     return _StopOnDeviceHalt(dir, guard, every)
+
+
+class _LRPlateauHook:
+    """``torch.optim.lr_scheduler.ReduceLROnPlateau`` on an `LRSchedule`'s scale: called after every evaluation (an
+    `evaluation.make_evaluation_hook`-style hook behind the one that fills ``st_it[key]``), it multiplies
+    ``schedule.scale`` by ``factor`` once ``st_it[key]`` has not improved for ``patience`` calls in a row, never below
+    ``min_scale``, and starts counting again.  Host logic: the scale is one device write at a launch boundary."""
+
+    def __init__(self, schedule: "LRSchedule", key: str, low_is_good: bool, factor: float, patience: int,
+                 min_scale: float = 0.0):
+        if not 0.0 < factor < 1.0 or patience < 1 or min_scale < 0.0:
+            raise ValueError(f"plateau hook: 0 < factor < 1, patience >= 1, min_scale >= 0; got {factor}, {patience}, {min_scale}")
+        self.schedule, self.key, self.low_is_good = schedule, key, bool(low_is_good)
+        self.factor, self.patience, self.min_scale = float(factor), int(patience), float(min_scale)
+        self.best_value = float("inf") if low_is_good else float("-inf")
+        self.num_bad_calls = 0
+
+    def __call__(self, st_x: StX, st_it: StIt) -> None:
+        value = float(st_it[self.key])
+        if (value < self.best_value) if self.low_is_good else (value > self.best_value):
+            self.best_value, self.num_bad_calls = value, 0
+            return
+        self.num_bad_calls += 1
+        if self.num_bad_calls >= self.patience:
+            self.num_bad_calls = 0
+            new = LRSchedule._validated_scale(max(self.schedule.scale * self.factor, self.min_scale))   # as the block holds it
+            if new != self.schedule.scale:
+                self.schedule.scale = new
+                getLogger(__name__).info(f"{self.key} on a plateau at st_it['num_iters_done']={st_it.get('num_iters_done')}: "
+                                         f"learning-rate scale -> {self.schedule.scale}")
+
+
+def make_lr_plateau_hook(schedule: "LRSchedule", key: str, low_is_good: bool, factor: float, patience: int,
+                         min_scale: float = 0.0) -> Callable[[StX, StIt], None]:
+    return _LRPlateauHook(schedule, key, low_is_good, factor, patience, min_scale)
 
 
 def log_parameters_stats(st_x: StX, st_it: StIt) -> None:

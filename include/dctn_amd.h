@@ -492,6 +492,56 @@ int dctn_sgd_l2_step_master_guarded(void* master, void* params, const void* grad
                                     int first_step, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Learning-rate schedule (version 510): the optimizer launch itself evaluates a table of knots at the device step
+ * count, so that a replayed graph - and each of the K iterations inside one launch - steps with its own rate, with no
+ * host write and no further graph node.
+ *
+ * `schedule`: dctn_lr_schedule_bytes = 784 bytes, 16-byte aligned, laid out as
+ *   int32  n_knots        1..64
+ *   float  scale          multiplies every value; 1.0f leaves the bits alone
+ *   int32  reserved[2]    0
+ *   int32  k[64]          strictly increasing step indices, k[0] >= 0
+ *   float  lr[64]         the rate at each knot (finite, >= 0)
+ *   int32  hold[64]       1: lr[i] holds on [k[i], k[i+1]); 0: linear from lr[i] to lr[i+1]
+ * Slots at and past n_knots are never used, whatever they hold.  The caller writes the block in stream order between
+ * launches; the launches only read it.
+ *
+ * The value at s = steps_done, the 0-based index of the step being taken (the first step uses the value at 0):
+ *   lr[0] for s < k[0];  lr[n-1] for s >= k[n-1];  lr[i] on a hold segment;  on a linear segment the float32 rounding of
+ *     (double)lr[i] + ((double)lr[i+1] - (double)lr[i]) * ((double)(s - k[i]) / (double)(k[i+1] - k[i]))
+ *   with one float64 division, one multiplication and one addition, each rounded on its own (no FMA contraction);
+ *   the value is then multiplied by `scale` as one rounded float32 product.
+ * dctn_lr_schedule_value runs exactly this arithmetic on the HOST over a host copy of the block (no device, no stream).
+ * It validates the block - n_knots in 1..64, k[0] >= 0 and k strictly increasing, every used lr and the scale finite and
+ * >= 0, step >= 0 - and returns DCTN_ERR_BAD_SHAPE otherwise; the step entry points below do not read the block on the
+ * host and validate nothing of it.
+ *
+ * dctn_adam_l2_step_scheduled : dctn_adam_l2_step with the rate taken from `schedule` instead of state->lr (which the
+ *   launch does not read).  master_or_null: null, or the float32 master copy of bf16 parameters (dtype must then be
+ *   DCTN_BF16; as dctn_adam_l2_step_master).  guard_or_null: null, or the guard block (as the guarded steps:
+ *   dctn_grad_guard_check ran in front).  The launch leaves steps_done + 1 AND the rate it used in the state block, so
+ *   state->lr reports the rate of the step just taken.  A halted guarded launch writes nothing: steps_done stays, and
+ *   with it the schedule's position.  Given lr = the schedule's value, every result is, bit for bit, what the
+ *   unscheduled entry points leave.
+ * dctn_sgd_l2_step_scheduled : dctn_sgd_l2_step with a device state block of the same 16 bytes
+ *   {int32 steps_done, float lr, uint32 ticket, uint32 reserved} (zeroes before the first step): first_step is
+ *   steps_done == 0 read on the device, the rate comes from `schedule`, and the launch leaves steps_done + 1 and the
+ *   rate it used.  master_or_null / guard_or_null as above.
+ * Return codes, decided on the host before any launch: DCTN_ERR_NULL, DCTN_ERR_BAD_SHAPE, DCTN_ERR_BAD_DTYPE as the
+ * unscheduled steps.  No workspace; the calls only enqueue and can be captured.  These launches do not report to
+ * dctn_last_kernel.
+ * ------------------------------------------------------------------------------------------ */
+size_t dctn_lr_schedule_bytes(void);
+int dctn_lr_schedule_value(const void* host_block, int64_t step, float* out);
+int dctn_adam_l2_step_scheduled(void* master_or_null, void* params, const void* grads, void* exp_avg, void* exp_avg_sq,
+                                void* sq_sum, void* state, const void* guard_or_null, const void* schedule, int64_t n,
+                                int64_t n_reg, double beta1, double beta2, float eps, float weight_decay, float l2,
+                                int dtype, void* stream);
+int dctn_sgd_l2_step_scheduled(void* master_or_null, void* params, const void* grads, void* momentum_buf, void* sq_sum,
+                               void* state, const void* guard_or_null, const void* schedule, int64_t n, int64_t n_reg,
+                               float momentum, float l2, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Scoring (reference: dctn/evaluation.py:7-22): one launch per batch ADDS to acc = three float64 values
  * {sum of the rows' cross-entropies, number of correct rows, number of rows}.  logits (B, C) contiguous, DCTN_F32 /
  * DCTN_BF16; labels int64.  Per row a max-shifted log-sum-exp with float32 exponentials; the row's sum, its
