@@ -96,6 +96,11 @@ SIGNATURES = {
     "dctn_adam_l2_step_scheduled": (c_int, [c_void] * 9 + [c_i64, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_float,
                                             ctypes.c_float, ctypes.c_float, c_int, c_void]),
     "dctn_sgd_l2_step_scheduled": (c_int, [c_void] * 8 + [c_i64, c_i64, ctypes.c_float, ctypes.c_float, c_int, c_void]),
+    "dctn_param_groups_bytes": (c_size, []),
+    "dctn_param_groups_check": (c_int, [c_void, c_i64]),
+    "dctn_adam_l2_step_grouped": (c_int, [c_void] * 10 + [c_i64, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_float,
+                                          ctypes.c_float, c_int, c_void]),
+    "dctn_sgd_l2_step_grouped": (c_int, [c_void] * 9 + [c_i64, c_i64, ctypes.c_float, ctypes.c_float, c_int, c_void]),
     "dctn_step_trace_head_bytes": (c_size, []),
     "dctn_step_trace_record_bytes": (c_size, []),
     "dctn_step_trace_record": (c_int, [c_void] * 9 + [c_int, c_i64, c_int, c_int, c_void]),

@@ -277,7 +277,10 @@ def _tensor_regions(model, optimizer, batch_source, guard, trace=None):
         # disagree about the schedule differ at this entry first
         if getattr(optimizer, "schedule", None) is not None:
             regions.append(("optimizer.schedule", optimizer.schedule._block))
-        if getattr(optimizer, "_state", None) is not None:   # FlatAdam; a FlatSGD with a schedule
+        # a grouped optimizer: the table's block, the segments' step counts in it
+        if getattr(optimizer, "groups", None) is not None:
+            regions.append(("optimizer.groups", optimizer.groups._block))
+        if getattr(optimizer, "_state", None) is not None:   # FlatAdam; a FlatSGD with a schedule or a group table
             regions.append(("optimizer.state", optimizer._state))
         regions.append(("optimizer.sq_sum", optimizer.sq_sum))
     entries = []
@@ -309,7 +312,9 @@ class RunState:
     moments (or the momentum buffer), the master copy, the 16-byte step block and ``sq_sum``; with an `LRSchedule` on the
     optimizer the schedule's block as ``optimizer.schedule`` (and the step block of a scheduled `FlatSGD` as
     ``optimizer.state``; a file and a run that disagree about the schedule are refused at that entry, and runs without a
-    schedule keep their region lists and their files); every entry of the model's
+    schedule keep their region lists and their files); with a `ParamGroups` table on the optimizer its block, the
+    segments' step counts in it, as ``optimizer.groups`` behind ``optimizer.schedule`` (runs without one keep their
+    region lists and files too); every entry of the model's
     state_dict that does not live in the flat buffer (the buffer ``p``; without an optimizer every parameter) as a region
     of its own; ``model._dropout_state`` when the fused dropout is on; ``guard._block`` (``guard`` defaults to the
     optimizer's); ``batch_source._state``; with ``trace`` (a `training.StepTrace`) its head and ring as ``trace.head`` /
@@ -460,6 +465,9 @@ class RunState:
         if getattr(self.optimizer, "schedule", None) is not None:   # the block came back: the host copy of the table follows
             block = next(r for r in manifest["regions"] if r["name"] == "optimizer.schedule")
             self.optimizer.schedule._mirror_block(arena[block["offset"]: block["offset"] + block["bytes"]].view("<i4"))
+        if getattr(self.optimizer, "groups", None) is not None:   # likewise the host copy of the group table
+            block = next(r for r in manifest["regions"] if r["name"] == "optimizer.groups")
+            self.optimizer.groups._mirror_block(arena[block["offset"]: block["offset"] + block["bytes"]].view("<i4"))
         if self.trace is not None:   # head and ring came back with their regions: the records before the head count as read
             head = next(r for r in manifest["regions"] if r["name"] == "trace.head")
             done = int(arena[head["offset"]: head["offset"] + 4].view("<u4")[0])

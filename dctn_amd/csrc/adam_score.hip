@@ -9,6 +9,7 @@
 #include "common.h"
 #include "grad_guard.h"
 #include "lr_schedule.h"
+#include "param_groups.h"
 
 #include <cmath>
 
@@ -90,14 +91,182 @@ template <bool GUARD> __device__ __forceinline__ float clipped(float g, float co
 // finds the segment with a ballot, and lane 0 publishes step and bc2_sqrt as in the other forms.  The workgroup that
 // draws the last ticket writes the rate it used to state->lr beside steps_done: the block reports the rate of the step
 // just taken.  A halted guarded step returns before the ticket, so the schedule holds its place with steps_done.
+// GROUPED (the pack ends with a ParamGroupBlock*): the launch obeys a parameter-group table (param_groups.h states the
+// semantics).  Wave 0 loads the table, one segment per lane, beside steps_done and the rate - no load depends on
+// another - and every lane forms ITS segment's step size and second correction from the segment's own count, in the
+// float64 expressions of the ungrouped kernel's lane 0, and publishes them with the segment's end, weight decay and
+// frozen flag through LDS.  Every lane of the workgroup then walks a cursor over the ends as its elements increase.  A
+// vector of four elements that lies inside one segment takes the vector path with that segment's constants (nothing is
+// loaded but w for a frozen one, and only below n_reg); a vector that straddles an end is done element by element,
+// each with its own segment's constants and its own stores.  adam_elem sees the values the ungrouped kernel would give
+// it, in the same order per lane, so with an all-default table every buffer and sq_sum slot holds the ungrouped bits.
+struct AdamSegment {
+  float step, bc2_sqrt, wd;
+  bool frozen;
+};
+
+template <typename S, bool MASTER, bool GUARD>
+__device__ __forceinline__ void adam_grouped_elem(long long i, S* __restrict__ w, float* __restrict__ wm,
+                                                  const S* __restrict__ g, float* __restrict__ ea,
+                                                  float* __restrict__ eas, bool reg, const AdamCoef& k,
+                                                  const AdamSegment& sg, float coef, float& part) {
+  if (sg.frozen) {   // only the regulariser's value: no gradient read, no store
+    if (reg) {
+      const float wi = MASTER ? wm[i] : (float)w[i];
+      part = fmaf(wi, wi, part);
+    }
+    return;
+  }
+  AdamCoef ks = k;
+  ks.wd = sg.wd;
+  float m = ea[i], v = eas[i];
+  const float wi = adam_elem(MASTER ? wm[i] : (float)w[i], clipped<GUARD>((float)g[i], coef), m, v, reg, ks, sg.step,
+                             sg.bc2_sqrt, part);
+  w[i] = (S)wi;
+  if (MASTER) wm[i] = wi;
+  ea[i] = m, eas[i] = v;
+}
+
+template <typename S, bool VEC, bool MASTER, bool GUARD, bool SCHED>
+__device__ __forceinline__ void adam_grouped_body(S* __restrict__ w, float* __restrict__ wm, const S* __restrict__ g,
+                                                  float* __restrict__ ea, float* __restrict__ eas,
+                                                  float* __restrict__ sq_sum, AdamState* __restrict__ state, long long n,
+                                                  long long n_reg, const AdamCoef& k, const GradGuardBlock* guard,
+                                                  const LrScheduleBlock* sched, ParamGroupBlock* groups) {
+  __shared__ float red[16];
+  __shared__ float decision[2];                       // halted, coef
+  __shared__ long long seg_end[DCTN_PG_MAX_SEGMENTS];
+  __shared__ float seg_step[DCTN_PG_MAX_SEGMENTS], seg_bc2[DCTN_PG_MAX_SEGMENTS], seg_wd[DCTN_PG_MAX_SEGMENTS];
+  __shared__ int seg_frozen[DCTN_PG_MAX_SEGMENTS];
+  __shared__ int seg_count;
+  int t = 0, my_steps = 0;
+  float lr = 0.f;
+  bool my_live = false;   // wave 0: this lane's segment is in use and not frozen
+  if (threadIdx.x < 64) {   // wave 0, every lane
+    const int lane = threadIdx.x;
+    const ParamGroupLane sg = param_group_lane_load(groups, lane);
+    if constexpr (SCHED) {
+      const LrScheduleLane knot = lr_schedule_lane_load(sched, lane);
+      t = __hip_atomic_load(&state->steps_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
+      lr = lr_schedule_wave_value(knot, lane, t - 1);
+    } else {
+      t = __hip_atomic_load(&state->steps_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
+      lr = __hip_atomic_load(&state->lr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if constexpr (GUARD) {
+      if (lane == 0) {
+        decision[0] = __hip_atomic_load(&guard->halted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ? 1.f : 0.f;
+        decision[1] = __hip_atomic_load(&guard->coef, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+    // the segment's rate: one rounded product; its corrections from ITS count, as lane 0 of the ungrouped kernel
+    const float rate = __fmul_rn(lr, sg.lr_scale);
+    const int ts = sg.steps + 1;
+    my_steps = sg.steps;
+    my_live = lane < sg.n_segments && (sg.flags & DCTN_PG_FROZEN) == 0u;
+    seg_end[lane] = sg.end;
+    seg_step[lane] = (float)((double)rate / -expm1((double)ts * k.ln_b1));
+    seg_bc2[lane] = (float)sqrt(-expm1((double)ts * k.ln_b2));
+    seg_wd[lane] = sg.weight_decay;
+    seg_frozen[lane] = (sg.flags & DCTN_PG_FROZEN) != 0u ? 1 : 0;
+    if (lane == 0) seg_count = sg.n_segments;
+  }
+  __syncthreads();
+  float coef = 1.f;
+  if constexpr (GUARD) {
+    if (decision[0] != 0.f) return;   // the whole workgroup, before any store and before the ticket
+    coef = decision[1];
+  }
+  const int n_seg = seg_count;
+  ParamGroupCursor cur{0, param_group_end(seg_end, 0, n_seg)};
+  AdamSegment sg{seg_step[0], seg_bc2[0], seg_wd[0], seg_frozen[0] != 0};
+  auto follow = [&](ParamGroupCursor& c, AdamSegment& s, long long i) {
+    if (param_group_advance(c, i, seg_end, n_seg))
+      s = AdamSegment{seg_step[c.seg], seg_bc2[c.seg], seg_wd[c.seg], seg_frozen[c.seg] != 0};
+  };
+  float part = 0.f;
+  const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, nthr = (long long)gridDim.x * blockDim.x;
+  const long long n_vec = VEC ? (n & ~3LL) : 0;
+  if (VEC) {
+    for (long long i = tid * 4; i < n_vec; i += nthr * 4) {
+      follow(cur, sg, i);
+      if (i + 3 < cur.end) {   // the four elements share a segment
+        if (sg.frozen) {
+          if (i < n_reg) {
+            float wi[4];
+            if (MASTER) load4(wm + i, wi); else load4(w + i, wi);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+              if (i + e < n_reg) part = fmaf(wi[e], wi[e], part);
+          }
+          continue;
+        }
+        AdamCoef ks = k;
+        ks.wd = sg.wd;
+        float wi[4], gi[4], mi[4], vi[4];
+        if (MASTER) load4(wm + i, wi); else load4(w + i, wi);
+        load4(g + i, gi), load4(ea + i, mi), load4(eas + i, vi);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) gi[e] = clipped<GUARD>(gi[e], coef);
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          wi[e] = adam_elem(wi[e], gi[e], mi[e], vi[e], i + e < n_reg, ks, sg.step, sg.bc2_sqrt, part);
+        store4(ea + i, mi), store4(eas + i, vi), store4(w + i, wi);
+        if (MASTER) store4(wm + i, wi);
+      } else {   // an end inside the vector: element by element, each with its own segment's constants and stores
+        for (int e = 0; e < 4; ++e) {
+          follow(cur, sg, i + e);
+          adam_grouped_elem<S, MASTER, GUARD>(i + e, w, wm, g, ea, eas, i + e < n_reg, k, sg, coef, part);
+        }
+      }
+    }
+  }
+  for (long long i = n_vec + tid; i < n; i += nthr) {
+    follow(cur, sg, i);
+    adam_grouped_elem<S, MASTER, GUARD>(i, w, wm, g, ea, eas, i < n_reg, k, sg, coef, part);
+  }
+  for (int off = 32; off > 0; off >>= 1) part += __shfl_down(part, off, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
+  __syncthreads();
+  if (threadIdx.x < 64) {   // wave 0: lane 0 draws the ticket, every lane hears the answer
+    unsigned drawn = 0u;
+    if (threadIdx.x == 0) {
+      float total = 0.f;
+      for (int j = 0; j < 16; ++j) total += red[j];
+      if (sq_sum) sq_sum[blockIdx.x] = total;
+      // the ticket of the ungrouped kernel; the wait covers this wave's loads of steps_done, the rate and the table
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      drawn = __hip_atomic_fetch_add(&state->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    drawn = __shfl(drawn, 0, 64);
+    if (drawn == gridDim.x - 1) {   // plain vector stores; the next launch starts from ticket 0 again
+      if (my_live) groups->steps[threadIdx.x] = my_steps + 1;
+      if (threadIdx.x == 0) {
+        state->steps_done = t;
+        if constexpr (SCHED) state->lr = lr;   // the GLOBAL rate of this step, before any segment's scale
+        state->ticket = 0u;
+      }
+    }
+  }
+}
+
 template <typename S, bool VEC, bool MASTER, typename... G>
 __global__ __launch_bounds__(1024) void adam_l2_k(S* __restrict__ w, float* __restrict__ wm, const S* __restrict__ g,
                                                  float* __restrict__ ea, float* __restrict__ eas,
                                                  float* __restrict__ sq_sum, AdamState* __restrict__ state, long long n,
                                                  long long n_reg, AdamCoef k, G... guard_block) {
-  // G holds a const GradGuardBlock* (GUARD), a const LrScheduleBlock* (SCHED), both in that order, or nothing: the plain
-  // kernel, parameter for parameter
+  // G holds a const GradGuardBlock* (GUARD), a const LrScheduleBlock* (SCHED), a ParamGroupBlock* (GROUPED), any of them
+  // in that order, or nothing: the plain kernel, parameter for parameter
   constexpr bool GUARD = pack_has_v<const GradGuardBlock*, G...>, SCHED = pack_has_v<const LrScheduleBlock*, G...>;
+  if constexpr (pack_has_v<ParamGroupBlock*, G...>) {   // GROUPED: a body of its own; the rest of this one is untouched
+    const GradGuardBlock* guard = nullptr;
+    const LrScheduleBlock* sched = nullptr;
+    if constexpr (GUARD) guard = pack_get<const GradGuardBlock*>(guard_block...);
+    if constexpr (SCHED) sched = pack_get<const LrScheduleBlock*>(guard_block...);
+    adam_grouped_body<S, VEC, MASTER, GUARD, SCHED>(w, wm, g, ea, eas, sq_sum, state, n, n_reg, k, guard, sched,
+                                                    pack_get<ParamGroupBlock*>(guard_block...));
+    return;
+  }
   __shared__ float red[16];
   __shared__ float scale[GUARD ? 4 : 2];
   if constexpr (GUARD) {
@@ -278,8 +447,10 @@ int dctn_adam_l2_num_partials(int64_t n) { return n < 1 ? 0 : (int)adam_blocks_f
 static int adam_launch(void* master, void* params, const void* grads, void* exp_avg, void* exp_avg_sq, void* sq_sum,
                        void* state, int64_t n, int64_t n_reg, double beta1, double beta2, float eps, float weight_decay,
                        float l2, int dtype, void* stream, bool guarded = false, const void* guard = nullptr,
-                       bool scheduled = false, const void* schedule = nullptr) {
-  if (!params || !grads || !exp_avg || !exp_avg_sq || !state || (guarded && !guard) || (scheduled && !schedule))
+                       bool scheduled = false, const void* schedule = nullptr, bool grouped = false,
+                       void* groups = nullptr) {
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !state || (guarded && !guard) || (scheduled && !schedule) ||
+      (grouped && !groups))
     return DCTN_ERR_NULL;
   if (n < 1 || n_reg < 0 || n_reg > n) return DCTN_ERR_BAD_SHAPE;
   if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return DCTN_ERR_BAD_SHAPE;   // torch raises ValueError
@@ -301,7 +472,24 @@ static int adam_launch(void* master, void* params, const void* grads, void* exp_
   hipLaunchKernelGGL((adam_l2_k<S, VEC, MASTER, const GradGuardBlock*>), g, b, 0, st, (S*)params, (float*)master,   \
                      (const S*)grads, (float*)exp_avg, (float*)exp_avg_sq, (float*)sq_sum, sp, (long long)n,        \
                      (long long)n_reg, k, (const GradGuardBlock*)guard)
-  if (scheduled) {
+  if (grouped) {   // every pack that ends with the table: guard and schedule in front of it when they are there
+    const LrScheduleBlock* sched = (const LrScheduleBlock*)schedule;
+    const GradGuardBlock* gp = (const GradGuardBlock*)guard;
+    ParamGroupBlock* pg = (ParamGroupBlock*)groups;
+#define DCTN_ADAM_ARGS vec, g, b, st, params, master, grads, exp_avg, exp_avg_sq, sq_sum, sp, (long long)n, (long long)n_reg, k
+#define DCTN_ADAM_GROUPED(S, MASTER)                                                              \
+  do {                                                                                            \
+    if (guarded && scheduled) adam_launch_pack<S, MASTER>(DCTN_ADAM_ARGS, gp, sched, pg);         \
+    else if (guarded) adam_launch_pack<S, MASTER>(DCTN_ADAM_ARGS, gp, pg);                        \
+    else if (scheduled) adam_launch_pack<S, MASTER>(DCTN_ADAM_ARGS, sched, pg);                   \
+    else adam_launch_pack<S, MASTER>(DCTN_ADAM_ARGS, pg);                                         \
+  } while (0)
+    if (master) DCTN_ADAM_GROUPED(bf16_t, true);
+    else if (dtype == DCTN_F32) DCTN_ADAM_GROUPED(float, false);
+    else DCTN_ADAM_GROUPED(bf16_t, false);
+#undef DCTN_ADAM_GROUPED
+#undef DCTN_ADAM_ARGS
+  } else if (scheduled) {
     const LrScheduleBlock* sched = (const LrScheduleBlock*)schedule;
     const GradGuardBlock* gp = (const GradGuardBlock*)guard;
 #define DCTN_ADAM_ARGS vec, g, b, st, params, master, grads, exp_avg, exp_avg_sq, sq_sum, sp, (long long)n, (long long)n_reg, k
@@ -372,6 +560,35 @@ int dctn_adam_l2_step_scheduled(void* master_or_null, void* params, const void* 
   if (master_or_null && dtype != DCTN_BF16) return DCTN_ERR_BAD_DTYPE;   // a master copy goes with bf16 parameters
   return adam_launch(master_or_null, params, grads, exp_avg, exp_avg_sq, sq_sum, state, n, n_reg, beta1, beta2, eps,
                      weight_decay, l2, dtype, stream, guard_or_null != nullptr, guard_or_null, true, schedule);
+}
+
+// The table carries every segment's weight decay: the launch has no weight_decay argument
+int dctn_adam_l2_step_grouped(void* master_or_null, void* params, const void* grads, void* exp_avg, void* exp_avg_sq,
+                              void* sq_sum, void* state, const void* guard_or_null, const void* schedule_or_null,
+                              void* groups, int64_t n, int64_t n_reg, double beta1, double beta2, float eps, float l2,
+                              int dtype, void* stream) {
+  if (!groups) return DCTN_ERR_NULL;
+  if (master_or_null && dtype != DCTN_BF16) return DCTN_ERR_BAD_DTYPE;   // a master copy goes with bf16 parameters
+  return adam_launch(master_or_null, params, grads, exp_avg, exp_avg_sq, sq_sum, state, n, n_reg, beta1, beta2, eps, 0.f,
+                     l2, dtype, stream, guard_or_null != nullptr, guard_or_null, schedule_or_null != nullptr,
+                     schedule_or_null, true, groups);
+}
+
+size_t dctn_param_groups_bytes(void) { return sizeof(ParamGroupBlock); }
+
+// Host only: validates a HOST copy of the table for a flat buffer of n elements
+int dctn_param_groups_check(const void* host_block, int64_t n) {
+  if (!host_block) return DCTN_ERR_NULL;
+  const ParamGroupBlock& b = *(const ParamGroupBlock*)host_block;
+  if (n < 1 || b.n_segments < 1 || b.n_segments > DCTN_PG_MAX_SEGMENTS) return DCTN_ERR_BAD_SHAPE;
+  for (int i = 0; i < b.n_segments; ++i) {
+    if (b.end[i] <= (i > 0 ? b.end[i - 1] : 0)) return DCTN_ERR_BAD_SHAPE;   // no empty segment
+    if (!(std::isfinite(b.lr_scale[i]) && b.lr_scale[i] >= 0.f)) return DCTN_ERR_BAD_SHAPE;
+    if (!(std::isfinite(b.weight_decay[i]) && b.weight_decay[i] >= 0.f)) return DCTN_ERR_BAD_SHAPE;
+    if ((b.flags[i] & ~DCTN_PG_FROZEN) != 0u || b.steps[i] < 0) return DCTN_ERR_BAD_SHAPE;
+  }
+  if (b.end[b.n_segments - 1] != (long long)n) return DCTN_ERR_BAD_SHAPE;
+  return DCTN_OK;
 }
 
 size_t dctn_lr_schedule_bytes(void) { return sizeof(LrScheduleBlock); }

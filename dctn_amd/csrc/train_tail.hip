@@ -15,6 +15,7 @@
 #include "common.h"
 #include "grad_guard.h"
 #include "lr_schedule.h"
+#include "param_groups.h"
 
 namespace {
 
@@ -131,14 +132,122 @@ template <bool GUARD> __device__ __forceinline__ float clipped(float g, float co
 // == 0) through LDS, together with the guard's decision when there is one; the workgroup that draws the last ticket
 // writes steps_done + 1 and the rate it used.  A halted guarded step returns before the ticket: steps_done stays, and
 // the schedule holds its place.
+// GROUPED (the pack ends with a ParamGroupBlock*, and always holds a StepStateBlock*): the launch obeys a parameter-group
+// table (param_groups.h states the semantics).  Wave 0 loads the table, one segment per lane, beside steps_done and the
+// rate - state->lr, or the schedule's value at the GLOBAL steps_done - and publishes every segment's end, rate (one
+// rounded product rate * lr_scale), first_step = (the SEGMENT's steps == 0) and frozen flag through LDS.  Every lane
+// walks a cursor over the ends as its elements increase.  A frozen element only adds w * w below n_reg: its gradient
+// and momentum are not read and nothing of it is stored.  The table's weight_decay is not used: sgd_l2_k has none.
+template <typename S, bool MASTER, bool GUARD, bool SCHED>
+__device__ __forceinline__ void sgd_grouped_body(S* __restrict__ w, float* __restrict__ wm, const S* __restrict__ g,
+                                                 float* __restrict__ buf, float* __restrict__ sq_sum, long long n,
+                                                 long long n_reg, float momentum, float l2, const GradGuardBlock* guard,
+                                                 StepStateBlock* state, const LrScheduleBlock* sched,
+                                                 ParamGroupBlock* groups) {
+  __shared__ float red[4];
+  __shared__ float decision[2];                       // halted, coef
+  __shared__ long long seg_end[DCTN_PG_MAX_SEGMENTS];
+  __shared__ float seg_lr[DCTN_PG_MAX_SEGMENTS];
+  __shared__ int seg_first[DCTN_PG_MAX_SEGMENTS], seg_frozen[DCTN_PG_MAX_SEGMENTS];
+  __shared__ int seg_count;
+  int steps_done = 0, my_steps = 0;
+  float rate = 0.f;
+  bool my_live = false;   // wave 0: this lane's segment is in use and not frozen
+  if (threadIdx.x < 64) {   // wave 0, every lane
+    const int lane = threadIdx.x;
+    const ParamGroupLane sg = param_group_lane_load(groups, lane);
+    if constexpr (SCHED) {
+      const LrScheduleLane knot = lr_schedule_lane_load(sched, lane);
+      steps_done = __hip_atomic_load(&state->steps_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      rate = lr_schedule_wave_value(knot, lane, steps_done);
+    } else {
+      steps_done = __hip_atomic_load(&state->steps_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      rate = __hip_atomic_load(&state->lr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if constexpr (GUARD) {
+      if (lane == 0) {
+        decision[0] = __hip_atomic_load(&guard->halted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ? 1.f : 0.f;
+        decision[1] = __hip_atomic_load(&guard->coef, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+    my_steps = sg.steps;
+    my_live = lane < sg.n_segments && (sg.flags & DCTN_PG_FROZEN) == 0u;
+    seg_end[lane] = sg.end;
+    seg_lr[lane] = __fmul_rn(rate, sg.lr_scale);
+    seg_first[lane] = sg.steps == 0 ? 1 : 0;
+    seg_frozen[lane] = (sg.flags & DCTN_PG_FROZEN) != 0u ? 1 : 0;
+    if (lane == 0) seg_count = sg.n_segments;
+  }
+  __syncthreads();
+  float coef = 1.f;
+  if constexpr (GUARD) {
+    if (decision[0] != 0.f) return;   // the whole workgroup, before any store and before the ticket
+    coef = decision[1];
+  }
+  const int n_seg = seg_count;
+  ParamGroupCursor cur{0, param_group_end(seg_end, 0, n_seg)};
+  float lr = seg_lr[0];
+  int first_step = seg_first[0];
+  bool frozen = seg_frozen[0] != 0;
+  float part = 0.f;
+  const float two_l2 = 2.f * l2;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    if (param_group_advance(cur, i, seg_end, n_seg))
+      lr = seg_lr[cur.seg], first_step = seg_first[cur.seg], frozen = seg_frozen[cur.seg] != 0;
+    if (frozen) {
+      if (i < n_reg) {
+        const float wi = MASTER ? wm[i] : (float)w[i];
+        part = fmaf(wi, wi, part);
+      }
+      continue;
+    }
+    const float wi = sgd_elem(MASTER ? wm[i] : (float)w[i], clipped<GUARD>((float)g[i], coef), buf + i, i < n_reg, lr,
+                              momentum, two_l2, first_step, part);
+    w[i] = (S)wi;
+    if (MASTER) wm[i] = wi;
+  }
+  for (int off = 32; off > 0; off >>= 1) part += __shfl_down(part, off, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
+  __syncthreads();
+  if (threadIdx.x < 64) {   // wave 0: lane 0 draws the ticket, every lane hears the answer
+    unsigned drawn = 0u;
+    if (threadIdx.x == 0) {
+      if (sq_sum) sq_sum[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+      // the ticket of adam_l2_k; the wait covers this wave's loads of steps_done, the rate and the table
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      drawn = __hip_atomic_fetch_add(&state->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    drawn = __shfl(drawn, 0, 64);
+    if (drawn == gridDim.x - 1) {   // plain vector stores; the next launch starts from ticket 0 again
+      if (my_live) groups->steps[threadIdx.x] = my_steps + 1;
+      if (threadIdx.x == 0) {
+        state->steps_done = steps_done + 1;
+        if constexpr (SCHED) state->lr = rate;   // the GLOBAL rate of this step, before any segment's scale
+        state->ticket = 0u;
+      }
+    }
+  }
+}
+
 template <typename S, bool MASTER, typename... G>
 __global__ __launch_bounds__(256) void sgd_l2_k(S* __restrict__ w, float* __restrict__ wm, const S* __restrict__ g,
                                                 float* __restrict__ buf, float* __restrict__ sq_sum, long long n,
                                                 long long n_reg, float lr, float momentum, float l2, int first_step,
                                                 G... guard_block) {
-  // G holds a const GradGuardBlock* (GUARD), a StepStateBlock* and a const LrScheduleBlock* (SCHED), all three in that
-  // order, or nothing: the plain kernel, parameter for parameter
+  // G holds a const GradGuardBlock* (GUARD), a StepStateBlock* and a const LrScheduleBlock* (SCHED), a ParamGroupBlock*
+  // (GROUPED, with the StepStateBlock* whether or not there is a schedule), in that order, or nothing: the plain kernel,
+  // parameter for parameter
   constexpr bool GUARD = pack_has_v<const GradGuardBlock*, G...>, SCHED = pack_has_v<const LrScheduleBlock*, G...>;
+  if constexpr (pack_has_v<ParamGroupBlock*, G...>) {   // GROUPED: a body of its own; the rest of this one is untouched
+    const GradGuardBlock* guard = nullptr;
+    const LrScheduleBlock* sched = nullptr;
+    if constexpr (GUARD) guard = pack_get<const GradGuardBlock*>(guard_block...);
+    if constexpr (SCHED) sched = pack_get<const LrScheduleBlock*>(guard_block...);
+    sgd_grouped_body<S, MASTER, GUARD, SCHED>(w, wm, g, buf, sq_sum, n, n_reg, momentum, l2, guard,
+                                              pack_get<StepStateBlock*>(guard_block...), sched,
+                                              pack_get<ParamGroupBlock*>(guard_block...));
+    return;
+  }
   __shared__ float red[4];
   float coef = 1.f;
   int steps_done = 0;
@@ -320,6 +429,36 @@ int dctn_sgd_l2_step_scheduled(void* master_or_null, void* params, const void* g
   } else {
     if (gp) sgd_launch_pack<bf16_t, false>(DCTN_SGD_ARGS, gp, sp, sched); else sgd_launch_pack<bf16_t, false>(DCTN_SGD_ARGS, sp, sched);
   }
+#undef DCTN_SGD_ARGS
+  DCTN_CHECK_LAUNCH();
+  return DCTN_OK;
+}
+
+// The grouped form always takes the 16-byte step block: without a schedule the rate is state->lr, as adam_l2_k's
+int dctn_sgd_l2_step_grouped(void* master_or_null, void* params, const void* grads, void* momentum_buf, void* sq_sum,
+                             void* state, const void* guard_or_null, const void* schedule_or_null, void* groups,
+                             int64_t n, int64_t n_reg, float momentum, float l2, int dtype, void* stream) {
+  if (!params || !grads || !momentum_buf || !state || !groups) return DCTN_ERR_NULL;
+  if (n < 1 || n_reg < 0 || n_reg > n) return DCTN_ERR_BAD_SHAPE;
+  if ((dtype != DCTN_F32 && dtype != DCTN_BF16) || (master_or_null && dtype != DCTN_BF16)) return DCTN_ERR_BAD_DTYPE;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 g(blocks_for(n)), b(256);
+  const GradGuardBlock* gp = (const GradGuardBlock*)guard_or_null;
+  StepStateBlock* sp = (StepStateBlock*)state;
+  const LrScheduleBlock* sched = (const LrScheduleBlock*)schedule_or_null;
+  ParamGroupBlock* pg = (ParamGroupBlock*)groups;
+#define DCTN_SGD_ARGS g, b, st, params, master_or_null, grads, momentum_buf, sq_sum, (long long)n, (long long)n_reg, momentum, l2
+#define DCTN_SGD_GROUPED(S, MASTER)                                                       \
+  do {                                                                                    \
+    if (gp && sched) sgd_launch_pack<S, MASTER>(DCTN_SGD_ARGS, gp, sp, sched, pg);        \
+    else if (gp) sgd_launch_pack<S, MASTER>(DCTN_SGD_ARGS, gp, sp, pg);                   \
+    else if (sched) sgd_launch_pack<S, MASTER>(DCTN_SGD_ARGS, sp, sched, pg);             \
+    else sgd_launch_pack<S, MASTER>(DCTN_SGD_ARGS, sp, pg);                               \
+  } while (0)
+  if (master_or_null) DCTN_SGD_GROUPED(bf16_t, true);
+  else if (dtype == DCTN_F32) DCTN_SGD_GROUPED(float, false);
+  else DCTN_SGD_GROUPED(bf16_t, false);
+#undef DCTN_SGD_GROUPED
 #undef DCTN_SGD_ARGS
   DCTN_CHECK_LAUNCH();
   return DCTN_OK;

@@ -768,6 +768,279 @@ class LRSchedule:
         return cls(device, knots, hold=[1] * len(knots))
 
 
+class ParamGroup:
+    """One entry of a `ParamGroups` table: the parameters it names (matched by identity) get ``lr_scale``,
+    ``weight_decay`` (None: the optimizer's own value) and ``frozen``."""
+
+    def __init__(self, params, lr_scale: float = 1.0, weight_decay: Optional[float] = None, frozen: bool = False):
+        self.params = [params] if isinstance(params, Tensor) else list(params)
+        self.lr_scale, self.weight_decay, self.frozen = lr_scale, weight_decay, bool(frozen)
+
+
+class ParamGroups:
+    """A parameter-group table that lives on the device (`dctn_adam_l2_step_grouped` / `dctn_sgd_l2_step_grouped`,
+    include/dctn_amd.h): one SEGMENT per parameter of the optimizer's flat buffer, each with its own rate multiplier,
+    weight decay, frozen flag and step count, in a 1552-byte DEVICE block that the ONE optimizer launch obeys.  Pass it
+    to ``FlatAdam(..., groups=g)`` or ``FlatSGD(..., groups=g)``.
+
+    ``params``: the optimizer's parameters in flat order (regularised + others), at most 64 (NotImplementedError).
+    ``entries``: `ParamGroup` objects; a parameter no entry names takes the defaults (scale 1, the optimizer's weight
+    decay, not frozen); naming a parameter that is not in ``params``, or one twice, raises ValueError.
+
+    A segment's rate is the float32 product ``rate * lr_scale``; Adam's bias corrections and SGD's first step follow the
+    SEGMENT's own count of steps, as ``torch.optim`` keeps one ``state["step"]`` / ``momentum_buffer`` per parameter.  A
+    frozen segment is not touched at all - parameters, master copy, moments and its count stay, its gradient is not read
+    (it may be None) - but it still counts in ``reg_value()``: the reference's regulariser sums every core whatever
+    ``requires_grad`` says.  ``from_requires_grad`` freezes what has ``requires_grad = False``: the reference's
+    ``--freeze-eps``.
+
+    ``set`` / ``freeze`` are small writes on the current stream BETWEEN launches (RuntimeError during a capture, as
+    ``LRSchedule.set``): replays of an already captured graph follow them.  ``steps`` reads the counts from the device
+    (it synchronises).  ``segment_of(i)`` is the host mirror of the kernel's lookup.  The guard's norm and the
+    all-reduce still cover the whole flat buffer, frozen segments included.
+    """
+
+    MAX_SEGMENTS = 64
+    WORDS = 388   # 1552 bytes: n_segments, reserved[3], int64 end[64], lr_scale[64], weight_decay[64], flags[64], steps[64]
+    _END, _SCALE, _WD, _FLAGS, _STEPS = 4, 132, 196, 260, 324   # word offsets
+
+    def __init__(self, params, entries=()):
+        import numpy as np
+
+        self.params = [p for p in params]
+        if not self.params:
+            raise ValueError("ParamGroups: no parameters")
+        if len(self.params) > self.MAX_SEGMENTS:
+            raise NotImplementedError(f"ParamGroups: at most {self.MAX_SEGMENTS} parameters (one segment per lane of a "
+                                      f"wave), got {len(self.params)}")
+        if any(p.numel() < 1 for p in self.params):
+            raise ValueError("ParamGroups: a parameter without elements has no segment")
+        self.device = self.params[0].device
+        self._index = {id(p): i for i, p in enumerate(self.params)}
+        if len(self._index) != len(self.params):
+            raise ValueError("ParamGroups: a parameter appears twice in `params`")
+        k = len(self.params)
+        self._ends = np.cumsum([p.numel() for p in self.params]).astype(np.int64)
+        self._scale = [1.0] * k
+        self._wd: list = [None] * k            # None: the optimizer's own value, known once an optimizer binds the table
+        self._frozen = [False] * k
+        self._default_wd, self._wd_allowed = 0.0, True
+        named = set()
+        for entry in entries:
+            if not isinstance(entry, ParamGroup):
+                raise TypeError(f"ParamGroups: an entry is a ParamGroup, got {type(entry).__name__}")
+            scale, wd = self._validated("lr_scale", entry.lr_scale), entry.weight_decay
+            wd = None if wd is None else self._validated("weight_decay", wd)
+            for p in entry.params:
+                i = self._index.get(id(p))
+                if i is None:
+                    raise ValueError("ParamGroups: an entry names a parameter that is not one of the optimizer's")
+                if i in named:
+                    raise ValueError(f"ParamGroups: parameter {i} is named by two entries")
+                named.add(i)
+                self._scale[i], self._wd[i], self._frozen[i] = scale, wd, entry.frozen
+        self._block = torch.zeros(self.WORDS, dtype=torch.int32, device=self.device)
+        self._upload(np.zeros(k, dtype=np.int32))
+
+    @classmethod
+    def from_requires_grad(cls, params, entries=()) -> "ParamGroups":
+        """The table of ``entries`` with every parameter whose ``requires_grad`` is False frozen as well."""
+        groups = cls(params, entries)
+        for i, p in enumerate(groups.params):
+            if not p.requires_grad:
+                groups._frozen[i] = True
+        groups._upload(groups._host_steps())
+        return groups
+
+    # ---------------------------------------------------------------------------------------- host side
+    @staticmethod
+    def _validated(what: str, value) -> float:
+        import math
+
+        import numpy as np
+
+        with np.errstate(over="ignore"):
+            v = float(np.float32(value))
+        if not (math.isfinite(v) and v >= 0.0):
+            raise ValueError(f"ParamGroups: {what} must be finite (in float32) and >= 0, got {value!r}")
+        return v
+
+    def __len__(self) -> int:
+        return len(self.params)
+
+    def index_of(self, param) -> int:
+        """The segment of a parameter (or the index itself when an int is given)."""
+        if isinstance(param, int):
+            if not 0 <= param < len(self.params):
+                raise ValueError(f"ParamGroups: no segment {param}")
+            return param
+        i = self._index.get(id(param))
+        if i is None:
+            raise ValueError("ParamGroups: not one of the table's parameters")
+        return i
+
+    def segment_of(self, i: int) -> int:
+        """The segment that holds flat element ``i``: what the kernel's cursor finds."""
+        import numpy as np
+
+        if not 0 <= int(i) < int(self._ends[-1]):
+            raise IndexError(f"ParamGroups.segment_of: element {i} of {int(self._ends[-1])}")
+        return int(np.searchsorted(self._ends, int(i), side="right"))
+
+    @property
+    def ends(self):
+        return [int(e) for e in self._ends]
+
+    @property
+    def lr_scales(self):
+        return list(self._scale)
+
+    @property
+    def weight_decays(self):
+        """Every segment's weight decay as the kernel gets it (None entries resolved to the optimizer's value)."""
+        return [self._default_wd if w is None else w for w in self._wd]
+
+    @property
+    def frozen(self):
+        return list(self._frozen)
+
+    def host_block(self, steps=None):
+        """The 1552 bytes of the block as a numpy int32 array of 388 words (what `dctn_param_groups_check` takes), with
+        ``steps`` as the counts (zeros when None)."""
+        import numpy as np
+
+        k = len(self.params)
+        words = np.zeros(self.WORDS, dtype=np.int32)
+        words[0] = k
+        words[self._END: self._END + 128].view(np.int64)[:k] = self._ends
+        floats = words.view(np.float32)
+        floats[self._SCALE: self._SCALE + k] = self._scale
+        floats[self._WD: self._WD + k] = self.weight_decays
+        words[self._FLAGS: self._FLAGS + k] = [1 if f else 0 for f in self._frozen]
+        if steps is not None:
+            words[self._STEPS: self._STEPS + k] = steps
+        return words
+
+    # ---------------------------------------------------------------------------------------- the device block
+    def _no_capture(self, what: str) -> None:
+        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"ParamGroups.{what} during a graph capture: the captured step reads the table from the "
+                               "device, change it between replays")
+
+    def _host_steps(self):
+        return self._block[self._STEPS: self._STEPS + len(self.params)].cpu().numpy()
+
+    def _upload(self, steps) -> None:
+        with torch.no_grad():
+            self._block.copy_(torch.from_numpy(self.host_block(steps)))
+
+    def _write_cell(self, word: int, value, as_float: bool) -> None:
+        cell = self._block.view(torch.float32)[word: word + 1] if as_float else self._block[word: word + 1]
+        if self.device.type == "cuda":
+            with torch.cuda.device(self.device):
+                cell.fill_(value)
+        else:
+            cell.fill_(value)
+
+    def _bind(self, default_weight_decay: Optional[float], owner: str) -> None:
+        """An optimizer takes the table: None weight decays become its value; an optimizer without weight decay
+        (``default_weight_decay`` None) refuses explicit ones."""
+        if default_weight_decay is None:
+            if any(w is not None for w in self._wd):
+                raise ValueError(f"{owner} has no weight decay: a ParamGroup for it must leave weight_decay=None")
+            self._default_wd, self._wd_allowed = 0.0, False
+        else:
+            self._default_wd, self._wd_allowed = self._validated("weight_decay", default_weight_decay), True
+        self._upload(self._host_steps())
+
+    def set(self, param, lr_scale: Optional[float] = None, weight_decay: Optional[float] = None,
+            frozen: Optional[bool] = None) -> None:
+        """Changes one segment (``param``: the parameter, or its index) in place; arguments left None stay as they are.
+        The next launch, a replay included, follows it."""
+        self._no_capture("set()")
+        i = self.index_of(param)
+        if weight_decay is not None and not self._wd_allowed:
+            raise ValueError("ParamGroups.set: the optimizer that holds this table has no weight decay")
+        if lr_scale is not None:
+            self._scale[i] = self._validated("lr_scale", lr_scale)
+            self._write_cell(self._SCALE + i, self._scale[i], True)
+        if weight_decay is not None:
+            self._wd[i] = self._validated("weight_decay", weight_decay)
+            self._write_cell(self._WD + i, self._wd[i], True)
+        if frozen is not None:
+            self._frozen[i] = bool(frozen)
+            self._write_cell(self._FLAGS + i, 1 if frozen else 0, False)
+
+    def freeze(self, param, flag: bool = True) -> None:
+        """Freezes (or with ``flag=False`` releases) one segment from the next launch on.  A released segment goes on from
+        its own count of steps: its bias corrections are those of a parameter that has taken that many steps."""
+        self.set(param, frozen=bool(flag))
+
+    @property
+    def steps(self):
+        """The segments' step counts, read from the device (it synchronises)."""
+        return [int(s) for s in self._host_steps()]
+
+    def state_dict(self) -> Dict[str, Any]:
+        return {"ends": self.ends, "lr_scale": list(self._scale), "weight_decay": list(self._wd),
+                "frozen": [bool(f) for f in self._frozen], "steps": self.steps}
+
+    def load_state_dict(self, state: Dict[str, Any]) -> None:
+        self._no_capture("load_state_dict()")
+        k = len(self.params)
+        if [int(e) for e in state["ends"]] != self.ends:
+            raise ValueError(f"ParamGroups.load_state_dict: the state's segments end at {list(state['ends'])}, this "
+                             f"table's at {self.ends}")
+        if not (len(state["lr_scale"]) == len(state["weight_decay"]) == len(state["frozen"]) == len(state["steps"]) == k):
+            raise ValueError(f"ParamGroups.load_state_dict: {k} segments, the state's lists disagree")
+        wds = [None if w is None else self._validated("weight_decay", w) for w in state["weight_decay"]]
+        if not self._wd_allowed and any(w is not None for w in wds):
+            raise ValueError("ParamGroups.load_state_dict: the optimizer that holds this table has no weight decay")
+        steps = [int(s) for s in state["steps"]]
+        if any(s < 0 for s in steps):
+            raise ValueError("ParamGroups.load_state_dict: a negative step count")
+        self._scale = [self._validated("lr_scale", s) for s in state["lr_scale"]]
+        self._wd, self._frozen = wds, [bool(f) for f in state["frozen"]]
+        import numpy as np
+
+        self._upload(np.array(steps, dtype=np.int32))
+
+    def _mirror_block(self, words) -> None:
+        """Sets the host copy from the block's bytes (`checkpoint.RunState.load` put the block itself back)."""
+        import numpy as np
+
+        words = np.ascontiguousarray(words).view("<i4").reshape(-1)
+        k = len(self.params)
+        if words.size != self.WORDS or int(words[0]) != k:
+            raise ValueError(f"ParamGroups: the block describes {int(words[0]) if words.size else '?'} segments, this "
+                             f"table has {k}")
+        ends = words[self._END: self._END + 128].view(np.int64)[:k]
+        if not np.array_equal(ends, self._ends):
+            raise ValueError(f"ParamGroups: the block's segments end at {ends.tolist()}, this table's at {self.ends}")
+        floats = words.view(np.float32)
+        self._scale = [float(x) for x in floats[self._SCALE: self._SCALE + k]]
+        saved = [float(x) for x in floats[self._WD: self._WD + k]]
+        # (a None stays a None where the block holds the bound optimizer's value; an optimizer without weight decay)
+        self._wd = [None if not self._wd_allowed or (old is None and x == self._default_wd) else x
+                    for old, x in zip(self._wd, saved)]
+        self._frozen = [bool(x & 1) for x in words[self._FLAGS: self._FLAGS + k]]
+
+
+def param_groups_for(model, freeze_eps=(), head_lr_scale: float = 1.0) -> ParamGroups:
+    """The table of an ``EPSesPlusLinear`` for the runner's flags, over the parameters in the order
+    ``list(model.epses) + [model.linear.weight, model.linear.bias]`` (what `FlatAdam` is given as regularised + others):
+    the cores listed in ``freeze_eps`` (the reference's ``--freeze-eps INDEX``) and every parameter whose
+    ``requires_grad`` is False are frozen, and the head (``linear.weight`` and ``linear.bias``) steps with
+    ``head_lr_scale`` times the rate."""
+    epses = list(model.epses)
+    frozen = sorted({int(i) for i in freeze_eps})
+    if any(not 0 <= i < len(epses) for i in frozen):
+        raise ValueError(f"param_groups_for: freeze_eps {list(freeze_eps)} with {len(epses)} EPSes")
+    entries = [ParamGroup([epses[i] for i in frozen], frozen=True)] if frozen else []
+    entries.append(ParamGroup([model.linear.weight, model.linear.bias], lr_scale=head_lr_scale))
+    return ParamGroups.from_requires_grad(epses + [model.linear.weight, model.linear.bias], entries)
+
+
 class _FlatOptimizer:
     """What FlatSGD and FlatAdam share: the parameters moved into ONE flat buffer (their ``.data`` become views of it,
     in the order regularised + others), the gradients read in place when they already sit back to back in that
@@ -779,7 +1052,9 @@ class _FlatOptimizer:
     float32 parameters the option changes nothing and ``master`` is None."""
 
     def __init__(self, regularised, others, num_partials: Callable[[int], int], master_weights: bool = False,
-                 guard: Optional["GradGuard"] = None, guard_loss=None, schedule: Optional["LRSchedule"] = None):
+                 guard: Optional["GradGuard"] = None, guard_loss=None, schedule: Optional["LRSchedule"] = None,
+                 groups: Optional["ParamGroups"] = None):
+        # groups: a ParamGroups table over exactly these parameters that the step kernel obeys
         # guard: a GradGuard whose check runs in front of every step; guard_loss: the float32 device scalar the check
         # looks at beside the gradients, or a callable that returns it (the loss tensor of a training loop is a new one
         # every iteration)
@@ -810,6 +1085,16 @@ class _FlatOptimizer:
             self.master = self.flat.to(torch.float32)
         if schedule is not None and schedule.device != self.flat.device:
             raise ValueError(f"the schedule's block is on {schedule.device}, the parameters on {self.flat.device}")
+        if groups is not None:
+            if not isinstance(groups, ParamGroups):
+                raise TypeError(f"groups must be a ParamGroups, got {type(groups).__name__}")
+            if len(groups.params) != len(self.params) or any(a is not b for a, b in zip(groups.params, self.params)):
+                raise ValueError("the ParamGroups table must be built over the optimizer's parameters in flat order "
+                                 "(regularised + others)")
+            if groups.device != self.flat.device:
+                raise ValueError(f"the group table's block is on {groups.device}, the parameters on {self.flat.device}")
+            assert L.lib().dctn_param_groups_bytes() == 4 * ParamGroups.WORDS and groups.ends[-1] == self.n
+        self.groups = groups
 
     def _scheduled_lr(self) -> float:
         """``schedule.value(t)``, scale applied: the rate of the next step (reads the step count from the device)."""
@@ -875,7 +1160,10 @@ class _FlatOptimizer:
         """Writes the 16-byte step block of a scheduled optimizer: ``steps`` taken, the rate of the last of them."""
         host = torch.zeros(4, dtype=torch.int32)
         host[0] = int(steps)
-        host.view(torch.float32)[1] = self.schedule.value(steps - 1) if steps > 0 else 0.0
+        if self.schedule is None:   # a grouped FlatSGD without a schedule: the cell holds the rate the host set
+            host.view(torch.float32)[1] = self._lr
+        else:
+            host.view(torch.float32)[1] = self.schedule.value(steps - 1) if steps > 0 else 0.0
         with torch.no_grad():
             self._state.copy_(host)
 
@@ -916,13 +1204,22 @@ class FlatSGD(_FlatOptimizer):
     not used.  The schedule object is fixed for the life of a captured graph; its table and scale may change between
     replays.  ``opt.t`` and ``state_dict()["steps"]`` are read from the block.  Without a schedule ``step()`` makes
     the calls it always made.
+
+    ``groups`` (a `ParamGroups` over exactly these parameters): ``step()`` launches `dctn_sgd_l2_step_grouped` (behind
+    the guard's check when there is a guard): every parameter steps with ``rate * lr_scale`` of its segment, takes its
+    first step when ITS count is 0, and is left alone while frozen.  The optimizer then owns the 16-byte step block
+    whether or not there is a schedule: without one ``opt.lr = x`` writes the block's rate cell (not during a capture),
+    and a captured step follows it.  ``opt.t`` stays the global count.  A `ParamGroup` for this optimizer leaves
+    ``weight_decay=None`` (ValueError otherwise).  The table's state is not part of ``state_dict()``; save
+    ``groups.state_dict()`` beside it (`checkpoint.RunState` carries its block).  Without ``groups`` ``step()`` makes
+    the calls it always made.
     """
 
     def __init__(self, regularised, others=(), lr: float = 1e-3, momentum: float = 0.0, l2: float = 0.0,
                  master_weights: bool = False, guard: Optional["GradGuard"] = None, guard_loss=None, *,
-                 schedule: Optional["LRSchedule"] = None):
+                 schedule: Optional["LRSchedule"] = None, groups: Optional["ParamGroups"] = None):
         super().__init__(regularised, others, L.lib().dctn_sgd_l2_num_partials, master_weights, guard, guard_loss,
-                         schedule)
+                         schedule, groups)
         self._lr, self.momentum, self.l2 = float(lr), float(momentum), float(l2)
         self.buf = torch.zeros(self.n, dtype=torch.float32, device=self.flat.device)
         self._steps = 0
@@ -931,6 +1228,12 @@ class FlatSGD(_FlatOptimizer):
         if schedule is not None:
             assert L.lib().dctn_adam_state_bytes() == 16 and L.lib().dctn_lr_schedule_bytes() == 4 * LRSchedule.WORDS
             self._state = torch.zeros(4, dtype=torch.int32, device=self.flat.device)
+        if groups is not None:   # the grouped step always takes the block; without a schedule it reads the rate cell
+            groups._bind(None, "FlatSGD")
+            if self._state is None:
+                assert L.lib().dctn_adam_state_bytes() == 16
+                self._state = torch.zeros(4, dtype=torch.int32, device=self.flat.device)
+                self._put_step_block(0)
 
     @property
     def lr(self) -> float:
@@ -941,11 +1244,23 @@ class FlatSGD(_FlatOptimizer):
     def lr(self, value: float) -> None:
         if self.schedule is not None:
             self._refuse_lr()
+        if self.groups is not None:   # the grouped step reads the rate from the block: a small write, as FlatAdam's
+            if self.flat.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("FlatSGD.lr cannot be assigned during a graph capture: the captured grouped step reads "
+                                   "the rate from the device, assign it between replays")
+            self._lr = float(value)
+            cell = self._state.view(torch.float32)[1:2]
+            if self.flat.device.type == "cuda":
+                with torch.cuda.device(self.flat.device):
+                    cell.fill_(self._lr)
+            else:
+                cell.fill_(self._lr)
+            return
         self._lr = float(value)
 
     @property
     def t(self) -> int:
-        """Number of steps taken: with a schedule read from the device block (it synchronises; steps the guard skipped
+        """Number of steps taken: with a schedule or a group table read from the device block (it synchronises; steps the guard skipped
         do not count), otherwise the host's count of launches."""
         return self._steps if self._state is None else int(self._state[0].item())
 
@@ -953,6 +1268,17 @@ class FlatSGD(_FlatOptimizer):
     def step(self) -> None:
         g = self._grads()
         dev = self.flat.device
+        if self.groups is not None:
+            block = self._run_guard(g) if self.guard is not None else None
+            L.check(L.lib().dctn_sgd_l2_step_grouped(None if self.master is None else self.master.data_ptr(),
+                                                     self.flat.data_ptr(), g.data_ptr(), self.buf.data_ptr(),
+                                                     self.sq_sum.data_ptr(), self._state.data_ptr(), block,
+                                                     None if self.schedule is None else self.schedule._block.data_ptr(),
+                                                     self.groups._block.data_ptr(), self.n, self.n_reg, self.momentum,
+                                                     self.l2, L.dtype_code(self.flat), L.stream_ptr(dev)),
+                    "grouped fused SGD step")
+            self._steps += 1
+            return
         if self.schedule is not None:
             block = self._run_guard(g) if self.guard is not None else None
             L.check(L.lib().dctn_sgd_l2_step_scheduled(None if self.master is None else self.master.data_ptr(),
@@ -1009,6 +1335,8 @@ class FlatSGD(_FlatOptimizer):
         self._steps = int(state["steps"])
         if self.schedule is None:
             self.lr = float(state["lr"])
+            if self._state is not None:   # a group table: the block holds the count beside the rate
+                self._put_step_block(self._steps)
         else:   # the block as the scheduled kernel would have left it: the count, and the rate of the last step
             self._put_step_block(self._steps)
         self._load_master(state)
@@ -1052,13 +1380,25 @@ class FlatAdam(_FlatOptimizer):
     graph; its table and scale may change between replays.  The schedule's state is not part of ``state_dict()``; save
     ``schedule.state_dict()`` beside it (`checkpoint.RunState` carries its block).  Without a schedule ``step()``
     makes the calls it always made.
+
+    ``groups`` (a `ParamGroups` over exactly these parameters): ``step()`` launches `dctn_adam_l2_step_grouped` (behind
+    the guard's check when there is a guard, with the schedule when there is one): ``torch.optim.Adam`` with
+    ``param_groups`` and parameters without a gradient, in the one launch.  Every parameter steps with
+    ``rate * lr_scale`` and the weight decay of its segment, its bias corrections follow ITS count of steps, and a frozen
+    parameter is left alone - value, master copy, moments and count; a gradient of None is fine - while its squares
+    still count in ``reg_value()``.  ``opt.t`` stays the global count; ``groups.steps`` reads the segments'.  A clipped
+    step clips every unfrozen segment by the one coefficient: the guard's norm, like the all-reduce, covers the whole
+    flat buffer, frozen segments included.  The table's state is not part of ``state_dict()``; save
+    ``groups.state_dict()`` beside it (`checkpoint.RunState` carries its block).  Without ``groups`` ``step()`` makes
+    the calls it always made.
     """
 
     def __init__(self, regularised, others=(), lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, l2: float = 0.0, master_weights: bool = False,
-                 guard: Optional["GradGuard"] = None, guard_loss=None, *, schedule: Optional["LRSchedule"] = None):
+                 guard: Optional["GradGuard"] = None, guard_loss=None, *, schedule: Optional["LRSchedule"] = None,
+                 groups: Optional["ParamGroups"] = None):
         super().__init__(regularised, others, L.lib().dctn_adam_l2_num_partials, master_weights, guard, guard_loss,
-                         schedule)
+                         schedule, groups)
         if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0 and lr >= 0.0 and eps >= 0.0 and weight_decay >= 0.0):
             raise ValueError(f"invalid Adam hyper-parameters: lr={lr} betas={betas} eps={eps} weight_decay={weight_decay}")
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
@@ -1076,6 +1416,8 @@ class FlatAdam(_FlatOptimizer):
         else:   # the block's rate cell is the kernel's to write: the rate of the step just taken
             self._lr = float(lr)
             assert L.lib().dctn_lr_schedule_bytes() == 4 * LRSchedule.WORDS
+        if groups is not None:
+            groups._bind(self.weight_decay, "FlatAdam")
 
     @property
     def lr(self) -> float:
@@ -1102,6 +1444,17 @@ class FlatAdam(_FlatOptimizer):
     def step(self) -> None:
         g = self._grads()
         dev = self.flat.device
+        if self.groups is not None:   # (every segment's weight decay is in the table)
+            block = self._run_guard(g) if self.guard is not None else None
+            L.check(L.lib().dctn_adam_l2_step_grouped(None if self.master is None else self.master.data_ptr(),
+                                                      self.flat.data_ptr(), g.data_ptr(), self.m.data_ptr(),
+                                                      self.v.data_ptr(), self.sq_sum.data_ptr(), self._state.data_ptr(),
+                                                      block,
+                                                      None if self.schedule is None else self.schedule._block.data_ptr(),
+                                                      self.groups._block.data_ptr(), self.n, self.n_reg, self.betas[0],
+                                                      self.betas[1], self.eps, self.l2, L.dtype_code(self.flat),
+                                                      L.stream_ptr(dev)), "grouped fused Adam step")
+            return
         if self.schedule is not None:
             block = self._run_guard(g) if self.guard is not None else None
             L.check(L.lib().dctn_adam_l2_step_scheduled(None if self.master is None else self.master.data_ptr(),

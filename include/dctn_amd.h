@@ -542,6 +542,61 @@ int dctn_sgd_l2_step_scheduled(void* master_or_null, void* params, const void* g
                                float momentum, float l2, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Parameter groups (version 511): one optimizer launch obeys a table that gives every parameter of the flat buffer its
+ * own rate multiplier, weight decay, frozen flag and step count (the reference freezes cores with requires_grad = False
+ * and torch.optim.Adam then skips them: new_runner.py:443-444, :496-498).
+ *
+ * `groups`: dctn_param_groups_bytes = 1552 bytes, 16-byte aligned, laid out as
+ *   int32   n_segments        1..64
+ *   int32   reserved[3]       0
+ *   int64   end[64]           exclusive element index where a segment ends; strictly increasing; the last used one is n
+ *   float   lr_scale[64]      multiplies the rate; 1.0f leaves the bits alone
+ *   float   weight_decay[64]  Adam's coupled weight decay of the segment (the SGD step does not use it)
+ *   uint32  flags[64]         bit 0: frozen
+ *   int32   steps[64]         steps the segment has taken; the launch advances it
+ * One segment is one parameter, in flat order: elements [end[s-1], end[s]), end[-1] = 0.  Slots at and past n_segments
+ * are never used, whatever they hold.  The caller writes the block in stream order between launches.  The regularised
+ * set stays the prefix n_reg (it may end inside a segment) and l2 stays one scalar.
+ *
+ * Semantics:
+ *   The rate of a segment is ONE rounded float32 product rate * lr_scale, where rate is state->lr, or with a schedule
+ *     its value at the GLOBAL steps_done.  lr_scale == 1.0f leaves the bits unchanged.
+ *   Adam's bias corrections use the SEGMENT's count steps + 1 (torch.optim.Adam's per-parameter state["step"]), formed
+ *     in float64 exactly as the ungrouped step forms them from steps_done + 1.
+ *   SGD's first step (the momentum buffer takes the gradient) is steps == 0 of the segment.
+ *   A frozen segment: no element of params, master, exp_avg, exp_avg_sq or momentum_buf is stored to, its gradient is
+ *     not read, and its steps does not advance.  Its w * w still goes into sq_sum where it lies under n_reg (the
+ *     reference's regulariser sums every core whatever requires_grad says; only the gradient term is dropped).
+ *   The launch writes steps + 1 for every unfrozen segment, beside steps_done + 1 (the GLOBAL count of launches that
+ *     were not halted); with a schedule state->lr gets the global rate, before any segment's scale.
+ *   A halted guarded launch writes nothing and advances nothing.
+ *   When every segment has lr_scale 1 and one weight_decay, none is frozen and every count equals steps_done, the
+ *     launch leaves the ungrouped launch's bits (with that weight_decay) in every buffer, the sq_sum slots included.
+ *
+ * dctn_adam_l2_step_grouped : dctn_adam_l2_step_scheduled's arguments with `groups` behind the schedule and without
+ *   weight_decay (the table holds it).  master_or_null / guard_or_null as there; schedule_or_null: null reads state->lr.
+ * dctn_sgd_l2_step_grouped : dctn_sgd_l2_step_scheduled's arguments with `groups` behind the schedule.  It always takes
+ *   the 16-byte state block; with schedule_or_null null it reads state->lr, as the Adam step does.
+ * dctn_param_groups_check : HOST only, over a host copy of the block: n_segments in 1..64, end[0] >= 1 and strictly
+ *   increasing with end[n_segments-1] == n, every used lr_scale and weight_decay finite and >= 0, no flag bit but bit 0,
+ *   steps >= 0; DCTN_ERR_BAD_SHAPE otherwise.
+ * The step entry points do not read the block on the host and validate nothing of it.  A malformed table may give a
+ * wrong update; it never gives an access outside the buffers: the kernels keep the segment index inside the used
+ * slots (n_segments clamped to 1..64), let the last used segment reach to n, and index elements only by i < n.
+ * Return codes as the scheduled steps.  No workspace; the calls only enqueue and can be captured.  These launches do
+ * not report to dctn_last_kernel.
+ * ------------------------------------------------------------------------------------------ */
+size_t dctn_param_groups_bytes(void);
+int dctn_param_groups_check(const void* host_block, int64_t n);
+int dctn_adam_l2_step_grouped(void* master_or_null, void* params, const void* grads, void* exp_avg, void* exp_avg_sq,
+                              void* sq_sum, void* state, const void* guard_or_null, const void* schedule_or_null,
+                              void* groups, int64_t n, int64_t n_reg, double beta1, double beta2, float eps, float l2,
+                              int dtype, void* stream);
+int dctn_sgd_l2_step_grouped(void* master_or_null, void* params, const void* grads, void* momentum_buf, void* sq_sum,
+                             void* state, const void* guard_or_null, const void* schedule_or_null, void* groups,
+                             int64_t n, int64_t n_reg, float momentum, float l2, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Scoring (reference: dctn/evaluation.py:7-22): one launch per batch ADDS to acc = three float64 values
  * {sum of the rows' cross-entropies, number of correct rows, number of rows}.  logits (B, C) contiguous, DCTN_F32 /
  * DCTN_BF16; labels int64.  Per row a max-shifted log-sum-exp with float32 exponentials; the row's sum, its

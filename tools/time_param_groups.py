@@ -1,0 +1,138 @@
+"""What the device-side parameter-group table costs a graphed training iteration, and what it buys, in one process.
+
+cfg2 (bf16, B = 1024, FlatAdam with master weights) as a GraphedTrainStep whose graph draws its own batches from a
+`DeviceBatches` source over `--samples` synthetic 28 x 28 uint8 images, one iteration per launch:
+
+  A   the parent's loop, ungrouped.  With `--parent-lib PATH` (a libdctn_amd.so built from the parent commit) its graph
+      is captured over that library's kernels; without it A is a second instance of this build's ungrouped loop
+      ("parent_lib": null in the result) - either way A against B shows the run's own noise
+  B   this build, ungrouped: `FlatAdam(lr=...)`
+  C   this build, grouped: `FlatAdam(..., groups=param_groups_for(model, head_lr_scale=0.1))` - the model's three
+      segments (the core, `linear.weight`, `linear.bias`), the head at a tenth of the rate, in the ONE optimizer launch
+  D   the alternative a user has today: one ungrouped `FlatAdam` per group - the core at the rate, the head at a tenth of
+      it - which is k = 2 optimizer launches per iteration
+
+Each variant is timed over `--repeats` blocks of `--steps` iterations with device synchronisation around each block; the
+variants alternate block by block so that clock and thermal drift fall on all alike.  Prints one JSON line: per variant
+the median, min and max of the per-iteration time over the blocks (us) and their spread, and B - A (must sit inside A's
+spread), C - B (the feature's price) and C - D (what one launch buys over k).
+
+    python tools/time_param_groups.py [--steps 10000] [--repeats 5] [--samples 50000] [--variants A,B,C,D]
+                                      [--parent-lib PATH]
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from dctn_amd import _lib as L  # noqa: E402
+from dctn_amd.batches import DeviceBatches  # noqa: E402
+from dctn_amd.eps_plus_linear import EPSesPlusLinear, UnitTheoreticalOutputStd  # noqa: E402
+from dctn_amd.training import FlatAdam, GraphedTrainStep, fused_cross_entropy, param_groups_for  # noqa: E402
+
+SPEC, SIZE, DTYPE, BATCH = ((3, 4),), 28, torch.bfloat16, 1024
+LR, HEAD_SCALE, L2 = 1e-4, 0.1, 1e-4
+
+
+def parent_library(path):
+    """The parent's library bound with the signatures it has (the entry points this build added are not in it)."""
+    handle = ctypes.CDLL(path)
+    for name, (res, args) in L.SIGNATURES.items():
+        fn = getattr(handle, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = res, args
+    return handle
+
+
+class PerGroupAdams:
+    """One ungrouped FlatAdam per group behind the two calls a GraphedTrainStep makes"""
+
+    def __init__(self, optimizers):
+        self.optimizers = optimizers
+
+    def zero_grad(self, set_to_none=True):
+        for opt in self.optimizers:
+            opt.zero_grad(set_to_none)
+
+    def step(self):
+        for opt in self.optimizers:
+            opt.step()
+
+
+def make_variant(name, images, labels, dev, parent):
+    """Returns a callable that runs one launch (one iteration)."""
+    ours = L.lib()
+    if name == "A" and parent is not None:
+        L._lib = parent   # construction, warm-up and capture go through the parent's kernels; replays need no binding
+    try:
+        torch.manual_seed(0)
+        model = EPSesPlusLinear(SPEC, UnitTheoreticalOutputStd(), 1.0, dev, DTYPE, image_size=SIZE)
+        cores, weight, bias = list(model.epses), model.linear.weight, model.linear.bias
+        if name == "D":
+            opt = PerGroupAdams([FlatAdam(cores, [], lr=LR, l2=L2, master_weights=True),
+                                 FlatAdam([weight], [bias], lr=LR * HEAD_SCALE, l2=L2, master_weights=True)])
+        else:
+            groups = param_groups_for(model, head_lr_scale=HEAD_SCALE) if name == "C" else None
+            kw = {} if groups is None else {"groups": groups}   # (the parent's FlatAdam is this build's: same Python)
+            opt = FlatAdam(cores + [weight], [bias], lr=LR, l2=L2, master_weights=True, **kw)
+        src = DeviceBatches(images, labels, BATCH, dtype=DTYPE, seed=2024)
+        return GraphedTrainStep(model, None, None, fused_cross_entropy, opt, warmup=2, batch_source=src)
+    finally:
+        L._lib = ours
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=10000)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--samples", type=int, default=50000)
+    ap.add_argument("--variants", default="A,B,C,D")
+    ap.add_argument("--parent-lib", default=None)
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    g = torch.Generator().manual_seed(1)
+    images = torch.randint(0, 256, (args.samples, SIZE, SIZE), dtype=torch.uint8, generator=g)
+    labels = torch.randint(0, 10, (args.samples,), generator=g)
+    names = args.variants.split(",")
+    parent = parent_library(args.parent_lib) if args.parent_lib else None
+    result = {"workload": "cfg2 bf16 B=1024 FlatAdam(master) graphed, batch source", "samples": args.samples,
+              "steps": args.steps, "repeats": args.repeats, "date": time.strftime("%Y-%m-%d"),
+              "device": torch.cuda.get_device_name(dev), "parent_lib": args.parent_lib,
+              "parent_version": None if parent is None else parent.dctn_version(), "version": L.lib().dctn_version(),
+              "groups": f"3 segments (core, linear.weight, linear.bias), head lr_scale {HEAD_SCALE}; D: 2 FlatAdam instances"}
+    runs = {v: make_variant(v, images, labels, dev, parent) for v in names}
+    times = {v: [] for v in names}
+    for v in names:   # one short untimed block each: clocks, allocator and caches settle before the first timed one
+        for _ in range(min(args.steps, 200)):
+            runs[v]()
+    for r in range(args.repeats):
+        for v in names:   # alternating
+            run = runs[v]
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                run()
+            torch.cuda.synchronize(dev)
+            times[v].append((time.perf_counter() - t0) * 1e6 / args.steps)
+            print(f"repeat {r} {v}: {times[v][-1]:.2f} us/iteration", file=sys.stderr, flush=True)
+    result["variants"] = {v: {"median_us": statistics.median(t), "min_us": min(t), "max_us": max(t),
+                              "spread_us": max(t) - min(t), "blocks_us": [round(b, 2) for b in t]}
+                          for v, t in times.items()}
+    med = {v: result["variants"][v]["median_us"] for v in names}
+    for hi, lo in (("B", "A"), ("C", "B"), ("C", "D")):
+        if hi in med and lo in med:
+            result[f"{hi}_minus_{lo}_us"] = med[hi] - med[lo]
+    if "A" in med:
+        result["A_spread_us"] = result["variants"]["A"]["spread_us"]
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
