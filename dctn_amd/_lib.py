@@ -44,6 +44,16 @@ _I64P = ctypes.POINTER(c_i64)
 _IntP = ctypes.POINTER(c_int)
 _PtrP = ctypes.POINTER(c_void)
 
+
+class FlatStep(ctypes.Structure):
+    """dctn_flat_step_t: every buffer and block of one flat-optimizer step; an option that is off is None (NULL)."""
+    _fields_ = [("params", c_void), ("master", c_void), ("grads", c_void), ("sq_sum", c_void), ("state", c_void),
+                ("guard", c_void), ("schedule", c_void), ("groups", c_void), ("n", c_i64), ("n_reg", c_i64),
+                ("l2", ctypes.c_float), ("dtype", c_int)]
+
+
+_FlatStepP = ctypes.POINTER(FlatStep)
+
 # name -> (restype, argtypes); mirrors include/dctn_amd.h one to one
 SIGNATURES = {
     "dctn_version": (c_int, []),
@@ -101,6 +111,10 @@ SIGNATURES = {
     "dctn_adam_l2_step_grouped": (c_int, [c_void] * 10 + [c_i64, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_float,
                                           ctypes.c_float, c_int, c_void]),
     "dctn_sgd_l2_step_grouped": (c_int, [c_void] * 9 + [c_i64, c_i64, ctypes.c_float, ctypes.c_float, c_int, c_void]),
+    "dctn_flat_step_bytes": (c_size, []),
+    "dctn_adam_flat_step": (c_int, [_FlatStepP, c_void, c_void, ctypes.c_double, ctypes.c_double, ctypes.c_float,
+                                    ctypes.c_float, c_void]),
+    "dctn_sgd_flat_step": (c_int, [_FlatStepP, c_void, ctypes.c_float, ctypes.c_float, c_int, c_void]),
     "dctn_step_trace_head_bytes": (c_size, []),
     "dctn_step_trace_record_bytes": (c_size, []),
     "dctn_step_trace_record": (c_int, [c_void] * 9 + [c_int, c_i64, c_int, c_int, c_void]),

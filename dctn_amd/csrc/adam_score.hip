@@ -17,6 +17,7 @@ namespace {
 
 constexpr long long DCTN_CE_IGNORE = -100;   // torch.nn.functional.cross_entropy's default ignore_index
 
+// (not merged with lr_schedule.h's StepStateBlock: the type is in the mangled name of every adam_l2_k instantiation)
 struct AdamState {   // include/dctn_amd.h documents this layout: it is part of the ABI
   int steps_done;
   float lr;
@@ -72,11 +73,6 @@ __device__ __forceinline__ void store4(bf16_t* p, const float (&x)[4]) {
 // Workgroups of 1024 threads, at most 256 of them: the ticket at the end is one atomic per workgroup on ONE address,
 // and those serialise at about 12 ns each (measured: 1024 workgroups of 256 threads took 17.7 us over 1.9 M
 // parameters where the same stream without a ticket, sgd_l2_k, takes 5.7 us).
-// the guarded step's gradient: one rounded float32 product, never contracted into the FMA that follows
-template <bool GUARD> __device__ __forceinline__ float clipped(float g, float coef) {
-  if constexpr (GUARD) return __fmul_rn(g, coef); else return g;
-}
-
 // GUARD: the step obeys a gradient guard's decision (grad_guard.hip, launched in front of this kernel).  Lane 0 of every
 // workgroup reads `halted` and `coef` from the guard block before anything else.  Halted: the workgroup returns at once
 // - it writes no parameter, master value, moment or sq_sum slot and draws no ticket, so steps_done does not advance.
@@ -358,17 +354,52 @@ unsigned adam_blocks_for(long long n) {   // one vector access of every lane per
   return (unsigned)(b < 1 ? 1 : b);
 }
 
-// the scheduled forms: one launcher for every pack, the vector or the scalar kernel by alignment
-template <typename S, bool MASTER, typename... G>
-void adam_launch_pack(bool vec, dim3 g, dim3 b, hipStream_t st, void* params, void* master, const void* grads,
-                      void* exp_avg, void* exp_avg_sq, void* sq_sum, AdamState* sp, long long n, long long n_reg,
-                      const AdamCoef& k, G... pack) {
-  if (vec)
-    hipLaunchKernelGGL((adam_l2_k<S, true, MASTER, G...>), g, b, 0, st, (S*)params, (float*)master, (const S*)grads,
-                       (float*)exp_avg, (float*)exp_avg_sq, (float*)sq_sum, sp, n, n_reg, k, pack...);
-  else
-    hipLaunchKernelGGL((adam_l2_k<S, false, MASTER, G...>), g, b, 0, st, (S*)params, (float*)master, (const S*)grads,
-                       (float*)exp_avg, (float*)exp_avg_sq, (float*)sq_sum, sp, n, n_reg, k, pack...);
+// One step as the host sees it: the descriptor (include/dctn_amd.h) and what only Adam has
+struct AdamStep {
+  const dctn_flat_step_t& d;
+  void *exp_avg, *exp_avg_sq;
+  AdamCoef k;
+  hipStream_t st;
+};
+
+// The one launcher, for every pack: the vector or the scalar kernel by alignment
+template <typename S, bool MASTER, typename... G> void adam_launch(const AdamStep& a, G... pack) {
+  const dctn_flat_step_t& d = a.d;
+  const size_t esz = sizeof(S);
+  const bool vec = ((uintptr_t)d.params | (uintptr_t)d.grads) % (4 * esz) == 0 &&
+                   ((uintptr_t)a.exp_avg | (uintptr_t)a.exp_avg_sq | (uintptr_t)d.master) % 16 == 0;
+  const auto kernel = vec ? adam_l2_k<S, true, MASTER, G...> : adam_l2_k<S, false, MASTER, G...>;
+  hipLaunchKernelGGL(kernel, dim3(adam_blocks_for(d.n)), dim3(1024), 0, a.st, (S*)d.params, (float*)d.master,
+                     (const S*)d.grads, (float*)a.exp_avg, (float*)a.exp_avg_sq, (float*)d.sq_sum, (AdamState*)d.state,
+                     (long long)d.n, (long long)d.n_reg, a.k, pack...);
+}
+
+// The pack is the optional blocks the step has, in the order adam_l2_k expects: guard, schedule, group table
+template <typename S, bool MASTER> void adam_dispatch(const AdamStep& a) {
+  with_blocks([&](auto... pack) { adam_launch<S, MASTER>(a, pack...); }, (const GradGuardBlock*)a.d.guard,
+              (const LrScheduleBlock*)a.d.schedule, (ParamGroupBlock*)a.d.groups);
+}
+
+// Validates and launches.  master_first: the _scheduled / _grouped entry points answer a master copy beside a dtype
+// that is not bf16 in front of every other check; everywhere else it is part of the dtype check, the last one
+int adam_step(const dctn_flat_step_t& d, void* exp_avg, void* exp_avg_sq, double beta1, double beta2, float eps,
+              float weight_decay, void* stream, bool master_first = false) {
+  const bool master_dtype = d.master && d.dtype != DCTN_BF16;   // a master copy goes with bf16 parameters
+  if (master_first && master_dtype) return DCTN_ERR_BAD_DTYPE;
+  if (!d.params || !d.grads || !exp_avg || !exp_avg_sq || !d.state) return DCTN_ERR_NULL;
+  if (d.n < 1 || d.n_reg < 0 || d.n_reg > d.n) return DCTN_ERR_BAD_SHAPE;
+  if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return DCTN_ERR_BAD_SHAPE;   // torch raises ValueError
+  if ((d.dtype != DCTN_F32 && d.dtype != DCTN_BF16) || master_dtype) return DCTN_ERR_BAD_DTYPE;
+  AdamCoef k;
+  k.b1 = (float)beta1, k.omb1 = (float)(1.0 - beta1), k.b2 = (float)beta2, k.omb2 = (float)(1.0 - beta2);
+  k.ln_b1 = std::log(beta1), k.ln_b2 = std::log(beta2);   // beta = 0: -inf, and 1 - beta^t = -expm1(-inf) = 1
+  k.eps = eps, k.wd = d.groups ? 0.f : weight_decay, k.two_l2 = 2.f * d.l2;   // a table carries every segment's decay
+  const AdamStep a{d, exp_avg, exp_avg_sq, k, (hipStream_t)stream};
+  if (d.master) adam_dispatch<bf16_t, true>(a);
+  else if (d.dtype == DCTN_F32) adam_dispatch<float, false>(a);
+  else adam_dispatch<bf16_t, false>(a);
+  DCTN_CHECK_LAUNCH();
+  return DCTN_OK;
 }
 
 __device__ __forceinline__ float ld_f32(const float* p) { return *p; }
@@ -438,118 +469,47 @@ extern "C" {
 
 size_t dctn_adam_state_bytes(void) { return sizeof(AdamState); }
 
+size_t dctn_flat_step_bytes(void) { return sizeof(dctn_flat_step_t); }
+
 int dctn_adam_l2_num_partials(int64_t n) { return n < 1 ? 0 : (int)adam_blocks_for(n); }
 
-// master == nullptr: the parameters are updated in their own dtype; otherwise they are bf16, written only, and the step
-// runs on the float32 `master`
-// guarded: the step obeys the guard block `guard` (dctn_grad_guard_check ran in front of it on the same stream)
-// scheduled: the rate comes from the schedule block `schedule`, not from state->lr
-static int adam_launch(void* master, void* params, const void* grads, void* exp_avg, void* exp_avg_sq, void* sq_sum,
-                       void* state, int64_t n, int64_t n_reg, double beta1, double beta2, float eps, float weight_decay,
-                       float l2, int dtype, void* stream, bool guarded = false, const void* guard = nullptr,
-                       bool scheduled = false, const void* schedule = nullptr, bool grouped = false,
-                       void* groups = nullptr) {
-  if (!params || !grads || !exp_avg || !exp_avg_sq || !state || (guarded && !guard) || (scheduled && !schedule) ||
-      (grouped && !groups))
-    return DCTN_ERR_NULL;
-  if (n < 1 || n_reg < 0 || n_reg > n) return DCTN_ERR_BAD_SHAPE;
-  if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return DCTN_ERR_BAD_SHAPE;   // torch raises ValueError
-  if (dtype != DCTN_F32 && dtype != DCTN_BF16) return DCTN_ERR_BAD_DTYPE;
-  hipStream_t st = (hipStream_t)stream;
-  AdamCoef k;
-  k.b1 = (float)beta1, k.omb1 = (float)(1.0 - beta1), k.b2 = (float)beta2, k.omb2 = (float)(1.0 - beta2);
-  k.ln_b1 = std::log(beta1), k.ln_b2 = std::log(beta2);   // beta = 0: -inf, and 1 - beta^t = -expm1(-inf) = 1
-  k.eps = eps, k.wd = weight_decay, k.two_l2 = 2.f * l2;
-  const size_t esz = dtype == DCTN_F32 ? 4 : 2;
-  const bool vec = ((uintptr_t)params | (uintptr_t)grads) % (4 * esz) == 0 &&
-                   ((uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)master) % 16 == 0;
-  const dim3 g(adam_blocks_for(n)), b(1024);
-  AdamState* sp = (AdamState*)state;
-#define DCTN_ADAM_LAUNCH(S, VEC, MASTER)                                                                            \
-  hipLaunchKernelGGL((adam_l2_k<S, VEC, MASTER>), g, b, 0, st, (S*)params, (float*)master, (const S*)grads,        \
-                     (float*)exp_avg, (float*)exp_avg_sq, (float*)sq_sum, sp, (long long)n, (long long)n_reg, k)
-#define DCTN_ADAM_LAUNCH_GUARDED(S, VEC, MASTER)                                                                    \
-  hipLaunchKernelGGL((adam_l2_k<S, VEC, MASTER, const GradGuardBlock*>), g, b, 0, st, (S*)params, (float*)master,   \
-                     (const S*)grads, (float*)exp_avg, (float*)exp_avg_sq, (float*)sq_sum, sp, (long long)n,        \
-                     (long long)n_reg, k, (const GradGuardBlock*)guard)
-  if (grouped) {   // every pack that ends with the table: guard and schedule in front of it when they are there
-    const LrScheduleBlock* sched = (const LrScheduleBlock*)schedule;
-    const GradGuardBlock* gp = (const GradGuardBlock*)guard;
-    ParamGroupBlock* pg = (ParamGroupBlock*)groups;
-#define DCTN_ADAM_ARGS vec, g, b, st, params, master, grads, exp_avg, exp_avg_sq, sq_sum, sp, (long long)n, (long long)n_reg, k
-#define DCTN_ADAM_GROUPED(S, MASTER)                                                              \
-  do {                                                                                            \
-    if (guarded && scheduled) adam_launch_pack<S, MASTER>(DCTN_ADAM_ARGS, gp, sched, pg);         \
-    else if (guarded) adam_launch_pack<S, MASTER>(DCTN_ADAM_ARGS, gp, pg);                        \
-    else if (scheduled) adam_launch_pack<S, MASTER>(DCTN_ADAM_ARGS, sched, pg);                   \
-    else adam_launch_pack<S, MASTER>(DCTN_ADAM_ARGS, pg);                                         \
-  } while (0)
-    if (master) DCTN_ADAM_GROUPED(bf16_t, true);
-    else if (dtype == DCTN_F32) DCTN_ADAM_GROUPED(float, false);
-    else DCTN_ADAM_GROUPED(bf16_t, false);
-#undef DCTN_ADAM_GROUPED
-#undef DCTN_ADAM_ARGS
-  } else if (scheduled) {
-    const LrScheduleBlock* sched = (const LrScheduleBlock*)schedule;
-    const GradGuardBlock* gp = (const GradGuardBlock*)guard;
-#define DCTN_ADAM_ARGS vec, g, b, st, params, master, grads, exp_avg, exp_avg_sq, sq_sum, sp, (long long)n, (long long)n_reg, k
-    if (master) {
-      if (guarded) adam_launch_pack<bf16_t, true>(DCTN_ADAM_ARGS, gp, sched); else adam_launch_pack<bf16_t, true>(DCTN_ADAM_ARGS, sched);
-    } else if (dtype == DCTN_F32) {
-      if (guarded) adam_launch_pack<float, false>(DCTN_ADAM_ARGS, gp, sched); else adam_launch_pack<float, false>(DCTN_ADAM_ARGS, sched);
-    } else {
-      if (guarded) adam_launch_pack<bf16_t, false>(DCTN_ADAM_ARGS, gp, sched); else adam_launch_pack<bf16_t, false>(DCTN_ADAM_ARGS, sched);
-    }
-#undef DCTN_ADAM_ARGS
-  } else if (guarded) {
-    if (master) {
-      if (vec) DCTN_ADAM_LAUNCH_GUARDED(bf16_t, true, true); else DCTN_ADAM_LAUNCH_GUARDED(bf16_t, false, true);
-    } else if (dtype == DCTN_F32) {
-      if (vec) DCTN_ADAM_LAUNCH_GUARDED(float, true, false); else DCTN_ADAM_LAUNCH_GUARDED(float, false, false);
-    } else {
-      if (vec) DCTN_ADAM_LAUNCH_GUARDED(bf16_t, true, false); else DCTN_ADAM_LAUNCH_GUARDED(bf16_t, false, false);
-    }
-  } else if (master) {
-    if (vec) DCTN_ADAM_LAUNCH(bf16_t, true, true); else DCTN_ADAM_LAUNCH(bf16_t, false, true);
-  } else if (dtype == DCTN_F32) {
-    if (vec) DCTN_ADAM_LAUNCH(float, true, false); else DCTN_ADAM_LAUNCH(float, false, false);
-  } else {
-    if (vec) DCTN_ADAM_LAUNCH(bf16_t, true, false); else DCTN_ADAM_LAUNCH(bf16_t, false, false);
-  }
-#undef DCTN_ADAM_LAUNCH
-#undef DCTN_ADAM_LAUNCH_GUARDED
-  DCTN_CHECK_LAUNCH();
-  return DCTN_OK;
+int dctn_adam_flat_step(const dctn_flat_step_t* step, void* exp_avg, void* exp_avg_sq, double beta1, double beta2,
+                        float eps, float weight_decay, void* stream) {
+  if (!step) return DCTN_ERR_NULL;
+  return adam_step(*step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, stream);
 }
 
+// The six entry points older than the descriptor: each fills one and takes adam_step.  An entry point that requires a
+// block answers its null pointer itself (in front of the master / dtype check of the _scheduled / _grouped forms)
 int dctn_adam_l2_step(void* params, const void* grads, void* exp_avg, void* exp_avg_sq, void* sq_sum, void* state,
                       int64_t n, int64_t n_reg, double beta1, double beta2, float eps, float weight_decay, float l2,
                       int dtype, void* stream) {
-  return adam_launch(nullptr, params, grads, exp_avg, exp_avg_sq, sq_sum, state, n, n_reg, beta1, beta2, eps,
-                     weight_decay, l2, dtype, stream);
+  const dctn_flat_step_t d = {params, nullptr, grads, sq_sum, state, nullptr, nullptr, nullptr, n, n_reg, l2, dtype};
+  return adam_step(d, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, stream);
 }
 
 int dctn_adam_l2_step_master(void* master, void* params, const void* grads, void* exp_avg, void* exp_avg_sq,
                              void* sq_sum, void* state, int64_t n, int64_t n_reg, double beta1, double beta2, float eps,
                              float weight_decay, float l2, void* stream) {
   if (!master) return DCTN_ERR_NULL;
-  return adam_launch(master, params, grads, exp_avg, exp_avg_sq, sq_sum, state, n, n_reg, beta1, beta2, eps,
-                     weight_decay, l2, DCTN_BF16, stream);
+  const dctn_flat_step_t d = {params, master, grads, sq_sum, state, nullptr, nullptr, nullptr, n, n_reg, l2, DCTN_BF16};
+  return adam_step(d, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, stream);
 }
 
 int dctn_adam_l2_step_guarded(void* params, const void* grads, void* exp_avg, void* exp_avg_sq, void* sq_sum, void* state,
                               const void* guard, int64_t n, int64_t n_reg, double beta1, double beta2, float eps,
                               float weight_decay, float l2, int dtype, void* stream) {
-  return adam_launch(nullptr, params, grads, exp_avg, exp_avg_sq, sq_sum, state, n, n_reg, beta1, beta2, eps,
-                     weight_decay, l2, dtype, stream, true, guard);
+  if (!guard) return DCTN_ERR_NULL;
+  const dctn_flat_step_t d = {params, nullptr, grads, sq_sum, state, guard, nullptr, nullptr, n, n_reg, l2, dtype};
+  return adam_step(d, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, stream);
 }
 
 int dctn_adam_l2_step_master_guarded(void* master, void* params, const void* grads, void* exp_avg, void* exp_avg_sq,
                                      void* sq_sum, void* state, const void* guard, int64_t n, int64_t n_reg,
                                      double beta1, double beta2, float eps, float weight_decay, float l2, void* stream) {
-  if (!master) return DCTN_ERR_NULL;
-  return adam_launch(master, params, grads, exp_avg, exp_avg_sq, sq_sum, state, n, n_reg, beta1, beta2, eps,
-                     weight_decay, l2, DCTN_BF16, stream, true, guard);
+  if (!master || !guard) return DCTN_ERR_NULL;
+  const dctn_flat_step_t d = {params, master, grads, sq_sum, state, guard, nullptr, nullptr, n, n_reg, l2, DCTN_BF16};
+  return adam_step(d, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, stream);
 }
 
 int dctn_adam_l2_step_scheduled(void* master_or_null, void* params, const void* grads, void* exp_avg, void* exp_avg_sq,
@@ -557,9 +517,9 @@ int dctn_adam_l2_step_scheduled(void* master_or_null, void* params, const void* 
                                 int64_t n_reg, double beta1, double beta2, float eps, float weight_decay, float l2,
                                 int dtype, void* stream) {
   if (!schedule) return DCTN_ERR_NULL;
-  if (master_or_null && dtype != DCTN_BF16) return DCTN_ERR_BAD_DTYPE;   // a master copy goes with bf16 parameters
-  return adam_launch(master_or_null, params, grads, exp_avg, exp_avg_sq, sq_sum, state, n, n_reg, beta1, beta2, eps,
-                     weight_decay, l2, dtype, stream, guard_or_null != nullptr, guard_or_null, true, schedule);
+  const dctn_flat_step_t d = {params, master_or_null, grads, sq_sum, state, guard_or_null, schedule, nullptr,
+                              n, n_reg, l2, dtype};
+  return adam_step(d, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, stream, true);
 }
 
 // The table carries every segment's weight decay: the launch has no weight_decay argument
@@ -568,10 +528,9 @@ int dctn_adam_l2_step_grouped(void* master_or_null, void* params, const void* gr
                               void* groups, int64_t n, int64_t n_reg, double beta1, double beta2, float eps, float l2,
                               int dtype, void* stream) {
   if (!groups) return DCTN_ERR_NULL;
-  if (master_or_null && dtype != DCTN_BF16) return DCTN_ERR_BAD_DTYPE;   // a master copy goes with bf16 parameters
-  return adam_launch(master_or_null, params, grads, exp_avg, exp_avg_sq, sq_sum, state, n, n_reg, beta1, beta2, eps, 0.f,
-                     l2, dtype, stream, guard_or_null != nullptr, guard_or_null, schedule_or_null != nullptr,
-                     schedule_or_null, true, groups);
+  const dctn_flat_step_t d = {params, master_or_null, grads, sq_sum, state, guard_or_null, schedule_or_null, groups,
+                              n, n_reg, l2, dtype};
+  return adam_step(d, exp_avg, exp_avg_sq, beta1, beta2, eps, 0.f, stream, true);
 }
 
 size_t dctn_param_groups_bytes(void) { return sizeof(ParamGroupBlock); }

@@ -2,6 +2,8 @@
 // writes it; the guarded forms of adam_l2_k (adam_score.hip) and sgd_l2_k (train_tail.hip) read `halted` and `coef`.
 #pragma once
 
+#include "step_pack.h"
+
 struct GradGuardBlock {
   float max_norm;     // clip threshold, +inf = never clip; the host writes it
   float last_norm;    // norm seen by the last launch (may be inf / NaN)
@@ -13,3 +15,10 @@ struct GradGuardBlock {
   float coef;         // decision for the step that follows: the gradient multiplier (0 when the step is not applied)
 };
 static_assert(sizeof(GradGuardBlock) == 32, "the guard block is 32 bytes (include/dctn_amd.h)");
+
+#if defined(__HIPCC__)
+// the guarded step's gradient: one rounded float32 product, never contracted into the FMA that follows
+template <bool GUARD> __device__ __forceinline__ float clipped(float g, float coef) {
+  if constexpr (GUARD) return __fmul_rn(g, coef); else return g;
+}
+#endif

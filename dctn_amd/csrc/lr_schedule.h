@@ -5,7 +5,8 @@
 #pragma once
 
 #include <cstdint>
-#include <type_traits>
+
+#include "step_pack.h"
 
 constexpr int DCTN_LR_MAX_KNOTS = 64;   // one knot per lane of a wave
 
@@ -20,6 +21,7 @@ struct LrScheduleBlock {
 static_assert(sizeof(LrScheduleBlock) == 784, "the schedule block is 784 bytes (include/dctn_amd.h)");
 
 // The 16-byte step block of a scheduled sgd_l2_k: adam_l2_k's AdamState, field for field
+// (two types on purpose: merging them changes the mangled names of every adam_l2_k and sgd_l2_k instantiation)
 struct StepStateBlock {
   int steps_done;
   float lr;
@@ -53,13 +55,6 @@ inline float lr_schedule_value_host(const LrScheduleBlock& b, long long s) {
 }
 
 #if defined(__HIPCC__)
-// Members of a kernel's trailing parameter pack by type: whether one is there, and its value
-template <typename T, typename... G> constexpr bool pack_has_v = (std::is_same_v<T, G> || ...);
-template <typename T, typename First, typename... Rest>
-__device__ __forceinline__ T pack_get(First first, Rest... rest) {
-  if constexpr (std::is_same_v<T, First>) return first; else return pack_get<T>(rest...);
-}
-
 // What one lane of wave 0 holds of the block: its own knot and the two header words.  Every load is unconditional and
 // independent of every other (the block is always 784 bytes), so they go out together with the caller's load of
 // steps_done; a lane at or past n_knots never counts as reached, whatever its slot holds.

@@ -23,6 +23,8 @@
 
 #include <cstdint>
 
+#include "step_pack.h"
+
 constexpr int DCTN_PG_MAX_SEGMENTS = 64;   // one segment per lane of a wave, as the schedule's knots
 constexpr unsigned DCTN_PG_FROZEN = 1u;
 

@@ -115,11 +115,6 @@ __device__ __forceinline__ float sgd_elem(float wi, float gi, float* __restrict_
 
 // MASTER (S = bf16_t): the weight comes from and goes back to the float32 array `wm`; `w` gets its bf16 rounding and is
 // not read, and `wm` and the sq_sum slots are the float instantiation's bits.  Without MASTER `wm` is unused (null).
-// the guarded step's gradient: one rounded float32 product, never contracted into the FMA that follows
-template <bool GUARD> __device__ __forceinline__ float clipped(float g, float coef) {
-  if constexpr (GUARD) return __fmul_rn(g, coef); else return g;
-}
-
 // GUARD: the step obeys a gradient guard's decision (grad_guard.hip, launched in front of this kernel), as
 // adam_l2_k's guarded form does: lane 0 of every workgroup reads `halted` and `coef` before anything else; halted, the
 // workgroup returns at once and writes no parameter, master value, momentum or sq_sum slot; otherwise every gradient is
@@ -320,13 +315,47 @@ unsigned blocks_for(long long n) {
   return (unsigned)(b < 1 ? 1 : b);
 }
 
-// the scheduled forms: rate and first_step come from the device (the launch arguments are zeros)
-template <typename S, bool MASTER, typename... G>
-void sgd_launch_pack(dim3 g, dim3 b, hipStream_t st, void* params, void* master, const void* grads,
-                            void* momentum_buf, void* sq_sum, long long n, long long n_reg, float momentum, float l2,
-                            G... pack) {
-  hipLaunchKernelGGL((sgd_l2_k<S, MASTER, G...>), g, b, 0, st, (S*)params, (float*)master, (const S*)grads,
-                     (float*)momentum_buf, (float*)sq_sum, n, n_reg, 0.f, momentum, l2, 0, pack...);
+// One step as the host sees it: the descriptor (include/dctn_amd.h) and what only SGD has
+struct SgdStep {
+  const dctn_flat_step_t& d;
+  void* momentum_buf;
+  float lr, momentum;
+  int first_step;
+  hipStream_t st;
+};
+
+// The one launcher.  sgd_l2_k is built for the packs that hold the step block exactly when they hold a schedule or a
+// group table; sgd_step hands the block over in no other case, so the packs left out are never asked for.
+template <typename S, bool MASTER, typename... G> void sgd_launch(const SgdStep& a, G... pack) {
+  if constexpr (pack_has_v<StepStateBlock*, G...> ==
+                (pack_has_v<const LrScheduleBlock*, G...> || pack_has_v<ParamGroupBlock*, G...>)) {
+    const dctn_flat_step_t& d = a.d;
+    hipLaunchKernelGGL((sgd_l2_k<S, MASTER, G...>), dim3(blocks_for(d.n)), dim3(256), 0, a.st, (S*)d.params,
+                       (float*)d.master, (const S*)d.grads, (float*)a.momentum_buf, (float*)d.sq_sum, (long long)d.n,
+                       (long long)d.n_reg, a.lr, a.momentum, d.l2, a.first_step, pack...);
+  }
+}
+
+// The pack is the optional blocks the step has, in the order sgd_l2_k expects: guard, step state, schedule, group table
+template <typename S, bool MASTER> void sgd_dispatch(const SgdStep& a, StepStateBlock* state) {
+  with_blocks([&](auto... pack) { sgd_launch<S, MASTER>(a, pack...); }, (const GradGuardBlock*)a.d.guard, state,
+              (const LrScheduleBlock*)a.d.schedule, (ParamGroupBlock*)a.d.groups);
+}
+
+// Validates and launches.  With a schedule or a group table the rate and first_step come from the step block on the
+// device: the block is required, and the two launch arguments are zeros whatever the caller passed.
+int sgd_step(const dctn_flat_step_t& d, void* momentum_buf, float lr, float momentum, int first_step, void* stream) {
+  const bool on_device = d.schedule || d.groups;
+  if (!d.params || !d.grads || !momentum_buf || (on_device && !d.state)) return DCTN_ERR_NULL;
+  if (d.n < 1 || d.n_reg < 0 || d.n_reg > d.n) return DCTN_ERR_BAD_SHAPE;
+  if ((d.dtype != DCTN_F32 && d.dtype != DCTN_BF16) || (d.master && d.dtype != DCTN_BF16)) return DCTN_ERR_BAD_DTYPE;
+  const SgdStep a{d, momentum_buf, on_device ? 0.f : lr, momentum, on_device ? 0 : first_step, (hipStream_t)stream};
+  StepStateBlock* state = on_device ? (StepStateBlock*)d.state : nullptr;
+  if (d.master) sgd_dispatch<bf16_t, true>(a, state);
+  else if (d.dtype == DCTN_F32) sgd_dispatch<float, false>(a, state);
+  else sgd_dispatch<bf16_t, false>(a, state);
+  DCTN_CHECK_LAUNCH();
+  return DCTN_OK;
 }
 
 }  // namespace
@@ -383,111 +412,60 @@ int dctn_ce_loss_bwd(const void* logits, const void* labels, const void* dloss, 
 
 int dctn_sgd_l2_num_partials(int64_t n) { return n < 1 ? 0 : (int)blocks_for(n); }
 
-// master == nullptr: the parameters are updated in their own dtype; otherwise they are bf16, written only
-// guarded: the step obeys the guard block `guard` (dctn_grad_guard_check ran in front of it on the same stream)
-static int sgd_launch(void* master, void* params, const void* grads, void* momentum_buf, void* sq_sum, int64_t n,
-                      int64_t n_reg, float lr, float momentum, float l2, int first_step, int dtype, void* stream,
-                      bool guarded = false, const void* guard = nullptr) {
-  if (!params || !grads || !momentum_buf || (guarded && !guard)) return DCTN_ERR_NULL;
-  if (n < 1 || n_reg < 0 || n_reg > n) return DCTN_ERR_BAD_SHAPE;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype != DCTN_F32 && dtype != DCTN_BF16) return DCTN_ERR_BAD_DTYPE;
-  const dim3 g(blocks_for(n)), b(256);
-  const GradGuardBlock* gp = (const GradGuardBlock*)guard;
-  if (guarded && master)
-    hipLaunchKernelGGL((sgd_l2_k<bf16_t, true, const GradGuardBlock*>), g, b, 0, st, (bf16_t*)params, (float*)master, (const bf16_t*)grads, (float*)momentum_buf, (float*)sq_sum, (long long)n, (long long)n_reg, lr, momentum, l2, first_step, gp);
-  else if (guarded && dtype == DCTN_F32)
-    hipLaunchKernelGGL((sgd_l2_k<float, false, const GradGuardBlock*>), g, b, 0, st, (float*)params, (float*)nullptr, (const float*)grads, (float*)momentum_buf, (float*)sq_sum, (long long)n, (long long)n_reg, lr, momentum, l2, first_step, gp);
-  else if (guarded)
-    hipLaunchKernelGGL((sgd_l2_k<bf16_t, false, const GradGuardBlock*>), g, b, 0, st, (bf16_t*)params, (float*)nullptr, (const bf16_t*)grads, (float*)momentum_buf, (float*)sq_sum, (long long)n, (long long)n_reg, lr, momentum, l2, first_step, gp);
-  else if (master)
-    hipLaunchKernelGGL((sgd_l2_k<bf16_t, true>), g, b, 0, st, (bf16_t*)params, (float*)master, (const bf16_t*)grads, (float*)momentum_buf, (float*)sq_sum, (long long)n, (long long)n_reg, lr, momentum, l2, first_step);
-  else if (dtype == DCTN_F32)
-    hipLaunchKernelGGL((sgd_l2_k<float, false>), g, b, 0, st, (float*)params, (float*)nullptr, (const float*)grads, (float*)momentum_buf, (float*)sq_sum, (long long)n, (long long)n_reg, lr, momentum, l2, first_step);
-  else
-    hipLaunchKernelGGL((sgd_l2_k<bf16_t, false>), g, b, 0, st, (bf16_t*)params, (float*)nullptr, (const bf16_t*)grads, (float*)momentum_buf, (float*)sq_sum, (long long)n, (long long)n_reg, lr, momentum, l2, first_step);
-  DCTN_CHECK_LAUNCH();
-  return DCTN_OK;
+int dctn_sgd_flat_step(const dctn_flat_step_t* step, void* momentum_buf, float lr, float momentum, int first_step,
+                       void* stream) {
+  if (!step) return DCTN_ERR_NULL;
+  return sgd_step(*step, momentum_buf, lr, momentum, first_step, stream);
+}
+
+// The six entry points older than the descriptor: each fills one and takes sgd_step.  An entry point that requires a
+// block answers its null pointer itself; the _scheduled / _grouped forms have no lr and first_step to pass
+int dctn_sgd_l2_step(void* params, const void* grads, void* momentum_buf, void* sq_sum, int64_t n, int64_t n_reg,
+                     float lr, float momentum, float l2, int first_step, int dtype, void* stream) {
+  const dctn_flat_step_t d = {params, nullptr, grads, sq_sum, nullptr, nullptr, nullptr, nullptr, n, n_reg, l2, dtype};
+  return sgd_step(d, momentum_buf, lr, momentum, first_step, stream);
+}
+
+int dctn_sgd_l2_step_master(void* master, void* params, const void* grads, void* momentum_buf, void* sq_sum,
+                            int64_t n, int64_t n_reg, float lr, float momentum, float l2, int first_step, void* stream) {
+  if (!master) return DCTN_ERR_NULL;
+  const dctn_flat_step_t d = {params, master, grads, sq_sum, nullptr, nullptr, nullptr, nullptr, n, n_reg, l2, DCTN_BF16};
+  return sgd_step(d, momentum_buf, lr, momentum, first_step, stream);
+}
+
+int dctn_sgd_l2_step_guarded(void* params, const void* grads, void* momentum_buf, void* sq_sum, const void* guard,
+                             int64_t n, int64_t n_reg, float lr, float momentum, float l2, int first_step, int dtype,
+                             void* stream) {
+  if (!guard) return DCTN_ERR_NULL;
+  const dctn_flat_step_t d = {params, nullptr, grads, sq_sum, nullptr, guard, nullptr, nullptr, n, n_reg, l2, dtype};
+  return sgd_step(d, momentum_buf, lr, momentum, first_step, stream);
+}
+
+int dctn_sgd_l2_step_master_guarded(void* master, void* params, const void* grads, void* momentum_buf, void* sq_sum,
+                                    const void* guard, int64_t n, int64_t n_reg, float lr, float momentum, float l2,
+                                    int first_step, void* stream) {
+  if (!master || !guard) return DCTN_ERR_NULL;
+  const dctn_flat_step_t d = {params, master, grads, sq_sum, nullptr, guard, nullptr, nullptr, n, n_reg, l2, DCTN_BF16};
+  return sgd_step(d, momentum_buf, lr, momentum, first_step, stream);
 }
 
 int dctn_sgd_l2_step_scheduled(void* master_or_null, void* params, const void* grads, void* momentum_buf, void* sq_sum,
                                void* state, const void* guard_or_null, const void* schedule, int64_t n, int64_t n_reg,
                                float momentum, float l2, int dtype, void* stream) {
-  if (!params || !grads || !momentum_buf || !state || !schedule) return DCTN_ERR_NULL;
-  if (n < 1 || n_reg < 0 || n_reg > n) return DCTN_ERR_BAD_SHAPE;
-  if ((dtype != DCTN_F32 && dtype != DCTN_BF16) || (master_or_null && dtype != DCTN_BF16)) return DCTN_ERR_BAD_DTYPE;
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 g(blocks_for(n)), b(256);
-  const GradGuardBlock* gp = (const GradGuardBlock*)guard_or_null;
-  StepStateBlock* sp = (StepStateBlock*)state;
-  const LrScheduleBlock* sched = (const LrScheduleBlock*)schedule;
-#define DCTN_SGD_ARGS g, b, st, params, master_or_null, grads, momentum_buf, sq_sum, (long long)n, (long long)n_reg, momentum, l2
-  if (master_or_null) {
-    if (gp) sgd_launch_pack<bf16_t, true>(DCTN_SGD_ARGS, gp, sp, sched); else sgd_launch_pack<bf16_t, true>(DCTN_SGD_ARGS, sp, sched);
-  } else if (dtype == DCTN_F32) {
-    if (gp) sgd_launch_pack<float, false>(DCTN_SGD_ARGS, gp, sp, sched); else sgd_launch_pack<float, false>(DCTN_SGD_ARGS, sp, sched);
-  } else {
-    if (gp) sgd_launch_pack<bf16_t, false>(DCTN_SGD_ARGS, gp, sp, sched); else sgd_launch_pack<bf16_t, false>(DCTN_SGD_ARGS, sp, sched);
-  }
-#undef DCTN_SGD_ARGS
-  DCTN_CHECK_LAUNCH();
-  return DCTN_OK;
+  if (!schedule) return DCTN_ERR_NULL;
+  const dctn_flat_step_t d = {params, master_or_null, grads, sq_sum, state, guard_or_null, schedule, nullptr,
+                              n, n_reg, l2, dtype};
+  return sgd_step(d, momentum_buf, 0.f, momentum, 0, stream);
 }
 
 // The grouped form always takes the 16-byte step block: without a schedule the rate is state->lr, as adam_l2_k's
 int dctn_sgd_l2_step_grouped(void* master_or_null, void* params, const void* grads, void* momentum_buf, void* sq_sum,
                              void* state, const void* guard_or_null, const void* schedule_or_null, void* groups,
                              int64_t n, int64_t n_reg, float momentum, float l2, int dtype, void* stream) {
-  if (!params || !grads || !momentum_buf || !state || !groups) return DCTN_ERR_NULL;
-  if (n < 1 || n_reg < 0 || n_reg > n) return DCTN_ERR_BAD_SHAPE;
-  if ((dtype != DCTN_F32 && dtype != DCTN_BF16) || (master_or_null && dtype != DCTN_BF16)) return DCTN_ERR_BAD_DTYPE;
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 g(blocks_for(n)), b(256);
-  const GradGuardBlock* gp = (const GradGuardBlock*)guard_or_null;
-  StepStateBlock* sp = (StepStateBlock*)state;
-  const LrScheduleBlock* sched = (const LrScheduleBlock*)schedule_or_null;
-  ParamGroupBlock* pg = (ParamGroupBlock*)groups;
-#define DCTN_SGD_ARGS g, b, st, params, master_or_null, grads, momentum_buf, sq_sum, (long long)n, (long long)n_reg, momentum, l2
-#define DCTN_SGD_GROUPED(S, MASTER)                                                       \
-  do {                                                                                    \
-    if (gp && sched) sgd_launch_pack<S, MASTER>(DCTN_SGD_ARGS, gp, sp, sched, pg);        \
-    else if (gp) sgd_launch_pack<S, MASTER>(DCTN_SGD_ARGS, gp, sp, pg);                   \
-    else if (sched) sgd_launch_pack<S, MASTER>(DCTN_SGD_ARGS, sp, sched, pg);             \
-    else sgd_launch_pack<S, MASTER>(DCTN_SGD_ARGS, sp, pg);                               \
-  } while (0)
-  if (master_or_null) DCTN_SGD_GROUPED(bf16_t, true);
-  else if (dtype == DCTN_F32) DCTN_SGD_GROUPED(float, false);
-  else DCTN_SGD_GROUPED(bf16_t, false);
-#undef DCTN_SGD_GROUPED
-#undef DCTN_SGD_ARGS
-  DCTN_CHECK_LAUNCH();
-  return DCTN_OK;
-}
-
-int dctn_sgd_l2_step(void* params, const void* grads, void* momentum_buf, void* sq_sum, int64_t n, int64_t n_reg,
-                     float lr, float momentum, float l2, int first_step, int dtype, void* stream) {
-  return sgd_launch(nullptr, params, grads, momentum_buf, sq_sum, n, n_reg, lr, momentum, l2, first_step, dtype, stream);
-}
-
-int dctn_sgd_l2_step_master(void* master, void* params, const void* grads, void* momentum_buf, void* sq_sum,
-                            int64_t n, int64_t n_reg, float lr, float momentum, float l2, int first_step, void* stream) {
-  if (!master) return DCTN_ERR_NULL;
-  return sgd_launch(master, params, grads, momentum_buf, sq_sum, n, n_reg, lr, momentum, l2, first_step, DCTN_BF16, stream);
-}
-
-int dctn_sgd_l2_step_guarded(void* params, const void* grads, void* momentum_buf, void* sq_sum, const void* guard,
-                             int64_t n, int64_t n_reg, float lr, float momentum, float l2, int first_step, int dtype,
-                             void* stream) {
-  return sgd_launch(nullptr, params, grads, momentum_buf, sq_sum, n, n_reg, lr, momentum, l2, first_step, dtype, stream,
-                    true, guard);
-}
-
-int dctn_sgd_l2_step_master_guarded(void* master, void* params, const void* grads, void* momentum_buf, void* sq_sum,
-                                    const void* guard, int64_t n, int64_t n_reg, float lr, float momentum, float l2,
-                                    int first_step, void* stream) {
-  if (!master) return DCTN_ERR_NULL;
-  return sgd_launch(master, params, grads, momentum_buf, sq_sum, n, n_reg, lr, momentum, l2, first_step, DCTN_BF16,
-                    stream, true, guard);
+  if (!groups) return DCTN_ERR_NULL;
+  const dctn_flat_step_t d = {params, master_or_null, grads, sq_sum, state, guard_or_null, schedule_or_null, groups,
+                              n, n_reg, l2, dtype};
+  return sgd_step(d, momentum_buf, 0.f, momentum, 0, stream);
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@ and only rank 0 touches checkpoint files.
 """
 from __future__ import annotations
 
+import ctypes
 import os
 from collections import deque
 from logging import getLogger
@@ -1150,11 +1151,33 @@ class _FlatOptimizer:
                   out=self.flat_grad)
         return self.flat_grad
 
-    def _run_guard(self, g: Tensor) -> int:
-        """Launches the guard's check over the gradients; returns the block's address for the guarded step."""
-        loss = self.guard_loss() if callable(self.guard_loss) else self.guard_loss
-        self.guard.check(g, loss)
-        return self.guard._block.data_ptr()
+    def _describe(self, what: str) -> None:
+        """Builds the step's descriptor (dctn_flat_step_t, include/dctn_amd.h) once, when the subclass has allocated its
+        buffers: every pointer in it - ``flat``, ``master``, ``sq_sum``, the step block, the guard, schedule and group
+        blocks - is stable for the optimizer's life.  An option that is off is NULL.  ``what`` names the call, with the
+        active options, in the message of a failed check."""
+        assert L.lib().dctn_flat_step_bytes() == ctypes.sizeof(L.FlatStep)
+        blocks = {"master weights": self.master, "guard": None if self.guard is None else self.guard._block,
+                  "schedule": None if self.schedule is None else self.schedule._block,
+                  "groups": None if self.groups is None else self.groups._block}
+        ptr = {name: None if t is None else t.data_ptr() for name, t in blocks.items()}
+        self._desc = L.FlatStep(params=self.flat.data_ptr(), master=ptr["master weights"], grads=None,
+                                sq_sum=self.sq_sum.data_ptr(),
+                                state=None if self._state is None else self._state.data_ptr(), guard=ptr["guard"],
+                                schedule=ptr["schedule"], groups=ptr["groups"], n=self.n, n_reg=self.n_reg, l2=self.l2,
+                                dtype=L.dtype_code(self.flat))
+        self._desc_ref = ctypes.byref(self._desc)
+        on = [name for name, p in ptr.items() if p is not None]
+        self._what = what + (f" ({', '.join(on)})" if on else "")
+
+    def _begin_step(self) -> None:
+        """What changes from one step to the next goes into the descriptor - where the gradients lie, and ``n_reg`` and
+        ``l2``, plain attributes a caller may have assigned - and the guard's check is launched in front of the step."""
+        g = self._grads()
+        d = self._desc
+        d.grads, d.n_reg, d.l2 = g.data_ptr(), self.n_reg, self.l2
+        if self.guard is not None:
+            self.guard.check(g, self.guard_loss() if callable(self.guard_loss) else self.guard_loss)
 
     def _put_step_block(self, steps: int) -> None:
         """Writes the 16-byte step block of a scheduled optimizer: ``steps`` taken, the rate of the last of them."""
@@ -1174,7 +1197,9 @@ class _FlatOptimizer:
 
 class FlatSGD(_FlatOptimizer):
     """SGD with momentum plus the reference's L2 regulariser, as ONE kernel per step over one flat
-    parameter buffer (`dctn_sgd_l2_step`).
+    parameter buffer.  ``step()`` makes one library call whatever the options, `dctn_sgd_flat_step` with a descriptor of
+    the step built at construction; alone it launches the kernel of `dctn_sgd_l2_step`, and each option below names the
+    older entry point that launches the same kernel as that option does here.
 
     ``regularised``: the parameters whose squared Frobenius norms the regulariser sums (for
     EPSesPlusLinear.epswise_l2_regularizer: every core and ``linear.weight``,
@@ -1187,16 +1212,16 @@ class FlatSGD(_FlatOptimizer):
     otherwise they are gathered first.  Semantics of torch.optim.SGD(momentum, dampening = 0).
 
     ``master_weights=True``: bfloat16 parameters get a float32 master copy that the kernel updates
-    (`dctn_sgd_l2_step_master`); an update below half an ulp of the bfloat16 value is then kept instead of rounded
+    (the kernel of `dctn_sgd_l2_step_master`); an update below half an ulp of the bfloat16 value is then kept instead of rounded
     away.  ``state_dict()`` / ``load_state_dict()`` carry the momentum buffer, the step count, the hyper-parameters
     and the master copy.
 
     ``guard`` (a `GradGuard`) / ``guard_loss``: ``step()`` launches the guard's check and then the guarded kernel
-    (`dctn_sgd_l2_step_guarded`): gradients clipped to ``guard.max_norm`` in front of the ``2 * l2 * w`` term, and no
+    (that of `dctn_sgd_l2_step_guarded`): gradients clipped to ``guard.max_norm`` in front of the ``2 * l2 * w`` term, and no
     write at all once the guard has halted.  Without a guard ``step()`` makes the calls it always made.
 
-    ``schedule`` (an `LRSchedule`): ``step()`` launches `dctn_sgd_l2_step_scheduled` (behind the guard's check when there
-    is a guard).  The optimizer then owns a 16-byte DEVICE block {steps_done, lr, ticket, reserved} - `FlatAdam`'s - that
+    ``schedule`` (an `LRSchedule`): ``step()`` launches the kernel of `dctn_sgd_l2_step_scheduled` (behind the guard's check
+    when there is a guard).  The optimizer then owns a 16-byte DEVICE block {steps_done, lr, ticket, reserved} - `FlatAdam`'s - that
     the launch advances: the rate is the schedule's value at ``steps_done`` and the first step is ``steps_done == 0``,
     both read on the device, so a captured step changes its rate from replay to replay (without a schedule a captured
     step replays the ``lr`` and ``first_step`` it was captured with).  ``opt.lr`` returns ``schedule.value(opt.t)``;
@@ -1205,8 +1230,8 @@ class FlatSGD(_FlatOptimizer):
     replays.  ``opt.t`` and ``state_dict()["steps"]`` are read from the block.  Without a schedule ``step()`` makes
     the calls it always made.
 
-    ``groups`` (a `ParamGroups` over exactly these parameters): ``step()`` launches `dctn_sgd_l2_step_grouped` (behind
-    the guard's check when there is a guard): every parameter steps with ``rate * lr_scale`` of its segment, takes its
+    ``groups`` (a `ParamGroups` over exactly these parameters): ``step()`` launches the kernel of
+    `dctn_sgd_l2_step_grouped` (behind the guard's check when there is a guard): every parameter steps with ``rate * lr_scale`` of its segment, takes its
     first step when ITS count is 0, and is left alone while frozen.  The optimizer then owns the 16-byte step block
     whether or not there is a schedule: without one ``opt.lr = x`` writes the block's rate cell (not during a capture),
     and a captured step follows it.  ``opt.t`` stays the global count.  A `ParamGroup` for this optimizer leaves
@@ -1234,6 +1259,7 @@ class FlatSGD(_FlatOptimizer):
                 assert L.lib().dctn_adam_state_bytes() == 16
                 self._state = torch.zeros(4, dtype=torch.int32, device=self.flat.device)
                 self._put_step_block(0)
+        self._describe("fused SGD step")
 
     @property
     def lr(self) -> float:
@@ -1266,57 +1292,13 @@ class FlatSGD(_FlatOptimizer):
 
     @torch.no_grad()
     def step(self) -> None:
-        g = self._grads()
-        dev = self.flat.device
-        if self.groups is not None:
-            block = self._run_guard(g) if self.guard is not None else None
-            L.check(L.lib().dctn_sgd_l2_step_grouped(None if self.master is None else self.master.data_ptr(),
-                                                     self.flat.data_ptr(), g.data_ptr(), self.buf.data_ptr(),
-                                                     self.sq_sum.data_ptr(), self._state.data_ptr(), block,
-                                                     None if self.schedule is None else self.schedule._block.data_ptr(),
-                                                     self.groups._block.data_ptr(), self.n, self.n_reg, self.momentum,
-                                                     self.l2, L.dtype_code(self.flat), L.stream_ptr(dev)),
-                    "grouped fused SGD step")
-            self._steps += 1
-            return
-        if self.schedule is not None:
-            block = self._run_guard(g) if self.guard is not None else None
-            L.check(L.lib().dctn_sgd_l2_step_scheduled(None if self.master is None else self.master.data_ptr(),
-                                                       self.flat.data_ptr(), g.data_ptr(), self.buf.data_ptr(),
-                                                       self.sq_sum.data_ptr(), self._state.data_ptr(), block,
-                                                       self.schedule._block.data_ptr(), self.n, self.n_reg,
-                                                       self.momentum, self.l2, L.dtype_code(self.flat),
-                                                       L.stream_ptr(dev)), "scheduled fused SGD step")
-            self._steps += 1
-            return
-        first = 1 if self._steps == 0 else 0
-        if self.guard is not None:
-            # `first` is the host's count of launches, and the host does not know whether the guard let a launch
-            # through.  A skipped step 0 leaves the momentum buffer at its zeros, and the next launch, with first = 0,
-            # forms momentum * 0 + g = g: the update a first step makes.
-            block = self._run_guard(g)
-            if self.master is not None:
-                L.check(L.lib().dctn_sgd_l2_step_master_guarded(self.master.data_ptr(), self.flat.data_ptr(),
-                                                                g.data_ptr(), self.buf.data_ptr(), self.sq_sum.data_ptr(),
-                                                                block, self.n, self.n_reg, self.lr, self.momentum,
-                                                                self.l2, first, L.stream_ptr(dev)),
-                        "guarded fused SGD step (master weights)")
-            else:
-                L.check(L.lib().dctn_sgd_l2_step_guarded(self.flat.data_ptr(), g.data_ptr(), self.buf.data_ptr(),
-                                                         self.sq_sum.data_ptr(), block, self.n, self.n_reg, self.lr,
-                                                         self.momentum, self.l2, first, L.dtype_code(self.flat),
-                                                         L.stream_ptr(dev)), "guarded fused SGD step")
-            self._steps += 1
-            return
-        if self.master is not None:
-            L.check(L.lib().dctn_sgd_l2_step_master(self.master.data_ptr(), self.flat.data_ptr(), g.data_ptr(),
-                                                    self.buf.data_ptr(), self.sq_sum.data_ptr(), self.n, self.n_reg,
-                                                    self.lr, self.momentum, self.l2, first, L.stream_ptr(dev)),
-                    "fused SGD step (master weights)")
-        else:
-            L.check(L.lib().dctn_sgd_l2_step(self.flat.data_ptr(), g.data_ptr(), self.buf.data_ptr(),
-                                             self.sq_sum.data_ptr(), self.n, self.n_reg, self.lr, self.momentum, self.l2,
-                                             first, L.dtype_code(self.flat), L.stream_ptr(dev)), "fused SGD step")
+        self._begin_step()
+        # Without a schedule or a group table the launch takes the rate and `first` from the host.  `first` is the host's
+        # count of launches, and under a guard the host does not know whether the guard let a launch through.  A skipped
+        # step 0 leaves the momentum buffer at its zeros, and the next launch, with first = 0, forms momentum * 0 + g = g:
+        # the update a first step makes.  (With either option the kernel reads both from the step block instead.)
+        L.check(L.lib().dctn_sgd_flat_step(self._desc_ref, self.buf.data_ptr(), self._lr, self.momentum,
+                                           1 if self._steps == 0 else 0, L.stream_ptr(self.flat.device)), self._what)
         self._steps += 1
 
     def state_dict(self) -> Dict[str, Any]:
@@ -1345,7 +1327,9 @@ class FlatSGD(_FlatOptimizer):
 class FlatAdam(_FlatOptimizer):
     """torch.optim.Adam (coupled ``weight_decay``, no amsgrad - what the reference's recipe builds,
     new_runner.py:496-498) plus the reference's L2 regulariser, as ONE kernel per step over one flat parameter
-    buffer (`dctn_adam_l2_step`).  Construction, gradient handling and ``reg_value()`` are FlatSGD's; the moments
+    buffer.  ``step()`` makes one library call whatever the options, `dctn_adam_flat_step` with a descriptor of the step
+    built at construction; alone it launches the kernel of `dctn_adam_l2_step`, and each option below names the older
+    entry point that launches the same kernel as that option does here.  Construction, gradient handling and ``reg_value()`` are FlatSGD's; the moments
     ``m`` / ``v`` are float32 whatever the parameter dtype.
 
     The step count ``t`` and the learning rate live in a small DEVICE block that the kernel reads and whose ``t`` the
@@ -1356,22 +1340,22 @@ class FlatAdam(_FlatOptimizer):
     the hyper-parameters and the master copy when there is one: a run resumed from them continues bit-identically.
 
     ``master_weights=True``: bfloat16 parameters get a float32 master copy ``master`` that the same launch updates
-    (`dctn_adam_l2_step_master`); the parameters receive its rounding and are never read by the step.  Without it a
+    (the kernel of `dctn_adam_l2_step_master`); the parameters receive its rounding and are never read by the step.  Without it a
     bfloat16 weight whose Adam step (about ``lr``) is below half an ulp of its value does not move at all.  The
     master follows, bit for bit, what FlatAdam does on float32 parameters given the same gradients.  Call
     ``refresh_master()`` after writing the parameters from outside.
 
     ``guard`` (a `GradGuard`) / ``guard_loss`` (a float32 device scalar, or a callable returning one): ``step()``
-    launches the guard's check over the gradients and then the guarded kernel (`dctn_adam_l2_step_guarded`, two
-    launches instead of one).  The gradients are clipped to ``guard.max_norm`` as they stand in the buffer - after the
+    launches the guard's check over the gradients and then the guarded kernel (that of `dctn_adam_l2_step_guarded`;
+    two launches instead of one).  The gradients are clipped to ``guard.max_norm`` as they stand in the buffer - after the
     all-reduce, in front of ``weight_decay * w`` and the fused ``2 * l2 * w``: ``clip_grad_norm_`` followed by
     ``Adam(weight_decay=...)``; a regulariser passed through ``reg_fn`` is in the buffer and is clipped with it.  Once
     the guard has halted, a step writes nothing: parameters, ``m``, ``v``, ``master`` and ``t`` stay as they are.  The
     guard's state is not part of this optimizer's ``state_dict()``; save ``guard.state_dict()`` beside it.  Without a
     guard ``step()`` makes the calls it always made.
 
-    ``schedule`` (an `LRSchedule`): ``step()`` launches `dctn_adam_l2_step_scheduled` (behind the guard's check when
-    there is a guard): the kernel evaluates the schedule's table at the device step count instead of reading the
+    ``schedule`` (an `LRSchedule`): ``step()`` launches the kernel of `dctn_adam_l2_step_scheduled` (behind the guard's
+    check when there is a guard): the kernel evaluates the schedule's table at the device step count instead of reading the
     block's rate, and leaves the rate it used in the block, so `StepTrace` records the rate of every iteration.  Every
     replay of a captured step, and each of the K iterations of one launch, gets its own rate with no host write.
     ``opt.lr`` returns ``schedule.value(opt.t)`` (it reads the device); assigning it raises RuntimeError
@@ -1381,8 +1365,8 @@ class FlatAdam(_FlatOptimizer):
     ``schedule.state_dict()`` beside it (`checkpoint.RunState` carries its block).  Without a schedule ``step()``
     makes the calls it always made.
 
-    ``groups`` (a `ParamGroups` over exactly these parameters): ``step()`` launches `dctn_adam_l2_step_grouped` (behind
-    the guard's check when there is a guard, with the schedule when there is one): ``torch.optim.Adam`` with
+    ``groups`` (a `ParamGroups` over exactly these parameters): ``step()`` launches the kernel of
+    `dctn_adam_l2_step_grouped` (behind the guard's check when there is a guard, with the schedule when there is one): ``torch.optim.Adam`` with
     ``param_groups`` and parameters without a gradient, in the one launch.  Every parameter steps with
     ``rate * lr_scale`` and the weight decay of its segment, its bias corrections follow ITS count of steps, and a frozen
     parameter is left alone - value, master copy, moments and count; a gradient of None is fine - while its squares
@@ -1418,6 +1402,7 @@ class FlatAdam(_FlatOptimizer):
             assert L.lib().dctn_lr_schedule_bytes() == 4 * LRSchedule.WORDS
         if groups is not None:
             groups._bind(self.weight_decay, "FlatAdam")
+        self._describe("fused Adam step")
 
     @property
     def lr(self) -> float:
@@ -1442,58 +1427,11 @@ class FlatAdam(_FlatOptimizer):
 
     @torch.no_grad()
     def step(self) -> None:
-        g = self._grads()
-        dev = self.flat.device
-        if self.groups is not None:   # (every segment's weight decay is in the table)
-            block = self._run_guard(g) if self.guard is not None else None
-            L.check(L.lib().dctn_adam_l2_step_grouped(None if self.master is None else self.master.data_ptr(),
-                                                      self.flat.data_ptr(), g.data_ptr(), self.m.data_ptr(),
-                                                      self.v.data_ptr(), self.sq_sum.data_ptr(), self._state.data_ptr(),
-                                                      block,
-                                                      None if self.schedule is None else self.schedule._block.data_ptr(),
-                                                      self.groups._block.data_ptr(), self.n, self.n_reg, self.betas[0],
-                                                      self.betas[1], self.eps, self.l2, L.dtype_code(self.flat),
-                                                      L.stream_ptr(dev)), "grouped fused Adam step")
-            return
-        if self.schedule is not None:
-            block = self._run_guard(g) if self.guard is not None else None
-            L.check(L.lib().dctn_adam_l2_step_scheduled(None if self.master is None else self.master.data_ptr(),
-                                                        self.flat.data_ptr(), g.data_ptr(), self.m.data_ptr(),
-                                                        self.v.data_ptr(), self.sq_sum.data_ptr(),
-                                                        self._state.data_ptr(), block, self.schedule._block.data_ptr(),
-                                                        self.n, self.n_reg, self.betas[0], self.betas[1], self.eps,
-                                                        self.weight_decay, self.l2, L.dtype_code(self.flat),
-                                                        L.stream_ptr(dev)), "scheduled fused Adam step")
-            return
-        if self.guard is not None:
-            block = self._run_guard(g)
-            if self.master is not None:
-                L.check(L.lib().dctn_adam_l2_step_master_guarded(self.master.data_ptr(), self.flat.data_ptr(),
-                                                                 g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-                                                                 self.sq_sum.data_ptr(), self._state.data_ptr(), block,
-                                                                 self.n, self.n_reg, self.betas[0], self.betas[1],
-                                                                 self.eps, self.weight_decay, self.l2,
-                                                                 L.stream_ptr(dev)),
-                        "guarded fused Adam step (master weights)")
-            else:
-                L.check(L.lib().dctn_adam_l2_step_guarded(self.flat.data_ptr(), g.data_ptr(), self.m.data_ptr(),
-                                                          self.v.data_ptr(), self.sq_sum.data_ptr(),
-                                                          self._state.data_ptr(), block, self.n, self.n_reg,
-                                                          self.betas[0], self.betas[1], self.eps, self.weight_decay,
-                                                          self.l2, L.dtype_code(self.flat), L.stream_ptr(dev)),
-                        "guarded fused Adam step")
-            return
-        if self.master is not None:
-            L.check(L.lib().dctn_adam_l2_step_master(self.master.data_ptr(), self.flat.data_ptr(), g.data_ptr(),
-                                                     self.m.data_ptr(), self.v.data_ptr(), self.sq_sum.data_ptr(),
-                                                     self._state.data_ptr(), self.n, self.n_reg, self.betas[0],
-                                                     self.betas[1], self.eps, self.weight_decay, self.l2,
-                                                     L.stream_ptr(dev)), "fused Adam step (master weights)")
-            return
-        L.check(L.lib().dctn_adam_l2_step(self.flat.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-                                          self.sq_sum.data_ptr(), self._state.data_ptr(), self.n, self.n_reg,
-                                          self.betas[0], self.betas[1], self.eps, self.weight_decay, self.l2,
-                                          L.dtype_code(self.flat), L.stream_ptr(dev)), "fused Adam step")
+        self._begin_step()
+        # (with a group table every segment's weight decay is in the table, and the launch ignores this one)
+        L.check(L.lib().dctn_adam_flat_step(self._desc_ref, self.m.data_ptr(), self.v.data_ptr(), self.betas[0],
+                                            self.betas[1], self.eps, self.weight_decay, L.stream_ptr(self.flat.device)),
+                self._what)
 
     def state_dict(self) -> Dict[str, Any]:
         """Everything a resumed run needs besides the parameters themselves (those are the model's state_dict)."""

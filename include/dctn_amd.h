@@ -597,7 +597,54 @@ int dctn_sgd_l2_step_grouped(void* master_or_null, void* params, const void* gra
                              int64_t n, int64_t n_reg, float momentum, float l2, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Scoring (reference: dctn/evaluation.py:7-22): one launch per batch ADDS to acc = three float64 values
+ * One description of a flat-optimizer step (version 512).  Master weights, the guard, the schedule and the group table
+ * are four options that do not depend on one another; dctn_flat_step_t names every buffer and block of a step once, an
+ * option that is off is a NULL pointer, and one entry point per optimizer takes it.  The twelve dctn_adam_l2_step* /
+ * dctn_sgd_l2_step* entry points above are conveniences over these two: each fills the struct and launches the same
+ * kernel with the same arguments.
+ *
+ * dctn_flat_step_t: dctn_flat_step_bytes() = 88 bytes on the HOST, read during the call only (the caller may keep one
+ * for the life of an optimizer and rewrite `grads` per step).  Every pointer in it is a DEVICE pointer:
+ *   void*       params    n values of `dtype`; with `master` they are bf16, OVERWRITTEN and never read
+ *   void*       master    NULL, or the float32 master copy of bf16 parameters (dtype must then be DCTN_BF16)
+ *   const void* grads     n values of `dtype`
+ *   void*       sq_sum    NULL, or dctn_*_l2_num_partials(n) float32 slots, OVERWRITTEN
+ *   void*       state     the 16-byte step block {steps_done, lr, ticket, reserved}.  Adam: required.  SGD: required
+ *                         with a schedule or a group table, and not looked at otherwise
+ *   const void* guard     NULL, or the 32-byte guard block: the step obeys it (dctn_grad_guard_check ran in front)
+ *   const void* schedule  NULL, or the 784-byte schedule block: the rate is its value at steps_done, not state->lr
+ *   void*       groups    NULL, or the 1552-byte group table.  Adam then takes every segment's weight decay from it
+ *                         and ignores its weight_decay argument
+ *   int64_t     n, n_reg  elements of the flat buffer; the first n_reg are regularised
+ *   float       l2        the regulariser's coefficient
+ *   int         dtype     DCTN_F32 / DCTN_BF16
+ * dctn_adam_flat_step : the struct plus exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay (dctn_adam_l2_step's).
+ * dctn_sgd_flat_step  : the struct plus momentum_buf, lr, momentum, first_step (dctn_sgd_l2_step's).  With a schedule or
+ *   a group table lr and first_step are not used: both are read from the step block on the device.
+ * Return codes, decided on the host before any launch: DCTN_ERR_NULL (the struct, or a required pointer), then
+ * DCTN_ERR_BAD_SHAPE (n < 1, n_reg outside 0..n; Adam: a beta outside [0, 1)), then DCTN_ERR_BAD_DTYPE (a dtype that is
+ * neither DCTN_F32 nor DCTN_BF16, or a master copy beside one that is not DCTN_BF16).  The semantics of every option are
+ * stated with its block above.  No workspace; the calls only enqueue and can be captured.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  void *params, *master;
+  const void* grads;
+  void* sq_sum;
+  void* state;
+  const void *guard, *schedule;
+  void* groups;
+  int64_t n, n_reg;
+  float l2;
+  int dtype;
+} dctn_flat_step_t;
+size_t dctn_flat_step_bytes(void);
+int dctn_adam_flat_step(const dctn_flat_step_t* step, void* exp_avg, void* exp_avg_sq, double beta1, double beta2,
+                        float eps, float weight_decay, void* stream);
+int dctn_sgd_flat_step(const dctn_flat_step_t* step, void* momentum_buf, float lr, float momentum, int first_step,
+                       void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Scoring(reference: dctn/evaluation.py:7-22): one launch per batch ADDS to acc = three float64 values
  * {sum of the rows' cross-entropies, number of correct rows, number of rows}.  logits (B, C) contiguous, DCTN_F32 /
  * DCTN_BF16; labels int64.  Per row a max-shifted log-sum-exp with float32 exponentials; the row's sum, its
  * logarithm and the sums over the rows are float64, in a fixed order: the same bits from run to run (the float32

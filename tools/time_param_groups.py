@@ -3,8 +3,9 @@
 cfg2 (bf16, B = 1024, FlatAdam with master weights) as a GraphedTrainStep whose graph draws its own batches from a
 `DeviceBatches` source over `--samples` synthetic 28 x 28 uint8 images, one iteration per launch:
 
-  A   the parent's loop, ungrouped.  With `--parent-lib PATH` (a libdctn_amd.so built from the parent commit) its graph
-      is captured over that library's kernels; without it A is a second instance of this build's ungrouped loop
+  A   the parent's loop, ungrouped.  With `--parent-lib PATH` (a libdctn_amd.so built from the parent commit, in the
+      dctn_amd directory of a checkout of that commit) A is that tree's Python over that library's kernels, imported
+      beside this build under another name; without it A is a second instance of this build's ungrouped loop
       ("parent_lib": null in the result) - either way A against B shows the run's own noise
   B   this build, ungrouped: `FlatAdam(lr=...)`
   C   this build, grouped: `FlatAdam(..., groups=param_groups_for(model, head_lr_scale=0.1))` - the model's three
@@ -21,7 +22,8 @@ spread), C - B (the feature's price) and C - D (what one launch buys over k).
                                       [--parent-lib PATH]
 """
 import argparse
-import ctypes
+import importlib
+import importlib.util
 import json
 import os
 import statistics
@@ -41,14 +43,17 @@ SPEC, SIZE, DTYPE, BATCH = ((3, 4),), 28, torch.bfloat16, 1024
 LR, HEAD_SCALE, L2 = 1e-4, 0.1, 1e-4
 
 
-def parent_library(path):
-    """The parent's library bound with the signatures it has (the entry points this build added are not in it)."""
-    handle = ctypes.CDLL(path)
-    for name, (res, args) in L.SIGNATURES.items():
-        fn = getattr(handle, name, None)
-        if fn is not None:
-            fn.restype, fn.argtypes = res, args
-    return handle
+def parent_package(lib_path):
+    """The `dctn_amd` package that holds the parent's library, imported as `dctn_parent`: its own Python over its own
+    library (this build's `step()` calls entry points the parent's library does not have)."""
+    path = os.path.dirname(os.path.abspath(lib_path))
+    spec = importlib.util.spec_from_file_location("dctn_parent", os.path.join(path, "__init__.py"),
+                                                  submodule_search_locations=[path])
+    module = importlib.util.module_from_spec(spec)
+    sys.modules["dctn_parent"] = module
+    spec.loader.exec_module(module)
+    assert os.path.samefile(module._lib.LIB_PATH, lib_path)
+    return module
 
 
 class PerGroupAdams:
@@ -68,24 +73,25 @@ class PerGroupAdams:
 
 def make_variant(name, images, labels, dev, parent):
     """Returns a callable that runs one launch (one iteration)."""
-    ours = L.lib()
-    if name == "A" and parent is not None:
-        L._lib = parent   # construction, warm-up and capture go through the parent's kernels; replays need no binding
-    try:
+    if name == "A" and parent is not None:   # the parent's classes: construction, warm-up and capture go through its library
+        T, M = importlib.import_module("dctn_parent.training"), importlib.import_module("dctn_parent.eps_plus_linear")
+        src = importlib.import_module("dctn_parent.batches").DeviceBatches(images, labels, BATCH, dtype=DTYPE, seed=2024)
         torch.manual_seed(0)
-        model = EPSesPlusLinear(SPEC, UnitTheoreticalOutputStd(), 1.0, dev, DTYPE, image_size=SIZE)
-        cores, weight, bias = list(model.epses), model.linear.weight, model.linear.bias
-        if name == "D":
-            opt = PerGroupAdams([FlatAdam(cores, [], lr=LR, l2=L2, master_weights=True),
-                                 FlatAdam([weight], [bias], lr=LR * HEAD_SCALE, l2=L2, master_weights=True)])
-        else:
-            groups = param_groups_for(model, head_lr_scale=HEAD_SCALE) if name == "C" else None
-            kw = {} if groups is None else {"groups": groups}   # (the parent's FlatAdam is this build's: same Python)
-            opt = FlatAdam(cores + [weight], [bias], lr=LR, l2=L2, master_weights=True, **kw)
-        src = DeviceBatches(images, labels, BATCH, dtype=DTYPE, seed=2024)
-        return GraphedTrainStep(model, None, None, fused_cross_entropy, opt, warmup=2, batch_source=src)
-    finally:
-        L._lib = ours
+        model = M.EPSesPlusLinear(SPEC, M.UnitTheoreticalOutputStd(), 1.0, dev, DTYPE, image_size=SIZE)
+        opt = T.FlatAdam(list(model.epses) + [model.linear.weight], [model.linear.bias], lr=LR, l2=L2, master_weights=True)
+        return T.GraphedTrainStep(model, None, None, T.fused_cross_entropy, opt, warmup=2, batch_source=src)
+    torch.manual_seed(0)
+    model = EPSesPlusLinear(SPEC, UnitTheoreticalOutputStd(), 1.0, dev, DTYPE, image_size=SIZE)
+    cores, weight, bias = list(model.epses), model.linear.weight, model.linear.bias
+    if name == "D":
+        opt = PerGroupAdams([FlatAdam(cores, [], lr=LR, l2=L2, master_weights=True),
+                             FlatAdam([weight], [bias], lr=LR * HEAD_SCALE, l2=L2, master_weights=True)])
+    else:
+        groups = param_groups_for(model, head_lr_scale=HEAD_SCALE) if name == "C" else None
+        kw = {} if groups is None else {"groups": groups}
+        opt = FlatAdam(cores + [weight], [bias], lr=LR, l2=L2, master_weights=True, **kw)
+    src = DeviceBatches(images, labels, BATCH, dtype=DTYPE, seed=2024)
+    return GraphedTrainStep(model, None, None, fused_cross_entropy, opt, warmup=2, batch_source=src)
 
 
 def main():
@@ -101,11 +107,11 @@ def main():
     images = torch.randint(0, 256, (args.samples, SIZE, SIZE), dtype=torch.uint8, generator=g)
     labels = torch.randint(0, 10, (args.samples,), generator=g)
     names = args.variants.split(",")
-    parent = parent_library(args.parent_lib) if args.parent_lib else None
+    parent = parent_package(args.parent_lib) if args.parent_lib else None
     result = {"workload": "cfg2 bf16 B=1024 FlatAdam(master) graphed, batch source", "samples": args.samples,
               "steps": args.steps, "repeats": args.repeats, "date": time.strftime("%Y-%m-%d"),
               "device": torch.cuda.get_device_name(dev), "parent_lib": args.parent_lib,
-              "parent_version": None if parent is None else parent.dctn_version(), "version": L.lib().dctn_version(),
+              "parent_version": None if parent is None else parent._lib.lib().dctn_version(), "version": L.lib().dctn_version(),
               "groups": f"3 segments (core, linear.weight, linear.bias), head lr_scale {HEAD_SCALE}; D: 2 FlatAdam instances"}
     runs = {v: make_variant(v, images, labels, dev, parent) for v in names}
     times = {v: [] for v in names}
