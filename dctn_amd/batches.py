@@ -568,3 +568,20 @@ class DeviceBatches:
         words = _state_words(state["seed"], state["batches_done"])
         self._state.copy_(torch.tensor(words, dtype=torch.int32))   # in place: a captured graph keeps its pointer
         self.seed = int(state["seed"])
+
+    # A part of a run (`checkpoint.RunState`): the device tensors that travel, the host scalars
+    # beside them, what of those a run refuses before anything is written, and how the host mirrors follow.
+    def run_regions(self):
+        return [("state", self._state)]
+
+    def run_host(self) -> Dict[str, int]:
+        return dict(n=self.n, batch_size=self.batch_size, seed=self.seed)
+
+    def run_check(self, host: Dict[str, int]) -> None:
+        for key in ("n", "batch_size"):
+            if host[key] != getattr(self, key):
+                raise ValueError(f"snapshot: entry 'batch_source.{key}' is {host[key]} in the file, "
+                                 f"{getattr(self, key)} in the run")
+
+    def run_restored(self, host: Dict[str, int], blocks) -> None:
+        self.seed = int(host["seed"])

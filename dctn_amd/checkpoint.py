@@ -27,10 +27,10 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
-import torch.distributed as dist
 from torch import Tensor
 
 from . import _lib as L
+from .ddp import is_rank0
 
 MAGIC = b"DCTNRUN1"
 FORMAT_VERSION = 1
@@ -253,36 +253,31 @@ class Snapshot:
         return path
 
 
-def _tensor_regions(model, optimizer, batch_source, guard, trace=None):
-    """``(regions, model entries, optimizer kind)``: the named device tensors of a run, in file order."""
-    from . import training
-
-    if optimizer is not None and not isinstance(optimizer, (training.FlatAdam, training.FlatSGD)):
+def run_parts(model, optimizer, batch_source, guard, trace=None) -> List[Tuple[str, Any]]:
+    """``[(slot, part), ...]`` in file order: the components of a run that say themselves what they keep on the device.
+    A part has ``run_regions()`` -> ``[(local name, tensor), ...]`` in file order, ``run_host()`` -> its JSON-able host
+    scalars or None, ``run_restored(host, blocks)`` which sets its host mirrors once its regions were put back
+    (``blocks``: local name -> the file's bytes of that region, a uint8 view into the arena), and, where there is
+    something to refuse, ``run_check(host)`` which raises ValueError before anything is written.  The model is a part
+    only for what its state_dict does not hold; any other ``nn.Module`` is none."""
+    if optimizer is not None and not hasattr(optimizer, "run_regions"):
         raise TypeError(f"RunState takes a FlatAdam or a FlatSGD, got {type(optimizer).__name__}: a snapshot gathers FIXED "
                         "device buffers that captured graphs replay, and a torch.optim optimizer keeps its state in "
                         "per-parameter tensors it creates lazily and may replace")
+    slots = (("optimizer", optimizer), ("model", model if hasattr(model, "run_regions") else None), ("guard", guard),
+             ("batch_source", batch_source), ("trace", trace))
+    return [(slot, part) for slot, part in slots if part is not None]
+
+
+def run_regions(model, optimizer, batch_source, guard, trace=None):
+    """``(regions, model entries)``: the named device tensors of a run, in file order - the optimizer's, every entry of
+    the model's state_dict that does not lie inside ``optimizer.flat``, then the other parts' - and where each
+    state_dict entry lies in them.  Needs no device."""
     regions: List[Tuple[str, Tensor]] = []
-    kind = None
-    flat = None
-    if optimizer is not None:
-        kind = type(optimizer).__name__
-        flat = optimizer.flat
-        regions.append(("optimizer.flat", flat))
-        names = ("m", "v") if isinstance(optimizer, training.FlatAdam) else ("buf",)
-        for name in names:
-            regions.append((f"optimizer.{name}", getattr(optimizer, name)))
-        if optimizer.master is not None:
-            regions.append(("optimizer.master", optimizer.master))
-        # a scheduled optimizer: the schedule's block, and in front of the step block so that a file and a run that
-        # disagree about the schedule differ at this entry first
-        if getattr(optimizer, "schedule", None) is not None:
-            regions.append(("optimizer.schedule", optimizer.schedule._block))
-        # a grouped optimizer: the table's block, the segments' step counts in it
-        if getattr(optimizer, "groups", None) is not None:
-            regions.append(("optimizer.groups", optimizer.groups._block))
-        if getattr(optimizer, "_state", None) is not None:   # FlatAdam; a FlatSGD with a schedule or a group table
-            regions.append(("optimizer.state", optimizer._state))
-        regions.append(("optimizer.sq_sum", optimizer.sq_sum))
+    behind: List[Tuple[str, Tensor]] = []
+    for slot, part in run_parts(model, optimizer, batch_source, guard, trace):
+        (regions if slot == "optimizer" else behind).extend((f"{slot}.{name}", t) for name, t in part.run_regions())
+    flat = dict(regions).get("optimizer.flat")
     entries = []
     for key, t in model.state_dict(keep_vars=True).items():
         t = t.detach()
@@ -295,32 +290,20 @@ def _tensor_regions(model, optimizer, batch_source, guard, trace=None):
         else:
             regions.append((f"model.{key}", t))
             entries.append(dict(key=key, region=f"model.{key}", offset=0, dtype=_dtype_name(t.dtype), shape=list(t.shape)))
-    if getattr(model, "_dropout_state", None) is not None:
-        regions.append(("model.dropout_state", model._dropout_state))
-    if guard is not None:
-        regions.append(("guard.block", guard._block))
-    if batch_source is not None:
-        regions.append(("batch_source.state", batch_source._state))
-    if trace is not None:
-        regions.append(("trace.head", trace._head))
-        regions.append(("trace.ring", trace._ring))
-    return regions, entries, kind
+    return regions + behind, entries
 
 
 class RunState:
-    """The device state of a training run as named regions: with a `FlatAdam` / `FlatSGD` its flat parameter buffer, the
-    moments (or the momentum buffer), the master copy, the 16-byte step block and ``sq_sum``; with an `LRSchedule` on the
-    optimizer the schedule's block as ``optimizer.schedule`` (and the step block of a scheduled `FlatSGD` as
-    ``optimizer.state``; a file and a run that disagree about the schedule are refused at that entry, and runs without a
-    schedule keep their region lists and their files); with a `ParamGroups` table on the optimizer its block, the
-    segments' step counts in it, as ``optimizer.groups`` behind ``optimizer.schedule`` (runs without one keep their
-    region lists and files too); every entry of the model's
-    state_dict that does not live in the flat buffer (the buffer ``p``; without an optimizer every parameter) as a region
-    of its own; ``model._dropout_state`` when the fused dropout is on; ``guard._block`` (``guard`` defaults to the
-    optimizer's); ``batch_source._state``; with ``trace`` (a `training.StepTrace`) its head and ring as ``trace.head`` /
-    ``trace.ring``, so that a resumed run continues its ``seq`` (without the argument the region list is unchanged).  The
-    host scalars travel in the manifest: the hyper-parameters and ``lr``, `FlatSGD`'s step count, the source's ``n`` /
-    ``batch_size`` / ``seed``, ``guard.max_norm``.
+    """The device state of a training run as named regions.  Each part of the run (`run_parts`) lists its own, and
+    `RunState` puts the slot's name in front: a `FlatAdam` / `FlatSGD` as ``optimizer.`` its flat parameter buffer, the
+    moments (or the momentum buffer), the master copy, the blocks of its `LRSchedule` and its `ParamGroups` table, the
+    16-byte step block and ``sq_sum``, each only when the optimizer has it (a file and a run that disagree about an option
+    are refused at that entry; runs without an option keep their region lists and their files); every entry of the
+    model's state_dict that does not live in the flat buffer (the buffer ``p``; without an optimizer every parameter) as
+    a region of its own; the model's fused dropout state; the guard's block (``guard`` defaults to the optimizer's); the
+    batch source's block; with ``trace`` (a `training.StepTrace`) its head and ring, so that a resumed run continues its
+    ``seq``.  The host scalars travel in the manifest, one entry per part that has some: the hyper-parameters and ``lr``,
+    `FlatSGD`'s step count, the source's ``n`` / ``batch_size`` / ``seed``, ``guard.max_norm``.
 
     ``snapshot(extras)`` never blocks the host: it enqueues the gather on the current stream (one launch per 16 regions)
     and the copy of arena and digests to pinned memory on a side stream behind an event; the next ``snapshot()`` makes the
@@ -333,7 +316,8 @@ class RunState:
             guard = getattr(optimizer, "guard", None)
         self.model, self.optimizer, self.batch_source, self.guard = model, optimizer, batch_source, guard
         self.trace = trace
-        regions, self._model_entries, self._kind = _tensor_regions(model, optimizer, batch_source, guard, trace)
+        self._parts = run_parts(model, optimizer, batch_source, guard, trace)
+        regions, self._model_entries = run_regions(model, optimizer, batch_source, guard, trace)
         if not regions:
             raise ValueError("RunState: nothing to save")
         self.device = L.require_device(*(t for _, t in regions))
@@ -380,21 +364,8 @@ class RunState:
                                           "(a bfloat16 view at an odd element): nothing was launched")
 
     def _host_scalars(self) -> Dict[str, Any]:
-        host: Dict[str, Any] = {}
-        opt = self.optimizer
-        if opt is not None:
-            # (`_lr`: the host copy; with a schedule the rate is in the blocks, and reading `lr` would synchronise)
-            if self._kind == "FlatAdam":
-                host["optimizer"] = dict(kind=self._kind, lr=opt._lr, betas=list(opt.betas), eps=opt.eps,
-                                         weight_decay=opt.weight_decay, l2=opt.l2)
-            else:
-                host["optimizer"] = dict(kind=self._kind, lr=opt._lr, momentum=opt.momentum, l2=opt.l2, steps=opt._steps)
-        if self.batch_source is not None:
-            src = self.batch_source
-            host["batch_source"] = dict(n=src.n, batch_size=src.batch_size, seed=src.seed)
-        if self.guard is not None:
-            host["guard"] = dict(max_norm=self.guard.max_norm)
-        return host
+        scalars = ((slot, part.run_host()) for slot, part in self._parts)
+        return {slot: host for slot, host in scalars if host is not None}
 
     # ------------------------------------------------------------------------------------------ snapshot
     def snapshot(self, extras: Optional[Dict[str, Any]] = None) -> Snapshot:
@@ -426,18 +397,14 @@ class RunState:
 
     # ------------------------------------------------------------------------------------------ load
     def _check_host(self, host: Dict[str, Any]) -> None:
-        saved = host.get("optimizer")
-        if (saved is None) != (self.optimizer is None) or (saved is not None and saved["kind"] != self._kind):
-            raise ValueError(f"snapshot: entry 'optimizer' is {None if saved is None else saved['kind']} in the file, "
-                             f"{self._kind} in the run")
-        for part, live in (("batch_source", self.batch_source), ("guard", self.guard)):
-            if (host.get(part) is None) != (live is None):
-                raise ValueError(f"snapshot: entry {part!r} is {'missing from' if live is not None else 'only in'} the file")
-        if self.batch_source is not None:
-            for key in ("n", "batch_size"):
-                if host["batch_source"][key] != getattr(self.batch_source, key):
-                    raise ValueError(f"snapshot: entry 'batch_source.{key}' is {host['batch_source'][key]} in the file, "
-                                     f"{getattr(self.batch_source, key)} in the run")
+        """Every part's host scalars are in the file, no other part's are, and no part refuses its own."""
+        live = self._host_scalars()
+        for slot in {**live, **host}:
+            if (host.get(slot) is None) != (slot not in live):
+                raise ValueError(f"snapshot: entry {slot!r} is {'missing from' if slot in live else 'only in'} the file")
+        for slot, part in self._parts:
+            if hasattr(part, "run_check"):
+                part.run_check(host[slot])
 
     def load(self, path: str) -> Dict[str, Any]:
         """Puts a saved run back IN PLACE and returns its extras.  Nothing on the device is written before every name,
@@ -461,40 +428,11 @@ class RunState:
             if (int(s1), int(s2)) != (r["s1"], r["s2"]):
                 raise RuntimeError(f"{path}: region {r['name']!r} was damaged on its way to the device: the scatter read "
                                    f"the digest {(int(s1), int(s2))}, the manifest says {(r['s1'], r['s2'])}")
-        self._set_host_mirrors(manifest["host"])
-        if getattr(self.optimizer, "schedule", None) is not None:   # the block came back: the host copy of the table follows
-            block = next(r for r in manifest["regions"] if r["name"] == "optimizer.schedule")
-            self.optimizer.schedule._mirror_block(arena[block["offset"]: block["offset"] + block["bytes"]].view("<i4"))
-        if getattr(self.optimizer, "groups", None) is not None:   # likewise the host copy of the group table
-            block = next(r for r in manifest["regions"] if r["name"] == "optimizer.groups")
-            self.optimizer.groups._mirror_block(arena[block["offset"]: block["offset"] + block["bytes"]].view("<i4"))
-        if self.trace is not None:   # head and ring came back with their regions: the records before the head count as read
-            head = next(r for r in manifest["regions"] if r["name"] == "trace.head")
-            done = int(arena[head["offset"]: head["offset"] + 4].view("<u4")[0])
-            self.trace._last_read, self.trace.lost = done, 0
+        # the regions came back: every part's host mirrors follow, from its host scalars and the file's bytes of its regions
+        saved = {r["name"]: arena[r["offset"]: r["offset"] + r["bytes"]] for r in manifest["regions"]}
+        for slot, part in self._parts:
+            part.run_restored(manifest["host"].get(slot), {name: saved[f"{slot}.{name}"] for name, _ in part.run_regions()})
         return manifest["extras"]
-
-    def _set_host_mirrors(self, host: Dict[str, Any]) -> None:
-        opt = self.optimizer
-        if opt is not None:
-            saved = host["optimizer"]
-            if self._kind == "FlatAdam":   # the rate itself came back with the 16-byte block
-                opt._lr = float(saved["lr"])
-                opt.betas, opt.eps = (float(saved["betas"][0]), float(saved["betas"][1])), float(saved["eps"])
-                opt.weight_decay, opt.l2 = float(saved["weight_decay"]), float(saved["l2"])
-            else:
-                opt._lr, opt.momentum, opt.l2 = float(saved["lr"]), float(saved["momentum"]), float(saved["l2"])
-                opt._steps = int(saved["steps"])
-        if self.guard is not None:
-            self.guard._max_norm = float(host["guard"]["max_norm"])
-        if self.batch_source is not None:
-            self.batch_source.seed = int(host["batch_source"]["seed"])
-        if hasattr(self.model, "_refresh_p"):
-            self.model._refresh_p()
-
-
-def _is_rank0() -> bool:
-    return not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
 
 
 class RunCheckpointer:
@@ -515,7 +453,7 @@ class RunCheckpointer:
         self._pending: Optional[Tuple[Snapshot, str]] = None
 
     def __call__(self, st_x: Dict[Any, Any], st_it: Dict[Any, Any]) -> None:
-        if not _is_rank0():
+        if not is_rank0():
             return
         more = {} if self.extras is None else dict(self.extras(st_x, st_it))
         done = int(st_it["num_iters_done"])

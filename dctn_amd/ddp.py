@@ -111,6 +111,11 @@ def probe_allreduce_capture(timeout: float = 240.0, numel: int = 29098, dtype: t
         return False
 
 
+def is_rank0() -> bool:
+    """Whether this process touches checkpoint files: rank 0, or no process group at all."""
+    return not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
+
+
 def all_ranks_agree(flag: bool, device: Optional[torch.device] = None) -> bool:
     """True iff `flag` is true on every rank (every rank must then take the same branch, or collectives stop
     pairing up)."""

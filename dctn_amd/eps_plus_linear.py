@@ -365,6 +365,17 @@ class EPSesPlusLinear(nn.Module):
         with torch.no_grad():
             self._dropout_state.copy_(new)
 
+    # A part of a run (`checkpoint.RunState`), for what is not in the state_dict: the device
+    # tensors that travel, no host scalars, and the host mirror that follows a ``p`` that was put back.
+    def run_regions(self):
+        return [] if self._dropout_state is None else [("dropout_state", self._dropout_state)]
+
+    def run_host(self) -> None:
+        return None
+
+    def run_restored(self, host, blocks) -> None:
+        self._refresh_p()
+
     def epswise_l2_regularizer(self) -> Tensor:
         """||linear.weight||^2 + sum of squared Frobenius norms of the cores (bias excluded)."""
         return self.linear.weight.norm(p="fro") ** 2 + epses_composition.epswise_squared_fro_norm(self.epses)

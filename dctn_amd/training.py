@@ -319,6 +319,16 @@ def fused_cross_entropy(logits: Tensor, labels: Tensor) -> Tensor:
 fused_cross_entropy.accepts_low_precision = True   # train_step / GraphedTrainStep skip their float32 cast
 
 
+def _write_cell(cell: Tensor, value) -> None:
+    """The small write into one cell of a device block (a one-element view of it): asynchronous, on the current stream of
+    the cell's device, so that replays of an already captured graph read the new value.  The caller refuses captures."""
+    if cell.is_cuda:
+        with torch.cuda.device(cell.device):
+            cell.fill_(value)
+    else:
+        cell.fill_(value)
+
+
 class GradGuard:
     """The device-side gradient guard: a non-finite halt and global norm clipping that a captured iteration carries
     with it (`dctn_grad_guard_check`, include/dctn_amd.h).  Pass one to ``FlatAdam(..., guard=g)`` or
@@ -379,8 +389,7 @@ class GradGuard:
             raise RuntimeError("GradGuard.max_norm cannot be assigned during a graph capture: the captured check reads "
                                "the threshold from the device, assign it between replays")
         self._max_norm = float("inf") if value is None else float(value)
-        with torch.cuda.device(self.device):
-            self._cells[0:1].fill_(self._max_norm)
+        _write_cell(self._cells[0:1], self._max_norm)
 
     def check(self, grads: Tensor, loss: Optional[Tensor] = None) -> None:
         """Launches the check over the flat gradient buffer ``grads`` (and the float32 device scalar ``loss``)."""
@@ -417,6 +426,17 @@ class GradGuard:
 
     def load_state_dict(self, state: Dict[str, Any]) -> None:
         self._write({**state, "ticket": 0})
+
+    # A part of a run (`checkpoint.RunState`): the device tensors that travel, the host scalars
+    # beside them, and how the host mirrors follow tensors that were put back.
+    def run_regions(self):
+        return [("block", self._block)]
+
+    def run_host(self) -> Dict[str, Any]:
+        return dict(max_norm=self._max_norm)
+
+    def run_restored(self, host: Dict[str, Any], blocks) -> None:
+        self._max_norm = float(host["max_norm"])
 
     @staticmethod
     def decide(total_sq: float, max_norm: float, halted_before: bool = False, loss: Optional[float] = None):
@@ -536,6 +556,17 @@ class StepTrace:
         with torch.no_grad():
             self._head.copy_(host)
         self._last_read, self.lost = done, 0
+
+    # a part of a run, as `GradGuard`
+    def run_regions(self):
+        return [("head", self._head), ("ring", self._ring)]
+
+    def run_host(self) -> None:
+        return None
+
+    def run_restored(self, host, blocks) -> None:
+        """Head and ring came back with their regions: the records before the head count as read."""
+        self._last_read, self.lost = int(blocks["head"][:4].view("<u4")[0]), 0
 
 
 def _trace_record_dtype():
@@ -698,11 +729,7 @@ class LRSchedule:
     def scale(self, value: float) -> None:
         self._no_capture("scale cannot be assigned")
         self._scale = self._validated_scale(value)
-        if self.device.type == "cuda":
-            with torch.cuda.device(self.device):
-                self._scale_cell.fill_(self._scale)
-        else:
-            self._scale_cell.fill_(self._scale)
+        _write_cell(self._scale_cell, self._scale)
 
     @property
     def knots(self):
@@ -722,9 +749,16 @@ class LRSchedule:
         self._scale = scale
         self._upload()
 
-    def _mirror_block(self, words) -> None:
+    # a part of a run, as `GradGuard`; the optimizer that holds the schedule lists the block among its own regions
+    def run_regions(self):
+        return [("schedule", self._block)]
+
+    def run_host(self) -> None:
+        return None
+
+    def run_restored(self, host, blocks) -> None:
         """Sets the host copy from the block's bytes (`checkpoint.RunState.load` put the block itself back)."""
-        knots, hold, scale = self.decode(words)
+        knots, hold, scale = self.decode(blocks["schedule"])
         self._k, self._lr, self._hold = self._validated(knots, hold)
         self._scale = self._validated_scale(scale)
 
@@ -935,14 +969,6 @@ class ParamGroups:
         with torch.no_grad():
             self._block.copy_(torch.from_numpy(self.host_block(steps)))
 
-    def _write_cell(self, word: int, value, as_float: bool) -> None:
-        cell = self._block.view(torch.float32)[word: word + 1] if as_float else self._block[word: word + 1]
-        if self.device.type == "cuda":
-            with torch.cuda.device(self.device):
-                cell.fill_(value)
-        else:
-            cell.fill_(value)
-
     def _bind(self, default_weight_decay: Optional[float], owner: str) -> None:
         """An optimizer takes the table: None weight decays become its value; an optimizer without weight decay
         (``default_weight_decay`` None) refuses explicit ones."""
@@ -962,15 +988,16 @@ class ParamGroups:
         i = self.index_of(param)
         if weight_decay is not None and not self._wd_allowed:
             raise ValueError("ParamGroups.set: the optimizer that holds this table has no weight decay")
+        floats = self._block.view(torch.float32)
         if lr_scale is not None:
             self._scale[i] = self._validated("lr_scale", lr_scale)
-            self._write_cell(self._SCALE + i, self._scale[i], True)
+            _write_cell(floats[self._SCALE + i: self._SCALE + i + 1], self._scale[i])
         if weight_decay is not None:
             self._wd[i] = self._validated("weight_decay", weight_decay)
-            self._write_cell(self._WD + i, self._wd[i], True)
+            _write_cell(floats[self._WD + i: self._WD + i + 1], self._wd[i])
         if frozen is not None:
             self._frozen[i] = bool(frozen)
-            self._write_cell(self._FLAGS + i, 1 if frozen else 0, False)
+            _write_cell(self._block[self._FLAGS + i: self._FLAGS + i + 1], 1 if frozen else 0)
 
     def freeze(self, param, flag: bool = True) -> None:
         """Freezes (or with ``flag=False`` releases) one segment from the next launch on.  A released segment goes on from
@@ -1006,11 +1033,18 @@ class ParamGroups:
 
         self._upload(np.array(steps, dtype=np.int32))
 
-    def _mirror_block(self, words) -> None:
+    # a part of a run, as `GradGuard`; the optimizer that holds the table lists the block among its own regions
+    def run_regions(self):
+        return [("groups", self._block)]
+
+    def run_host(self) -> None:
+        return None
+
+    def run_restored(self, host, blocks) -> None:
         """Sets the host copy from the block's bytes (`checkpoint.RunState.load` put the block itself back)."""
         import numpy as np
 
-        words = np.ascontiguousarray(words).view("<i4").reshape(-1)
+        words = np.ascontiguousarray(blocks["groups"]).view("<i4").reshape(-1)
         k = len(self.params)
         if words.size != self.WORDS or int(words[0]) != k:
             raise ValueError(f"ParamGroups: the block describes {int(words[0]) if words.size else '?'} segments, this "
@@ -1194,6 +1228,33 @@ class _FlatOptimizer:
         """l2 * sum of squared Frobenius norms of the regularised parameters, as of the last step."""
         return self.sq_sum.sum() * self.l2
 
+    # A part of a run, as `GradGuard`.  `_MOMENTS` names the subclass's per-element buffers; its `run_host()` is the
+    # dictionary of its hyper-parameters (`_lr`: the host copy - with a schedule the rate is in the blocks, and reading
+    # `lr` would synchronise), and its `run_restored()` sets them before it calls this one.
+    def run_regions(self):
+        """In file order.  The schedule's block stands in front of the step block, so that a file and a run that disagree
+        about the schedule differ at that entry first; the group table's block, the segments' step counts in it, follows
+        it.  ``state``: FlatAdam; a FlatSGD with a schedule or a group table."""
+        regions = [("flat", self.flat)] + [(name, getattr(self, name)) for name in self._MOMENTS]
+        if self.master is not None:
+            regions.append(("master", self.master))
+        for part in (self.schedule, self.groups):
+            if part is not None:
+                regions += part.run_regions()
+        if self._state is not None:
+            regions.append(("state", self._state))
+        return regions + [("sq_sum", self.sq_sum)]
+
+    def run_check(self, host: Dict[str, Any]) -> None:
+        if host["kind"] != type(self).__name__:
+            raise ValueError(f"snapshot: entry 'optimizer' is {host['kind']} in the file, {type(self).__name__} in the run")
+
+    def run_restored(self, host: Dict[str, Any], blocks) -> None:
+        """The blocks came back: the host copies of the schedule's and the group table's follow theirs."""
+        for part in (self.schedule, self.groups):
+            if part is not None:
+                part.run_restored(None, {name: blocks[name] for name, _ in part.run_regions()})
+
 
 class FlatSGD(_FlatOptimizer):
     """SGD with momentum plus the reference's L2 regulariser, as ONE kernel per step over one flat
@@ -1275,12 +1336,7 @@ class FlatSGD(_FlatOptimizer):
                 raise RuntimeError("FlatSGD.lr cannot be assigned during a graph capture: the captured grouped step reads "
                                    "the rate from the device, assign it between replays")
             self._lr = float(value)
-            cell = self._state.view(torch.float32)[1:2]
-            if self.flat.device.type == "cuda":
-                with torch.cuda.device(self.flat.device):
-                    cell.fill_(self._lr)
-            else:
-                cell.fill_(self._lr)
+            _write_cell(self._state.view(torch.float32)[1:2], self._lr)
             return
         self._lr = float(value)
 
@@ -1322,6 +1378,16 @@ class FlatSGD(_FlatOptimizer):
         else:   # the block as the scheduled kernel would have left it: the count, and the rate of the last step
             self._put_step_block(self._steps)
         self._load_master(state)
+
+    _MOMENTS = ("buf",)
+
+    def run_host(self) -> Dict[str, Any]:
+        return dict(kind=type(self).__name__, lr=self._lr, momentum=self.momentum, l2=self.l2, steps=self._steps)
+
+    def run_restored(self, host: Dict[str, Any], blocks) -> None:
+        self._lr, self.momentum, self.l2 = float(host["lr"]), float(host["momentum"]), float(host["l2"])
+        self._steps = int(host["steps"])
+        super().run_restored(host, blocks)
 
 
 class FlatAdam(_FlatOptimizer):
@@ -1417,8 +1483,7 @@ class FlatAdam(_FlatOptimizer):
             raise RuntimeError("FlatAdam.lr cannot be assigned during a graph capture: the captured step reads the "
                                "rate from the device, assign it between replays")
         self._lr = float(value)
-        with torch.cuda.device(self.flat.device):
-            self._lr_cell.fill_(self._lr)
+        _write_cell(self._lr_cell, self._lr)
 
     @property
     def t(self) -> int:
@@ -1457,16 +1522,24 @@ class FlatAdam(_FlatOptimizer):
             self._put_step_block(int(state["t"]))
         self._load_master(state)
 
+    _MOMENTS = ("m", "v")
+
+    def run_host(self) -> Dict[str, Any]:
+        return dict(kind=type(self).__name__, lr=self._lr, betas=list(self.betas), eps=self.eps,
+                    weight_decay=self.weight_decay, l2=self.l2)
+
+    def run_restored(self, host: Dict[str, Any], blocks) -> None:
+        self._lr = float(host["lr"])   # the rate itself came back with the 16-byte block
+        self.betas, self.eps = (float(host["betas"][0]), float(host["betas"][1])), float(host["eps"])
+        self.weight_decay, self.l2 = float(host["weight_decay"]), float(host["l2"])
+        super().run_restored(host, blocks)
+
 
 # ------------------------------------------------------------------------------------------------
 # The reference's training loop and its hooks (dctn/training.py:14-248), one process per GPU
 # ------------------------------------------------------------------------------------------------
 def _world() -> int:
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-
-
-def _is_rank0() -> bool:
-    return _world() == 1 or dist.get_rank() == 0
 
 
 def batches_forever(dl: Iterable) -> Iterator[Any]:
@@ -1639,11 +1712,11 @@ class Checkpointer:
         self.dir = dir
 
     def save(self, st_x: StX, filename: str) -> None:
-        if _is_rank0():
+        if ddp.is_rank0():
             torch.save(st_x["model"].state_dict(), os.path.join(self.dir, filename))
 
     def remove_file(self, filename: str) -> None:
-        if _is_rank0():
+        if ddp.is_rank0():
             os.remove(os.path.join(self.dir, filename))
 
 

@@ -387,7 +387,7 @@ def test_state_dict_round_trip_and_set():
     assert b.scale == float(np.float32(0.7)) and b.value(3) == float(np.float32(0.5) * np.float32(0.7))
     assert b._block.numpy()[0] == 1 and not b._block.numpy()[5:68].any()   # the old knots are gone from the block
     c = LRSchedule.constant("cpu", 1.0)
-    c._mirror_block(a.host_block())
+    c.run_restored(None, {"schedule": a.host_block()})
     assert c.state_dict() == a.state_dict()
 
 

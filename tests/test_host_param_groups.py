@@ -224,7 +224,7 @@ def test_set_freeze_steps_and_the_state_dict():
     with pytest.raises(ValueError, match="end at"):
         ParamGroups(_params([5, 5])).load_state_dict(state)
     mirror = ParamGroups(_params())
-    mirror._mirror_block(g._block.numpy())
+    mirror.run_restored(None, {"groups": g._block.numpy()})
     assert mirror.lr_scales == g.lr_scales and mirror.frozen == g.frozen and mirror.weight_decays == g.weight_decays
     with pytest.raises(ValueError, match="not one of"):
         g.freeze(torch.nn.Parameter(torch.ones(1)))
@@ -294,7 +294,7 @@ def test_run_state_lists_the_table_behind_the_schedule_and_nothing_new_without_o
             kw["groups"] = ParamGroups(params)
         cls = kw.pop("cls")
         opt = cls(params[:4], params[4:], **kw)
-        regions, _, _ = C._tensor_regions(model, opt, None, None)
+        regions, _ = C.run_regions(model, opt, None, None)
         if "groups" in kw:
             assert next(t for name, t in regions if name == "optimizer.groups") is kw["groups"]._block
         return [name for name, _ in regions]
