@@ -27,11 +27,9 @@ SAVED, PARTIAL = 1, 2   # positive success codes (include/dctn_amd.h)
  EPS_FAMILY_BIGCORE_BF16X3) = range(6)
 SBS_MATRIX_CORE_SWEEP = 1 << 8   # OR-ed into the dtype argument of the dctn_convsbs_* calls
 SBS_WIDE_SWEEP = 1 << 9   # likewise: the backward on the wide family (convsbs_wide.hip) for any string it covers
-BATCH_SRC_U8_TABLE, BATCH_SRC_ROWS = 0, 1   # DCTN_BATCH_SRC_*: `src_kind` of dctn_batch_draw / dctn_batch_gather
-BATCH_IDENTITY_ORDER, BATCH_PAD_TAIL = 1, 2  # `flags` of dctn_batch_draw
-# Python side only: the source kind of `DeviceBatches.from_colour`, which goes through dctn_batch_draw_cols /
-# dctn_batch_gather_cols (entry points of their own: the C `src_kind` stays 0 / 1)
-BATCH_SRC_COLOUR = 2
+# DCTN_BATCH_SRC_*: `src_kind` of dctn_batch_call_t; dctn_batch_draw / dctn_batch_gather take the first two
+BATCH_SRC_U8_TABLE, BATCH_SRC_ROWS, BATCH_SRC_COLOUR = 0, 1, 2
+BATCH_IDENTITY_ORDER, BATCH_PAD_TAIL = 1, 2  # `flags` of a draw
 TRACE_HAS_REG, TRACE_HAS_GUARD, TRACE_HAS_ADAM, TRACE_HAS_SOURCE = 1, 2, 4, 8   # DCTN_TRACE_HAS_*: a record's `present`
 AUG_HFLIP = 1   # DCTN_AUG_HFLIP: `aug_flags` of dctn_batch_draw_aug / dctn_batch_draw_cols_aug
 
@@ -53,6 +51,19 @@ class FlatStep(ctypes.Structure):
 
 
 _FlatStepP = ctypes.POINTER(FlatStep)
+
+
+class BatchCall(ctypes.Structure):
+    """dctn_batch_call_t: every buffer, shape and option of one batch-source launch; what a kind or an operation does not
+    use stays None / 0."""
+    _fields_ = [("src", c_void), ("table", c_void), ("labels", c_void), ("sample_idx", c_void), ("x", c_void), ("y", c_void),
+                ("indices", c_void), ("state", c_void), ("n", c_i64), ("global_batch", c_i64), ("count", c_i64),
+                ("rank_offset", c_i64), ("row_len", c_i64), ("height", c_i64), ("width_px", c_i64), ("src_kind", c_int),
+                ("src_channels", c_int), ("width", c_int), ("flags", c_int), ("dtype", c_int), ("augment", c_int),
+                ("max_shift", c_int), ("aug_flags", c_int), ("fill", c_u32)]
+
+
+_BatchCallP = ctypes.POINTER(BatchCall)
 
 # name -> (restype, argtypes); mirrors include/dctn_amd.h one to one
 SIGNATURES = {
@@ -130,6 +141,9 @@ SIGNATURES = {
     "dctn_batch_gather_cols": (c_int, [c_void] * 7 + [c_i64] * 3 + [c_int] * 3 + [c_void]),
     "dctn_batch_draw_aug": (c_int, [c_void] * 7 + [c_i64] * 6 + [c_int] * 5 + [c_u32, c_void]),
     "dctn_batch_draw_cols_aug": (c_int, [c_void] * 7 + [c_i64] * 6 + [c_int] * 6 + [c_u32, c_void]),
+    "dctn_batch_call_bytes": (c_size, []),
+    "dctn_batch_draw_call": (c_int, [_BatchCallP, c_void]),
+    "dctn_batch_gather_call": (c_int, [_BatchCallP, c_void]),
     "dctn_state_max_regions": (c_int, []),
     "dctn_state_arena_bytes": (c_size, [_I64P, c_int]),
     "dctn_state_gather": (c_int, [_PtrP, _I64P, c_int, c_void, c_size, c_void, c_void]),

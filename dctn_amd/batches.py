@@ -20,6 +20,7 @@ augmentations after a resume, other ones on every replay of a captured graph.  `
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Callable, Dict, Iterator, List, Optional, Sequence, Tuple, Union
 
 import torch
@@ -344,7 +345,7 @@ class DeviceBatches:
         L.dtype_code(x_full)
         C, n, rest = x_full.shape[0], x_full.shape[1], tuple(x_full.shape[2:])
         self._plan(n, labels, batch_size, seed, shuffle, drop_last, rank, world)
-        self.augment = None
+        self._plan_augment(None, 0, 0, 1)   # rows have no height, width or source channels
         dev = self._device(None, x_full)
         self.kind, self.dtype = L.BATCH_SRC_ROWS, x_full.dtype
         self.src = x_full.to(dev).contiguous()
@@ -380,7 +381,7 @@ class DeviceBatches:
         self.kind, self.dtype = L.BATCH_SRC_COLOUR, dtype
         self.src = images_u8.to(dev).contiguous()
         self.table = table.to(dev)
-        self.row_len, self.channels, self.width = H * W, C, Wout
+        self.row_len, self.width = H * W, Wout
         self.x_shape = lambda count: (1, count, H, W, Wout)
         self._finish(labels, dev)
         return self
@@ -407,7 +408,7 @@ class DeviceBatches:
 
     def _plan_augment(self, augment: Optional[Augment], H: int, Wd: int, channels: int) -> None:
         """The augmentation's own errors, before the device as well; `_plan` has run."""
-        self.augment, self.height, self.width_px = augment, int(H), int(Wd)
+        self.augment, self.height, self.width_px, self.channels, self._fill = augment, int(H), int(Wd), int(channels), 0
         if augment is None:
             return
         if not isinstance(augment, Augment):
@@ -436,6 +437,21 @@ class DeviceBatches:
             dist.broadcast(self._state, src=0)
             self.seed = self.state_dict()["seed"]
         self._all = None   # arange(n) for the sequential passes, made on first use
+        # The one description of this source's launches (dctn_batch_call_t): everything that is stable for the source's
+        # life, written once.  `_draw` and `gather` write the outputs and what the two operations do not share.
+        assert L.lib().dctn_batch_call_bytes() == ctypes.sizeof(L.BatchCall)
+        aug = self.augment
+        self._call = L.BatchCall(
+            src=self.src.data_ptr(), table=None if self.table is None else self.table.data_ptr(),
+            labels=self.labels.data_ptr(), state=self._state.data_ptr(), n=self.n, global_batch=self.batch_size,
+            count=self.local_batch, rank_offset=self.rank * self.local_batch, row_len=self.row_len, height=self.height,
+            width_px=self.width_px, src_kind=self.kind, src_channels=self.channels, width=self.width,
+            dtype=L.dtype_code(torch.empty(0, dtype=self.dtype)), augment=aug is not None,
+            max_shift=0 if aug is None else aug.max_shift, aug_flags=0 if aug is None else aug.flags, fill=self._fill)
+        self._call_ref = ctypes.byref(self._call)
+        colour = "colour " if self.kind == L.BATCH_SRC_COLOUR else ""
+        self._what = {"draw": ("augmented " if aug is not None else "") + colour + "batch draw",
+                      "gather": colour + "batch gather"}
 
     # ---------------------------------------------------------------------------------------------- batches
     def __len__(self) -> int:
@@ -458,31 +474,11 @@ class DeviceBatches:
 
     def _draw(self, x: Tensor, y: Tensor, indices: Tensor, flags: int) -> None:
         self._check_out(x, y, indices, self.local_batch)
+        c = self._call
+        c.x, c.y, c.indices, c.flags = x.data_ptr(), y.data_ptr(), indices.data_ptr(), flags
+        c.count, c.augment = self.local_batch, self.augment is not None   # (a gather leaves its own there)
         with torch.cuda.device(self.device):
-            if self.augment is not None:
-                head = (self.src.data_ptr(), self.table.data_ptr(), self.labels.data_ptr(), x.data_ptr(), y.data_ptr(),
-                        indices.data_ptr(), self._state.data_ptr(), self.n, self.batch_size, self.local_batch,
-                        self.rank * self.local_batch, self.height, self.width_px)
-                tail = (flags, L.dtype_code(x), self.augment.max_shift, self.augment.flags, self._fill,
-                        L.stream_ptr(self.device))
-                if self.kind == L.BATCH_SRC_COLOUR:
-                    L.check(L.lib().dctn_batch_draw_cols_aug(*head, self.channels, self.width, *tail),
-                            "augmented colour batch draw")
-                else:
-                    L.check(L.lib().dctn_batch_draw_aug(*head, self.width, *tail), "augmented batch draw")
-                return
-            if self.kind == L.BATCH_SRC_COLOUR:
-                L.check(L.lib().dctn_batch_draw_cols(
-                    self.src.data_ptr(), self.table.data_ptr(), self.labels.data_ptr(), x.data_ptr(), y.data_ptr(),
-                    indices.data_ptr(), self._state.data_ptr(), self.n, self.batch_size, self.local_batch,
-                    self.rank * self.local_batch, self.row_len, self.channels, self.width, flags, L.dtype_code(x),
-                    L.stream_ptr(self.device)), "colour batch draw")
-                return
-            L.check(L.lib().dctn_batch_draw(
-                self.src.data_ptr(), None if self.table is None else self.table.data_ptr(), self.labels.data_ptr(),
-                x.data_ptr(), y.data_ptr(), indices.data_ptr(), self._state.data_ptr(), self.n, self.batch_size,
-                self.local_batch, self.rank * self.local_batch, self.row_len, self.width, self.kind, flags,
-                L.dtype_code(x), L.stream_ptr(self.device)), "batch draw")
+            L.check(L.lib().dctn_batch_draw_call(self._call_ref, L.stream_ptr(self.device)), self._what["draw"])
 
     def draw_into(self, x: Tensor, y: Tensor, indices: Tensor) -> None:
         """The next batch (this rank's shard of it) into caller-owned buffers: one launch, capturable.  With ``augment``
@@ -513,17 +509,11 @@ class DeviceBatches:
             raise ValueError("gather takes a non-empty int64 vector of sample numbers")
         idx = sample_idx.contiguous()
         x, y, indices = self.empty_batch(idx.numel())
+        c = self._call
+        c.x, c.y, c.indices = x.data_ptr(), y.data_ptr(), indices.data_ptr()
+        c.sample_idx, c.count, c.augment = idx.data_ptr(), idx.numel(), 0
         with torch.cuda.device(self.device):
-            if self.kind == L.BATCH_SRC_COLOUR:
-                L.check(L.lib().dctn_batch_gather_cols(
-                    self.src.data_ptr(), self.table.data_ptr(), self.labels.data_ptr(), idx.data_ptr(), x.data_ptr(),
-                    y.data_ptr(), indices.data_ptr(), self.n, idx.numel(), self.row_len, self.channels, self.width,
-                    L.dtype_code(x), L.stream_ptr(self.device)), "colour batch gather")
-                return x, y, indices
-            L.check(L.lib().dctn_batch_gather(
-                self.src.data_ptr(), None if self.table is None else self.table.data_ptr(), self.labels.data_ptr(),
-                idx.data_ptr(), x.data_ptr(), y.data_ptr(), indices.data_ptr(), self.n, idx.numel(), self.row_len,
-                self.width, self.kind, L.dtype_code(x), L.stream_ptr(self.device)), "batch gather")
+            L.check(L.lib().dctn_batch_gather_call(self._call_ref, L.stream_ptr(self.device)), self._what["gather"])
         return x, y, indices
 
     def __iter__(self) -> Iterator[Tuple[Tensor, Tensor, Tensor]]:

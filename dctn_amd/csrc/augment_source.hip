@@ -19,10 +19,9 @@
 // region is at most AUG_WAVE_LDS = 13 KiB (64 x 64 x 3 is 12 KiB), which keeps the workgroup below the 64 KiB that need no
 // opt-in; a larger sample is DCTN_ERR_UNSUPPORTED before any launch.
 #include "draw_order.h"
+#include "batch_plan.h"
 
 namespace {
-
-constexpr unsigned AUG_WAVE_LDS = 13u * 1024u;   // bytes of one wave's sample region
 
 struct AugArgs {   // passed by value in the kernel argument
   BatchArgs b;     // row_len = H * Wd pixels
@@ -296,12 +295,6 @@ __global__ __launch_bounds__(BATCH_THREADS) void aug_cols_k(AugArgs a) {
   if (threadIdx.x == 0) batch_take_ticket(a.b, head.k);
 }
 
-// [grey / colour][dtype code]
-const char* const AUG_NAMES[2][3] = {
-    {"aug_draw_u8_f32", "aug_draw_u8_f64", "aug_draw_u8_bf16"},
-    {"aug_draw_cols_f32", "aug_draw_cols_f64", "aug_draw_cols_bf16"},
-};
-
 template <typename S>
 void aug_launch_u8(const AugArgs& a, dim3 g, size_t lds, hipStream_t st) {
   const dim3 b(BATCH_THREADS);
@@ -331,72 +324,19 @@ void aug_launch_typed(const AugArgs& a, bool grey, int channels, dim3 g, size_t 
   }
 }
 
-// everything is decided here, on the host, before any launch: the siblings' rules in the siblings' order (null, shape,
-// dtype, unsupported).  The grey form has one source channel, which goes through a (256, width) table.
-int aug_launch(BatchArgs b, int64_t n, int64_t G, int64_t count, int64_t offset, int64_t height, int64_t width_px, bool grey,
-               int channels, int width, int flags, int dtype, int max_shift, int aug_flags, uint32_t fill, void* stream) {
-  if (!b.src || !b.table || !b.labels || !b.x || !b.y || !b.indices || !b.state) return DCTN_ERR_NULL;
-  if (n < 1 || n >= (int64_t)1 << 31 || count < 1 || count >= (int64_t)1 << 31) return DCTN_ERR_BAD_SHAPE;
-  if (height < 1 || height >= (int64_t)1 << 31 || width_px < 1 || width_px >= (int64_t)1 << 31) return DCTN_ERR_BAD_SHAPE;
-  const int64_t pixels = height * width_px;
-  if (pixels >= (int64_t)1 << 31 || channels < 1 || width < 1) return DCTN_ERR_BAD_SHAPE;
-  if (G < 1 || G > n || offset < 0 || offset + count > G) return DCTN_ERR_BAD_SHAPE;
-  if (flags & ~DCTN_BATCH_IDENTITY_ORDER) return DCTN_ERR_BAD_SHAPE;   // an evaluation pass (DCTN_BATCH_PAD_TAIL) is not augmented
-  if (max_shift < 0 || max_shift >= 1 << 15 || (aug_flags & ~DCTN_AUG_HFLIP)) return DCTN_ERR_BAD_SHAPE;
-  if (channels < 4 && (fill >> (8 * channels))) return DCTN_ERR_BAD_SHAPE;   // fill bytes above the source channels
-  if (dtype != DCTN_F32 && dtype != DCTN_F64 && dtype != DCTN_BF16) return DCTN_ERR_BAD_DTYPE;
-  if (width > 4 || (!grey && (channels > 4 || width < channels || width > channels + 1))) return DCTN_ERR_UNSUPPORTED;
-  const int64_t region = (pixels * (channels > 4 ? 4 : channels) + 15) / 16 * 16;
-  if (region > (int64_t)AUG_WAVE_LDS) return DCTN_ERR_UNSUPPORTED;
-  AugArgs a = {};
-  a.b = b;
-  a.b.n = (unsigned)n, a.b.Bl = (unsigned)count, a.b.row_len = (unsigned)pixels, a.b.width = (unsigned)width;
-  a.b.identity = (flags & DCTN_BATCH_IDENTITY_ORDER) ? 1u : 0u;
-  a.b.G = (unsigned)G, a.b.S = (unsigned)(n / G), a.b.offset = (unsigned)offset;
-  a.b.bits = 2;
-  while (a.b.bits < 31 && ((int64_t)1 << a.b.bits) < n) ++a.b.bits;
-  a.H = (unsigned)height, a.Wd = (unsigned)width_px, a.m = (unsigned)max_shift;
-  a.hflip = (aug_flags & DCTN_AUG_HFLIP) ? 1u : 0u, a.fill = fill, a.region = (unsigned)region;
-  long long wgs = (count + BATCH_WAVES - 1) / BATCH_WAVES;
-  const long long cap = dctn_dev().cus < BATCH_MAX_WGS ? (dctn_dev().cus < 1 ? 1 : dctn_dev().cus) : BATCH_MAX_WGS;
-  if (wgs > cap) wgs = cap;
-  const dim3 g((unsigned)wgs);
-  const size_t lds = (size_t)region * BATCH_WAVES;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == DCTN_F32) aug_launch_typed<float>(a, grey, channels, g, lds, st);
-  else if (dtype == DCTN_F64) aug_launch_typed<double>(a, grey, channels, g, lds, st);
-  else aug_launch_typed<bf16_t>(a, grey, channels, g, lds, st);
-  DCTN_CHECK_LAUNCH();
-  dctn_set_last_kernel(AUG_NAMES[grey ? 0 : 1][dtype]);
-  return DCTN_OK;
-}
-
-BatchArgs aug_pointers(const void* src, const void* table, const void* labels, void* x, void* y, void* indices, void* state) {
-  BatchArgs b = {};
-  b.src = src, b.table = table, b.labels = static_cast<const long long*>(labels);
-  b.x = x, b.y = static_cast<long long*>(y), b.indices = static_cast<long long*>(indices);
-  b.state = static_cast<BatchState*>(state);
-  return b;
-}
-
 }  // namespace
 
-extern "C" {
-
-int dctn_batch_draw_aug(const void* src, const void* table, const void* labels, void* x, void* y, void* indices, void* state,
-                        int64_t n, int64_t global_batch, int64_t local_batch, int64_t rank_offset, int64_t height,
-                        int64_t width_px, int width, int flags, int dtype, int max_shift, int aug_flags, uint32_t fill,
-                        void* stream) {
-  return aug_launch(aug_pointers(src, table, labels, x, y, indices, state), n, global_batch, local_batch, rank_offset,
-                    height, width_px, true, 1, width, flags, dtype, max_shift, aug_flags, fill, stream);
+// batch_call.hip has checked and planned the launch: a draw of one of the two byte sources.  The grey form has one
+// source channel, which goes through a (256, width) table.
+void augment_source_launch(const dctn_batch_call_t& c, const BatchPlan& p, hipStream_t st) {
+  AugArgs a = {};
+  a.b = batch_args(c, p);
+  a.H = (unsigned)c.height, a.Wd = (unsigned)c.width_px, a.m = (unsigned)c.max_shift;
+  a.hflip = (c.aug_flags & DCTN_AUG_HFLIP) ? 1u : 0u, a.fill = c.fill, a.region = p.region;
+  const bool grey = c.src_kind == DCTN_BATCH_SRC_U8_TABLE;
+  const dim3 g(p.wgs);
+  const size_t lds = (size_t)p.region * BATCH_WAVES;
+  if (c.dtype == DCTN_F32) aug_launch_typed<float>(a, grey, p.channels, g, lds, st);
+  else if (c.dtype == DCTN_F64) aug_launch_typed<double>(a, grey, p.channels, g, lds, st);
+  else aug_launch_typed<bf16_t>(a, grey, p.channels, g, lds, st);
 }
-
-int dctn_batch_draw_cols_aug(const void* src, const void* table, const void* labels, void* x, void* y, void* indices,
-                             void* state, int64_t n, int64_t global_batch, int64_t local_batch, int64_t rank_offset,
-                             int64_t height, int64_t width_px, int src_channels, int width, int flags, int dtype,
-                             int max_shift, int aug_flags, uint32_t fill, void* stream) {
-  return aug_launch(aug_pointers(src, table, labels, x, y, indices, state), n, global_batch, local_batch, rank_offset,
-                    height, width_px, false, src_channels, width, flags, dtype, max_shift, aug_flags, fill, stream);
-}
-
-}  // extern "C"

@@ -13,6 +13,7 @@
 // share the row.  The launch is latency-bound, not bandwidth-bound: at cfg2's batch (1024 x 784 pixels, bf16, Q = 2) it
 // reads 0.8 MB and writes 3.2 MB, a few microseconds of dependent round trips (block -> order -> row -> table -> store).
 #include "draw_order.h"
+#include "batch_plan.h"
 
 namespace {
 
@@ -138,14 +139,6 @@ __global__ __launch_bounds__(BATCH_THREADS) void batch_rows_k(BatchArgs a) {
   if (DRAW && threadIdx.x == 0) batch_take_ticket(a, head.k);
 }
 
-// [draw / gather][source kind][dtype code]
-const char* const BATCH_NAMES[2][2][3] = {
-    {{"batch_draw_u8_f32", "batch_draw_u8_f64", "batch_draw_u8_bf16"},
-     {"batch_draw_rows_f32", "batch_draw_rows_f64", "batch_draw_rows_bf16"}},
-    {{"batch_gather_u8_f32", "batch_gather_u8_f64", "batch_gather_u8_bf16"},
-     {"batch_gather_rows_f32", "batch_gather_rows_f64", "batch_gather_rows_bf16"}},
-};
-
 template <typename S, bool DRAW, bool PAD>
 void batch_launch_padded(const BatchArgs& a, int kind, dim3 g, hipStream_t st) {
   const dim3 b(BATCH_THREADS);
@@ -169,65 +162,19 @@ void batch_launch_typed(const BatchArgs& a, int kind, bool pad, dim3 g, hipStrea
   batch_launch_padded<S, DRAW, false>(a, kind, g, st);
 }
 
-// everything is decided here, on the host, before any launch
 template <bool DRAW>
-int batch_launch(BatchArgs a, int64_t n, int64_t G, int64_t count, int64_t offset, int64_t row_len, int width, int kind,
-                 int flags, int dtype, void* stream) {
-  if (!a.src || !a.labels || !a.x || !a.y || !a.indices || (DRAW ? !a.state : !a.sample_idx)) return DCTN_ERR_NULL;
-  if (kind != DCTN_BATCH_SRC_U8_TABLE && kind != DCTN_BATCH_SRC_ROWS) return DCTN_ERR_BAD_SHAPE;
-  if (kind == DCTN_BATCH_SRC_U8_TABLE && !a.table) return DCTN_ERR_NULL;
-  if (n < 1 || n >= (int64_t)1 << 31 || count < 1 || count >= (int64_t)1 << 31) return DCTN_ERR_BAD_SHAPE;
-  if (row_len < 1 || row_len >= (int64_t)1 << 31 || width < 1) return DCTN_ERR_BAD_SHAPE;
-  if (DRAW && (G < 1 || G > n || offset < 0 || offset + count > G)) return DCTN_ERR_BAD_SHAPE;
-  if (DRAW && (flags & ~(DCTN_BATCH_IDENTITY_ORDER | DCTN_BATCH_PAD_TAIL))) return DCTN_ERR_BAD_SHAPE;
-  if (DRAW && (flags & DCTN_BATCH_PAD_TAIL) && !(flags & DCTN_BATCH_IDENTITY_ORDER)) return DCTN_ERR_BAD_SHAPE;
-  if (dtype != DCTN_F32 && dtype != DCTN_F64 && dtype != DCTN_BF16) return DCTN_ERR_BAD_DTYPE;
-  if (width > 4) return DCTN_ERR_UNSUPPORTED;
-  const bool pad = DRAW && (flags & DCTN_BATCH_PAD_TAIL);
-  a.n = (unsigned)n, a.Bl = (unsigned)count, a.row_len = (unsigned)row_len, a.width = (unsigned)width;
-  if (DRAW) {
-    a.identity = (flags & DCTN_BATCH_IDENTITY_ORDER) ? 1u : 0u;
-    a.G = (unsigned)G, a.S = (unsigned)(pad ? (n + G - 1) / G : n / G), a.offset = (unsigned)offset;
-    a.bits = 2;
-    while (a.bits < 31 && ((int64_t)1 << a.bits) < n) ++a.bits;
-  }
-  long long wgs = (count + BATCH_WAVES - 1) / BATCH_WAVES;
-  const long long cap = dctn_dev().cus < BATCH_MAX_WGS ? (dctn_dev().cus < 1 ? 1 : dctn_dev().cus) : BATCH_MAX_WGS;
-  if (wgs > cap) wgs = cap;
-  const dim3 g((unsigned)wgs);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == DCTN_F32) batch_launch_typed<float, DRAW>(a, kind, pad, g, st);
-  else if (dtype == DCTN_F64) batch_launch_typed<double, DRAW>(a, kind, pad, g, st);
-  else batch_launch_typed<bf16_t, DRAW>(a, kind, pad, g, st);
-  DCTN_CHECK_LAUNCH();
-  dctn_set_last_kernel(BATCH_NAMES[DRAW ? 0 : 1][kind][dtype]);
-  return DCTN_OK;
+void batch_launch_op(const BatchArgs& a, const dctn_batch_call_t& c, const BatchPlan& p, hipStream_t st) {
+  const dim3 g(p.wgs);
+  if (c.dtype == DCTN_F32) batch_launch_typed<float, DRAW>(a, c.src_kind, p.pad, g, st);
+  else if (c.dtype == DCTN_F64) batch_launch_typed<double, DRAW>(a, c.src_kind, p.pad, g, st);
+  else batch_launch_typed<bf16_t, DRAW>(a, c.src_kind, p.pad, g, st);
 }
 
 }  // namespace
 
-extern "C" {
-
-size_t dctn_batch_state_bytes(void) { return sizeof(BatchState); }
-
-int dctn_batch_draw(const void* src, const void* table, const void* labels, void* x, void* y, void* indices, void* state,
-                    int64_t n, int64_t global_batch, int64_t local_batch, int64_t rank_offset, int64_t row_len, int width,
-                    int src_kind, int flags, int dtype, void* stream) {
-  BatchArgs a = {};
-  a.src = src, a.table = table, a.labels = static_cast<const long long*>(labels);
-  a.x = x, a.y = static_cast<long long*>(y), a.indices = static_cast<long long*>(indices);
-  a.state = static_cast<BatchState*>(state);
-  return batch_launch<true>(a, n, global_batch, local_batch, rank_offset, row_len, width, src_kind, flags, dtype, stream);
+// batch_call.hip has checked and planned the launch
+void batch_source_launch(const dctn_batch_call_t& c, const BatchPlan& p, hipStream_t st) {
+  const BatchArgs a = batch_args(c, p);
+  if (p.draw) batch_launch_op<true>(a, c, p, st);
+  else batch_launch_op<false>(a, c, p, st);
 }
-
-int dctn_batch_gather(const void* src, const void* table, const void* labels, const void* sample_idx, void* x, void* y,
-                      void* indices, int64_t n, int64_t count, int64_t row_len, int width, int src_kind, int dtype,
-                      void* stream) {
-  BatchArgs a = {};
-  a.src = src, a.table = table, a.labels = static_cast<const long long*>(labels);
-  a.sample_idx = static_cast<const long long*>(sample_idx);
-  a.x = x, a.y = static_cast<long long*>(y), a.indices = static_cast<long long*>(indices);
-  return batch_launch<false>(a, n, 1, count, 0, row_len, width, src_kind, 0, dtype, stream);
-}
-
-}  // extern "C"

@@ -15,6 +15,7 @@
 // bf16 (two neighbouring values share a word), and a 64-bank pair for float64.  Byte-indexed lookups of independent
 // pixels conflict at random in any layout; this one spreads them over every bank.
 #include "draw_order.h"
+#include "batch_plan.h"
 
 namespace {
 
@@ -95,12 +96,6 @@ __global__ __launch_bounds__(BATCH_THREADS) void colour_k(BatchArgs a) {
   if (DRAW && threadIdx.x == 0) batch_take_ticket(a, head.k);
 }
 
-// [draw / gather][dtype code]
-const char* const COLOUR_NAMES[2][3] = {
-    {"colour_draw_f32", "colour_draw_f64", "colour_draw_bf16"},
-    {"colour_gather_f32", "colour_gather_f64", "colour_gather_bf16"},
-};
-
 template <typename S, int C, bool DRAW, bool PAD>
 void colour_launch_width(const BatchArgs& a, int width, dim3 g, hipStream_t st) {
   const dim3 b(BATCH_THREADS);
@@ -126,61 +121,19 @@ void colour_launch_typed(const BatchArgs& a, int channels, int width, bool pad, 
   colour_launch_padded<S, DRAW, false>(a, channels, width, g, st);
 }
 
-// everything is decided here, on the host, before any launch: batch_launch's rules, with the two widths in place of one
 template <bool DRAW>
-int colour_launch(BatchArgs a, int64_t n, int64_t G, int64_t count, int64_t offset, int64_t pixels, int channels, int width,
-                  int flags, int dtype, void* stream) {
-  if (!a.src || !a.table || !a.labels || !a.x || !a.y || !a.indices || (DRAW ? !a.state : !a.sample_idx)) return DCTN_ERR_NULL;
-  if (n < 1 || n >= (int64_t)1 << 31 || count < 1 || count >= (int64_t)1 << 31) return DCTN_ERR_BAD_SHAPE;
-  if (pixels < 1 || pixels >= (int64_t)1 << 31 || channels < 1 || width < 1) return DCTN_ERR_BAD_SHAPE;
-  if (DRAW && (G < 1 || G > n || offset < 0 || offset + count > G)) return DCTN_ERR_BAD_SHAPE;
-  if (DRAW && (flags & ~(DCTN_BATCH_IDENTITY_ORDER | DCTN_BATCH_PAD_TAIL))) return DCTN_ERR_BAD_SHAPE;
-  if (DRAW && (flags & DCTN_BATCH_PAD_TAIL) && !(flags & DCTN_BATCH_IDENTITY_ORDER)) return DCTN_ERR_BAD_SHAPE;
-  if (dtype != DCTN_F32 && dtype != DCTN_F64 && dtype != DCTN_BF16) return DCTN_ERR_BAD_DTYPE;
-  if (channels > 4 || width > 4 || width < channels || width > channels + 1) return DCTN_ERR_UNSUPPORTED;
-  const bool pad = DRAW && (flags & DCTN_BATCH_PAD_TAIL);
-  a.n = (unsigned)n, a.Bl = (unsigned)count, a.row_len = (unsigned)pixels, a.width = (unsigned)width;
-  if (DRAW) {
-    a.identity = (flags & DCTN_BATCH_IDENTITY_ORDER) ? 1u : 0u;
-    a.G = (unsigned)G, a.S = (unsigned)(pad ? (n + G - 1) / G : n / G), a.offset = (unsigned)offset;
-    a.bits = 2;
-    while (a.bits < 31 && ((int64_t)1 << a.bits) < n) ++a.bits;
-  }
-  long long wgs = (count + BATCH_WAVES - 1) / BATCH_WAVES;
-  const long long cap = dctn_dev().cus < BATCH_MAX_WGS ? (dctn_dev().cus < 1 ? 1 : dctn_dev().cus) : BATCH_MAX_WGS;
-  if (wgs > cap) wgs = cap;
-  const dim3 g((unsigned)wgs);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == DCTN_F32) colour_launch_typed<float, DRAW>(a, channels, width, pad, g, st);
-  else if (dtype == DCTN_F64) colour_launch_typed<double, DRAW>(a, channels, width, pad, g, st);
-  else colour_launch_typed<bf16_t, DRAW>(a, channels, width, pad, g, st);
-  DCTN_CHECK_LAUNCH();
-  dctn_set_last_kernel(COLOUR_NAMES[DRAW ? 0 : 1][dtype]);
-  return DCTN_OK;
+void colour_launch_op(const BatchArgs& a, const dctn_batch_call_t& c, const BatchPlan& p, hipStream_t st) {
+  const dim3 g(p.wgs);
+  if (c.dtype == DCTN_F32) colour_launch_typed<float, DRAW>(a, p.channels, c.width, p.pad, g, st);
+  else if (c.dtype == DCTN_F64) colour_launch_typed<double, DRAW>(a, p.channels, c.width, p.pad, g, st);
+  else colour_launch_typed<bf16_t, DRAW>(a, p.channels, c.width, p.pad, g, st);
 }
 
 }  // namespace
 
-extern "C" {
-
-int dctn_batch_draw_cols(const void* src, const void* table, const void* labels, void* x, void* y, void* indices,
-                         void* state, int64_t n, int64_t global_batch, int64_t local_batch, int64_t rank_offset,
-                         int64_t pixels, int src_channels, int width, int flags, int dtype, void* stream) {
-  BatchArgs a = {};
-  a.src = src, a.table = table, a.labels = static_cast<const long long*>(labels);
-  a.x = x, a.y = static_cast<long long*>(y), a.indices = static_cast<long long*>(indices);
-  a.state = static_cast<BatchState*>(state);
-  return colour_launch<true>(a, n, global_batch, local_batch, rank_offset, pixels, src_channels, width, flags, dtype, stream);
+// batch_call.hip has checked and planned the launch
+void colour_source_launch(const dctn_batch_call_t& c, const BatchPlan& p, hipStream_t st) {
+  const BatchArgs a = batch_args(c, p);
+  if (p.draw) colour_launch_op<true>(a, c, p, st);
+  else colour_launch_op<false>(a, c, p, st);
 }
-
-int dctn_batch_gather_cols(const void* src, const void* table, const void* labels, const void* sample_idx, void* x, void* y,
-                           void* indices, int64_t n, int64_t count, int64_t pixels, int src_channels, int width, int dtype,
-                           void* stream) {
-  BatchArgs a = {};
-  a.src = src, a.table = table, a.labels = static_cast<const long long*>(labels);
-  a.sample_idx = static_cast<const long long*>(sample_idx);
-  a.x = x, a.y = static_cast<long long*>(y), a.indices = static_cast<long long*>(indices);
-  return colour_launch<false>(a, n, 1, count, 0, pixels, src_channels, width, 0, dtype, stream);
-}
-
-}  // extern "C"

@@ -819,7 +819,9 @@ int dctn_core_dropout_mask(void* const* mask, const int64_t* numel, int n_cores,
  * DCTN_ERR_UNSUPPORTED (width > 4).  No workspace.
  * dctn_last_kernel(): batch_{draw,gather}_{u8,rows}_{f32,f64,bf16}.
  * ------------------------------------------------------------------------------------------ */
-enum { DCTN_BATCH_SRC_U8_TABLE = 0, DCTN_BATCH_SRC_ROWS = 1 };
+/* DCTN_BATCH_SRC_COLOUR (version 513) is the colour source below: dctn_batch_call_t names it; dctn_batch_draw and
+ * dctn_batch_gather refuse it (DCTN_ERR_BAD_SHAPE), as they refuse an unknown kind. */
+enum { DCTN_BATCH_SRC_U8_TABLE = 0, DCTN_BATCH_SRC_ROWS = 1, DCTN_BATCH_SRC_COLOUR = 2 };
 enum { DCTN_BATCH_IDENTITY_ORDER = 1 };   /* `flags` of dctn_batch_draw */
 /* `flags` of dctn_batch_draw, version 504: with DCTN_BATCH_IDENTITY_ORDER only.  A macro beside the enum, not a member of
  * it: tests/test_host_batches.py takes every `DCTN_BATCH_x = n` of this header for the complete list of the version 503
@@ -836,8 +838,8 @@ int dctn_batch_gather(const void* src, const void* table, const void* labels, co
 /* Raw colour images (version 506; reference: get_cifar10_colored_data_loaders, dctn/dataset_loading.py:331-389 -
  * to_tensor, the optional per-channel centring and scaling, the optional constant channel, the per-channel nu).  Every
  * value of that pipeline is a function of one byte and its channel, so one 256-row table per channel holds them all
- * (dctn_amd/batches.py `colour_table`).  A third source form with entry points of its own; `src_kind` above keeps its two
- * values.
+ * (dctn_amd/batches.py `colour_table`).  A third source form with entry points of its own: the `src_kind` argument of
+ * dctn_batch_draw / dctn_batch_gather keeps its two values.
  *   src   = (n, P, C) uint8, the channels interleaved (what torchvision's CIFAR10 `.data` holds), P = pixels,
  *           C = src_channels;
  *   table = (W, 256) values of `dtype`, W = width: row c is channel c's table;
@@ -908,6 +910,68 @@ int dctn_batch_draw_cols_aug(const void* src, const void* table, const void* lab
                              void* state, int64_t n, int64_t global_batch, int64_t local_batch, int64_t rank_offset,
                              int64_t height, int64_t width_px, int src_channels, int width, int flags, int dtype,
                              int max_shift, int aug_flags, uint32_t fill, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * One description of a batch-source launch (version 513).  The three source kinds, the two operations and the augmentation
+ * are one data movement with options; dctn_batch_call_t names every buffer, shape and option of a launch once, and one
+ * entry point per operation takes it - two, because a draw advances the state block and a gather has none.  The six entry
+ * points above are conveniences over these two: each fills the struct and launches the same kernel with the same
+ * arguments.  Everything said above about the order, the state block, the kinds, the augmentation and the buffer contract
+ * holds here word for word.
+ *
+ * dctn_batch_call_t: dctn_batch_call_bytes() = 160 bytes on the HOST, read during the call only (the caller may keep one
+ * for the life of a source and rewrite x, y, indices per launch; a captured launch holds no reference to it).  Every
+ * pointer in it is a DEVICE pointer:
+ *   const void* src          the data set, laid out as its kind says
+ *   const void* table        the kind's table; DCTN_BATCH_SRC_ROWS ignores it (may be NULL)
+ *   const void* labels       n int64 values
+ *   const void* sample_idx   gather: `count` int64 sample numbers.  A draw ignores it
+ *   void *x, *y, *indices    the outputs, fully overwritten
+ *   void*       state        draw: the 16-byte block.  A gather ignores it
+ *   int64_t n                samples of the data set
+ *   int64_t global_batch, rank_offset   draw: G and the first position of this launch's shard.  A gather ignores them
+ *   int64_t count            this launch's samples: the local_batch of a draw, the length of sample_idx of a gather
+ *   int64_t row_len          pixels P of a sample (U8_TABLE, COLOUR), elements R of a row (ROWS)
+ *   int64_t height, width_px augmented draws: the image's H and Wd, and row_len must equal H * Wd.  Ignored otherwise
+ *   int src_kind             DCTN_BATCH_SRC_U8_TABLE, DCTN_BATCH_SRC_ROWS or DCTN_BATCH_SRC_COLOUR
+ *   int src_channels         COLOUR: C.  Ignored by the other kinds (U8_TABLE has one source channel)
+ *   int width                U8_TABLE: table columns Q;  ROWS: channels C;  COLOUR: output columns W
+ *   int flags                draw: DCTN_BATCH_IDENTITY_ORDER, DCTN_BATCH_PAD_TAIL.  A gather ignores it
+ *   int dtype                DCTN_F32 / DCTN_F64 / DCTN_BF16
+ *   int augment              0: the plain kernels.  Not 0: the augmented ones - also with max_shift = 0 and no flip, which
+ *                            moves the bytes unchanged through the augmented kernel.  Draws of U8_TABLE and COLOUR only
+ *   int max_shift, aug_flags; uint32_t fill    the augmentation's arguments.  Ignored when augment is 0
+ * Return codes, all decided on the host before any launch, in this order:
+ *   DCTN_ERR_NULL         the struct; src, labels, x, y, indices; state (draw) or sample_idx (gather)
+ *   DCTN_ERR_BAD_SHAPE    an unknown src_kind; augment with a gather or with DCTN_BATCH_SRC_ROWS
+ *   DCTN_ERR_NULL         table, unless the kind is DCTN_BATCH_SRC_ROWS - only the kind says whether there is one, so it is
+ *                         looked at in front of the table; the older entry points answered in this order and still do
+ *   DCTN_ERR_BAD_SHAPE    every shape rule stated above: n, count, row_len outside [1, 2^31); width or src_channels < 1;
+ *                         a draw's global_batch, rank_offset and flags (an augmented draw accepts the identity order
+ *                         only); an augmented draw's height, width_px, their product against row_len, max_shift,
+ *                         aug_flags and fill
+ *   DCTN_ERR_BAD_DTYPE
+ *   DCTN_ERR_UNSUPPORTED  width > 4; COLOUR: src_channels > 4 or width outside src_channels .. src_channels + 1; an
+ *                         augmented sample of more than 13 KiB
+ * No workspace; the calls only enqueue and can be captured.  dctn_last_kernel(): the names stated with each kind above.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  const void *src, *table, *labels;
+  const void* sample_idx;
+  void *x, *y, *indices;
+  void* state;
+  int64_t n, global_batch, count, rank_offset;
+  int64_t row_len;
+  int64_t height, width_px;
+  int src_kind;
+  int src_channels, width, flags, dtype;
+  int augment;
+  int max_shift, aug_flags;
+  uint32_t fill;
+} dctn_batch_call_t;
+size_t dctn_batch_call_bytes(void);
+int dctn_batch_draw_call(const dctn_batch_call_t* call, void* stream);
+int dctn_batch_gather_call(const dctn_batch_call_t* call, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Whole-run snapshots (version 508; the reference's runner only has --load-model-state): everything a training run keeps

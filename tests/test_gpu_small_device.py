@@ -349,7 +349,7 @@ def fold_row(Wn, L):
 
 # ------------------------------------------------------------------------------------------------ helper kernels
 def _capped_by_cus(units, const):
-    """min(cus, const) workgroups (batch_source.hip:195, colour_source.hip:150, augment_source.hip:361,
+    """min(cus, const) workgroups (batch_call.hip: batch_plan, for the three batch-source kernel files;
     core_dropout.hip:177): the CU count is the bound, and it binds"""
     return lambda cus: cus < const and units > cus
 
@@ -390,11 +390,11 @@ def helper_rows():
     from tests.test_gpu_run_state import REGIONS
     state_tiles = sum(ceil_div(nbytes, 4096) for nbytes, _, _ in REGIONS)                 # run_state.hip:192
     return [
-        {"name": "batch_source", "site": "batch_source.hip: batch_launch", "run": batches,     # 2100 samples, 4 waves a workgroup
+        {"name": "batch_source", "site": "batch_call.hip: batch_plan (the grey and row kernels)", "run": batches,     # 2100 samples, 4 waves a workgroup
          "regime": [alternative("the grid cap is the CU count", _capped_by_cus(ceil_div(2100, 4), 256))]},
-        {"name": "colour_source", "site": "colour_source.hip: colour_launch", "run": colour,   # 1100 samples
+        {"name": "colour_source", "site": "batch_call.hip: batch_plan (the colour kernels)", "run": colour,   # 1100 samples
          "regime": [alternative("the grid cap is the CU count", _capped_by_cus(ceil_div(1100, 4), 256))]},
-        {"name": "augment_source", "site": "augment_source.hip: augment_launch", "run": augment,   # 1030 samples
+        {"name": "augment_source", "site": "batch_call.hip: batch_plan (the augmented kernels)", "run": augment,   # 1030 samples
          "regime": [alternative("the grid cap is the CU count", _capped_by_cus(ceil_div(1030, 4), 256))]},
         {"name": "core_dropout", "site": "core_dropout.hip: drop_launch", "run": dropout,       # 2051 blocks of 4 elements, 1024 lanes
          "regime": [alternative("the grid cap is the CU count", _capped_by_cus(ceil_div(1025 + 1026, 1024), 256))]},

@@ -182,9 +182,11 @@ def test_kernel_names_come_from_a_table():
     """tests/test_host_buffer_contract.py asks for a GUARDED entry for every LITERAL name in a dctn_set_last_kernel call;
     the augmented draws report theirs through a table, and tests/test_gpu_augment.py holds them to the buffer contract."""
     src = open(os.path.join(ROOT, "dctn_amd", "csrc", "augment_source.hip")).read()
-    calls = re.findall(r"dctn_set_last_kernel\((.*?)\);", src, re.S)
-    assert len(calls) == 1 and '"' not in calls[0] and "AUG_NAMES[" in calls[0]
-    names = set(re.findall(r'"(aug_[a-z0-9_]+)"', src))
+    assert "dctn_set_last_kernel" not in src
+    call = open(os.path.join(ROOT, "dctn_amd", "csrc", "batch_call.hip")).read()   # the one table of all batch kernels
+    calls = re.findall(r"dctn_set_last_kernel\((.*?)\);", call, re.S)
+    assert len(calls) == 1 and '"' not in calls[0] and "BATCH_KERNEL_NAMES[" in calls[0]
+    names = set(re.findall(r'"(aug_[a-z0-9_]+)"', call))
     assert names == {f"aug_draw_{kind}_{dt}" for kind in ("u8", "cols") for dt in ("f32", "f64", "bf16")}
     # the order has one definition: the shared header, not restated
     assert '#include "draw_order.h"' in src and "perm_once(unsigned" not in src and "struct BatchState" not in src

@@ -72,6 +72,7 @@ def test_version_state_block_size_and_constants():
     enums = dict(re.findall(r"DCTN_(BATCH_[A-Z0-9_]+)\s*=\s*(\d+)", header))
     assert {k: int(v) for k, v in enums.items()} == {"BATCH_SRC_U8_TABLE": _lib.BATCH_SRC_U8_TABLE,
                                                      "BATCH_SRC_ROWS": _lib.BATCH_SRC_ROWS,
+                                                     "BATCH_SRC_COLOUR": _lib.BATCH_SRC_COLOUR,
                                                      "BATCH_IDENTITY_ORDER": _lib.BATCH_IDENTITY_ORDER}
 
 
@@ -109,10 +110,13 @@ def test_entry_points_validate_their_arguments_without_a_device():
 
 def test_kernel_names_come_from_a_table():
     """tests/test_host_buffer_contract.py asks for a GUARDED entry for every LITERAL name in a dctn_set_last_kernel call;
-    the batch kernels report theirs through a table, and tests/test_gpu_batches.py holds them to the contract."""
-    src = open(os.path.join(ROOT, "dctn_amd", "csrc", "batch_source.hip")).read()
+    the batch kernels report theirs through a table, and tests/test_gpu_batches.py holds them to the contract.  The
+    table and its one call are batch_call.hip's, for all three kernel files."""
+    assert "dctn_set_last_kernel" not in open(os.path.join(ROOT, "dctn_amd", "csrc", "batch_source.hip")).read()
+    src = open(os.path.join(ROOT, "dctn_amd", "csrc", "batch_call.hip")).read()
     calls = re.findall(r"dctn_set_last_kernel\((.*?)\);", src, re.S)
-    assert calls == ["BATCH_NAMES[DRAW ? 0 : 1][kind][dtype]"]
+    assert calls == ["BATCH_KERNEL_NAMES[draw ? 0 : 1][c->augment ? 1 : 0][c->src_kind][c->dtype]"]
+    assert len(re.findall(r'"([a-z0-9_]+)"', src)) == 24   # (the table holds nothing but today's 12 + 6 + 6 names)
     names = set(re.findall(r'"(batch_[a-z0-9_]+)"', src))
     assert names == {f"batch_{op}_{kind}_{dt}" for op in ("draw", "gather") for kind in ("u8", "rows")
                      for dt in ("f32", "f64", "bf16")}

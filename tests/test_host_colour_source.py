@@ -87,9 +87,11 @@ def test_kernel_names_come_from_a_table():
     the colour kernels report theirs through a table, as the batch kernels do, and tests/test_gpu_colour_source.py holds
     them to the buffer contract."""
     src = open(os.path.join(ROOT, "dctn_amd", "csrc", "colour_source.hip")).read()
-    calls = re.findall(r"dctn_set_last_kernel\((.*?)\);", src, re.S)
-    assert len(calls) == 1 and '"' not in calls[0] and "COLOUR_NAMES[" in calls[0]
-    names = set(re.findall(r'"(colour_[a-z0-9_]+)"', src))
+    assert "dctn_set_last_kernel" not in src
+    call = open(os.path.join(ROOT, "dctn_amd", "csrc", "batch_call.hip")).read()   # the one table of all batch kernels
+    calls = re.findall(r"dctn_set_last_kernel\((.*?)\);", call, re.S)
+    assert len(calls) == 1 and '"' not in calls[0] and "BATCH_KERNEL_NAMES[" in calls[0]
+    names = set(re.findall(r'"(colour_[a-z0-9_]+)"', call))
     assert names == {f"colour_{op}_{dt}" for op in ("draw", "gather") for dt in ("f32", "f64", "bf16")}
     # the order has one definition: both sources take it from the shared header, and neither restates it
     batch = open(os.path.join(ROOT, "dctn_amd", "csrc", "batch_source.hip")).read()

@@ -83,7 +83,7 @@ def _files_with_call_sites():
 
 def test_every_cu_dependent_file_has_a_row():
     found = _files_with_call_sites()
-    assert len(found) >= 17, found
+    assert len(found) >= 15, found   # (17 until the three batch-source files got one planner, batch_call.hip)
     sites = " ".join(row["site"] for row in S.PLANS)
     named = set(re.findall(r"[a-z0-9_]+\.(?:hip|h)", sites))
     missing = sorted(set(found) - named - set(EXEMPT))
