@@ -53,6 +53,14 @@ class FlatStep(ctypes.Structure):
 _FlatStepP = ctypes.POINTER(FlatStep)
 
 
+class WeightEma(ctypes.Structure):
+    """dctn_weight_ema_t: the n float32 averages and the 32-byte block of a weight average, both device pointers."""
+    _fields_ = [("ema", c_void), ("block", c_void)]
+
+
+_WeightEmaP = ctypes.POINTER(WeightEma)
+
+
 class BatchCall(ctypes.Structure):
     """dctn_batch_call_t: every buffer, shape and option of one batch-source launch; what a kind or an operation does not
     use stays None / 0."""
@@ -126,6 +134,13 @@ SIGNATURES = {
     "dctn_adam_flat_step": (c_int, [_FlatStepP, c_void, c_void, ctypes.c_double, ctypes.c_double, ctypes.c_float,
                                     ctypes.c_float, c_void]),
     "dctn_sgd_flat_step": (c_int, [_FlatStepP, c_void, ctypes.c_float, ctypes.c_float, c_int, c_void]),
+    "dctn_weight_ema_bytes": (c_size, []),
+    "dctn_weight_ema_weight": (c_int, [c_void, c_i64, ctypes.POINTER(ctypes.c_float)]),
+    "dctn_adam_flat_step_ema": (c_int, [_FlatStepP, _WeightEmaP, c_void, c_void, ctypes.c_double, ctypes.c_double,
+                                        ctypes.c_float, ctypes.c_float, c_void]),
+    "dctn_sgd_flat_step_ema": (c_int, [_FlatStepP, _WeightEmaP, c_void, ctypes.c_float, ctypes.c_float, c_int, c_void]),
+    "dctn_weight_ema_apply": (c_int, [c_void, c_void, c_void, c_i64, c_int, c_void]),
+    "dctn_weight_ema_restore": (c_int, [c_void, c_void, c_i64, c_int, c_void]),
     "dctn_step_trace_head_bytes": (c_size, []),
     "dctn_step_trace_record_bytes": (c_size, []),
     "dctn_step_trace_record": (c_int, [c_void] * 9 + [c_int, c_i64, c_int, c_int, c_void]),

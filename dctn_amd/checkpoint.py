@@ -193,18 +193,32 @@ def load_arrays(path: str, expected: Optional[Sequence[Tuple[str, str, Sequence[
                       for r in manifest["regions"]}
 
 
-def read_model_state(path: str) -> Dict[str, Tensor]:
+def read_model_state(path: str, ema: bool = False) -> Dict[str, Tensor]:
     """The model's state_dict (``epses.i``, ``linear.weight``, ``linear.bias``, ``p``) of a snapshot file as CPU tensors,
-    for ``model.load_state_dict`` / ``--load-model-state``-style use without building the run.  Every digest is checked."""
+    for ``model.load_state_dict`` / ``--load-model-state``-style use without building the run.  Every digest is checked.
+    ``ema=True``: every entry that lies in the optimizer's flat buffer comes from the run's weight average
+    (`training.WeightEMA`) instead, its float32 values cast to the entry's dtype (round to nearest even, as
+    ``WeightEMA.apply()``); ValueError for a file without one."""
     manifest, arena = read_file(path)
     verify_digests(manifest, arena, path)
     regions = {r["name"]: r for r in manifest["regions"]}
+    averaged = regions.get("optimizer.ema")
+    if ema and averaged is None:
+        raise ValueError(f"{path}: the run was saved without a weight average (no region 'optimizer.ema')")
     state = {}
     for e in manifest["model"]:
         r = regions[e["region"]]
-        n = _ITEMSIZE[e["dtype"]] * int(np.prod(e["shape"], dtype=np.int64))
+        item = _ITEMSIZE[e["dtype"]]
+        n = item * int(np.prod(e["shape"], dtype=np.int64))
         if e["offset"] + n > r["bytes"]:
             raise ValueError(f"{path}: model entry {e['key']!r} reaches past region {r['name']!r}")
+        if ema and e["region"] == "optimizer.flat":   # the same elements of the float32 average
+            start = averaged["offset"] + e["offset"] // item * 4
+            if (e["offset"] // item) * 4 + n // item * 4 > averaged["bytes"]:
+                raise ValueError(f"{path}: model entry {e['key']!r} reaches past the weight average")
+            raw = torch.from_numpy(arena[start: start + n // item * 4].copy()).view(torch.float32)
+            state[e["key"]] = raw.to(_DTYPES[e["dtype"]]).reshape(e["shape"])
+            continue
         start = r["offset"] + e["offset"]
         raw = torch.from_numpy(arena[start: start + n].copy())
         state[e["key"]] = raw.view(_DTYPES[e["dtype"]]).reshape(e["shape"])
@@ -296,7 +310,8 @@ def run_regions(model, optimizer, batch_source, guard, trace=None):
 class RunState:
     """The device state of a training run as named regions.  Each part of the run (`run_parts`) lists its own, and
     `RunState` puts the slot's name in front: a `FlatAdam` / `FlatSGD` as ``optimizer.`` its flat parameter buffer, the
-    moments (or the momentum buffer), the master copy, the blocks of its `LRSchedule` and its `ParamGroups` table, the
+    moments (or the momentum buffer), the master copy, the values and the block of its `WeightEMA`, the blocks of its
+    `LRSchedule` and its `ParamGroups` table, the
     16-byte step block and ``sq_sum``, each only when the optimizer has it (a file and a run that disagree about an option
     are refused at that entry; runs without an option keep their region lists and their files); every entry of the
     model's state_dict that does not live in the flat buffer (the buffer ``p``; without an optimizer every parameter) as
@@ -363,6 +378,12 @@ class RunState:
                 raise NotImplementedError(f"RunState: region {name!r} starts at an address that is no multiple of 4 "
                                           "(a bfloat16 view at an odd element): nothing was launched")
 
+    def _refuse_applied(self, what: str) -> None:
+        """While a `training.WeightEMA` is applied the flat buffer holds the averaged weights, not the live ones."""
+        ema = getattr(self.optimizer, "ema", None)
+        if ema is not None:
+            ema._refuse_applied(what)
+
     def _host_scalars(self) -> Dict[str, Any]:
         scalars = ((slot, part.run_host()) for slot, part in self._parts)
         return {slot: host for slot, host in scalars if host is not None}
@@ -373,6 +394,7 @@ class RunState:
         hands back (``num_iters_done``, an early stopper's counters, the best value seen)."""
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("RunState.snapshot() records events and copies to the host: not during a graph capture")
+        self._refuse_applied("RunState.snapshot()")
         extras = json.loads(json.dumps({} if extras is None else extras))   # JSON-able, and a copy
         self._check_alignment()
         manifest = build_manifest(self.entries, [(0, 0)] * len(self.entries), self._model_entries, self._host_scalars(),
@@ -412,6 +434,7 @@ class RunState:
         device's digests of what it read are held to the manifest's."""
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("RunState.load() writes the run's buffers from the host: not during a graph capture")
+        self._refuse_applied("RunState.load()")
         manifest, arena = read_file(path)
         check_regions(manifest, self.entries, path)
         self._check_host(manifest["host"])

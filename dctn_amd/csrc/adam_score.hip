@@ -10,6 +10,7 @@
 #include "grad_guard.h"
 #include "lr_schedule.h"
 #include "param_groups.h"
+#include "weight_ema.h"
 
 #include <cmath>
 
@@ -101,11 +102,12 @@ struct AdamSegment {
   bool frozen;
 };
 
-template <typename S, bool MASTER, bool GUARD>
+template <typename S, bool MASTER, bool GUARD, bool EMA>
 __device__ __forceinline__ void adam_grouped_elem(long long i, S* __restrict__ w, float* __restrict__ wm,
                                                   const S* __restrict__ g, float* __restrict__ ea,
                                                   float* __restrict__ eas, bool reg, const AdamCoef& k,
-                                                  const AdamSegment& sg, float coef, float& part) {
+                                                  const AdamSegment& sg, float coef, float& part,
+                                                  float* __restrict__ em, float omd) {
   if (sg.frozen) {   // only the regulariser's value: no gradient read, no store
     if (reg) {
       const float wi = MASTER ? wm[i] : (float)w[i];
@@ -121,16 +123,18 @@ __device__ __forceinline__ void adam_grouped_elem(long long i, S* __restrict__ w
   w[i] = (S)wi;
   if (MASTER) wm[i] = wi;
   ea[i] = m, eas[i] = v;
+  if constexpr (EMA) em[i] = weight_ema_elem(em[i], weight_ema_kept<S, MASTER>(wi), omd);
 }
 
-template <typename S, bool VEC, bool MASTER, bool GUARD, bool SCHED>
+template <typename S, bool VEC, bool MASTER, bool GUARD, bool SCHED, bool EMA>
 __device__ __forceinline__ void adam_grouped_body(S* __restrict__ w, float* __restrict__ wm, const S* __restrict__ g,
                                                   float* __restrict__ ea, float* __restrict__ eas,
                                                   float* __restrict__ sq_sum, AdamState* __restrict__ state, long long n,
                                                   long long n_reg, const AdamCoef& k, const GradGuardBlock* guard,
-                                                  const LrScheduleBlock* sched, ParamGroupBlock* groups) {
+                                                  const LrScheduleBlock* sched, ParamGroupBlock* groups,
+                                                  WeightEma ema) {
   __shared__ float red[16];
-  __shared__ float decision[2];                       // halted, coef
+  __shared__ float decision[EMA ? 3 : 2];             // halted, coef; EMA: the launch's weight
   __shared__ long long seg_end[DCTN_PG_MAX_SEGMENTS];
   __shared__ float seg_step[DCTN_PG_MAX_SEGMENTS], seg_bc2[DCTN_PG_MAX_SEGMENTS], seg_wd[DCTN_PG_MAX_SEGMENTS];
   __shared__ int seg_frozen[DCTN_PG_MAX_SEGMENTS];
@@ -138,9 +142,13 @@ __device__ __forceinline__ void adam_grouped_body(S* __restrict__ w, float* __re
   int t = 0, my_steps = 0;
   float lr = 0.f;
   bool my_live = false;   // wave 0: this lane's segment is in use and not frozen
+  [[maybe_unused]] WeightEmaLane ema_lane{0, 0.f};   // lane 0
   if (threadIdx.x < 64) {   // wave 0, every lane
     const int lane = threadIdx.x;
     const ParamGroupLane sg = param_group_lane_load(groups, lane);
+    if constexpr (EMA) {
+      if (lane == 0) decision[2] = (ema_lane = weight_ema_lane_load(ema.block)).omd;
+    }
     if constexpr (SCHED) {
       const LrScheduleLane knot = lr_schedule_lane_load(sched, lane);
       t = __hip_atomic_load(&state->steps_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
@@ -173,6 +181,9 @@ __device__ __forceinline__ void adam_grouped_body(S* __restrict__ w, float* __re
     if (decision[0] != 0.f) return;   // the whole workgroup, before any store and before the ticket
     coef = decision[1];
   }
+  [[maybe_unused]] float omd = 0.f;
+  [[maybe_unused]] float* __restrict__ em = nullptr;
+  if constexpr (EMA) omd = decision[2], em = ema.values;
   const int n_seg = seg_count;
   ParamGroupCursor cur{0, param_group_end(seg_end, 0, n_seg)};
   AdamSegment sg{seg_step[0], seg_bc2[0], seg_wd[0], seg_frozen[0] != 0};
@@ -200,8 +211,10 @@ __device__ __forceinline__ void adam_grouped_body(S* __restrict__ w, float* __re
         AdamCoef ks = k;
         ks.wd = sg.wd;
         float wi[4], gi[4], mi[4], vi[4];
+        [[maybe_unused]] float ei[4];
         if (MASTER) load4(wm + i, wi); else load4(w + i, wi);
         load4(g + i, gi), load4(ea + i, mi), load4(eas + i, vi);
+        if constexpr (EMA) load4(em + i, ei);
 #pragma unroll
         for (int e = 0; e < 4; ++e) gi[e] = clipped<GUARD>(gi[e], coef);
 #pragma unroll
@@ -209,17 +222,22 @@ __device__ __forceinline__ void adam_grouped_body(S* __restrict__ w, float* __re
           wi[e] = adam_elem(wi[e], gi[e], mi[e], vi[e], i + e < n_reg, ks, sg.step, sg.bc2_sqrt, part);
         store4(ea + i, mi), store4(eas + i, vi), store4(w + i, wi);
         if (MASTER) store4(wm + i, wi);
+        if constexpr (EMA) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) ei[e] = weight_ema_elem(ei[e], weight_ema_kept<S, MASTER>(wi[e]), omd);
+          store4(em + i, ei);
+        }
       } else {   // an end inside the vector: element by element, each with its own segment's constants and stores
         for (int e = 0; e < 4; ++e) {
           follow(cur, sg, i + e);
-          adam_grouped_elem<S, MASTER, GUARD>(i + e, w, wm, g, ea, eas, i + e < n_reg, k, sg, coef, part);
+          adam_grouped_elem<S, MASTER, GUARD, EMA>(i + e, w, wm, g, ea, eas, i + e < n_reg, k, sg, coef, part, em, omd);
         }
       }
     }
   }
   for (long long i = n_vec + tid; i < n; i += nthr) {
     follow(cur, sg, i);
-    adam_grouped_elem<S, MASTER, GUARD>(i, w, wm, g, ea, eas, i < n_reg, k, sg, coef, part);
+    adam_grouped_elem<S, MASTER, GUARD, EMA>(i, w, wm, g, ea, eas, i < n_reg, k, sg, coef, part, em, omd);
   }
   for (int off = 32; off > 0; off >>= 1) part += __shfl_down(part, off, 64);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
@@ -240,6 +258,7 @@ __device__ __forceinline__ void adam_grouped_body(S* __restrict__ w, float* __re
       if (threadIdx.x == 0) {
         state->steps_done = t;
         if constexpr (SCHED) state->lr = lr;   // the GLOBAL rate of this step, before any segment's scale
+        if constexpr (EMA) weight_ema_advance(ema.block, ema_lane);
         state->ticket = 0u;
       }
     }
@@ -253,18 +272,24 @@ __global__ __launch_bounds__(1024) void adam_l2_k(S* __restrict__ w, float* __re
                                                  long long n_reg, AdamCoef k, G... guard_block) {
   // G holds a const GradGuardBlock* (GUARD), a const LrScheduleBlock* (SCHED), a ParamGroupBlock* (GROUPED), any of them
   // in that order, or nothing: the plain kernel, parameter for parameter
+  // and behind them a WeightEma (EMA, weight_ema.h): the average's values and block
   constexpr bool GUARD = pack_has_v<const GradGuardBlock*, G...>, SCHED = pack_has_v<const LrScheduleBlock*, G...>;
+  constexpr bool EMA = pack_has_v<WeightEma, G...>;
+  [[maybe_unused]] WeightEma ema{nullptr, nullptr};
+  if constexpr (EMA) ema = pack_get<WeightEma>(guard_block...);
   if constexpr (pack_has_v<ParamGroupBlock*, G...>) {   // GROUPED: a body of its own; the rest of this one is untouched
     const GradGuardBlock* guard = nullptr;
     const LrScheduleBlock* sched = nullptr;
     if constexpr (GUARD) guard = pack_get<const GradGuardBlock*>(guard_block...);
     if constexpr (SCHED) sched = pack_get<const LrScheduleBlock*>(guard_block...);
-    adam_grouped_body<S, VEC, MASTER, GUARD, SCHED>(w, wm, g, ea, eas, sq_sum, state, n, n_reg, k, guard, sched,
-                                                    pack_get<ParamGroupBlock*>(guard_block...));
+    adam_grouped_body<S, VEC, MASTER, GUARD, SCHED, EMA>(w, wm, g, ea, eas, sq_sum, state, n, n_reg, k, guard, sched,
+                                                         pack_get<ParamGroupBlock*>(guard_block...), ema);
     return;
   }
   __shared__ float red[16];
-  __shared__ float scale[GUARD ? 4 : 2];
+  constexpr int OMD = GUARD ? 4 : 2;   // EMA: the launch's weight, behind the other published values
+  __shared__ float scale[OMD + (EMA ? 1 : 0)];
+  [[maybe_unused]] WeightEmaLane ema_lane{0, 0.f};   // thread 0
   if constexpr (GUARD) {
     if (threadIdx.x == 0) {
       const GradGuardBlock* guard = pack_get<const GradGuardBlock*>(guard_block...);
@@ -289,6 +314,7 @@ __global__ __launch_bounds__(1024) void adam_l2_k(S* __restrict__ w, float* __re
       t = __hip_atomic_load(&state->steps_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
       lr = __hip_atomic_load(&state->lr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+    if constexpr (EMA) scale[OMD] = (ema_lane = weight_ema_lane_load(ema.block)).omd;
     // The two bias corrections in float64, once per workgroup, rounded once - what torch's host arithmetic gives.  In
     // float32 the difference 1 - beta2^t cancels: at t = 1 it is 0.001 with the absolute error of 0.999, a relative
     // 6e-5 in every update of the first steps.  (From t itself, not as running products, which drift.)
@@ -302,20 +328,30 @@ __global__ __launch_bounds__(1024) void adam_l2_k(S* __restrict__ w, float* __re
     if (scale[2] != 0.f) return;   // the whole workgroup, before any store and before the ticket
     coef = scale[3];
   }
+  [[maybe_unused]] float omd = 0.f;
+  [[maybe_unused]] float* __restrict__ em = nullptr;
+  if constexpr (EMA) omd = scale[OMD], em = ema.values;
   float part = 0.f;
   const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, nthr = (long long)gridDim.x * blockDim.x;
   const long long n_vec = VEC ? (n & ~3LL) : 0;
   if (VEC) {
     for (long long i = tid * 4; i < n_vec; i += nthr * 4) {
       float wi[4], gi[4], mi[4], vi[4];
+      [[maybe_unused]] float ei[4];
       if (MASTER) load4(wm + i, wi); else load4(w + i, wi);
       load4(g + i, gi), load4(ea + i, mi), load4(eas + i, vi);
+      if constexpr (EMA) load4(em + i, ei);
 #pragma unroll
       for (int e = 0; e < 4; ++e) gi[e] = clipped<GUARD>(gi[e], coef);
 #pragma unroll
       for (int e = 0; e < 4; ++e) wi[e] = adam_elem(wi[e], gi[e], mi[e], vi[e], i + e < n_reg, k, step, bc2_sqrt, part);
       store4(ea + i, mi), store4(eas + i, vi), store4(w + i, wi);
       if (MASTER) store4(wm + i, wi);
+      if constexpr (EMA) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ei[e] = weight_ema_elem(ei[e], weight_ema_kept<S, MASTER>(wi[e]), omd);
+        store4(em + i, ei);
+      }
     }
   }
   for (long long i = n_vec + tid; i < n; i += nthr) {
@@ -325,6 +361,7 @@ __global__ __launch_bounds__(1024) void adam_l2_k(S* __restrict__ w, float* __re
     w[i] = (S)wi;
     if (MASTER) wm[i] = wi;
     ea[i] = m, eas[i] = v;
+    if constexpr (EMA) em[i] = weight_ema_elem(em[i], weight_ema_kept<S, MASTER>(wi), omd);
   }
   for (int off = 32; off > 0; off >>= 1) part += __shfl_down(part, off, 64);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
@@ -343,6 +380,7 @@ __global__ __launch_bounds__(1024) void adam_l2_k(S* __restrict__ w, float* __re
     if (drawn == gridDim.x - 1) {   // plain vector stores; the next launch starts from ticket 0 again
       state->steps_done = t;
       if constexpr (SCHED) state->lr = lr;   // the rate this step used (no workgroup of a scheduled launch reads it)
+      if constexpr (EMA) weight_ema_advance(ema.block, ema_lane);
       state->ticket = 0u;
     }
   }
@@ -360,6 +398,7 @@ struct AdamStep {
   void *exp_avg, *exp_avg_sq;
   AdamCoef k;
   hipStream_t st;
+  const dctn_weight_ema_t* ema;   // null: no average
 };
 
 // The one launcher, for every pack: the vector or the scalar kernel by alignment
@@ -367,26 +406,30 @@ template <typename S, bool MASTER, typename... G> void adam_launch(const AdamSte
   const dctn_flat_step_t& d = a.d;
   const size_t esz = sizeof(S);
   const bool vec = ((uintptr_t)d.params | (uintptr_t)d.grads) % (4 * esz) == 0 &&
-                   ((uintptr_t)a.exp_avg | (uintptr_t)a.exp_avg_sq | (uintptr_t)d.master) % 16 == 0;
+                   ((uintptr_t)a.exp_avg | (uintptr_t)a.exp_avg_sq | (uintptr_t)d.master | (uintptr_t)(a.ema ? a.ema->ema : nullptr)) % 16 == 0;
   const auto kernel = vec ? adam_l2_k<S, true, MASTER, G...> : adam_l2_k<S, false, MASTER, G...>;
   hipLaunchKernelGGL(kernel, dim3(adam_blocks_for(d.n)), dim3(1024), 0, a.st, (S*)d.params, (float*)d.master,
                      (const S*)d.grads, (float*)a.exp_avg, (float*)a.exp_avg_sq, (float*)d.sq_sum, (AdamState*)d.state,
                      (long long)d.n, (long long)d.n_reg, a.k, pack...);
 }
 
-// The pack is the optional blocks the step has, in the order adam_l2_k expects: guard, schedule, group table
+// The pack is the optional blocks the step has, in the order adam_l2_k expects: guard, schedule, group table, and the
+// average (a pair by value) behind them
 template <typename S, bool MASTER> void adam_dispatch(const AdamStep& a) {
-  with_blocks([&](auto... pack) { adam_launch<S, MASTER>(a, pack...); }, (const GradGuardBlock*)a.d.guard,
-              (const LrScheduleBlock*)a.d.schedule, (ParamGroupBlock*)a.d.groups);
+  with_blocks([&](auto... pack) {
+    if (a.ema) adam_launch<S, MASTER>(a, pack..., WeightEma{(float*)a.ema->ema, (WeightEmaBlock*)a.ema->block});
+    else adam_launch<S, MASTER>(a, pack...);
+  }, (const GradGuardBlock*)a.d.guard, (const LrScheduleBlock*)a.d.schedule, (ParamGroupBlock*)a.d.groups);
 }
 
 // Validates and launches.  master_first: the _scheduled / _grouped entry points answer a master copy beside a dtype
 // that is not bf16 in front of every other check; everywhere else it is part of the dtype check, the last one
 int adam_step(const dctn_flat_step_t& d, void* exp_avg, void* exp_avg_sq, double beta1, double beta2, float eps,
-              float weight_decay, void* stream, bool master_first = false) {
+              float weight_decay, void* stream, bool master_first = false, const dctn_weight_ema_t* ema = nullptr) {
   const bool master_dtype = d.master && d.dtype != DCTN_BF16;   // a master copy goes with bf16 parameters
   if (master_first && master_dtype) return DCTN_ERR_BAD_DTYPE;
   if (!d.params || !d.grads || !exp_avg || !exp_avg_sq || !d.state) return DCTN_ERR_NULL;
+  if (ema && (!ema->ema || !ema->block)) return DCTN_ERR_NULL;
   if (d.n < 1 || d.n_reg < 0 || d.n_reg > d.n) return DCTN_ERR_BAD_SHAPE;
   if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return DCTN_ERR_BAD_SHAPE;   // torch raises ValueError
   if ((d.dtype != DCTN_F32 && d.dtype != DCTN_BF16) || master_dtype) return DCTN_ERR_BAD_DTYPE;
@@ -394,7 +437,7 @@ int adam_step(const dctn_flat_step_t& d, void* exp_avg, void* exp_avg_sq, double
   k.b1 = (float)beta1, k.omb1 = (float)(1.0 - beta1), k.b2 = (float)beta2, k.omb2 = (float)(1.0 - beta2);
   k.ln_b1 = std::log(beta1), k.ln_b2 = std::log(beta2);   // beta = 0: -inf, and 1 - beta^t = -expm1(-inf) = 1
   k.eps = eps, k.wd = d.groups ? 0.f : weight_decay, k.two_l2 = 2.f * d.l2;   // a table carries every segment's decay
-  const AdamStep a{d, exp_avg, exp_avg_sq, k, (hipStream_t)stream};
+  const AdamStep a{d, exp_avg, exp_avg_sq, k, (hipStream_t)stream, ema};
   if (d.master) adam_dispatch<bf16_t, true>(a);
   else if (d.dtype == DCTN_F32) adam_dispatch<float, false>(a);
   else adam_dispatch<bf16_t, false>(a);
@@ -461,6 +504,27 @@ __global__ __launch_bounds__(1024) void ce_score_k(const S* __restrict__ logits,
     for (int k = 0; k < 16; ++k) total += red[threadIdx.x][k];
     acc[threadIdx.x] += total;
   }
+}
+
+// The averaged weights in place of the live ones, for a scoring pass: stash = params, then params = (S)ema with the
+// step kernels' round-to-nearest-even cast.  A master copy is never touched.
+template <typename S>
+__global__ __launch_bounds__(256) void weight_ema_apply_k(S* __restrict__ w, S* __restrict__ stash,
+                                                          const float* __restrict__ em, long long n) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    stash[i] = w[i];
+    w[i] = (S)em[i];
+  }
+}
+template <typename S>
+__global__ __launch_bounds__(256) void weight_ema_restore_k(S* __restrict__ w, const S* __restrict__ stash, long long n) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+    w[i] = stash[i];
+}
+unsigned ema_copy_blocks_for(long long n) {
+  long long b = (n + 255) / 256;
+  if (b > 1024) b = 1024;
+  return (unsigned)(b < 1 ? 1 : b);
 }
 
 }  // namespace
@@ -531,6 +595,52 @@ int dctn_adam_l2_step_grouped(void* master_or_null, void* params, const void* gr
   const dctn_flat_step_t d = {params, master_or_null, grads, sq_sum, state, guard_or_null, schedule_or_null, groups,
                               n, n_reg, l2, dtype};
   return adam_step(d, exp_avg, exp_avg_sq, beta1, beta2, eps, 0.f, stream, true);
+}
+
+size_t dctn_weight_ema_bytes(void) { return sizeof(WeightEmaBlock); }
+
+// Host only: validates a HOST copy of the block and forms the weight of the launch at `updates` with the kernels' function
+int dctn_weight_ema_weight(const void* host_block, int64_t updates, float* one_minus_decay) {
+  if (!host_block || !one_minus_decay) return DCTN_ERR_NULL;
+  const WeightEmaBlock& b = *(const WeightEmaBlock*)host_block;
+  if (!(std::isfinite(b.decay) && b.decay >= 0.f && b.decay < 1.f)) return DCTN_ERR_BAD_SHAPE;
+  if ((b.flags & ~DCTN_EMA_WARMUP) != 0u) return DCTN_ERR_BAD_SHAPE;
+  if (b.updates < 0 || updates < 0 || updates > 0x7fffffffLL) return DCTN_ERR_BAD_SHAPE;
+  *one_minus_decay = weight_ema_omd(b.decay, b.flags, (int)updates);
+  return DCTN_OK;
+}
+
+// ema_or_null == NULL is dctn_adam_flat_step
+int dctn_adam_flat_step_ema(const dctn_flat_step_t* step, const dctn_weight_ema_t* ema_or_null, void* exp_avg,
+                            void* exp_avg_sq, double beta1, double beta2, float eps, float weight_decay, void* stream) {
+  if (!step) return DCTN_ERR_NULL;
+  return adam_step(*step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, stream, false, ema_or_null);
+}
+
+int dctn_weight_ema_apply(void* params, void* stash, const void* ema, int64_t n, int dtype, void* stream) {
+  if (!params || !stash || !ema) return DCTN_ERR_NULL;
+  if (n < 1) return DCTN_ERR_BAD_SHAPE;
+  if (dtype != DCTN_F32 && dtype != DCTN_BF16) return DCTN_ERR_BAD_DTYPE;
+  const dim3 grid(ema_copy_blocks_for(n)), block(256);
+  if (dtype == DCTN_F32)
+    hipLaunchKernelGGL(weight_ema_apply_k<float>, grid, block, 0, (hipStream_t)stream, (float*)params, (float*)stash, (const float*)ema, (long long)n);
+  else
+    hipLaunchKernelGGL(weight_ema_apply_k<bf16_t>, grid, block, 0, (hipStream_t)stream, (bf16_t*)params, (bf16_t*)stash, (const float*)ema, (long long)n);
+  DCTN_CHECK_LAUNCH();
+  return DCTN_OK;
+}
+
+int dctn_weight_ema_restore(void* params, const void* stash, int64_t n, int dtype, void* stream) {
+  if (!params || !stash) return DCTN_ERR_NULL;
+  if (n < 1) return DCTN_ERR_BAD_SHAPE;
+  if (dtype != DCTN_F32 && dtype != DCTN_BF16) return DCTN_ERR_BAD_DTYPE;
+  const dim3 grid(ema_copy_blocks_for(n)), block(256);
+  if (dtype == DCTN_F32)
+    hipLaunchKernelGGL(weight_ema_restore_k<float>, grid, block, 0, (hipStream_t)stream, (float*)params, (const float*)stash, (long long)n);
+  else
+    hipLaunchKernelGGL(weight_ema_restore_k<bf16_t>, grid, block, 0, (hipStream_t)stream, (bf16_t*)params, (const bf16_t*)stash, (long long)n);
+  DCTN_CHECK_LAUNCH();
+  return DCTN_OK;
 }
 
 size_t dctn_param_groups_bytes(void) { return sizeof(ParamGroupBlock); }

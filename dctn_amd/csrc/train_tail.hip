@@ -16,6 +16,7 @@
 #include "grad_guard.h"
 #include "lr_schedule.h"
 #include "param_groups.h"
+#include "weight_ema.h"
 
 namespace {
 
@@ -133,14 +134,18 @@ __device__ __forceinline__ float sgd_elem(float wi, float gi, float* __restrict_
 // rounded product rate * lr_scale), first_step = (the SEGMENT's steps == 0) and frozen flag through LDS.  Every lane
 // walks a cursor over the ends as its elements increase.  A frozen element only adds w * w below n_reg: its gradient
 // and momentum are not read and nothing of it is stored.  The table's weight_decay is not used: sgd_l2_k has none.
-template <typename S, bool MASTER, bool GUARD, bool SCHED>
+// EMA (the pack ends with a WeightEma, and always holds a StepStateBlock*): every element the step stores to also moves
+// its average, from the value the step keeps for it (weight_ema.h).  Lane 0 loads the block's three cells beside
+// steps_done and publishes the launch's weight; the last ticket writes updates + 1 and that weight.  Without a schedule
+// or a group table the rate is state->lr and first_step is steps_done == 0, as the grouped form reads them.
+template <typename S, bool MASTER, bool GUARD, bool SCHED, bool EMA>
 __device__ __forceinline__ void sgd_grouped_body(S* __restrict__ w, float* __restrict__ wm, const S* __restrict__ g,
                                                  float* __restrict__ buf, float* __restrict__ sq_sum, long long n,
                                                  long long n_reg, float momentum, float l2, const GradGuardBlock* guard,
                                                  StepStateBlock* state, const LrScheduleBlock* sched,
-                                                 ParamGroupBlock* groups) {
+                                                 ParamGroupBlock* groups, WeightEma ema) {
   __shared__ float red[4];
-  __shared__ float decision[2];                       // halted, coef
+  __shared__ float decision[EMA ? 3 : 2];             // halted, coef; EMA: the launch's weight
   __shared__ long long seg_end[DCTN_PG_MAX_SEGMENTS];
   __shared__ float seg_lr[DCTN_PG_MAX_SEGMENTS];
   __shared__ int seg_first[DCTN_PG_MAX_SEGMENTS], seg_frozen[DCTN_PG_MAX_SEGMENTS];
@@ -148,9 +153,13 @@ __device__ __forceinline__ void sgd_grouped_body(S* __restrict__ w, float* __res
   int steps_done = 0, my_steps = 0;
   float rate = 0.f;
   bool my_live = false;   // wave 0: this lane's segment is in use and not frozen
+  [[maybe_unused]] WeightEmaLane ema_lane{0, 0.f};   // lane 0
   if (threadIdx.x < 64) {   // wave 0, every lane
     const int lane = threadIdx.x;
     const ParamGroupLane sg = param_group_lane_load(groups, lane);
+    if constexpr (EMA) {
+      if (lane == 0) decision[2] = (ema_lane = weight_ema_lane_load(ema.block)).omd;
+    }
     if constexpr (SCHED) {
       const LrScheduleLane knot = lr_schedule_lane_load(sched, lane);
       steps_done = __hip_atomic_load(&state->steps_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -179,6 +188,9 @@ __device__ __forceinline__ void sgd_grouped_body(S* __restrict__ w, float* __res
     if (decision[0] != 0.f) return;   // the whole workgroup, before any store and before the ticket
     coef = decision[1];
   }
+  [[maybe_unused]] float omd = 0.f;
+  [[maybe_unused]] float* __restrict__ em = nullptr;
+  if constexpr (EMA) omd = decision[2], em = ema.values;
   const int n_seg = seg_count;
   ParamGroupCursor cur{0, param_group_end(seg_end, 0, n_seg)};
   float lr = seg_lr[0];
@@ -200,6 +212,7 @@ __device__ __forceinline__ void sgd_grouped_body(S* __restrict__ w, float* __res
                               momentum, two_l2, first_step, part);
     w[i] = (S)wi;
     if (MASTER) wm[i] = wi;
+    if constexpr (EMA) em[i] = weight_ema_elem(em[i], weight_ema_kept<S, MASTER>(wi), omd);
   }
   for (int off = 32; off > 0; off >>= 1) part += __shfl_down(part, off, 64);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
@@ -218,6 +231,7 @@ __device__ __forceinline__ void sgd_grouped_body(S* __restrict__ w, float* __res
       if (threadIdx.x == 0) {
         state->steps_done = steps_done + 1;
         if constexpr (SCHED) state->lr = rate;   // the GLOBAL rate of this step, before any segment's scale
+        if constexpr (EMA) weight_ema_advance(ema.block, ema_lane);
         state->ticket = 0u;
       }
     }
@@ -232,21 +246,59 @@ __global__ __launch_bounds__(256) void sgd_l2_k(S* __restrict__ w, float* __rest
   // G holds a const GradGuardBlock* (GUARD), a StepStateBlock* and a const LrScheduleBlock* (SCHED), a ParamGroupBlock*
   // (GROUPED, with the StepStateBlock* whether or not there is a schedule), in that order, or nothing: the plain kernel,
   // parameter for parameter
+  // and behind them a WeightEma (EMA, always with the StepStateBlock*): the average's values and block
   constexpr bool GUARD = pack_has_v<const GradGuardBlock*, G...>, SCHED = pack_has_v<const LrScheduleBlock*, G...>;
+  constexpr bool EMA = pack_has_v<WeightEma, G...>;
+  [[maybe_unused]] WeightEma ema{nullptr, nullptr};
+  if constexpr (EMA) ema = pack_get<WeightEma>(guard_block...);
   if constexpr (pack_has_v<ParamGroupBlock*, G...>) {   // GROUPED: a body of its own; the rest of this one is untouched
     const GradGuardBlock* guard = nullptr;
     const LrScheduleBlock* sched = nullptr;
     if constexpr (GUARD) guard = pack_get<const GradGuardBlock*>(guard_block...);
     if constexpr (SCHED) sched = pack_get<const LrScheduleBlock*>(guard_block...);
-    sgd_grouped_body<S, MASTER, GUARD, SCHED>(w, wm, g, buf, sq_sum, n, n_reg, momentum, l2, guard,
-                                              pack_get<StepStateBlock*>(guard_block...), sched,
-                                              pack_get<ParamGroupBlock*>(guard_block...));
+    sgd_grouped_body<S, MASTER, GUARD, SCHED, EMA>(w, wm, g, buf, sq_sum, n, n_reg, momentum, l2, guard,
+                                                   pack_get<StepStateBlock*>(guard_block...), sched,
+                                                   pack_get<ParamGroupBlock*>(guard_block...), ema);
     return;
   }
   __shared__ float red[4];
   float coef = 1.f;
   int steps_done = 0;
-  if constexpr (SCHED) {
+  [[maybe_unused]] float omd = 0.f;
+  [[maybe_unused]] WeightEmaLane ema_lane{0, 0.f};   // thread 0
+  // (The EMA prologue repeats the SCHED prologue below with one more published value and the state->lr branch.  The
+  // repetition is deliberate: the SCHED text stays as it was, so the instantiations without an average stay the same
+  // machine code.)
+  if constexpr (EMA) {   // the step block is there with or without a schedule; lane 0 also loads the average's block
+    __shared__ float published[5];   // rate, first_step, halted, coef, the average's weight
+    if (threadIdx.x < 64) {   // wave 0, every lane: the schedule's ballot needs them all
+      StepStateBlock* state = pack_get<StepStateBlock*>(guard_block...);
+      float rate;
+      if constexpr (SCHED) {
+        const LrScheduleLane knot = lr_schedule_lane_load(pack_get<const LrScheduleBlock*>(guard_block...), threadIdx.x);
+        steps_done = __hip_atomic_load(&state->steps_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        rate = lr_schedule_wave_value(knot, threadIdx.x, steps_done);
+      } else {
+        steps_done = __hip_atomic_load(&state->steps_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        rate = __hip_atomic_load(&state->lr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      if (threadIdx.x == 0) {
+        published[0] = rate, published[1] = steps_done == 0 ? 1.f : 0.f;
+        published[4] = (ema_lane = weight_ema_lane_load(ema.block)).omd;
+        if constexpr (GUARD) {
+          const GradGuardBlock* guard = pack_get<const GradGuardBlock*>(guard_block...);
+          published[2] = __hip_atomic_load(&guard->halted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ? 1.f : 0.f;
+          published[3] = __hip_atomic_load(&guard->coef, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
+    }
+    __syncthreads();
+    if constexpr (GUARD) {
+      if (published[2] != 0.f) return;   // the whole workgroup, before any store and before the ticket
+      coef = published[3];
+    }
+    lr = published[0], first_step = published[1] != 0.f ? 1 : 0, omd = published[4];
+  } else if constexpr (SCHED) {
     __shared__ float published[4];   // rate, first_step, halted, coef
     if (threadIdx.x < 64) {   // wave 0, every lane: the ballot needs them all
       const LrScheduleLane knot = lr_schedule_lane_load(pack_get<const LrScheduleBlock*>(guard_block...), threadIdx.x);
@@ -279,6 +331,8 @@ __global__ __launch_bounds__(256) void sgd_l2_k(S* __restrict__ w, float* __rest
     if (decision[0] != 0.f) return;   // the whole workgroup, before any store
     coef = decision[1];
   }
+  [[maybe_unused]] float* __restrict__ em = nullptr;
+  if constexpr (EMA) em = ema.values;
   float part = 0.f;
   const float two_l2 = 2.f * l2;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
@@ -286,6 +340,7 @@ __global__ __launch_bounds__(256) void sgd_l2_k(S* __restrict__ w, float* __rest
                               momentum, two_l2, first_step, part);
     w[i] = (S)wi;
     if (MASTER) wm[i] = wi;
+    if constexpr (EMA) em[i] = weight_ema_elem(em[i], weight_ema_kept<S, MASTER>(wi), omd);
   }
   for (int off = 32; off > 0; off >>= 1) part += __shfl_down(part, off, 64);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
@@ -293,7 +348,7 @@ __global__ __launch_bounds__(256) void sgd_l2_k(S* __restrict__ w, float* __rest
   // one slot per workgroup, stored (not accumulated): no fill before the kernel, no atomics, a fixed summation order;
   // the caller adds the dctn_sgd_l2_num_partials(n) slots when it wants the regulariser's value
   if (threadIdx.x == 0 && sq_sum) sq_sum[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-  if constexpr (SCHED) {
+  if constexpr (SCHED || EMA) {
     if (threadIdx.x == 0) {
       // The ticket of adam_l2_k: it orders every workgroup's read of steps_done before the last workgroup's write of it.
       // The wait makes sure this lane's load of steps_done has returned before the ticket is drawn.
@@ -302,7 +357,8 @@ __global__ __launch_bounds__(256) void sgd_l2_k(S* __restrict__ w, float* __rest
       const unsigned drawn = __hip_atomic_fetch_add(&state->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (drawn == gridDim.x - 1) {   // plain vector stores; the next launch starts from ticket 0 again
         state->steps_done = steps_done + 1;
-        state->lr = lr;
+        if constexpr (SCHED) state->lr = lr;   // without a schedule (EMA alone) the cell is the host's
+        if constexpr (EMA) weight_ema_advance(ema.block, ema_lane);
         state->ticket = 0u;
       }
     }
@@ -322,13 +378,15 @@ struct SgdStep {
   float lr, momentum;
   int first_step;
   hipStream_t st;
+  const dctn_weight_ema_t* ema;   // null: no average
 };
 
-// The one launcher.  sgd_l2_k is built for the packs that hold the step block exactly when they hold a schedule or a
-// group table; sgd_step hands the block over in no other case, so the packs left out are never asked for.
+// The one launcher.  sgd_l2_k is built for the packs that hold the step block exactly when they hold a schedule, a
+// group table or an average; sgd_step hands the block over in no other case, so the packs left out are never asked for.
 template <typename S, bool MASTER, typename... G> void sgd_launch(const SgdStep& a, G... pack) {
   if constexpr (pack_has_v<StepStateBlock*, G...> ==
-                (pack_has_v<const LrScheduleBlock*, G...> || pack_has_v<ParamGroupBlock*, G...>)) {
+                (pack_has_v<const LrScheduleBlock*, G...> || pack_has_v<ParamGroupBlock*, G...> ||
+                 pack_has_v<WeightEma, G...>)) {
     const dctn_flat_step_t& d = a.d;
     hipLaunchKernelGGL((sgd_l2_k<S, MASTER, G...>), dim3(blocks_for(d.n)), dim3(256), 0, a.st, (S*)d.params,
                        (float*)d.master, (const S*)d.grads, (float*)a.momentum_buf, (float*)d.sq_sum, (long long)d.n,
@@ -336,20 +394,25 @@ template <typename S, bool MASTER, typename... G> void sgd_launch(const SgdStep&
   }
 }
 
-// The pack is the optional blocks the step has, in the order sgd_l2_k expects: guard, step state, schedule, group table
+// The pack is the optional blocks the step has, in the order sgd_l2_k expects: guard, step state, schedule, group table,
+// and the average (a pair by value) behind them
 template <typename S, bool MASTER> void sgd_dispatch(const SgdStep& a, StepStateBlock* state) {
-  with_blocks([&](auto... pack) { sgd_launch<S, MASTER>(a, pack...); }, (const GradGuardBlock*)a.d.guard, state,
-              (const LrScheduleBlock*)a.d.schedule, (ParamGroupBlock*)a.d.groups);
+  with_blocks([&](auto... pack) {
+    if (a.ema) sgd_launch<S, MASTER>(a, pack..., WeightEma{(float*)a.ema->ema, (WeightEmaBlock*)a.ema->block});
+    else sgd_launch<S, MASTER>(a, pack...);
+  }, (const GradGuardBlock*)a.d.guard, state, (const LrScheduleBlock*)a.d.schedule, (ParamGroupBlock*)a.d.groups);
 }
 
-// Validates and launches.  With a schedule or a group table the rate and first_step come from the step block on the
-// device: the block is required, and the two launch arguments are zeros whatever the caller passed.
-int sgd_step(const dctn_flat_step_t& d, void* momentum_buf, float lr, float momentum, int first_step, void* stream) {
-  const bool on_device = d.schedule || d.groups;
+// Validates and launches.  With a schedule, a group table or an average the rate and first_step come from the step block
+// on the device: the block is required, and the two launch arguments are zeros whatever the caller passed.
+int sgd_step(const dctn_flat_step_t& d, void* momentum_buf, float lr, float momentum, int first_step, void* stream,
+             const dctn_weight_ema_t* ema = nullptr) {
+  const bool on_device = d.schedule || d.groups || ema;
   if (!d.params || !d.grads || !momentum_buf || (on_device && !d.state)) return DCTN_ERR_NULL;
+  if (ema && (!ema->ema || !ema->block)) return DCTN_ERR_NULL;
   if (d.n < 1 || d.n_reg < 0 || d.n_reg > d.n) return DCTN_ERR_BAD_SHAPE;
   if ((d.dtype != DCTN_F32 && d.dtype != DCTN_BF16) || (d.master && d.dtype != DCTN_BF16)) return DCTN_ERR_BAD_DTYPE;
-  const SgdStep a{d, momentum_buf, on_device ? 0.f : lr, momentum, on_device ? 0 : first_step, (hipStream_t)stream};
+  const SgdStep a{d, momentum_buf, on_device ? 0.f : lr, momentum, on_device ? 0 : first_step, (hipStream_t)stream, ema};
   StepStateBlock* state = on_device ? (StepStateBlock*)d.state : nullptr;
   if (d.master) sgd_dispatch<bf16_t, true>(a, state);
   else if (d.dtype == DCTN_F32) sgd_dispatch<float, false>(a, state);
@@ -416,6 +479,13 @@ int dctn_sgd_flat_step(const dctn_flat_step_t* step, void* momentum_buf, float l
                        void* stream) {
   if (!step) return DCTN_ERR_NULL;
   return sgd_step(*step, momentum_buf, lr, momentum, first_step, stream);
+}
+
+// ema_or_null == NULL is dctn_sgd_flat_step
+int dctn_sgd_flat_step_ema(const dctn_flat_step_t* step, const dctn_weight_ema_t* ema_or_null, void* momentum_buf,
+                           float lr, float momentum, int first_step, void* stream) {
+  if (!step) return DCTN_ERR_NULL;
+  return sgd_step(*step, momentum_buf, lr, momentum, first_step, stream, ema_or_null);
 }
 
 // The six entry points older than the descriptor: each fills one and takes sgd_step.  An entry point that requires a

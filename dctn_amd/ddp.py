@@ -135,7 +135,9 @@ def shard_batch(x: Tensor, rank: int, world: int, dim: int = 1) -> Tensor:
 
 @torch.no_grad()
 def broadcast_parameters(params: Iterable[Tensor], src: int = 0) -> None:
-    """Identical initial parameters on every rank (the reference seeds one process)."""
+    """Identical initial parameters on every rank (the reference seeds one process).  An optimizer built before the
+    call goes on from what it copied: ``optimizer.refresh_master()`` rebuilds a master copy from the new parameters and
+    ``optimizer.ema.reset()`` starts a `training.WeightEMA` again from them."""
     if not dist.is_initialized() or dist.get_world_size() == 1:
         return
     for p in params:

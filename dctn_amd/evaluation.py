@@ -155,16 +155,22 @@ class GraphedScore:
         return self.read()
 
 
-def make_evaluation_hook(train_scorer, val_scorer) -> Callable[[Dict[str, Any], Dict[str, Any]], None]:
+def make_evaluation_hook(train_scorer, val_scorer, ema=None) -> Callable[[Dict[str, Any], Dict[str, Any]], None]:
     """``f(st_x, st_it)`` that fills ``train_mean_ce``, ``train_acc``, ``val_mean_ce`` and ``val_acc`` - what
     `training._checkpoint_tag`, the checkpointers and the early stopper read - from two scorers with ``launch()`` /
     ``read()`` (`GraphedScore`); for ``at_iter_start=[every_n_iters_intervals(...)(hook), ...]`` of `training.train`.  Both
-    passes are enqueued before either is read."""
+    passes are enqueued before either is read.  ``ema`` (a `training.WeightEMA`): once both were read, the validation
+    scorer runs a second pass under ``ema.applied()`` - its graph reads the live parameter storage, which then holds the
+    averaged weights - and fills ``ema_val_mean_ce`` and ``ema_val_acc``."""
 
     def hook(st_x, st_it) -> None:
         train_scorer.launch()
         val_scorer.launch()
         st_it["train_mean_ce"], st_it["train_acc"] = train_scorer.read()
         st_it["val_mean_ce"], st_it["val_acc"] = val_scorer.read()
+        if ema is not None:
+            with ema.applied():
+                val_scorer.launch()
+                st_it["ema_val_mean_ce"], st_it["ema_val_acc"] = val_scorer.read()
 
     return hook

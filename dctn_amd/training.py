@@ -14,7 +14,9 @@ and only rank 0 touches checkpoint files.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import math
 import os
 from collections import deque
 from logging import getLogger
@@ -121,6 +123,7 @@ class GraphedTrainStep:
                  graph_allreduce: Optional[bool] = None, *, iters_per_launch: int = 1, trace=None, batch_source=None):
         self.model, self.optimizer, self.reducer = model, optimizer, reducer
         self.batch_source = batch_source
+        self._ema = getattr(optimizer, "ema", None)   # a WeightEMA: no replay while it is applied
         K = int(iters_per_launch)
         if K != iters_per_launch or K < 1:
             raise ValueError(f"iters_per_launch must be an integer >= 1, got {iters_per_launch!r}")
@@ -226,6 +229,8 @@ class GraphedTrainStep:
                 record(self.out, self.loss, self.reg)
 
     def __call__(self, x: Optional[Tensor] = None, y: Optional[Tensor] = None) -> Dict[str, Tensor]:
+        if self._ema is not None:
+            self._ema._refuse_applied("a GraphedTrainStep launch")
         if self.batch_source is not None:
             if x is not None or y is not None:
                 raise TypeError("a GraphedTrainStep with a batch_source draws its own batches: call it without arguments")
@@ -1076,6 +1081,218 @@ def param_groups_for(model, freeze_eps=(), head_lr_scale: float = 1.0) -> ParamG
     return ParamGroups.from_requires_grad(epses + [model.linear.weight, model.linear.bias], entries)
 
 
+class WeightEMA:
+    """An exponential moving average of the weights that the optimizer's step kernel keeps (include/dctn_amd.h, "A
+    weight average").  Pass one to ``FlatAdam(..., ema=e)`` or ``FlatSGD(..., ema=e)``: the optimizer binds it -
+    ``e.values`` (float32, one per element of the flat buffer) starts as the master copy where there is one, else as the
+    exact widening of the parameters - and every ``step()`` then updates the average in the launch that updates the
+    parameters, from the value the optimizer keeps for each element (the float32 master value, else the parameter as
+    stored): ``ema = ema + omd * (w - ema)`` in three rounded float32 operations.  A captured step, and each of the K
+    iterations of one launch, carries it; a step the guard skipped leaves it alone; a frozen segment's average stays.
+
+    ``omd = float32(1 - d_u)`` with ``d_u = decay``, or with ``warmup`` ``min(decay, (1 + u) / (10 + u))`` where ``u`` is
+    the number of updates so far, which the launch reads from and advances in a 32-byte DEVICE block {decay, flags,
+    updates, last_omd}.  ``e.updates`` and ``e.last_omd`` read the block (they synchronise); ``e.decay = x`` is a one-cell
+    asynchronous write between replays (not during a capture); ``e.reset()`` starts the average again from the current
+    weights with ``updates = 0`` - call it after ``refresh_master()``.  `weight` and `mirror` are the host mirrors of
+    the two pieces of arithmetic, bit for bit.
+
+    Every captured graph reads the LIVE parameter storage, so scoring the averaged model means putting it there:
+    ``e.apply()`` stashes the parameters and writes ``values`` rounded to their dtype in their place (one launch; the
+    master copy is not touched), ``e.restore()`` puts the stash back, ``with e.applied(): ...`` does both.  While applied,
+    ``optimizer.step()``, a `GraphedTrainStep` call, ``RunState.snapshot()`` and a second ``apply()`` raise RuntimeError.
+
+    One decay for all parameters.  ``state_dict()`` / ``load_state_dict()`` carry the block and the values; the
+    optimizer's own state_dict holds them under ``"ema"``, and `checkpoint.RunState` carries both as regions."""
+
+    WORDS = 8
+    _WARMUP = 1
+
+    def __init__(self, device, decay: float = 0.999, warmup: bool = True):
+        self.device = torch.device(device)
+        self._decay = self._validated(decay)
+        self.warmup = bool(warmup)
+        assert L.lib().dctn_weight_ema_bytes() == 4 * self.WORDS
+        self._block = torch.zeros(self.WORDS, dtype=torch.int32, device=self.device)
+        self._decay_cell = self._block.view(torch.float32)[0:1]
+        self.values: Optional[Tensor] = None
+        self._stash: Optional[Tensor] = None
+        self._owner = None
+        self._applied = False
+        self._upload(0, 0.0)
+
+    # ---------------------------------------------------------------------------------------- host arithmetic
+    @staticmethod
+    def _validated(decay) -> float:
+        import numpy as np
+
+        d = float(np.float32(decay))
+        if not (math.isfinite(d) and 0.0 <= d < 1.0):
+            raise ValueError(f"WeightEMA: decay must be in [0, 1) as a float32, got {decay!r}")
+        return d
+
+    @staticmethod
+    def weight(decay, warmup, u) -> float:
+        """``omd`` of the launch after ``u`` updates: the kernel's float64 arithmetic, rounded once to float32."""
+        import numpy as np
+
+        d = float(np.float32(decay))
+        if warmup:
+            d = min(d, (1.0 + float(u)) / (10.0 + float(u)))
+        return float(np.float32(1.0 - d))
+
+    @staticmethod
+    def mirror(ema, w, omd):
+        """The element update on numpy float32 arrays: a subtraction, a product and a sum, each rounded on its own."""
+        import numpy as np
+
+        ema, w = np.asarray(ema, dtype=np.float32), np.asarray(w, dtype=np.float32)
+        return ema + np.float32(omd) * (w - ema)
+
+    def host_block(self, updates: int = 0, last_omd: float = 0.0):
+        """The 32-byte block as int32 words (include/dctn_amd.h)."""
+        import numpy as np
+
+        words = np.zeros(self.WORDS, dtype=np.int32)
+        floats = words.view(np.float32)
+        floats[0] = self._decay
+        words[1] = self._WARMUP if self.warmup else 0
+        words[2] = int(updates)
+        floats[3] = float(last_omd)
+        return words
+
+    # ---------------------------------------------------------------------------------------- the device block
+    def _upload(self, updates: int, last_omd: float) -> None:
+        with torch.no_grad():
+            self._block.copy_(torch.from_numpy(self.host_block(updates, last_omd)))
+
+    def _no_capture(self, what: str) -> None:
+        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"WeightEMA.{what} during a graph capture: the captured step reads the block from the "
+                               "device, change it between replays")
+
+    @property
+    def decay(self) -> float:
+        return self._decay
+
+    @decay.setter
+    def decay(self, value: float) -> None:
+        self._no_capture("decay cannot be assigned")
+        self._decay = self._validated(value)
+        _write_cell(self._decay_cell, self._decay)
+
+    @property
+    def updates(self) -> int:
+        """Updates done so far (read from the device: synchronises; steps the guard skipped do not count)."""
+        return int(self._block[2].item())
+
+    @property
+    def last_omd(self) -> float:
+        """The weight the last update used, 0 before the first (read from the device: synchronises)."""
+        return float(self._block.view(torch.float32)[3].item())
+
+    @property
+    def is_applied(self) -> bool:
+        return self._applied
+
+    # ---------------------------------------------------------------------------------------- binding
+    def _bind(self, owner) -> None:
+        """The optimizer's constructor: allocates the values and the stash beside ``owner.flat`` and starts the average."""
+        if self._owner is not None:
+            raise ValueError("this WeightEMA already belongs to an optimizer: one average per optimizer")
+        if self.device != owner.flat.device:
+            raise ValueError(f"the average's block is on {self.device}, the parameters on {owner.flat.device}")
+        self.values = torch.empty(owner.n, dtype=torch.float32, device=self.device)
+        self._stash = torch.empty(owner.n, dtype=owner.flat.dtype, device=self.device)
+        self._owner = owner
+        self._desc = L.WeightEma(ema=self.values.data_ptr(), block=self._block.data_ptr())
+        self._desc_ref = ctypes.byref(self._desc)
+        self.reset()
+
+    def _bound(self, what: str):
+        if self._owner is None:
+            raise RuntimeError(f"WeightEMA.{what}: not bound to an optimizer (pass it as FlatAdam(..., ema=e))")
+        return self._owner
+
+    def reset(self) -> None:
+        """Starts the average again: the values from the master copy where there is one, else from the parameters by exact
+        widening, and ``updates = 0``.  Not during a capture, and not while applied."""
+        owner = self._bound("reset()")
+        self._no_capture("reset()")
+        if self._applied:
+            raise RuntimeError("WeightEMA.reset() while the average is applied: restore() first")
+        with torch.no_grad():
+            self.values.copy_(owner.flat if owner.master is None else owner.master)
+        self._upload(0, 0.0)
+
+    # ---------------------------------------------------------------------------------------- scoring under the average
+    def apply(self) -> None:
+        """Puts the averaged weights, rounded to the parameters' dtype, in the live parameter storage (one launch)."""
+        owner = self._bound("apply()")
+        if self._applied:
+            raise RuntimeError("WeightEMA.apply(): the average is already applied; restore() first")
+        flat = owner.flat
+        L.check(L.lib().dctn_weight_ema_apply(flat.data_ptr(), self._stash.data_ptr(), self.values.data_ptr(), owner.n,
+                                              L.dtype_code(flat), L.stream_ptr(flat.device)), "weight average apply")
+        self._applied = True
+
+    def restore(self) -> None:
+        """Puts the parameters back as `apply` found them."""
+        if not self._applied:
+            raise RuntimeError("WeightEMA.restore(): the average is not applied")
+        flat = self._owner.flat
+        L.check(L.lib().dctn_weight_ema_restore(flat.data_ptr(), self._stash.data_ptr(), self._owner.n,
+                                                L.dtype_code(flat), L.stream_ptr(flat.device)), "weight average restore")
+        self._applied = False
+
+    @contextlib.contextmanager
+    def applied(self):
+        self.apply()
+        try:
+            yield self
+        finally:
+            self.restore()
+
+    def _refuse_applied(self, what: str) -> None:
+        if self._applied:
+            raise RuntimeError(f"{what} while the weight average is applied: the parameter storage holds the averaged "
+                               "weights, call restore() first")
+
+    # ---------------------------------------------------------------------------------------- state
+    def state_dict(self) -> Dict[str, Any]:
+        self._bound("state_dict()")
+        return {"decay": self._decay, "warmup": self.warmup, "updates": self.updates, "last_omd": self.last_omd,
+                "values": self.values.clone()}
+
+    def load_state_dict(self, state: Dict[str, Any]) -> None:
+        owner = self._bound("load_state_dict()")
+        self._no_capture("load_state_dict()")
+        self._refuse_applied("WeightEMA.load_state_dict()")
+        if state["values"].numel() != owner.n:
+            raise ValueError(f"the state holds {state['values'].numel()} averaged values, the parameters {owner.n}")
+        self._decay, self.warmup = self._validated(state["decay"]), bool(state["warmup"])
+        with torch.no_grad():
+            self.values.copy_(state["values"].reshape(-1))
+        self._upload(int(state["updates"]), float(state["last_omd"]))
+
+    # a part of a run, as `GradGuard`; the optimizer that holds the average lists both among its own regions
+    def run_regions(self):
+        return [("ema", self.values), ("ema_block", self._block)]
+
+    def run_host(self) -> None:
+        return None
+
+    def run_restored(self, host, blocks) -> None:
+        """Sets the host copy from the block's bytes (`checkpoint.RunState.load` put the block itself back)."""
+        import numpy as np
+
+        words = np.ascontiguousarray(blocks["ema_block"]).view("<i4").reshape(-1)
+        if words.size != self.WORDS:
+            raise ValueError(f"WeightEMA: a block has {4 * self.WORDS} bytes, got {4 * words.size}")
+        self._decay = self._validated(words.view(np.float32)[0])
+        self.warmup = bool(int(words[1]) & self._WARMUP)
+
+
 class _FlatOptimizer:
     """What FlatSGD and FlatAdam share: the parameters moved into ONE flat buffer (their ``.data`` become views of it,
     in the order regularised + others), the gradients read in place when they already sit back to back in that
@@ -1088,7 +1305,8 @@ class _FlatOptimizer:
 
     def __init__(self, regularised, others, num_partials: Callable[[int], int], master_weights: bool = False,
                  guard: Optional["GradGuard"] = None, guard_loss=None, schedule: Optional["LRSchedule"] = None,
-                 groups: Optional["ParamGroups"] = None):
+                 groups: Optional["ParamGroups"] = None, ema: Optional["WeightEMA"] = None):
+        # ema: a WeightEMA that the step kernel updates; bound here, once the master copy exists
         # groups: a ParamGroups table over exactly these parameters that the step kernel obeys
         # guard: a GradGuard whose check runs in front of every step; guard_loss: the float32 device scalar the check
         # looks at beside the gradients, or a callable that returns it (the loss tensor of a training loop is a new one
@@ -1098,6 +1316,8 @@ class _FlatOptimizer:
         if schedule is not None and not isinstance(schedule, LRSchedule):
             raise TypeError(f"schedule must be an LRSchedule, got {type(schedule).__name__}")
         self.schedule = schedule
+        if ema is not None and not isinstance(ema, WeightEMA):
+            raise TypeError(f"ema must be a WeightEMA, got {type(ema).__name__}")
         self.reg_params = [p for p in regularised]
         self.params = self.reg_params + [p for p in others]
         assert self.params and len({p.dtype for p in self.params}) == 1 and len({p.device for p in self.params}) == 1
@@ -1130,6 +1350,9 @@ class _FlatOptimizer:
                 raise ValueError(f"the group table's block is on {groups.device}, the parameters on {self.flat.device}")
             assert L.lib().dctn_param_groups_bytes() == 4 * ParamGroups.WORDS and groups.ends[-1] == self.n
         self.groups = groups
+        self.ema = ema
+        if ema is not None:
+            ema._bind(self)
 
     def _scheduled_lr(self) -> float:
         """``schedule.value(t)``, scale applied: the rate of the next step (reads the step count from the device)."""
@@ -1143,7 +1366,8 @@ class _FlatOptimizer:
     def refresh_master(self) -> None:
         """Rebuilds the float32 master copy from the current bfloat16 parameters (nothing to do without one).  Call it
         after anything wrote the parameters behind the optimizer's back - ``model.load_state_dict``,
-        ``ddp.broadcast_parameters`` - or the next step starts from the values the master held before."""
+        ``ddp.broadcast_parameters`` - or the next step starts from the values the master held before.  A `WeightEMA`
+        goes on averaging from the old weights: ``ema.reset()`` starts it again from the new ones."""
         if self.master is not None:
             with torch.no_grad():
                 self.master.copy_(self.flat)
@@ -1159,6 +1383,16 @@ class _FlatOptimizer:
             raise ValueError(f"optimizer state holds {saved.numel()} master values, the parameters {self.n}")
         with torch.no_grad():
             self.master.copy_(saved.reshape(-1))
+
+    def _load_ema(self, state: Dict[str, Any]) -> None:
+        """After the parameters' and the master's values are in place: the saved average, or a fresh one from them."""
+        if self.ema is None:
+            return
+        saved = state.get("ema")
+        if saved is None:   # a state written without the option
+            self.ema.reset()
+        else:
+            self.ema.load_state_dict(saved)
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         for p in self.params:
@@ -1193,7 +1427,8 @@ class _FlatOptimizer:
         assert L.lib().dctn_flat_step_bytes() == ctypes.sizeof(L.FlatStep)
         blocks = {"master weights": self.master, "guard": None if self.guard is None else self.guard._block,
                   "schedule": None if self.schedule is None else self.schedule._block,
-                  "groups": None if self.groups is None else self.groups._block}
+                  "groups": None if self.groups is None else self.groups._block,
+                  "weight average": None if self.ema is None else self.ema._block}
         ptr = {name: None if t is None else t.data_ptr() for name, t in blocks.items()}
         self._desc = L.FlatStep(params=self.flat.data_ptr(), master=ptr["master weights"], grads=None,
                                 sq_sum=self.sq_sum.data_ptr(),
@@ -1201,12 +1436,15 @@ class _FlatOptimizer:
                                 schedule=ptr["schedule"], groups=ptr["groups"], n=self.n, n_reg=self.n_reg, l2=self.l2,
                                 dtype=L.dtype_code(self.flat))
         self._desc_ref = ctypes.byref(self._desc)
+        self._ema_ref = None if self.ema is None else self.ema._desc_ref   # dctn_weight_ema_t, built when it was bound
         on = [name for name, p in ptr.items() if p is not None]
         self._what = what + (f" ({', '.join(on)})" if on else "")
 
     def _begin_step(self) -> None:
         """What changes from one step to the next goes into the descriptor - where the gradients lie, and ``n_reg`` and
         ``l2``, plain attributes a caller may have assigned - and the guard's check is launched in front of the step."""
+        if self.ema is not None:
+            self.ema._refuse_applied(f"{type(self).__name__}.step()")
         g = self._grads()
         d = self._desc
         d.grads, d.n_reg, d.l2 = g.data_ptr(), self.n_reg, self.l2
@@ -1217,7 +1455,7 @@ class _FlatOptimizer:
         """Writes the 16-byte step block of a scheduled optimizer: ``steps`` taken, the rate of the last of them."""
         host = torch.zeros(4, dtype=torch.int32)
         host[0] = int(steps)
-        if self.schedule is None:   # a grouped FlatSGD without a schedule: the cell holds the rate the host set
+        if self.schedule is None:   # a FlatSGD with a group table or an average and no schedule: the rate the host set
             host.view(torch.float32)[1] = self._lr
         else:
             host.view(torch.float32)[1] = self.schedule.value(steps - 1) if steps > 0 else 0.0
@@ -1234,11 +1472,12 @@ class _FlatOptimizer:
     def run_regions(self):
         """In file order.  The schedule's block stands in front of the step block, so that a file and a run that disagree
         about the schedule differ at that entry first; the group table's block, the segments' step counts in it, follows
-        it.  ``state``: FlatAdam; a FlatSGD with a schedule or a group table."""
+        it.  ``state``: FlatAdam; a FlatSGD with a schedule, a group table or an average.  A `WeightEMA`'s values and block
+        stand behind the master copy."""
         regions = [("flat", self.flat)] + [(name, getattr(self, name)) for name in self._MOMENTS]
         if self.master is not None:
             regions.append(("master", self.master))
-        for part in (self.schedule, self.groups):
+        for part in (self.ema, self.schedule, self.groups):
             if part is not None:
                 regions += part.run_regions()
         if self._state is not None:
@@ -1250,8 +1489,8 @@ class _FlatOptimizer:
             raise ValueError(f"snapshot: entry 'optimizer' is {host['kind']} in the file, {type(self).__name__} in the run")
 
     def run_restored(self, host: Dict[str, Any], blocks) -> None:
-        """The blocks came back: the host copies of the schedule's and the group table's follow theirs."""
-        for part in (self.schedule, self.groups):
+        """The blocks came back: the host copies of the average's, the schedule's and the group table's follow theirs."""
+        for part in (self.ema, self.schedule, self.groups):
             if part is not None:
                 part.run_restored(None, {name: blocks[name] for name, _ in part.run_regions()})
 
@@ -1299,13 +1538,19 @@ class FlatSGD(_FlatOptimizer):
     ``weight_decay=None`` (ValueError otherwise).  The table's state is not part of ``state_dict()``; save
     ``groups.state_dict()`` beside it (`checkpoint.RunState` carries its block).  Without ``groups`` ``step()`` makes
     the calls it always made.
+
+    ``ema`` (a `WeightEMA`): ``step()`` calls `dctn_sgd_flat_step_ema`, and the one launch also moves the average of every
+    element it stores to, from the value the optimizer keeps for it.  The optimizer then owns the 16-byte step block, as
+    with a group table: the rate and the first step are read on the device, and ``opt.lr = x`` writes the block's rate
+    cell.  ``state_dict()`` holds the average under ``"ema"``.  Without ``ema`` ``step()`` makes the calls it always made.
     """
 
     def __init__(self, regularised, others=(), lr: float = 1e-3, momentum: float = 0.0, l2: float = 0.0,
                  master_weights: bool = False, guard: Optional["GradGuard"] = None, guard_loss=None, *,
-                 schedule: Optional["LRSchedule"] = None, groups: Optional["ParamGroups"] = None):
+                 schedule: Optional["LRSchedule"] = None, groups: Optional["ParamGroups"] = None,
+                 ema: Optional["WeightEMA"] = None):
         super().__init__(regularised, others, L.lib().dctn_sgd_l2_num_partials, master_weights, guard, guard_loss,
-                         schedule, groups)
+                         schedule, groups, ema)
         self._lr, self.momentum, self.l2 = float(lr), float(momentum), float(l2)
         self.buf = torch.zeros(self.n, dtype=torch.float32, device=self.flat.device)
         self._steps = 0
@@ -1314,8 +1559,9 @@ class FlatSGD(_FlatOptimizer):
         if schedule is not None:
             assert L.lib().dctn_adam_state_bytes() == 16 and L.lib().dctn_lr_schedule_bytes() == 4 * LRSchedule.WORDS
             self._state = torch.zeros(4, dtype=torch.int32, device=self.flat.device)
-        if groups is not None:   # the grouped step always takes the block; without a schedule it reads the rate cell
+        if groups is not None:
             groups._bind(None, "FlatSGD")
+        if groups is not None or ema is not None:   # these steps always take the block; without a schedule they read its rate cell
             if self._state is None:
                 assert L.lib().dctn_adam_state_bytes() == 16
                 self._state = torch.zeros(4, dtype=torch.int32, device=self.flat.device)
@@ -1331,10 +1577,11 @@ class FlatSGD(_FlatOptimizer):
     def lr(self, value: float) -> None:
         if self.schedule is not None:
             self._refuse_lr()
-        if self.groups is not None:   # the grouped step reads the rate from the block: a small write, as FlatAdam's
+        if self._state is not None:   # a group table or an average: the step reads the rate from the block, as FlatAdam's
             if self.flat.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("FlatSGD.lr cannot be assigned during a graph capture: the captured grouped step reads "
-                                   "the rate from the device, assign it between replays")
+                raise RuntimeError("FlatSGD.lr cannot be assigned during a graph capture: the captured step of an optimizer "
+                                   "with a group table or a weight average reads the rate from the device, assign it "
+                                   "between replays")
             self._lr = float(value)
             _write_cell(self._state.view(torch.float32)[1:2], self._lr)
             return
@@ -1342,7 +1589,7 @@ class FlatSGD(_FlatOptimizer):
 
     @property
     def t(self) -> int:
-        """Number of steps taken: with a schedule or a group table read from the device block (it synchronises; steps the guard skipped
+        """Number of steps taken: with a schedule, a group table or a weight average read from the device block (it synchronises; steps the guard skipped
         do not count), otherwise the host's count of launches."""
         return self._steps if self._state is None else int(self._state[0].item())
 
@@ -1353,8 +1600,13 @@ class FlatSGD(_FlatOptimizer):
         # count of launches, and under a guard the host does not know whether the guard let a launch through.  A skipped
         # step 0 leaves the momentum buffer at its zeros, and the next launch, with first = 0, forms momentum * 0 + g = g:
         # the update a first step makes.  (With either option the kernel reads both from the step block instead.)
-        L.check(L.lib().dctn_sgd_flat_step(self._desc_ref, self.buf.data_ptr(), self._lr, self.momentum,
-                                           1 if self._steps == 0 else 0, L.stream_ptr(self.flat.device)), self._what)
+        if self._ema_ref is None:
+            L.check(L.lib().dctn_sgd_flat_step(self._desc_ref, self.buf.data_ptr(), self._lr, self.momentum,
+                                               1 if self._steps == 0 else 0, L.stream_ptr(self.flat.device)), self._what)
+        else:
+            L.check(L.lib().dctn_sgd_flat_step_ema(self._desc_ref, self._ema_ref, self.buf.data_ptr(), self._lr,
+                                                   self.momentum, 1 if self._steps == 0 else 0,
+                                                   L.stream_ptr(self.flat.device)), self._what)
         self._steps += 1
 
     def state_dict(self) -> Dict[str, Any]:
@@ -1362,6 +1614,8 @@ class FlatSGD(_FlatOptimizer):
         state = {"steps": self.t, "lr": self.lr, "momentum": self.momentum, "l2": self.l2, "buf": self.buf.clone()}
         if self.master is not None:
             state["master"] = self.master.clone()
+        if self.ema is not None:
+            state["ema"] = self.ema.state_dict()
         return state
 
     def load_state_dict(self, state: Dict[str, Any]) -> None:
@@ -1373,11 +1627,12 @@ class FlatSGD(_FlatOptimizer):
         self._steps = int(state["steps"])
         if self.schedule is None:
             self.lr = float(state["lr"])
-            if self._state is not None:   # a group table: the block holds the count beside the rate
+            if self._state is not None:   # a group table or a weight average: the block holds the count beside the rate
                 self._put_step_block(self._steps)
         else:   # the block as the scheduled kernel would have left it: the count, and the rate of the last step
             self._put_step_block(self._steps)
         self._load_master(state)
+        self._load_ema(state)
 
     _MOMENTS = ("buf",)
 
@@ -1441,14 +1696,20 @@ class FlatAdam(_FlatOptimizer):
     flat buffer, frozen segments included.  The table's state is not part of ``state_dict()``; save
     ``groups.state_dict()`` beside it (`checkpoint.RunState` carries its block).  Without ``groups`` ``step()`` makes
     the calls it always made.
+
+    ``ema`` (a `WeightEMA`): ``step()`` calls `dctn_adam_flat_step_ema`, and the one launch also moves the average of
+    every element it stores to, from the value the optimizer keeps for it - the master value where there is one.  A step
+    the guard skipped and a frozen segment leave their averages alone; every other buffer holds the bits it would hold
+    without the average.  ``state_dict()`` holds the average under ``"ema"``; a state without one resets it from the
+    parameters.  Without ``ema`` ``step()`` makes the calls it always made.
     """
 
     def __init__(self, regularised, others=(), lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, l2: float = 0.0, master_weights: bool = False,
                  guard: Optional["GradGuard"] = None, guard_loss=None, *, schedule: Optional["LRSchedule"] = None,
-                 groups: Optional["ParamGroups"] = None):
+                 groups: Optional["ParamGroups"] = None, ema: Optional["WeightEMA"] = None):
         super().__init__(regularised, others, L.lib().dctn_adam_l2_num_partials, master_weights, guard, guard_loss,
-                         schedule, groups)
+                         schedule, groups, ema)
         if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0 and lr >= 0.0 and eps >= 0.0 and weight_decay >= 0.0):
             raise ValueError(f"invalid Adam hyper-parameters: lr={lr} betas={betas} eps={eps} weight_decay={weight_decay}")
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
@@ -1494,9 +1755,14 @@ class FlatAdam(_FlatOptimizer):
     def step(self) -> None:
         self._begin_step()
         # (with a group table every segment's weight decay is in the table, and the launch ignores this one)
-        L.check(L.lib().dctn_adam_flat_step(self._desc_ref, self.m.data_ptr(), self.v.data_ptr(), self.betas[0],
-                                            self.betas[1], self.eps, self.weight_decay, L.stream_ptr(self.flat.device)),
-                self._what)
+        if self._ema_ref is None:
+            L.check(L.lib().dctn_adam_flat_step(self._desc_ref, self.m.data_ptr(), self.v.data_ptr(), self.betas[0],
+                                                self.betas[1], self.eps, self.weight_decay, L.stream_ptr(self.flat.device)),
+                    self._what)
+        else:
+            L.check(L.lib().dctn_adam_flat_step_ema(self._desc_ref, self._ema_ref, self.m.data_ptr(), self.v.data_ptr(),
+                                                    self.betas[0], self.betas[1], self.eps, self.weight_decay,
+                                                    L.stream_ptr(self.flat.device)), self._what)
 
     def state_dict(self) -> Dict[str, Any]:
         """Everything a resumed run needs besides the parameters themselves (those are the model's state_dict)."""
@@ -1504,6 +1770,8 @@ class FlatAdam(_FlatOptimizer):
                  "eps": self.eps, "weight_decay": self.weight_decay, "l2": self.l2}
         if self.master is not None:
             state["master"] = self.master.clone()
+        if self.ema is not None:
+            state["ema"] = self.ema.state_dict()
         return state
 
     def load_state_dict(self, state: Dict[str, Any]) -> None:
@@ -1521,6 +1789,7 @@ class FlatAdam(_FlatOptimizer):
         else:
             self._put_step_block(int(state["t"]))
         self._load_master(state)
+        self._load_ema(state)
 
     _MOMENTS = ("m", "v")
 

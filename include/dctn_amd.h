@@ -644,6 +644,58 @@ int dctn_sgd_flat_step(const dctn_flat_step_t* step, void* momentum_buf, float l
                        void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * A weight average (EMA) inside the flat step (version 514): the fifth option of a flat step, independent of the other
+ * four.  A float32 buffer `ema` of n values sits beside the flat parameter buffer.  In the launch that updates the
+ * parameters, every element the step stores to also updates its average from the value the optimizer KEEPS for that
+ * element: with a master copy the float32 master value; without one the parameter as stored, rounded to `dtype` and
+ * widened again.  The update is three float32 operations, each rounded on its own (no FMA), so numpy float32 gives the
+ * same bits:
+ *     ema = ema + omd * (w_new - ema)
+ * omd is one float32 per launch: omd = (float)(1.0 - d_u), formed in float64; d_u = decay, or with the warm-up flag
+ * d_u = min(decay, (1 + u) / (10 + u)) (one float64 division), u = the block's count of updates done so far.
+ *
+ * The block: dctn_weight_ema_bytes() = 32 bytes, 16-byte aligned, on the DEVICE:
+ *   float   decay        in [0, 1); the caller writes it in stream order between launches
+ *   uint32  flags        bit 0: warm-up
+ *   int32   updates      updates done so far; the launch advances it
+ *   float   last_omd     the weight the last update used; 0 before the first
+ *   int32   reserved[4]  0
+ * The launch reads decay, flags and updates beside steps_done (no load depends on another); the workgroup that draws the
+ * last ticket of the step block writes updates + 1 and last_omd.
+ *
+ * With the other options: a halted guarded launch writes nothing - ema, updates and last_omd stay.  A frozen segment's
+ * ema is not stored to, exactly as its moments are not.  decay == 0 makes omd == 1; the three operations still run.  The
+ * step itself is unchanged: with or without the average every other buffer, block and sq_sum slot holds the same bits.
+ * SGD: with an average the 16-byte step block is required, as with a schedule or a group table; the rate (state->lr
+ * without a schedule) and first_step = (steps_done == 0) are read from it on the device, and the launch advances it.
+ *
+ * dctn_weight_ema_t: 16 bytes on the HOST, read during the call only; both members are DEVICE pointers.
+ * dctn_adam_flat_step_ema / dctn_sgd_flat_step_ema: dctn_adam_flat_step / dctn_sgd_flat_step with the average;
+ *   ema_or_null == NULL is exactly those.  Return codes in their order: DCTN_ERR_NULL also for a given dctn_weight_ema_t
+ *   with a null member and, for SGD, a missing step block; then shape; then dtype.  Nothing of the block is validated: a
+ *   bad block gives a wrong average, never an access outside the n floats.
+ * dctn_weight_ema_weight: HOST only, over a host copy of the block: the kernels' float64 arithmetic for the launch at
+ *   `updates`.  DCTN_ERR_NULL for a null pointer; DCTN_ERR_BAD_SHAPE for a decay outside [0, 1) or not finite, unknown
+ *   flag bits, a negative count (the block's or the argument; the argument is also at most 2^31 - 1).
+ * dctn_weight_ema_apply: ONE launch: stash[i] = params[i], then params[i] = (dtype)ema[i] with the round-to-nearest-even
+ *   cast of the step kernels.  It never touches a master copy.  dctn_weight_ema_restore copies params back from stash.
+ *   stash: n values of `dtype`.  DCTN_ERR_NULL, then n < 1: DCTN_ERR_BAD_SHAPE, then DCTN_ERR_BAD_DTYPE.
+ * All of these only enqueue and can be captured.  None reports to dctn_last_kernel.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  void* ema;
+  void* block;
+} dctn_weight_ema_t;
+size_t dctn_weight_ema_bytes(void);
+int dctn_weight_ema_weight(const void* host_block, int64_t updates, float* one_minus_decay);
+int dctn_adam_flat_step_ema(const dctn_flat_step_t* step, const dctn_weight_ema_t* ema_or_null, void* exp_avg,
+                            void* exp_avg_sq, double beta1, double beta2, float eps, float weight_decay, void* stream);
+int dctn_sgd_flat_step_ema(const dctn_flat_step_t* step, const dctn_weight_ema_t* ema_or_null, void* momentum_buf,
+                           float lr, float momentum, int first_step, void* stream);
+int dctn_weight_ema_apply(void* params, void* stash, const void* ema, int64_t n, int dtype, void* stream);
+int dctn_weight_ema_restore(void* params, const void* stash, int64_t n, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Scoring(reference: dctn/evaluation.py:7-22): one launch per batch ADDS to acc = three float64 values
  * {sum of the rows' cross-entropies, number of correct rows, number of rows}.  logits (B, C) contiguous, DCTN_F32 /
  * DCTN_BF16; labels int64.  Per row a max-shifted log-sum-exp with float32 exponentials; the row's sum, its
