@@ -139,6 +139,11 @@ SIGNATURES = {
     "dctn_adam_flat_step_ema": (c_int, [_FlatStepP, _WeightEmaP, c_void, c_void, ctypes.c_double, ctypes.c_double,
                                         ctypes.c_float, ctypes.c_float, c_void]),
     "dctn_sgd_flat_step_ema": (c_int, [_FlatStepP, _WeightEmaP, c_void, ctypes.c_float, ctypes.c_float, c_int, c_void]),
+    "dctn_rmsprop_num_partials": (c_int, [c_i64]),
+    "dctn_rmsprop_flat_step": (c_int, [_FlatStepP, _WeightEmaP, c_void, c_void, ctypes.c_double, ctypes.c_float,
+                                       ctypes.c_float, ctypes.c_float, c_void]),
+    "dctn_sgd_flat_step_decay": (c_int, [_FlatStepP, _WeightEmaP, c_void, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                         c_int, c_void]),
     "dctn_weight_ema_apply": (c_int, [c_void, c_void, c_void, c_i64, c_int, c_void]),
     "dctn_weight_ema_restore": (c_int, [c_void, c_void, c_i64, c_int, c_void]),
     "dctn_step_trace_head_bytes": (c_size, []),

@@ -11,7 +11,8 @@
 //                prefix, buf = momentum * buf + g, w -= lr * buf; the regulariser's value
 //                sum w^2 is left as one partial sum per workgroup (float32 arithmetic; the result is rounded back
 //                into the parameter's cell).  MASTER form (bf16 parameters): the step runs on a float32 master
-//                copy, which is read and written; the bf16 cell only receives the rounded result
+//                copy, which is read and written; the bf16 cell only receives the rounded result.  DECAY form:
+//                torch.optim.SGD's coupled weight decay, g += wd * w, in front of the 2 * l2 * w term
 #include "common.h"
 #include "grad_guard.h"
 #include "lr_schedule.h"
@@ -114,6 +115,24 @@ __device__ __forceinline__ float sgd_elem(float wi, float gi, float* __restrict_
   return fmaf(-lr, bi, wi);
 }
 
+// DECAY (the pack ends with an SgdDecay by value): torch.optim.SGD's coupled weight decay, g = fmaf(wd, w, g), in front of
+// the 2 * l2 * w term and the momentum - Adam's order, and torch's.  Without the member the gradient keeps its bits.
+struct SgdDecay {
+  float wd;
+};
+template <bool DECAY> __device__ __forceinline__ float sgd_decayed(float gi, float wi, float wd) {
+  if constexpr (DECAY) return fmaf(wd, wi, gi); else return gi;
+}
+// The grouped form's LDS copy of the segments' decays exists only in the DECAY instantiations
+template <bool DECAY> __device__ __forceinline__ float* sgd_seg_wd() {
+  if constexpr (DECAY) {
+    __shared__ float seg_wd[DCTN_PG_MAX_SEGMENTS];
+    return seg_wd;
+  } else {
+    return nullptr;
+  }
+}
+
 // MASTER (S = bf16_t): the weight comes from and goes back to the float32 array `wm`; `w` gets its bf16 rounding and is
 // not read, and `wm` and the sq_sum slots are the float instantiation's bits.  Without MASTER `wm` is unused (null).
 // GUARD: the step obeys a gradient guard's decision (grad_guard.hip, launched in front of this kernel), as
@@ -133,12 +152,13 @@ __device__ __forceinline__ float sgd_elem(float wi, float gi, float* __restrict_
 // rate - state->lr, or the schedule's value at the GLOBAL steps_done - and publishes every segment's end, rate (one
 // rounded product rate * lr_scale), first_step = (the SEGMENT's steps == 0) and frozen flag through LDS.  Every lane
 // walks a cursor over the ends as its elements increase.  A frozen element only adds w * w below n_reg: its gradient
-// and momentum are not read and nothing of it is stored.  The table's weight_decay is not used: sgd_l2_k has none.
+// and momentum are not read and nothing of it is stored.  The table's weight_decay is used by the DECAY form only: there
+// every segment takes its own decay from the table and the pack's value is not looked at.
 // EMA (the pack ends with a WeightEma, and always holds a StepStateBlock*): every element the step stores to also moves
 // its average, from the value the step keeps for it (weight_ema.h).  Lane 0 loads the block's three cells beside
 // steps_done and publishes the launch's weight; the last ticket writes updates + 1 and that weight.  Without a schedule
 // or a group table the rate is state->lr and first_step is steps_done == 0, as the grouped form reads them.
-template <typename S, bool MASTER, bool GUARD, bool SCHED, bool EMA>
+template <typename S, bool MASTER, bool GUARD, bool SCHED, bool EMA, bool DECAY>
 __device__ __forceinline__ void sgd_grouped_body(S* __restrict__ w, float* __restrict__ wm, const S* __restrict__ g,
                                                  float* __restrict__ buf, float* __restrict__ sq_sum, long long n,
                                                  long long n_reg, float momentum, float l2, const GradGuardBlock* guard,
@@ -150,6 +170,7 @@ __device__ __forceinline__ void sgd_grouped_body(S* __restrict__ w, float* __res
   __shared__ float seg_lr[DCTN_PG_MAX_SEGMENTS];
   __shared__ int seg_first[DCTN_PG_MAX_SEGMENTS], seg_frozen[DCTN_PG_MAX_SEGMENTS];
   __shared__ int seg_count;
+  [[maybe_unused]] float* const seg_wd = sgd_seg_wd<DECAY>();
   int steps_done = 0, my_steps = 0;
   float rate = 0.f;
   bool my_live = false;   // wave 0: this lane's segment is in use and not frozen
@@ -179,6 +200,7 @@ __device__ __forceinline__ void sgd_grouped_body(S* __restrict__ w, float* __res
     seg_end[lane] = sg.end;
     seg_lr[lane] = __fmul_rn(rate, sg.lr_scale);
     seg_first[lane] = sg.steps == 0 ? 1 : 0;
+    if constexpr (DECAY) seg_wd[lane] = sg.weight_decay;
     seg_frozen[lane] = (sg.flags & DCTN_PG_FROZEN) != 0u ? 1 : 0;
     if (lane == 0) seg_count = sg.n_segments;
   }
@@ -196,11 +218,15 @@ __device__ __forceinline__ void sgd_grouped_body(S* __restrict__ w, float* __res
   float lr = seg_lr[0];
   int first_step = seg_first[0];
   bool frozen = seg_frozen[0] != 0;
+  [[maybe_unused]] float wd = 0.f;
+  if constexpr (DECAY) wd = seg_wd[0];
   float part = 0.f;
   const float two_l2 = 2.f * l2;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    if (param_group_advance(cur, i, seg_end, n_seg))
+    if (param_group_advance(cur, i, seg_end, n_seg)) {
       lr = seg_lr[cur.seg], first_step = seg_first[cur.seg], frozen = seg_frozen[cur.seg] != 0;
+      if constexpr (DECAY) wd = seg_wd[cur.seg];
+    }
     if (frozen) {
       if (i < n_reg) {
         const float wi = MASTER ? wm[i] : (float)w[i];
@@ -208,7 +234,8 @@ __device__ __forceinline__ void sgd_grouped_body(S* __restrict__ w, float* __res
       }
       continue;
     }
-    const float wi = sgd_elem(MASTER ? wm[i] : (float)w[i], clipped<GUARD>((float)g[i], coef), buf + i, i < n_reg, lr,
+    const float w0 = MASTER ? wm[i] : (float)w[i];
+    const float wi = sgd_elem(w0, sgd_decayed<DECAY>(clipped<GUARD>((float)g[i], coef), w0, wd), buf + i, i < n_reg, lr,
                               momentum, two_l2, first_step, part);
     w[i] = (S)wi;
     if (MASTER) wm[i] = wi;
@@ -247,6 +274,10 @@ __global__ __launch_bounds__(256) void sgd_l2_k(S* __restrict__ w, float* __rest
   // (GROUPED, with the StepStateBlock* whether or not there is a schedule), in that order, or nothing: the plain kernel,
   // parameter for parameter
   // and behind them a WeightEma (EMA, always with the StepStateBlock*): the average's values and block
+  // and last an SgdDecay (DECAY): the weight decay, with or without any of the others
+  constexpr bool DECAY = pack_has_v<SgdDecay, G...>;
+  [[maybe_unused]] float wd = 0.f;
+  if constexpr (DECAY) wd = pack_get<SgdDecay>(guard_block...).wd;
   constexpr bool GUARD = pack_has_v<const GradGuardBlock*, G...>, SCHED = pack_has_v<const LrScheduleBlock*, G...>;
   constexpr bool EMA = pack_has_v<WeightEma, G...>;
   [[maybe_unused]] WeightEma ema{nullptr, nullptr};
@@ -256,7 +287,7 @@ __global__ __launch_bounds__(256) void sgd_l2_k(S* __restrict__ w, float* __rest
     const LrScheduleBlock* sched = nullptr;
     if constexpr (GUARD) guard = pack_get<const GradGuardBlock*>(guard_block...);
     if constexpr (SCHED) sched = pack_get<const LrScheduleBlock*>(guard_block...);
-    sgd_grouped_body<S, MASTER, GUARD, SCHED, EMA>(w, wm, g, buf, sq_sum, n, n_reg, momentum, l2, guard,
+    sgd_grouped_body<S, MASTER, GUARD, SCHED, EMA, DECAY>(w, wm, g, buf, sq_sum, n, n_reg, momentum, l2, guard,
                                                    pack_get<StepStateBlock*>(guard_block...), sched,
                                                    pack_get<ParamGroupBlock*>(guard_block...), ema);
     return;
@@ -336,7 +367,8 @@ __global__ __launch_bounds__(256) void sgd_l2_k(S* __restrict__ w, float* __rest
   float part = 0.f;
   const float two_l2 = 2.f * l2;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const float wi = sgd_elem(MASTER ? wm[i] : (float)w[i], clipped<GUARD>((float)g[i], coef), buf + i, i < n_reg, lr,
+    const float w0 = MASTER ? wm[i] : (float)w[i];
+    const float wi = sgd_elem(w0, sgd_decayed<DECAY>(clipped<GUARD>((float)g[i], coef), w0, wd), buf + i, i < n_reg, lr,
                               momentum, two_l2, first_step, part);
     w[i] = (S)wi;
     if (MASTER) wm[i] = wi;
@@ -379,6 +411,7 @@ struct SgdStep {
   int first_step;
   hipStream_t st;
   const dctn_weight_ema_t* ema;   // null: no average
+  const float* decay;             // null: the kernels without weight decay
 };
 
 // The one launcher.  sgd_l2_k is built for the packs that hold the step block exactly when they hold a schedule, a
@@ -395,24 +428,30 @@ template <typename S, bool MASTER, typename... G> void sgd_launch(const SgdStep&
 }
 
 // The pack is the optional blocks the step has, in the order sgd_l2_k expects: guard, step state, schedule, group table,
-// and the average (a pair by value) behind them
+// and the average (a pair by value) and the weight decay (by value) behind them
 template <typename S, bool MASTER> void sgd_dispatch(const SgdStep& a, StepStateBlock* state) {
   with_blocks([&](auto... pack) {
-    if (a.ema) sgd_launch<S, MASTER>(a, pack..., WeightEma{(float*)a.ema->ema, (WeightEmaBlock*)a.ema->block});
-    else sgd_launch<S, MASTER>(a, pack...);
+    const auto decayed = [&](auto... full) {
+      if (a.decay) sgd_launch<S, MASTER>(a, full..., SgdDecay{*a.decay});
+      else sgd_launch<S, MASTER>(a, full...);
+    };
+    if (a.ema) decayed(pack..., WeightEma{(float*)a.ema->ema, (WeightEmaBlock*)a.ema->block});
+    else decayed(pack...);
   }, (const GradGuardBlock*)a.d.guard, state, (const LrScheduleBlock*)a.d.schedule, (ParamGroupBlock*)a.d.groups);
 }
 
 // Validates and launches.  With a schedule, a group table or an average the rate and first_step come from the step block
 // on the device: the block is required, and the two launch arguments are zeros whatever the caller passed.
 int sgd_step(const dctn_flat_step_t& d, void* momentum_buf, float lr, float momentum, int first_step, void* stream,
-             const dctn_weight_ema_t* ema = nullptr) {
+             const dctn_weight_ema_t* ema = nullptr, const float* decay = nullptr) {
   const bool on_device = d.schedule || d.groups || ema;
   if (!d.params || !d.grads || !momentum_buf || (on_device && !d.state)) return DCTN_ERR_NULL;
   if (ema && (!ema->ema || !ema->block)) return DCTN_ERR_NULL;
   if (d.n < 1 || d.n_reg < 0 || d.n_reg > d.n) return DCTN_ERR_BAD_SHAPE;
+  if (decay && !(*decay >= 0.f)) return DCTN_ERR_BAD_SHAPE;
   if ((d.dtype != DCTN_F32 && d.dtype != DCTN_BF16) || (d.master && d.dtype != DCTN_BF16)) return DCTN_ERR_BAD_DTYPE;
-  const SgdStep a{d, momentum_buf, on_device ? 0.f : lr, momentum, on_device ? 0 : first_step, (hipStream_t)stream, ema};
+  const SgdStep a{d, momentum_buf, on_device ? 0.f : lr, momentum, on_device ? 0 : first_step, (hipStream_t)stream, ema,
+                  decay};
   StepStateBlock* state = on_device ? (StepStateBlock*)d.state : nullptr;
   if (d.master) sgd_dispatch<bf16_t, true>(a, state);
   else if (d.dtype == DCTN_F32) sgd_dispatch<float, false>(a, state);
@@ -486,6 +525,14 @@ int dctn_sgd_flat_step_ema(const dctn_flat_step_t* step, const dctn_weight_ema_t
                            float lr, float momentum, int first_step, void* stream) {
   if (!step) return DCTN_ERR_NULL;
   return sgd_step(*step, momentum_buf, lr, momentum, first_step, stream, ema_or_null);
+}
+
+// dctn_sgd_flat_step_ema with torch.optim.SGD's coupled weight decay: the DECAY kernels, for any weight_decay >= 0.  With
+// a group table every segment's decay comes from the table and the argument is not used
+int dctn_sgd_flat_step_decay(const dctn_flat_step_t* step, const dctn_weight_ema_t* ema_or_null, void* momentum_buf,
+                             float lr, float momentum, float weight_decay, int first_step, void* stream) {
+  if (!step) return DCTN_ERR_NULL;
+  return sgd_step(*step, momentum_buf, lr, momentum, first_step, stream, ema_or_null, &weight_decay);
 }
 
 // The six entry points older than the descriptor: each fills one and takes sgd_step.  An entry point that requires a

@@ -493,8 +493,9 @@ class StepTrace:
                guard: Optional["GradGuard"] = None, optimizer=None, batch_source=None) -> None:
         """Enqueues the launch on the current stream.  ``logits`` (B, C) float32 / bfloat16, ``labels`` int64, ``loss`` and
         ``reg`` float32 device scalars (a ``reg`` of another dtype is cast first: one more launch).  The Adam block is
-        taken from a `FlatAdam`, or from a `FlatSGD` with a schedule (the same layout); a `FlatSGD` without one (or any
-        other optimizer) has no device block and passes none."""
+        taken from a `FlatAdam` or a `FlatRMSprop`, or from a `FlatSGD` that owns one (with a schedule, a group table or
+        a weight average: the same layout); a `FlatSGD` without one (or any other optimizer) has no device block and
+        passes none."""
         dev = L.require_device(logits, labels, loss)
         if logits.ndim != 2 or labels.shape != (logits.shape[0],) or labels.dtype != torch.int64:
             raise TypeError("StepTrace.record: logits (batch, classes) and int64 labels (batch,)")
@@ -506,8 +507,8 @@ class StepTrace:
             if reg.numel() != 1:
                 raise TypeError("StepTrace.record: reg must be a scalar")
             reg = reg.detach().to(device=dev, dtype=torch.float32)
-        # (a FlatSGD has the block only with a schedule: the same 16 bytes)
-        adam = getattr(optimizer, "_state", None) if isinstance(optimizer, (FlatAdam, FlatSGD)) else None
+        # (a FlatSGD has the block only with a schedule: the same 16 bytes; a FlatRMSprop always has it)
+        adam = getattr(optimizer, "_state", None) if isinstance(optimizer, _FlatOptimizer) else None
         L.check(L.lib().dctn_step_trace_record(
             logits.data_ptr(), labels.data_ptr(), loss.data_ptr(), None if reg is None else reg.data_ptr(),
             None if guard is None else guard._block.data_ptr(), None if adam is None else adam.data_ptr(),
@@ -806,6 +807,18 @@ class LRSchedule:
             raise ValueError(f"LRSchedule.milestones: milestones are steps >= 1, got {list(milestones)}")
         knots = [(0, lr)] + [(m, lr * gamma ** (j + 1)) for j, m in enumerate(marks)]
         return cls(device, knots, hold=[1] * len(knots))
+
+    @classmethod
+    def per_epoch(cls, device, rates: Sequence[float], steps_per_epoch: int) -> "LRSchedule":
+        """One rate per epoch, held for the epoch's ``steps_per_epoch`` steps: step ``s`` gets
+        ``rates[s // steps_per_epoch]``, and the last rate holds from the last epoch on.  What a scheduler stepped once
+        per epoch gives (the reference's classifier warms up so, mnist.py:490-494); at most 64 epochs fit the table."""
+        rates = [r for r in rates]
+        if int(steps_per_epoch) != steps_per_epoch or int(steps_per_epoch) < 1:
+            raise ValueError(f"LRSchedule.per_epoch: steps_per_epoch is an integer >= 1, got {steps_per_epoch!r}")
+        if not 1 <= len(rates) <= cls.MAX_KNOTS:
+            raise ValueError(f"LRSchedule.per_epoch: 1 to {cls.MAX_KNOTS} rates (one knot per epoch), got {len(rates)}")
+        return cls(device, [(e * int(steps_per_epoch), r) for e, r in enumerate(rates)], hold=[1] * len(rates))
 
 
 class ParamGroup:
@@ -1294,7 +1307,7 @@ class WeightEMA:
 
 
 class _FlatOptimizer:
-    """What FlatSGD and FlatAdam share: the parameters moved into ONE flat buffer (their ``.data`` become views of it,
+    """What FlatSGD, FlatAdam and FlatRMSprop share: the parameters moved into ONE flat buffer (their ``.data`` become views of it,
     in the order regularised + others), the gradients read in place when they already sit back to back in that
     order (the fused EPS + head backward allocates them so) and gathered otherwise, and the regulariser's value left
     by the step kernel as one partial sum of squares per workgroup.
@@ -1534,8 +1547,8 @@ class FlatSGD(_FlatOptimizer):
     `dctn_sgd_l2_step_grouped` (behind the guard's check when there is a guard): every parameter steps with ``rate * lr_scale`` of its segment, takes its
     first step when ITS count is 0, and is left alone while frozen.  The optimizer then owns the 16-byte step block
     whether or not there is a schedule: without one ``opt.lr = x`` writes the block's rate cell (not during a capture),
-    and a captured step follows it.  ``opt.t`` stays the global count.  A `ParamGroup` for this optimizer leaves
-    ``weight_decay=None`` (ValueError otherwise).  The table's state is not part of ``state_dict()``; save
+    and a captured step follows it.  ``opt.t`` stays the global count.  Without the ``weight_decay`` option a `ParamGroup`
+    for this optimizer leaves ``weight_decay=None`` (ValueError otherwise).  The table's state is not part of ``state_dict()``; save
     ``groups.state_dict()`` beside it (`checkpoint.RunState` carries its block).  Without ``groups`` ``step()`` makes
     the calls it always made.
 
@@ -1543,15 +1556,25 @@ class FlatSGD(_FlatOptimizer):
     element it stores to, from the value the optimizer keeps for it.  The optimizer then owns the 16-byte step block, as
     with a group table: the rate and the first step are read on the device, and ``opt.lr = x`` writes the block's rate
     cell.  ``state_dict()`` holds the average under ``"ema"``.  Without ``ema`` ``step()`` makes the calls it always made.
+
+    ``weight_decay`` (a float >= 0, ``0.0`` included): torch.optim.SGD's coupled weight decay,
+    ``g += weight_decay * w`` in front of the ``2 * l2 * w`` term and the momentum (behind the guard's clip).  ``step()``
+    then calls `dctn_sgd_flat_step_decay` whatever the other options; a `ParamGroups` table is bound with this value as
+    its default, and a `ParamGroup` may name its own.  ``state_dict()`` and ``run_host()`` carry it under
+    ``"weight_decay"``.  ``None`` (the default): the optimizer has no weight decay, refuses a table that names one, and
+    ``step()`` makes the calls it always made.
     """
 
     def __init__(self, regularised, others=(), lr: float = 1e-3, momentum: float = 0.0, l2: float = 0.0,
                  master_weights: bool = False, guard: Optional["GradGuard"] = None, guard_loss=None, *,
                  schedule: Optional["LRSchedule"] = None, groups: Optional["ParamGroups"] = None,
-                 ema: Optional["WeightEMA"] = None):
+                 ema: Optional["WeightEMA"] = None, weight_decay: Optional[float] = None):
         super().__init__(regularised, others, L.lib().dctn_sgd_l2_num_partials, master_weights, guard, guard_loss,
                          schedule, groups, ema)
         self._lr, self.momentum, self.l2 = float(lr), float(momentum), float(l2)
+        if weight_decay is not None and not float(weight_decay) >= 0.0:
+            raise ValueError(f"invalid SGD weight_decay: {weight_decay}")
+        self.weight_decay: Optional[float] = None if weight_decay is None else float(weight_decay)
         self.buf = torch.zeros(self.n, dtype=torch.float32, device=self.flat.device)
         self._steps = 0
         # with a schedule: {int32 steps_done, float32 lr, uint32 ticket, uint32 reserved}, FlatAdam's block
@@ -1560,7 +1583,7 @@ class FlatSGD(_FlatOptimizer):
             assert L.lib().dctn_adam_state_bytes() == 16 and L.lib().dctn_lr_schedule_bytes() == 4 * LRSchedule.WORDS
             self._state = torch.zeros(4, dtype=torch.int32, device=self.flat.device)
         if groups is not None:
-            groups._bind(None, "FlatSGD")
+            groups._bind(self.weight_decay, "FlatSGD")
         if groups is not None or ema is not None:   # these steps always take the block; without a schedule they read its rate cell
             if self._state is None:
                 assert L.lib().dctn_adam_state_bytes() == 16
@@ -1600,7 +1623,11 @@ class FlatSGD(_FlatOptimizer):
         # count of launches, and under a guard the host does not know whether the guard let a launch through.  A skipped
         # step 0 leaves the momentum buffer at its zeros, and the next launch, with first = 0, forms momentum * 0 + g = g:
         # the update a first step makes.  (With either option the kernel reads both from the step block instead.)
-        if self._ema_ref is None:
+        if self.weight_decay is not None:
+            L.check(L.lib().dctn_sgd_flat_step_decay(self._desc_ref, self._ema_ref, self.buf.data_ptr(), self._lr,
+                                                     self.momentum, self.weight_decay, 1 if self._steps == 0 else 0,
+                                                     L.stream_ptr(self.flat.device)), self._what)
+        elif self._ema_ref is None:
             L.check(L.lib().dctn_sgd_flat_step(self._desc_ref, self.buf.data_ptr(), self._lr, self.momentum,
                                                1 if self._steps == 0 else 0, L.stream_ptr(self.flat.device)), self._what)
         else:
@@ -1612,6 +1639,8 @@ class FlatSGD(_FlatOptimizer):
     def state_dict(self) -> Dict[str, Any]:
         """Everything a resumed run needs besides the parameters themselves (those are the model's state_dict)."""
         state = {"steps": self.t, "lr": self.lr, "momentum": self.momentum, "l2": self.l2, "buf": self.buf.clone()}
+        if self.weight_decay is not None:
+            state["weight_decay"] = self.weight_decay
         if self.master is not None:
             state["master"] = self.master.clone()
         if self.ema is not None:
@@ -1622,6 +1651,8 @@ class FlatSGD(_FlatOptimizer):
         if state["buf"].numel() != self.n:
             raise ValueError(f"optimizer state holds {state['buf'].numel()} values, the parameters {self.n}")
         self.momentum, self.l2 = float(state["momentum"]), float(state["l2"])
+        if self.weight_decay is not None and "weight_decay" in state:   # (a state written without the option keeps this one's)
+            self.weight_decay = float(state["weight_decay"])
         with torch.no_grad():
             self.buf.copy_(state["buf"].reshape(-1))
         self._steps = int(state["steps"])
@@ -1637,10 +1668,15 @@ class FlatSGD(_FlatOptimizer):
     _MOMENTS = ("buf",)
 
     def run_host(self) -> Dict[str, Any]:
-        return dict(kind=type(self).__name__, lr=self._lr, momentum=self.momentum, l2=self.l2, steps=self._steps)
+        host = dict(kind=type(self).__name__, lr=self._lr, momentum=self.momentum, l2=self.l2, steps=self._steps)
+        if self.weight_decay is not None:
+            host["weight_decay"] = self.weight_decay
+        return host
 
     def run_restored(self, host: Dict[str, Any], blocks) -> None:
         self._lr, self.momentum, self.l2 = float(host["lr"]), float(host["momentum"]), float(host["l2"])
+        if self.weight_decay is not None and "weight_decay" in host:
+            self.weight_decay = float(host["weight_decay"])
         self._steps = int(host["steps"])
         super().run_restored(host, blocks)
 
@@ -1800,6 +1836,128 @@ class FlatAdam(_FlatOptimizer):
     def run_restored(self, host: Dict[str, Any], blocks) -> None:
         self._lr = float(host["lr"])   # the rate itself came back with the 16-byte block
         self.betas, self.eps = (float(host["betas"][0]), float(host["betas"][1])), float(host["eps"])
+        self.weight_decay, self.l2 = float(host["weight_decay"]), float(host["l2"])
+        super().run_restored(host, blocks)
+
+
+class FlatRMSprop(_FlatOptimizer):
+    """torch.optim.RMSprop (coupled ``weight_decay``, optional ``momentum``, not centered - what the reference's
+    classifier script builds, mnist.py:466-476) plus the reference's L2 regulariser, as ONE kernel per step over one
+    flat parameter buffer: ``step()`` makes one library call, `dctn_rmsprop_flat_step`, whatever the options.
+    Construction, gradient handling and ``reg_value()`` are FlatSGD's; ``square_avg`` is float32 whatever the parameter
+    dtype, and so is the momentum buffer ``buf``, which exists only with ``momentum > 0`` (fixed at construction: without
+    it the launch moves nothing for a buffer).  Both start from zeros, as torch's, so there is no first-step case.
+
+    The step count and the learning rate live in `FlatAdam`'s 16-byte DEVICE block, with its behaviour: the launch
+    advances the count, a captured ``step()`` follows ``opt.lr = x`` assigned between replays, ``opt.t`` reads the device.
+    ``master_weights``, ``guard`` / ``guard_loss``, ``schedule``, ``groups`` and ``ema`` are `FlatAdam`'s options with its
+    semantics (a segment of a group table has no bias correction to keep: it steps with ``rate * lr_scale`` and its own
+    weight decay, and its count only advances).  ``state_dict()`` / ``load_state_dict()`` carry t, lr, the buffers, the
+    hyper-parameters, the master copy and the average: a run resumed from them continues bit-identically.
+    ``centered=True`` is not offered.
+    """
+
+    def __init__(self, regularised, others=(), lr: float = 1e-2, alpha: float = 0.99, eps: float = 1e-8,
+                 weight_decay: float = 0.0, momentum: float = 0.0, l2: float = 0.0, master_weights: bool = False,
+                 guard: Optional["GradGuard"] = None, guard_loss=None, *, schedule: Optional["LRSchedule"] = None,
+                 groups: Optional["ParamGroups"] = None, ema: Optional["WeightEMA"] = None):
+        super().__init__(regularised, others, L.lib().dctn_rmsprop_num_partials, master_weights, guard, guard_loss,
+                         schedule, groups, ema)
+        if not (0.0 <= alpha < 1.0 and lr >= 0.0 and eps >= 0.0 and weight_decay >= 0.0 and momentum >= 0.0):
+            raise ValueError(f"invalid RMSprop hyper-parameters: lr={lr} alpha={alpha} eps={eps} "
+                             f"weight_decay={weight_decay} momentum={momentum}")
+        self.alpha, self.eps, self.momentum = float(alpha), float(eps), float(momentum)
+        self.weight_decay, self.l2 = float(weight_decay), float(l2)
+        dev = self.flat.device
+        self.square_avg = torch.zeros(self.n, dtype=torch.float32, device=dev)
+        self.buf: Optional[Tensor] = torch.zeros(self.n, dtype=torch.float32, device=dev) if self.momentum > 0.0 else None
+        self._MOMENTS = ("square_avg",) if self.buf is None else ("square_avg", "buf")
+        # {int32 steps_done, float32 lr, uint32 ticket, uint32 reserved}: include/dctn_amd.h
+        assert L.lib().dctn_adam_state_bytes() == 16
+        self._state = torch.zeros(4, dtype=torch.int32, device=dev)
+        self._lr_cell = self._state.view(torch.float32)[1:2]
+        self._lr = float("nan")
+        if schedule is None:
+            self.lr = lr
+        else:   # the block's rate cell is the kernel's to write: the rate of the step just taken
+            self._lr = float(lr)
+            assert L.lib().dctn_lr_schedule_bytes() == 4 * LRSchedule.WORDS
+        if groups is not None:
+            groups._bind(self.weight_decay, "FlatRMSprop")
+        self._describe("fused RMSprop step")
+
+    @property
+    def lr(self) -> float:
+        """Without a schedule the host copy of the rate; with one, ``schedule.value(t)`` (reads the device)."""
+        return self._lr if self.schedule is None else self._scheduled_lr()
+
+    @lr.setter
+    def lr(self, value: float) -> None:
+        if self.schedule is not None:
+            self._refuse_lr()
+        if self.flat.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FlatRMSprop.lr cannot be assigned during a graph capture: the captured step reads the "
+                               "rate from the device, assign it between replays")
+        self._lr = float(value)
+        _write_cell(self._lr_cell, self._lr)
+
+    @property
+    def t(self) -> int:
+        """Number of steps taken (read from the device)."""
+        return int(self._state[0].item())
+
+    @torch.no_grad()
+    def step(self) -> None:
+        self._begin_step()
+        # (with a group table every segment's weight decay is in the table, and the launch ignores this one)
+        L.check(L.lib().dctn_rmsprop_flat_step(self._desc_ref, self._ema_ref, self.square_avg.data_ptr(),
+                                               None if self.buf is None else self.buf.data_ptr(), self.alpha, self.eps,
+                                               self.weight_decay, self.momentum, L.stream_ptr(self.flat.device)),
+                self._what)
+
+    def state_dict(self) -> Dict[str, Any]:
+        """Everything a resumed run needs besides the parameters themselves (those are the model's state_dict)."""
+        state = {"t": self.t, "lr": self.lr, "square_avg": self.square_avg.clone(), "alpha": self.alpha,
+                 "eps": self.eps, "weight_decay": self.weight_decay, "momentum": self.momentum, "l2": self.l2}
+        if self.buf is not None:
+            state["buf"] = self.buf.clone()
+        if self.master is not None:
+            state["master"] = self.master.clone()
+        if self.ema is not None:
+            state["ema"] = self.ema.state_dict()
+        return state
+
+    def load_state_dict(self, state: Dict[str, Any]) -> None:
+        if state["square_avg"].numel() != self.n:
+            raise ValueError(f"optimizer state holds {state['square_avg'].numel()} values, the parameters {self.n}")
+        if (float(state["momentum"]) > 0.0) != (self.buf is not None):
+            raise ValueError(f"optimizer state was written with momentum {state['momentum']}, this optimizer was built "
+                             f"with {self.momentum}: the momentum buffer exists from construction or not at all")
+        self.alpha, self.eps, self.momentum = float(state["alpha"]), float(state["eps"]), float(state["momentum"])
+        self.weight_decay, self.l2 = float(state["weight_decay"]), float(state["l2"])
+        with torch.no_grad():
+            self.square_avg.copy_(state["square_avg"].reshape(-1))
+            if self.buf is not None:
+                self.buf.copy_(state["buf"].reshape(-1))
+            self._state.zero_()
+            self._state[0] = int(state["t"])
+        if self.schedule is None:
+            self.lr = state["lr"]
+        else:
+            self._put_step_block(int(state["t"]))
+        self._load_master(state)
+        self._load_ema(state)
+
+    def run_host(self) -> Dict[str, Any]:
+        return dict(kind=type(self).__name__, lr=self._lr, alpha=self.alpha, eps=self.eps,
+                    weight_decay=self.weight_decay, momentum=self.momentum, l2=self.l2)
+
+    def run_restored(self, host: Dict[str, Any], blocks) -> None:
+        if (float(host["momentum"]) > 0.0) != (self.buf is not None):
+            raise ValueError(f"snapshot: the optimizer was saved with momentum {host['momentum']}, the run's was built "
+                             f"with {self.momentum}")
+        self._lr = float(host["lr"])   # the rate itself came back with the 16-byte block
+        self.alpha, self.eps, self.momentum = float(host["alpha"]), float(host["eps"]), float(host["momentum"])
         self.weight_decay, self.l2 = float(host["weight_decay"]), float(host["l2"])
         super().run_restored(host, blocks)
 

@@ -551,7 +551,7 @@ int dctn_sgd_l2_step_scheduled(void* master_or_null, void* params, const void* g
  *   int32   reserved[3]       0
  *   int64   end[64]           exclusive element index where a segment ends; strictly increasing; the last used one is n
  *   float   lr_scale[64]      multiplies the rate; 1.0f leaves the bits alone
- *   float   weight_decay[64]  Adam's coupled weight decay of the segment (the SGD step does not use it)
+ *   float   weight_decay[64]  the segment's coupled weight decay (of the SGD steps only dctn_sgd_flat_step_decay uses it)
  *   uint32  flags[64]         bit 0: frozen
  *   int32   steps[64]         steps the segment has taken; the launch advances it
  * One segment is one parameter, in flat order: elements [end[s-1], end[s]), end[-1] = 0.  Slots at and past n_segments
@@ -694,6 +694,48 @@ int dctn_sgd_flat_step_ema(const dctn_flat_step_t* step, const dctn_weight_ema_t
                            float lr, float momentum, int first_step, void* stream);
 int dctn_weight_ema_apply(void* params, void* stash, const void* ema, int64_t n, int dtype, void* stream);
 int dctn_weight_ema_restore(void* params, const void* stash, int64_t n, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * RMSprop on the flat path, and weight decay for the flat SGD (version 515): with dctn_adam_flat_step the four
+ * optimizers the reference's training scripts build (new_runner.py:496-498, mnist.py:466-476).
+ *
+ * dctn_rmsprop_flat_step: torch.optim.RMSprop(lr, alpha, eps, weight_decay, momentum, centered=False) plus the fused L2
+ * term, ONE launch over the flat buffer described by a dctn_flat_step_t.  Per element, in float32, every product-sum one
+ * fused multiply-add in this order (g after the guard's clip, one rounded product g * coef):
+ *     g   = fma(wd, w, g)
+ *     g   = fma(2 * l2, w, g)                      below n_reg; sq_sum takes w * w
+ *     sq  = fma(alpha, sq, (oma * g) * g)          oma = (float)(1.0 - alpha), formed in double
+ *     avg = sqrt(sq) + eps                         correctly rounded square root and division
+ *     buf = fma(momentum, buf, g / avg);  w = fma(-rate, buf, w)        with a momentum buffer
+ *                                         w = fma(-rate, g / avg, w)    without one
+ * There is no first-step case: square_avg and the buffer start from zeros, as torch's.
+ *   square_avg            n float32 values, read and written
+ *   momentum_buf_or_null  n float32 values, required when momentum > 0.  momentum == 0: no buffer exists; the pointer
+ *                         is not looked at and the launch moves nothing for it
+ *   state                 the 16-byte step block, REQUIRED: the rate is read from it (or, with a schedule, evaluated at
+ *                         its steps_done and left in it), and the launch advances steps_done as dctn_adam_flat_step's
+ *   sq_sum                NULL, or dctn_rmsprop_num_partials(n) float32 slots, OVERWRITTEN
+ * Master copy, guard, schedule, group table and weight average mean what they mean for dctn_adam_flat_step_ema, Adam's
+ * per-segment bias corrections aside: a segment steps with rate * lr_scale and its own weight decay, a frozen one is not
+ * touched (its squares still count in sq_sum) and its `steps` does not advance.  With a group table the weight_decay
+ * argument is ignored.
+ * Return codes, decided on the host before any launch: DCTN_ERR_NULL (the struct, params, grads, square_avg or state; a
+ * given dctn_weight_ema_t with a null member; momentum > 0 without a buffer), then DCTN_ERR_BAD_SHAPE (n < 1, n_reg
+ * outside 0..n, alpha outside [0, 1) or not finite, momentum < 0, eps < 0, weight_decay < 0), then DCTN_ERR_BAD_DTYPE
+ * (a dtype that is neither DCTN_F32 nor DCTN_BF16, or a master copy beside one that is not DCTN_BF16).
+ *
+ * dctn_sgd_flat_step_decay: dctn_sgd_flat_step_ema with torch.optim.SGD's coupled weight decay, g = fma(wd, w, g) in
+ * front of the 2 * l2 * w term and the momentum.  With a group table every segment takes the table's weight_decay and
+ * the argument is ignored.  weight_decay == 0 leaves the bits of dctn_sgd_flat_step_ema (it launches other kernels).
+ * Return codes: dctn_sgd_flat_step_ema's, and weight_decay < 0 (or NaN) is DCTN_ERR_BAD_SHAPE.
+ * Both only enqueue and can be captured.  Neither reports to dctn_last_kernel.
+ * ------------------------------------------------------------------------------------------ */
+int dctn_rmsprop_flat_step(const dctn_flat_step_t* step, const dctn_weight_ema_t* ema_or_null, void* square_avg,
+                           void* momentum_buf_or_null, double alpha, float eps, float weight_decay, float momentum,
+                           void* stream);
+int dctn_rmsprop_num_partials(int64_t n);
+int dctn_sgd_flat_step_decay(const dctn_flat_step_t* step, const dctn_weight_ema_t* ema_or_null, void* momentum_buf,
+                             float lr, float momentum, float weight_decay, int first_step, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Scoring(reference: dctn/evaluation.py:7-22): one launch per batch ADDS to acc = three float64 values
