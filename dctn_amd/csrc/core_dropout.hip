@@ -3,7 +3,7 @@
 // function of (seed, draw, core number, element index): Philox4x32-10, nothing stored.  include/dctn_amd.h holds the
 // normative definition.  Three kernels from one template:
 //   fwd  : out = keep ? core / p : 0; reads the draw index from the 16-byte device block, leaves the draw record for
-//          the backward, and the launch itself advances the block (adam_l2_k's ticket): replays draw d, d + 1, ...
+//          the backward, and the launch itself advances the block (flat_step_k's ticket): replays draw d, d + 1, ...
 //   bwd  : d_core = keep ? d_out / p : 0 from the record (d_core may BE d_out: a lane reads its 4 values, then writes them)
 //   mask : 1 / 0 from the record (diagnostic)
 #include "common.h"
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(DROP_THREADS) void core_dropout_k(DropSegs segs, co
   }
 
   if (OP == DROP_FWD && threadIdx.x == 0) {
-    // The ticket, as adam_l2_k's.  It orders one thing only: every workgroup's read of the block before the last
+    // The ticket, as flat_step_k's (flat_step.h).  It orders one thing only: every workgroup's read of the block before the last
     // workgroup's write of it.  No data passes between workgroups (the kernel boundary publishes the cores); the wait
     // makes sure this lane's state loads have returned before the ticket is drawn, and the writer acts on the value its
     // own ticket returned.

@@ -1,5 +1,5 @@
 // The gradient guard's device block (include/dctn_amd.h documents this layout: it is part of the ABI).  grad_guard.hip
-// writes it; the guarded forms of adam_l2_k (adam_score.hip) and sgd_l2_k (train_tail.hip) read `halted` and `coef`.
+// writes it; the guarded forms of flat_step_k (flat_step.h) read `halted` and `coef`.
 #pragma once
 
 #include "step_pack.h"

@@ -25,9 +25,9 @@ __device__ __forceinline__ void gg_load4(const bf16_t* p, float (&x)[4]) {
   x[2] = __uint_as_float(t.y << 16), x[3] = __uint_as_float(t.y & 0xffff0000u);
 }
 
-// VEC: four elements per lane and access when the gradient pointer is aligned for it (adam_l2_k's rule); the tail of n
+// VEC: four elements per lane and access when the gradient pointer is aligned for it (the rule of flat_step_k's vector forms); the tail of n
 // and the unaligned case take one element per lane.  Workgroups of 1024 threads, at most 256 of them, grid-stride:
-// adam_l2_k's grid, so that the ticket costs what that kernel's does.
+// the grid of flat_step_k's 1024-thread rules, so that the ticket costs what that kernel's does.
 template <typename S, bool VEC>
 __global__ __launch_bounds__(1024) void grad_guard_k(const S* __restrict__ g, long long n, const float* __restrict__ loss,
                                                     double* __restrict__ partials, GradGuardBlock* __restrict__ guard) {
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(1024) void grad_guard_k(const S* __restrict__ g, lo
   guard->ticket = 0u;   // plain vector stores; the next launch starts from ticket 0 again
 }
 
-unsigned guard_blocks_for(long long n) {   // adam_l2_k's rule
+unsigned guard_blocks_for(long long n) {   // flat_step_blocks_for's rule for 1024 threads with a vector form
   long long b = (n + 4095) / 4096;
   if (b > 256) b = 256;
   return (unsigned)(b < 1 ? 1 : b);

@@ -1,6 +1,6 @@
 // The learning-rate schedule's device block and its arithmetic (include/dctn_amd.h documents the layout and the
-// evaluation: both are part of the ABI).  The scheduled forms of adam_l2_k (adam_score.hip) and sgd_l2_k
-// (train_tail.hip) evaluate it from the device step count inside the optimizer launch; dctn_lr_schedule_value runs the
+// evaluation: both are part of the ABI).  The scheduled forms of flat_step_k (flat_step.h)
+// evaluate it from the device step count inside the optimizer launch; dctn_lr_schedule_value runs the
 // same function on the host.
 #pragma once
 
@@ -20,8 +20,7 @@ struct LrScheduleBlock {
 };
 static_assert(sizeof(LrScheduleBlock) == 784, "the schedule block is 784 bytes (include/dctn_amd.h)");
 
-// The 16-byte step block of a scheduled sgd_l2_k: adam_l2_k's AdamState, field for field
-// (two types on purpose: merging them changes the mangled names of every adam_l2_k and sgd_l2_k instantiation)
+// The 16-byte step block of flat_step_k (include/dctn_amd.h documents this layout: it is part of the ABI)
 struct StepStateBlock {
   int steps_done;
   float lr;

@@ -1,12 +1,12 @@
 // The parameter-group table's device block (include/dctn_amd.h documents the layout and the semantics: both are part of
-// the ABI).  The grouped forms of adam_l2_k (adam_score.hip) and sgd_l2_k (train_tail.hip) obey it inside the one
+// the ABI).  The grouped forms of flat_step_k (flat_step.h) obey it inside the one
 // optimizer launch; dctn_param_groups_check validates a host copy.
 //
 // One SEGMENT is one parameter of the flat buffer, in flat order: elements [end[s-1], end[s]) (end[-1] = 0).
 //   rate of a segment  : ONE rounded float32 product rate * lr_scale, where rate is state->lr, or the schedule's value at
 //                        the GLOBAL steps_done.  lr_scale == 1.0f leaves the bits alone.
 //   Adam's corrections : formed from the SEGMENT's count steps + 1 (torch.optim.Adam's per-parameter state["step"]), in
-//                        float64, exactly as the ungrouped kernel's lane 0 forms them from steps_done + 1.
+//                        float64, exactly as lane 0 of a launch without a table forms them from steps_done + 1.
 //   SGD's first step   : steps == 0 of the segment (torch's `momentum_buffer is None`).
 //   frozen (flags bit 0): no element of w, master, m, v or buf of the segment is stored to, its gradient is not read and
 //                        its `steps` does not advance; w * w still goes into sq_sum below n_reg (the reference's
@@ -33,7 +33,7 @@ struct ParamGroupBlock {
   int reserved[3];
   long long end[DCTN_PG_MAX_SEGMENTS];          // exclusive, strictly increasing; the last used one equals n
   float lr_scale[DCTN_PG_MAX_SEGMENTS];         // multiplies the rate; 1.0f leaves the bits alone
-  float weight_decay[DCTN_PG_MAX_SEGMENTS];     // Adam's coupled weight decay of the segment (sgd_l2_k ignores it)
+  float weight_decay[DCTN_PG_MAX_SEGMENTS];     // the segment's coupled weight decay (SGD without SgdDecay ignores it)
   unsigned flags[DCTN_PG_MAX_SEGMENTS];         // bit 0: frozen
   int steps[DCTN_PG_MAX_SEGMENTS];              // steps taken by the segment; the kernel advances it
 };

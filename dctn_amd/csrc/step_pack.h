@@ -1,5 +1,5 @@
-// The trailing parameter pack of the flat optimizers' step kernels (adam_l2_k in adam_score.hip, sgd_l2_k in
-// train_tail.hip).  Every optional block of a step - guard, step state, schedule, group table - is one pointer type; a
+// The trailing parameter pack of the flat optimizers' step kernel (flat_step_k in flat_step.h, which
+// Adam, SGD and RMSprop share).  Every optional block of a step - guard, step state, schedule, group table - is one pointer type; a
 // kernel finds a block in its pack by that type, and the launchers build the pack from the blocks a step has.  The three
 // block headers include this file.
 #pragma once

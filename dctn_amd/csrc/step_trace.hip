@@ -21,7 +21,7 @@ struct TraceHead {   // include/dctn_amd.h documents this layout: it is part of 
 };
 static_assert(sizeof(TraceHead) == 16, "the trace head is 16 bytes (include/dctn_amd.h)");
 
-struct TraceAdamState {   // adam_score.hip's AdamState
+struct TraceAdamState {   // lr_schedule.h's StepStateBlock
   int steps_done;
   float lr;
   unsigned ticket, reserved;

@@ -1,5 +1,5 @@
 // The weight average's device block and its arithmetic (include/dctn_amd.h documents the layout and the update: both are
-// part of the ABI).  The EMA forms of adam_l2_k (adam_score.hip) and sgd_l2_k (train_tail.hip) update the average inside
+// part of the ABI).  The EMA forms of flat_step_k (flat_step.h) update the average inside
 // the optimizer launch, from the value they are about to store; dctn_weight_ema_weight runs the per-launch weight on the
 // host.
 #pragma once

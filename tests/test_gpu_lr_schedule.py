@@ -32,7 +32,7 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 BF16, F32 = torch.bfloat16, torch.float32
 LR, WD, L2 = 2e-3, 1e-3, 1e-2
-N, N_REG = 4099, 2050   # two workgroups of adam_l2_k (the ticket is real), a vector body and a scalar tail
+N, N_REG = 4099, 2050   # two workgroups of Adam's flat_step_k (the ticket is real), a vector body and a scalar tail
 STEPS = 12
 # eight knots: a warm-up from 0, a hold, a drop, a linear decay
 KNOTS = [(0, 0.0), (2, 1e-3), (3, 2e-3), (5, 2e-3), (6, 5e-4), (8, 4e-4), (10, 1e-4), (11, 5e-5)]

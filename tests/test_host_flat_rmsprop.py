@@ -20,7 +20,7 @@ def test_the_exports_exist():
     assert lib.dctn_version() >= 515
     for name in ("dctn_rmsprop_flat_step", "dctn_rmsprop_num_partials", "dctn_sgd_flat_step_decay"):
         assert name in _lib.SIGNATURES and getattr(lib, name) is not None
-    # adam_l2_k's geometry: one workgroup per 4096 elements, at most 256
+    # Adam's geometry of flat_step_k: one workgroup per 4096 elements, at most 256
     for n, want in ((-1, 0), (0, 0), (1, 1), (4096, 1), (4097, 2), (20007, 5), (256 * 4096, 256), (1 << 33, 256)):
         assert lib.dctn_rmsprop_num_partials(n) == want == lib.dctn_adam_l2_num_partials(n)
 

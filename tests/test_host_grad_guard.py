@@ -62,7 +62,7 @@ def test_version_and_block_size():
 
 
 def test_num_partials_follows_the_grid_rule():
-    """Workgroups of 1024 threads with one 4-element access per lane, at most 256 of them (adam_l2_k's rule)."""
+    """Workgroups of 1024 threads with one 4-element access per lane, at most 256 of them (the rule of flat_step_k's 1024-thread geometry)."""
     lib = _lib.lib()
     for n, want in ((-1, 0), (0, 0), (1, 1), (4096, 1), (4097, 2), (262147, 65), (256 * 4096, 256), (1048581, 256),
                     (1 << 40, 256)):

@@ -10,9 +10,9 @@ source over `--samples` synthetic 28 x 28 uint8 images, with K = 1 and K = 20 it
   sgd_wd   `FlatSGD(momentum=0.9, weight_decay=1e-4)`: the DECAY kernels
   torch    `torch.optim.RMSprop(momentum=0.9, capturable=True)` on the bf16 parameters, if this torch captures it (left out
            with a note otherwise)
-  p_adam, p_sgd   with `--parent-lib PATH` (a libdctn_amd.so built from the parent commit, in the dctn_amd directory of a
-           checkout of that commit): that tree's Python over that library's FlatAdam / FlatSGD, imported beside this build
-           under another name.  adam - p_adam and sgd - p_sgd must sit inside the run's own spread: the same machine code.
+  p_<name> for each of the five, with `--parent-lib PATH` (a libdctn_amd.so built from the parent commit, in the dctn_amd
+           directory of a checkout of that commit): that tree's Python over that library's optimizer, imported beside this
+           build under another name.  <name> - p_<name> is judged against the two variants' own block spreads in the run.
 
 Each variant is timed over `--repeats` blocks of `--steps` iterations with device synchronisation around each block; the
 variants alternate block by block so that clock and thermal drift fall on all alike.  Prints one JSON line: per K and
@@ -40,7 +40,8 @@ from dctn_amd import batches, eps_plus_linear, training  # noqa: E402
 
 SPEC, SIZE, DTYPE, BATCH = ((3, 4),), 28, torch.bfloat16, 1024
 LR, L2, WD = 1e-4, 1e-4, 1e-4
-ALL = ("rms0", "rms9", "adam", "sgd", "sgd_wd", "torch", "p_adam", "p_sgd")
+OURS = ("rms0", "rms9", "adam", "sgd", "sgd_wd")
+ALL = OURS + ("torch",) + tuple(f"p_{v}" for v in OURS)
 
 
 def parent_package(lib_path):
@@ -58,7 +59,9 @@ def parent_package(lib_path):
 
 def make_variant(name, K, images, labels, dev):
     """Returns a callable that runs one launch (K iterations)."""
-    if name.startswith("p_"):   # the parent's classes: construction, warm-up and capture go through its library
+    parents = name.startswith("p_")
+    name = name[2:] if parents else name
+    if parents:   # the parent's classes: construction, warm-up and capture go through its library
         T, M = importlib.import_module("dctn_parent.training"), importlib.import_module("dctn_parent.eps_plus_linear")
         B = importlib.import_module("dctn_parent.batches")
     else:
@@ -70,9 +73,9 @@ def make_variant(name, K, images, labels, dev):
     reg_fn, reg_coeff = None, 0.0
     if name in ("rms0", "rms9"):
         opt = T.FlatRMSprop(reg, others, momentum=0.0 if name == "rms0" else 0.9, weight_decay=WD, **common)
-    elif name in ("adam", "p_adam"):
+    elif name == "adam":
         opt = T.FlatAdam(reg, others, weight_decay=WD, **common)
-    elif name in ("sgd", "p_sgd"):
+    elif name == "sgd":
         opt = T.FlatSGD(reg, others, momentum=0.9, **common)
     elif name == "sgd_wd":
         opt = T.FlatSGD(reg, others, momentum=0.9, weight_decay=WD, **common)
@@ -137,7 +140,7 @@ def main():
                                   "spread_us": max(t) - min(t), "blocks_us": [round(b, 2) for b in t]}
                               for v, t in times.items()}}
         med = {v: entry["variants"][v]["median_us"] for v in order}
-        for hi, lo in (("adam", "p_adam"), ("sgd", "p_sgd"), ("sgd_wd", "sgd"), ("rms0", "adam"), ("rms9", "adam"),
+        for hi, lo in tuple((v, f"p_{v}") for v in OURS) + (("sgd_wd", "sgd"), ("rms0", "adam"), ("rms9", "adam"),
                        ("rms9", "rms0"), ("torch", "rms9")):
             if hi in med and lo in med:
                 entry[f"{hi}_minus_{lo}_us"] = med[hi] - med[lo]
