@@ -334,6 +334,34 @@ def _write_cell(cell: Tensor, value) -> None:
         cell.fill_(value)
 
 
+def _refuse_capture(device: torch.device, message: str) -> None:
+    """RuntimeError(``message``) while the current stream of a CUDA ``device`` is being captured: a write or a read of a
+    device block from the host would become a node of that graph, or fail it.  A block on the CPU is never captured, and
+    the runtime is not asked."""
+    if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(message)
+
+
+class _WordTable:
+    """What `LRSchedule`, `ParamGroups` and `WeightEMA` share: a block ``_block`` of ``WORDS`` int32 words on ``device``
+    that is uploaded whole from ``host_block(...)``, changed between launches only, and restored from its own bytes (no
+    host scalars travel beside it).  Each class turns restored bytes into words itself: the three complaints about a
+    wrong size differ in more than the class's name."""
+
+    _READS = "table"   # what the refusal says the captured step reads from the device
+
+    def _upload(self, *counts) -> None:
+        with torch.no_grad():
+            self._block.copy_(torch.from_numpy(self.host_block(*counts)))
+
+    def _no_capture(self, what: str) -> None:
+        _refuse_capture(self.device, f"{type(self).__name__}.{what} during a graph capture: the captured step reads the "
+                                     f"{self._READS} from the device, change it between replays")
+
+    def run_host(self) -> None:
+        return None
+
+
 class GradGuard:
     """The device-side gradient guard: a non-finite halt and global norm clipping that a captured iteration carries
     with it (`dctn_grad_guard_check`, include/dctn_amd.h).  Pass one to ``FlatAdam(..., guard=g)`` or
@@ -390,9 +418,8 @@ class GradGuard:
 
     @max_norm.setter
     def max_norm(self, value: Optional[float]) -> None:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("GradGuard.max_norm cannot be assigned during a graph capture: the captured check reads "
-                               "the threshold from the device, assign it between replays")
+        _refuse_capture(self.device, "GradGuard.max_norm cannot be assigned during a graph capture: the captured check "
+                                     "reads the threshold from the device, assign it between replays")
         self._max_norm = float("inf") if value is None else float(value)
         _write_cell(self._cells[0:1], self._max_norm)
 
@@ -418,8 +445,7 @@ class GradGuard:
     def reset(self, counters: bool = False) -> None:
         """Clears the latch and ``bad_step`` (asynchronous; not during a capture): the next step is applied again.
         ``counters=True`` also zeroes ``seen`` and ``clipped``, so that ``bad_step`` counts from here."""
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("GradGuard.reset() during a graph capture would become a node of that graph")
+        _refuse_capture(self.device, "GradGuard.reset() during a graph capture would become a node of that graph")
         with torch.no_grad():
             self._block[2:3].zero_()
             self._block[3:4].fill_(-1)
@@ -544,8 +570,7 @@ class StepTrace:
 
     def read(self):
         """The records not yet returned, ordered by ``seq`` (copies head and ring in stream order: it synchronises)."""
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("StepTrace.read() copies to the host: not during a graph capture")
+        _refuse_capture(self.device, "StepTrace.read() copies to the host: not during a graph capture")
         both = torch.cat((self._head, self._ring)).cpu().numpy()   # one copy kernel, one transfer: one point of the stream
         records, self.lost, done = self.decode(both[:4].tobytes(), both[4:].tobytes(), self.capacity, self._last_read)
         self._last_read = done
@@ -587,7 +612,7 @@ StepTrace.RECORD = _trace_record_dtype()
 assert StepTrace.RECORD.itemsize == 64
 
 
-class LRSchedule:
+class LRSchedule(_WordTable):
     """A learning-rate schedule that lives on the device (`dctn_adam_l2_step_scheduled` / `dctn_sgd_l2_step_scheduled`,
     include/dctn_amd.h): a table of at most 64 knots ``(step, lr)`` in a 784-byte DEVICE block that the optimizer launch
     itself evaluates at the device step count.  Pass one to ``FlatAdam(..., schedule=s)`` or ``FlatSGD(..., schedule=s)``:
@@ -712,15 +737,6 @@ class LRSchedule:
         return knots, [int(words[132 + i] != 0) for i in range(n)], float(floats[1])
 
     # ---------------------------------------------------------------------------------------- the device block
-    def _upload(self) -> None:
-        with torch.no_grad():
-            self._block.copy_(torch.from_numpy(self.host_block()))
-
-    def _no_capture(self, what: str) -> None:
-        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(f"LRSchedule.{what} during a graph capture: the captured step reads the table from the "
-                               "device, change it between replays")
-
     def set(self, knots, hold=None) -> None:
         """Rewrites the table in place (the scale stays): the next launch, a replay included, follows it."""
         self._no_capture("set()")
@@ -758,9 +774,6 @@ class LRSchedule:
     # a part of a run, as `GradGuard`; the optimizer that holds the schedule lists the block among its own regions
     def run_regions(self):
         return [("schedule", self._block)]
-
-    def run_host(self) -> None:
-        return None
 
     def run_restored(self, host, blocks) -> None:
         """Sets the host copy from the block's bytes (`checkpoint.RunState.load` put the block itself back)."""
@@ -830,7 +843,7 @@ class ParamGroup:
         self.lr_scale, self.weight_decay, self.frozen = lr_scale, weight_decay, bool(frozen)
 
 
-class ParamGroups:
+class ParamGroups(_WordTable):
     """A parameter-group table that lives on the device (`dctn_adam_l2_step_grouped` / `dctn_sgd_l2_step_grouped`,
     include/dctn_amd.h): one SEGMENT per parameter of the optimizer's flat buffer, each with its own rate multiplier,
     weight decay, frozen flag and step count, in a 1552-byte DEVICE block that the ONE optimizer launch obeys.  Pass it
@@ -975,17 +988,8 @@ class ParamGroups:
         return words
 
     # ---------------------------------------------------------------------------------------- the device block
-    def _no_capture(self, what: str) -> None:
-        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(f"ParamGroups.{what} during a graph capture: the captured step reads the table from the "
-                               "device, change it between replays")
-
     def _host_steps(self):
         return self._block[self._STEPS: self._STEPS + len(self.params)].cpu().numpy()
-
-    def _upload(self, steps) -> None:
-        with torch.no_grad():
-            self._block.copy_(torch.from_numpy(self.host_block(steps)))
 
     def _bind(self, default_weight_decay: Optional[float], owner: str) -> None:
         """An optimizer takes the table: None weight decays become its value; an optimizer without weight decay
@@ -1055,9 +1059,6 @@ class ParamGroups:
     def run_regions(self):
         return [("groups", self._block)]
 
-    def run_host(self) -> None:
-        return None
-
     def run_restored(self, host, blocks) -> None:
         """Sets the host copy from the block's bytes (`checkpoint.RunState.load` put the block itself back)."""
         import numpy as np
@@ -1094,7 +1095,7 @@ def param_groups_for(model, freeze_eps=(), head_lr_scale: float = 1.0) -> ParamG
     return ParamGroups.from_requires_grad(epses + [model.linear.weight, model.linear.bias], entries)
 
 
-class WeightEMA:
+class WeightEMA(_WordTable):
     """An exponential moving average of the weights that the optimizer's step kernel keeps (include/dctn_amd.h, "A
     weight average").  Pass one to ``FlatAdam(..., ema=e)`` or ``FlatSGD(..., ema=e)``: the optimizer binds it -
     ``e.values`` (float32, one per element of the flat buffer) starts as the master copy where there is one, else as the
@@ -1120,6 +1121,7 @@ class WeightEMA:
 
     WORDS = 8
     _WARMUP = 1
+    _READS = "block"
 
     def __init__(self, device, decay: float = 0.999, warmup: bool = True):
         self.device = torch.device(device)
@@ -1175,15 +1177,6 @@ class WeightEMA:
         return words
 
     # ---------------------------------------------------------------------------------------- the device block
-    def _upload(self, updates: int, last_omd: float) -> None:
-        with torch.no_grad():
-            self._block.copy_(torch.from_numpy(self.host_block(updates, last_omd)))
-
-    def _no_capture(self, what: str) -> None:
-        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(f"WeightEMA.{what} during a graph capture: the captured step reads the block from the "
-                               "device, change it between replays")
-
     @property
     def decay(self) -> float:
         return self._decay
@@ -1292,9 +1285,6 @@ class WeightEMA:
     def run_regions(self):
         return [("ema", self.values), ("ema_block", self._block)]
 
-    def run_host(self) -> None:
-        return None
-
     def run_restored(self, host, blocks) -> None:
         """Sets the host copy from the block's bytes (`checkpoint.RunState.load` put the block itself back)."""
         import numpy as np
@@ -1314,7 +1304,27 @@ class _FlatOptimizer:
 
     ``master_weights=True`` with bfloat16 parameters adds ``master``: a float32 copy of the flat buffer (initialised
     by exact widening) that the step kernel updates; the bfloat16 parameters then only receive its rounding.  With
-    float32 parameters the option changes nothing and ``master`` is None."""
+    float32 parameters the option changes nothing and ``master`` is None.
+
+    A subclass declares what it keeps, and `state_dict`, `load_state_dict`, `run_host` and `run_restored` are written
+    from that once:
+
+    ``_STATE``    the attributes that travel in ``state_dict()`` between ``lr`` and the master copy, in its key order:
+                  scalar hyper-parameters and per-element buffers.  One that is None (FlatSGD's ``weight_decay`` left off,
+                  FlatRMSprop's ``buf`` without momentum) does not travel.
+    ``_MOMENTS``  those of them that are per-element float32 buffers, which ``run_regions()`` lists as well.  The rest
+                  are the hyper-parameters: floats, or a tuple of floats (a list in ``run_host()``, whose file is JSON).
+    ``_COUNT``    the key of the step count in ``state_dict()``.
+    ``_BLOCK_ALWAYS``  whether the step kernel reads rate and count from the 16-byte step block whatever the options;
+                  False: only with a schedule, a group table or a weight average, and otherwise the launch takes them from
+                  the host (``_state`` is then None).
+    ``_READS_RATE``  who, in the words of the refusal to assign ``lr`` during a capture, reads the rate from the device."""
+
+    _STATE: Tuple[str, ...] = ()
+    _MOMENTS: Tuple[str, ...] = ()
+    _COUNT = "t"
+    _BLOCK_ALWAYS = True
+    _READS_RATE = "the captured step"
 
     def __init__(self, regularised, others, num_partials: Callable[[int], int], master_weights: bool = False,
                  guard: Optional["GradGuard"] = None, guard_loss=None, schedule: Optional["LRSchedule"] = None,
@@ -1367,6 +1377,50 @@ class _FlatOptimizer:
         if ema is not None:
             ema._bind(self)
 
+    def _finish_init(self, lr: float, what: str) -> None:
+        """A subclass's constructor ends here, its hyper-parameters set and its buffers allocated."""
+        self._own_step_block(lr)
+        if self.groups is not None:
+            self.groups._bind(self.weight_decay, type(self).__name__)
+        self._describe(what)
+
+    def _own_step_block(self, lr: float) -> None:
+        """Allocates the step block {int32 steps_done, float32 lr, uint32 ticket, uint32 reserved} (include/dctn_amd.h)
+        where the step kernel reads one, and sets the rate: in the block's cell, or, for a launch that takes it from the
+        host, in ``_lr`` alone."""
+        self._state: Optional[Tensor] = None
+        if self._BLOCK_ALWAYS or self.schedule is not None or self.groups is not None or self.ema is not None:
+            assert L.lib().dctn_adam_state_bytes() == 16
+            self._state = torch.zeros(4, dtype=torch.int32, device=self.flat.device)
+            self._lr_cell = self._state.view(torch.float32)[1:2]
+        if self.schedule is None:
+            self.lr = lr
+        else:   # the block's rate cell is the kernel's to write: the rate of the step just taken
+            self._lr = float(lr)
+            assert L.lib().dctn_lr_schedule_bytes() == 4 * LRSchedule.WORDS
+
+    @property
+    def lr(self) -> float:
+        """Without a schedule the host copy of the rate (what the next launch gets, or what the block's cell holds); with
+        one, ``schedule.value(t)`` (reads the device)."""
+        return self._lr if self.schedule is None else self._scheduled_lr()
+
+    @lr.setter
+    def lr(self, value: float) -> None:
+        if self.schedule is not None:
+            self._refuse_lr()
+        if self._state is not None:   # the step reads the rate from the block: a tiny asynchronous write
+            _refuse_capture(self.flat.device, f"{type(self).__name__}.lr cannot be assigned during a graph capture: "
+                                              f"{self._READS_RATE} reads the rate from the device, assign it between replays")
+            _write_cell(self._lr_cell, float(value))
+        self._lr = float(value)
+
+    @property
+    def t(self) -> int:
+        """Number of steps taken: read from the step block where there is one (it synchronises; steps the guard skipped
+        do not count), otherwise the host's count of launches."""
+        return self._steps if self._state is None else int(self._state[0].item())
+
     def _scheduled_lr(self) -> float:
         """``schedule.value(t)``, scale applied: the rate of the next step (reads the step count from the device)."""
         return self.schedule.value(self.t)
@@ -1406,6 +1460,46 @@ class _FlatOptimizer:
             self.ema.reset()
         else:
             self.ema.load_state_dict(saved)
+
+    def _hyper(self):
+        """The names of the hyper-parameters this optimizer has, in ``_STATE``'s order."""
+        return [k for k in self._STATE if k not in self._MOMENTS and getattr(self, k) is not None]
+
+    def _set_hyper(self, values: Dict[str, Any]) -> None:
+        for k in self._hyper():
+            v = values[k]
+            setattr(self, k, tuple(float(x) for x in v) if isinstance(v, (tuple, list)) else float(v))
+
+    def state_dict(self) -> Dict[str, Any]:
+        """Everything a resumed run needs besides the parameters themselves (those are the model's state_dict)."""
+        state = {self._COUNT: self.t, "lr": self.lr}
+        for k in self._STATE:
+            v = getattr(self, k)
+            if v is not None:
+                state[k] = v.clone() if k in self._MOMENTS else v
+        if self.master is not None:
+            state["master"] = self.master.clone()
+        if self.ema is not None:
+            state["ema"] = self.ema.state_dict()
+        return state
+
+    def _check_state(self, state: Dict[str, Any]) -> None:
+        """Refuses a state that does not fit this optimizer, before anything of it is taken."""
+        if any(state[k].numel() != self.n for k in self._MOMENTS):
+            raise ValueError(f"optimizer state holds {state[self._MOMENTS[0]].numel()} values, the parameters {self.n}")
+
+    def load_state_dict(self, state: Dict[str, Any]) -> None:
+        self._check_state(state)
+        self._set_hyper(state)
+        with torch.no_grad():
+            for k in self._MOMENTS:
+                getattr(self, k).copy_(state[k].reshape(-1))
+        if self.schedule is None:
+            self.lr = state["lr"]
+        if self._state is not None:   # the block as the kernel would have left it: the count, and the rate of the last step
+            self._put_step_block(int(state[self._COUNT]))
+        self._load_master(state)
+        self._load_ema(state)
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         for p in self.params:
@@ -1465,10 +1559,10 @@ class _FlatOptimizer:
             self.guard.check(g, self.guard_loss() if callable(self.guard_loss) else self.guard_loss)
 
     def _put_step_block(self, steps: int) -> None:
-        """Writes the 16-byte step block of a scheduled optimizer: ``steps`` taken, the rate of the last of them."""
+        """Writes the 16-byte step block: ``steps`` taken, the rate of the last of them."""
         host = torch.zeros(4, dtype=torch.int32)
         host[0] = int(steps)
-        if self.schedule is None:   # a FlatSGD with a group table or an average and no schedule: the rate the host set
+        if self.schedule is None:   # the rate the host set
             host.view(torch.float32)[1] = self._lr
         else:
             host.view(torch.float32)[1] = self.schedule.value(steps - 1) if steps > 0 else 0.0
@@ -1479,9 +1573,9 @@ class _FlatOptimizer:
         """l2 * sum of squared Frobenius norms of the regularised parameters, as of the last step."""
         return self.sq_sum.sum() * self.l2
 
-    # A part of a run, as `GradGuard`.  `_MOMENTS` names the subclass's per-element buffers; its `run_host()` is the
+    # A part of a run, as `GradGuard`.  `_MOMENTS` names the subclass's per-element buffers; `run_host()` is the
     # dictionary of its hyper-parameters (`_lr`: the host copy - with a schedule the rate is in the blocks, and reading
-    # `lr` would synchronise), and its `run_restored()` sets them before it calls this one.
+    # `lr` would synchronise), and `run_restored()` sets them again.
     def run_regions(self):
         """In file order.  The schedule's block stands in front of the step block, so that a file and a run that disagree
         about the schedule differ at that entry first; the group table's block, the segments' step counts in it, follows
@@ -1497,12 +1591,22 @@ class _FlatOptimizer:
             regions.append(("state", self._state))
         return regions + [("sq_sum", self.sq_sum)]
 
+    def run_host(self) -> Dict[str, Any]:
+        host = dict(kind=type(self).__name__, lr=self._lr)
+        for k in self._hyper():
+            v = getattr(self, k)
+            host[k] = list(v) if isinstance(v, tuple) else v
+        return host
+
     def run_check(self, host: Dict[str, Any]) -> None:
         if host["kind"] != type(self).__name__:
             raise ValueError(f"snapshot: entry 'optimizer' is {host['kind']} in the file, {type(self).__name__} in the run")
 
     def run_restored(self, host: Dict[str, Any], blocks) -> None:
-        """The blocks came back: the host copies of the average's, the schedule's and the group table's follow theirs."""
+        """The blocks came back - the rate itself with the 16-byte block: the host scalars follow the file's, and the host
+        copies of the average's, the schedule's and the group table's follow their blocks."""
+        self._lr = float(host["lr"])
+        self._set_hyper(host)
         for part in (self.ema, self.schedule, self.groups):
             if part is not None:
                 part.run_restored(None, {name: blocks[name] for name, _ in part.run_regions()})
@@ -1571,50 +1675,19 @@ class FlatSGD(_FlatOptimizer):
                  ema: Optional["WeightEMA"] = None, weight_decay: Optional[float] = None):
         super().__init__(regularised, others, L.lib().dctn_sgd_l2_num_partials, master_weights, guard, guard_loss,
                          schedule, groups, ema)
-        self._lr, self.momentum, self.l2 = float(lr), float(momentum), float(l2)
+        self.momentum, self.l2 = float(momentum), float(l2)
         if weight_decay is not None and not float(weight_decay) >= 0.0:
             raise ValueError(f"invalid SGD weight_decay: {weight_decay}")
         self.weight_decay: Optional[float] = None if weight_decay is None else float(weight_decay)
         self.buf = torch.zeros(self.n, dtype=torch.float32, device=self.flat.device)
-        self._steps = 0
-        # with a schedule: {int32 steps_done, float32 lr, uint32 ticket, uint32 reserved}, FlatAdam's block
-        self._state: Optional[Tensor] = None
-        if schedule is not None:
-            assert L.lib().dctn_adam_state_bytes() == 16 and L.lib().dctn_lr_schedule_bytes() == 4 * LRSchedule.WORDS
-            self._state = torch.zeros(4, dtype=torch.int32, device=self.flat.device)
-        if groups is not None:
-            groups._bind(self.weight_decay, "FlatSGD")
-        if groups is not None or ema is not None:   # these steps always take the block; without a schedule they read its rate cell
-            if self._state is None:
-                assert L.lib().dctn_adam_state_bytes() == 16
-                self._state = torch.zeros(4, dtype=torch.int32, device=self.flat.device)
-                self._put_step_block(0)
-        self._describe("fused SGD step")
+        self._steps = 0   # the host's count of launches: `t`, and the step's `first_step`, where there is no step block
+        self._finish_init(lr, "fused SGD step")
 
-    @property
-    def lr(self) -> float:
-        """Without a schedule the rate the next launch gets; with one, ``schedule.value(t)`` (reads the device)."""
-        return self._lr if self.schedule is None else self._scheduled_lr()
-
-    @lr.setter
-    def lr(self, value: float) -> None:
-        if self.schedule is not None:
-            self._refuse_lr()
-        if self._state is not None:   # a group table or an average: the step reads the rate from the block, as FlatAdam's
-            if self.flat.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("FlatSGD.lr cannot be assigned during a graph capture: the captured step of an optimizer "
-                                   "with a group table or a weight average reads the rate from the device, assign it "
-                                   "between replays")
-            self._lr = float(value)
-            _write_cell(self._state.view(torch.float32)[1:2], self._lr)
-            return
-        self._lr = float(value)
-
-    @property
-    def t(self) -> int:
-        """Number of steps taken: with a schedule, a group table or a weight average read from the device block (it synchronises; steps the guard skipped
-        do not count), otherwise the host's count of launches."""
-        return self._steps if self._state is None else int(self._state[0].item())
+    _STATE = ("momentum", "l2", "buf", "weight_decay")
+    _MOMENTS = ("buf",)
+    _COUNT = "steps"
+    _BLOCK_ALWAYS = False
+    _READS_RATE = "the captured step of an optimizer with a group table or a weight average"
 
     @torch.no_grad()
     def step(self) -> None:
@@ -1636,49 +1709,23 @@ class FlatSGD(_FlatOptimizer):
                                                    L.stream_ptr(self.flat.device)), self._what)
         self._steps += 1
 
-    def state_dict(self) -> Dict[str, Any]:
-        """Everything a resumed run needs besides the parameters themselves (those are the model's state_dict)."""
-        state = {"steps": self.t, "lr": self.lr, "momentum": self.momentum, "l2": self.l2, "buf": self.buf.clone()}
-        if self.weight_decay is not None:
-            state["weight_decay"] = self.weight_decay
-        if self.master is not None:
-            state["master"] = self.master.clone()
-        if self.ema is not None:
-            state["ema"] = self.ema.state_dict()
-        return state
+    def _with_own_decay(self, values: Dict[str, Any]) -> Dict[str, Any]:
+        """(a state written without the ``weight_decay`` option keeps this optimizer's value)"""
+        return values if self.weight_decay is None else {"weight_decay": self.weight_decay, **values}
 
     def load_state_dict(self, state: Dict[str, Any]) -> None:
-        if state["buf"].numel() != self.n:
-            raise ValueError(f"optimizer state holds {state['buf'].numel()} values, the parameters {self.n}")
-        self.momentum, self.l2 = float(state["momentum"]), float(state["l2"])
-        if self.weight_decay is not None and "weight_decay" in state:   # (a state written without the option keeps this one's)
-            self.weight_decay = float(state["weight_decay"])
-        with torch.no_grad():
-            self.buf.copy_(state["buf"].reshape(-1))
+        super().load_state_dict(self._with_own_decay(state))
         self._steps = int(state["steps"])
-        if self.schedule is None:
-            self.lr = float(state["lr"])
-            if self._state is not None:   # a group table or a weight average: the block holds the count beside the rate
-                self._put_step_block(self._steps)
-        else:   # the block as the scheduled kernel would have left it: the count, and the rate of the last step
-            self._put_step_block(self._steps)
-        self._load_master(state)
-        self._load_ema(state)
-
-    _MOMENTS = ("buf",)
 
     def run_host(self) -> Dict[str, Any]:
-        host = dict(kind=type(self).__name__, lr=self._lr, momentum=self.momentum, l2=self.l2, steps=self._steps)
-        if self.weight_decay is not None:
-            host["weight_decay"] = self.weight_decay
-        return host
+        host = super().run_host()
+        decay = host.pop("weight_decay", None)   # the count stands in front of it
+        host["steps"] = self._steps
+        return host if decay is None else dict(host, weight_decay=decay)
 
     def run_restored(self, host: Dict[str, Any], blocks) -> None:
-        self._lr, self.momentum, self.l2 = float(host["lr"]), float(host["momentum"]), float(host["l2"])
-        if self.weight_decay is not None and "weight_decay" in host:
-            self.weight_decay = float(host["weight_decay"])
         self._steps = int(host["steps"])
-        super().run_restored(host, blocks)
+        super().run_restored(self._with_own_decay(host), blocks)
 
 
 class FlatAdam(_FlatOptimizer):
@@ -1753,39 +1800,10 @@ class FlatAdam(_FlatOptimizer):
         dev = self.flat.device
         self.m = torch.zeros(self.n, dtype=torch.float32, device=dev)
         self.v = torch.zeros(self.n, dtype=torch.float32, device=dev)
-        # {int32 steps_done, float32 lr, uint32 ticket, uint32 reserved}: include/dctn_amd.h
-        assert L.lib().dctn_adam_state_bytes() == 16
-        self._state = torch.zeros(4, dtype=torch.int32, device=dev)
-        self._lr_cell = self._state.view(torch.float32)[1:2]
-        self._lr = float("nan")
-        if schedule is None:
-            self.lr = lr
-        else:   # the block's rate cell is the kernel's to write: the rate of the step just taken
-            self._lr = float(lr)
-            assert L.lib().dctn_lr_schedule_bytes() == 4 * LRSchedule.WORDS
-        if groups is not None:
-            groups._bind(self.weight_decay, "FlatAdam")
-        self._describe("fused Adam step")
+        self._finish_init(lr, "fused Adam step")
 
-    @property
-    def lr(self) -> float:
-        """Without a schedule the host copy of the rate; with one, ``schedule.value(t)`` (reads the device)."""
-        return self._lr if self.schedule is None else self._scheduled_lr()
-
-    @lr.setter
-    def lr(self, value: float) -> None:
-        if self.schedule is not None:
-            self._refuse_lr()
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("FlatAdam.lr cannot be assigned during a graph capture: the captured step reads the "
-                               "rate from the device, assign it between replays")
-        self._lr = float(value)
-        _write_cell(self._lr_cell, self._lr)
-
-    @property
-    def t(self) -> int:
-        """Number of steps taken (read from the device)."""
-        return int(self._state[0].item())
+    _STATE = ("m", "v", "betas", "eps", "weight_decay", "l2")
+    _MOMENTS = ("m", "v")
 
     @torch.no_grad()
     def step(self) -> None:
@@ -1799,45 +1817,6 @@ class FlatAdam(_FlatOptimizer):
             L.check(L.lib().dctn_adam_flat_step_ema(self._desc_ref, self._ema_ref, self.m.data_ptr(), self.v.data_ptr(),
                                                     self.betas[0], self.betas[1], self.eps, self.weight_decay,
                                                     L.stream_ptr(self.flat.device)), self._what)
-
-    def state_dict(self) -> Dict[str, Any]:
-        """Everything a resumed run needs besides the parameters themselves (those are the model's state_dict)."""
-        state = {"t": self.t, "lr": self.lr, "m": self.m.clone(), "v": self.v.clone(), "betas": self.betas,
-                 "eps": self.eps, "weight_decay": self.weight_decay, "l2": self.l2}
-        if self.master is not None:
-            state["master"] = self.master.clone()
-        if self.ema is not None:
-            state["ema"] = self.ema.state_dict()
-        return state
-
-    def load_state_dict(self, state: Dict[str, Any]) -> None:
-        if state["m"].numel() != self.n or state["v"].numel() != self.n:
-            raise ValueError(f"optimizer state holds {state['m'].numel()} values, the parameters {self.n}")
-        self.betas, self.eps = (float(state["betas"][0]), float(state["betas"][1])), float(state["eps"])
-        self.weight_decay, self.l2 = float(state["weight_decay"]), float(state["l2"])
-        with torch.no_grad():
-            self.m.copy_(state["m"].reshape(-1))
-            self.v.copy_(state["v"].reshape(-1))
-            self._state.zero_()
-            self._state[0] = int(state["t"])
-        if self.schedule is None:
-            self.lr = state["lr"]
-        else:
-            self._put_step_block(int(state["t"]))
-        self._load_master(state)
-        self._load_ema(state)
-
-    _MOMENTS = ("m", "v")
-
-    def run_host(self) -> Dict[str, Any]:
-        return dict(kind=type(self).__name__, lr=self._lr, betas=list(self.betas), eps=self.eps,
-                    weight_decay=self.weight_decay, l2=self.l2)
-
-    def run_restored(self, host: Dict[str, Any], blocks) -> None:
-        self._lr = float(host["lr"])   # the rate itself came back with the 16-byte block
-        self.betas, self.eps = (float(host["betas"][0]), float(host["betas"][1])), float(host["eps"])
-        self.weight_decay, self.l2 = float(host["weight_decay"]), float(host["l2"])
-        super().run_restored(host, blocks)
 
 
 class FlatRMSprop(_FlatOptimizer):
@@ -1872,39 +1851,9 @@ class FlatRMSprop(_FlatOptimizer):
         self.square_avg = torch.zeros(self.n, dtype=torch.float32, device=dev)
         self.buf: Optional[Tensor] = torch.zeros(self.n, dtype=torch.float32, device=dev) if self.momentum > 0.0 else None
         self._MOMENTS = ("square_avg",) if self.buf is None else ("square_avg", "buf")
-        # {int32 steps_done, float32 lr, uint32 ticket, uint32 reserved}: include/dctn_amd.h
-        assert L.lib().dctn_adam_state_bytes() == 16
-        self._state = torch.zeros(4, dtype=torch.int32, device=dev)
-        self._lr_cell = self._state.view(torch.float32)[1:2]
-        self._lr = float("nan")
-        if schedule is None:
-            self.lr = lr
-        else:   # the block's rate cell is the kernel's to write: the rate of the step just taken
-            self._lr = float(lr)
-            assert L.lib().dctn_lr_schedule_bytes() == 4 * LRSchedule.WORDS
-        if groups is not None:
-            groups._bind(self.weight_decay, "FlatRMSprop")
-        self._describe("fused RMSprop step")
+        self._finish_init(lr, "fused RMSprop step")
 
-    @property
-    def lr(self) -> float:
-        """Without a schedule the host copy of the rate; with one, ``schedule.value(t)`` (reads the device)."""
-        return self._lr if self.schedule is None else self._scheduled_lr()
-
-    @lr.setter
-    def lr(self, value: float) -> None:
-        if self.schedule is not None:
-            self._refuse_lr()
-        if self.flat.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("FlatRMSprop.lr cannot be assigned during a graph capture: the captured step reads the "
-                               "rate from the device, assign it between replays")
-        self._lr = float(value)
-        _write_cell(self._lr_cell, self._lr)
-
-    @property
-    def t(self) -> int:
-        """Number of steps taken (read from the device)."""
-        return int(self._state[0].item())
+    _STATE = ("square_avg", "alpha", "eps", "weight_decay", "momentum", "l2", "buf")   # (`_MOMENTS`: per instance)
 
     @torch.no_grad()
     def step(self) -> None:
@@ -1915,50 +1864,19 @@ class FlatRMSprop(_FlatOptimizer):
                                                self.weight_decay, self.momentum, L.stream_ptr(self.flat.device)),
                 self._what)
 
-    def state_dict(self) -> Dict[str, Any]:
-        """Everything a resumed run needs besides the parameters themselves (those are the model's state_dict)."""
-        state = {"t": self.t, "lr": self.lr, "square_avg": self.square_avg.clone(), "alpha": self.alpha,
-                 "eps": self.eps, "weight_decay": self.weight_decay, "momentum": self.momentum, "l2": self.l2}
-        if self.buf is not None:
-            state["buf"] = self.buf.clone()
-        if self.master is not None:
-            state["master"] = self.master.clone()
-        if self.ema is not None:
-            state["ema"] = self.ema.state_dict()
-        return state
+    def _same_momentum(self, saved, complaint: str) -> None:
+        if (float(saved) > 0.0) != (self.buf is not None):
+            raise ValueError(complaint.format(saved, self.momentum))
 
-    def load_state_dict(self, state: Dict[str, Any]) -> None:
-        if state["square_avg"].numel() != self.n:
-            raise ValueError(f"optimizer state holds {state['square_avg'].numel()} values, the parameters {self.n}")
-        if (float(state["momentum"]) > 0.0) != (self.buf is not None):
-            raise ValueError(f"optimizer state was written with momentum {state['momentum']}, this optimizer was built "
-                             f"with {self.momentum}: the momentum buffer exists from construction or not at all")
-        self.alpha, self.eps, self.momentum = float(state["alpha"]), float(state["eps"]), float(state["momentum"])
-        self.weight_decay, self.l2 = float(state["weight_decay"]), float(state["l2"])
-        with torch.no_grad():
-            self.square_avg.copy_(state["square_avg"].reshape(-1))
-            if self.buf is not None:
-                self.buf.copy_(state["buf"].reshape(-1))
-            self._state.zero_()
-            self._state[0] = int(state["t"])
-        if self.schedule is None:
-            self.lr = state["lr"]
-        else:
-            self._put_step_block(int(state["t"]))
-        self._load_master(state)
-        self._load_ema(state)
-
-    def run_host(self) -> Dict[str, Any]:
-        return dict(kind=type(self).__name__, lr=self._lr, alpha=self.alpha, eps=self.eps,
-                    weight_decay=self.weight_decay, momentum=self.momentum, l2=self.l2)
+    def _check_state(self, state: Dict[str, Any]) -> None:
+        if state["square_avg"].numel() == self.n:   # (a wrong size is refused first, below)
+            self._same_momentum(state["momentum"], "optimizer state was written with momentum {}, this optimizer was built "
+                                "with {}: the momentum buffer exists from construction or not at all")
+        super()._check_state(state)
 
     def run_restored(self, host: Dict[str, Any], blocks) -> None:
-        if (float(host["momentum"]) > 0.0) != (self.buf is not None):
-            raise ValueError(f"snapshot: the optimizer was saved with momentum {host['momentum']}, the run's was built "
-                             f"with {self.momentum}")
-        self._lr = float(host["lr"])   # the rate itself came back with the 16-byte block
-        self.alpha, self.eps, self.momentum = float(host["alpha"]), float(host["eps"]), float(host["momentum"])
-        self.weight_decay, self.l2 = float(host["weight_decay"]), float(host["l2"])
+        self._same_momentum(host["momentum"], "snapshot: the optimizer was saved with momentum {}, the run's was built "
+                            "with {}")
         super().run_restored(host, blocks)
 
 
