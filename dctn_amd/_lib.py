@@ -171,6 +171,10 @@ SIGNATURES = {
     "dctn_window_stats": (c_int, [c_void, _I64x5, c_void] + [c_int] * 6 + [c_int, c_void]),
     "dctn_phi_window_stats": (c_int, [c_void, c_void, c_int, c_int, c_int, c_int, c_void]),
     "dctn_phi_expand": (c_int, [c_void, c_void, c_i64, ctypes.c_float, c_int, c_void]),
+    "dctn_byte_histogram": (c_int, [c_void, c_i64, c_int, c_void, c_void]),
+    "dctn_byte_window_stats_workspace_bytes": (c_size, [c_i64]),
+    "dctn_byte_window_stats": (c_int, [c_void, c_i64, c_int, c_int, c_int, c_void, ctypes.c_double, ctypes.c_double, c_int,
+                                       c_void, c_void, c_void]),
     "dctn_convsbs_workspace_bytes": (c_size, [c_int, _IntP, _IntP] + [c_int] * 5 + [_IntP, _IntP, c_int, c_int]),
     "dctn_convsbs_fwd": (c_int, [c_void, _I64x5, _PtrP, c_void, c_int, _IntP, _IntP, _IntP, _IntP]
                          + [c_int] * 5 + [c_void, c_size, c_int, c_void]),

@@ -17,6 +17,12 @@ definition; `round_keys`, `order_at` and `expected_indices` restate it in plain 
 function of (seed, epoch, global position) as the order is: no new state, the same batch on every sharding, the same
 augmentations after a resume, other ones on every replay of a captured graph.  `augment_params`, `augment_bytes` and
 `DeviceBatches.expected_augment` restate the definition of include/dctn_amd.h.
+
+What the reference's loaders compute from the expanded training tensor before the first batch comes from the bytes too
+(dctn_amd/csrc/byte_stats.hip): `byte_histogram` / `colour_moments` give the per-channel mean and std, and
+``from_colour(center_and_normalize=, autoscale_kernel_size=)`` / ``DeviceBatches(autoscale_kernel_size=)`` put them and
+`window_stats.calc_scaling_factor_from_bytes` together in the reference's order - exact or fixed-order sums, the same
+table bits on every rank.
 """
 from __future__ import annotations
 
@@ -29,7 +35,7 @@ from torch import Tensor
 
 from . import _lib as L
 from .dropout import _MASK32, philox4x32_10
-from .window_stats import φ_cos_sin_squared_1
+from .window_stats import calc_scaling_factor_from_bytes, φ_cos_sin_squared_1
 
 TAG = 0x53485546   # counter word c3 of the round keys; dropout's c3 is a core number below 8
 MAX_WIDTH = 4      # table columns / channels of one launch (include/dctn_amd.h)
@@ -216,16 +222,17 @@ def _per_channel(value, channels: int, what: str) -> Tuple[float, ...]:
 
 
 def colour_table(channels: int, *, nu, mean: Optional[Tensor] = None, std: Optional[Tensor] = None,
-                 constant_channel: Optional[float] = None, dtype: torch.dtype) -> Tensor:
+                 constant_channel: Optional[float] = None, dtype: torch.dtype, nu_constant: float = 1.0) -> Tensor:
     """(W, 256), W = ``channels`` (+ 1 with a constant channel): row c holds what the reference's colour pipeline
     (dataset_loading.py:349-375) gives for each of the 256 byte values in channel c, cast to ``dtype``.  Every value of
     that pipeline is a function of one byte and its channel, so the table IS the pipeline: it is built on the CPU with
     the reference's own ops in the reference's order on a (256, channels) float32 tensor -
     ``arange(256, uint8).float().div(255)`` (``to_tensor``), in-place ``-= mean`` and ``/= std`` with float64 (channels,)
     tensors when given (both or neither), the concatenated column ``constant_channel * ones``, in-place
-    ``*= torch.tensor(nu)`` where ``nu`` gets ``(1.0,)`` appended when a constant channel is added - and indexing it with
-    the bytes gives the bits of the expanded tensor.  ``nu``: one value per channel, or one number for all of them.  Row
-    ``channels`` (the constant channel) holds one value 256 times."""
+    ``*= torch.tensor(nu)`` where ``nu`` gets ``(nu_constant,)`` appended when a constant channel is added - and indexing it
+    with the bytes gives the bits of the expanded tensor.  ``nu``: one value per channel, or one number for all of them.
+    ``nu_constant``: the factor of the constant column, 1.0 for a given ``nu`` (dataset_loading.py:369) and the one factor of
+    all columns under autoscale (:372).  Row ``channels`` (the constant channel) holds one value 256 times."""
     channels = int(channels)
     width = channels + (constant_channel is not None)
     if not 1 <= channels <= MAX_WIDTH or width > MAX_WIDTH:
@@ -244,7 +251,7 @@ def colour_table(channels: int, *, nu, mean: Optional[Tensor] = None, std: Optio
         t /= std
     if constant_channel is not None:
         t = torch.cat((t, constant_channel * torch.ones_like(t[:, :1])), dim=1)
-        nu = nu + (1.0,)
+        nu = nu + (float(nu_constant),)
     t *= torch.tensor(nu)
     return t.to(dtype).t().contiguous()
 
@@ -261,12 +268,71 @@ def channel_moments(images_u8: Tensor) -> Tuple[Tensor, Tensor]:
     flat = images_u8.reshape(-1, C)
     if flat.shape[0] < 1:
         raise ValueError("channel_moments needs at least one pixel")
-    counts = torch.stack([torch.bincount(flat[:, c].int(), minlength=256) for c in range(C)]).double()   # (C, 256)
+    return moments_from_counts(torch.stack([torch.bincount(flat[:, c].int(), minlength=256) for c in range(C)]))
+
+
+def moments_from_counts(counts: Tensor) -> Tuple[Tensor, Tensor]:
+    """``(mean, std)`` float64 (channels,) from the (channels, 256) histogram of the bytes: `channel_moments` from its
+    counts onward.  The sums run where ``counts`` lives; `colour_moments` hands it counts on the CPU, so its numbers are
+    those of ``channel_moments(bytes.cpu())`` on every device and rank."""
+    if counts.ndim != 2 or counts.shape[1] != 256 or counts.dtype.is_floating_point:
+        raise TypeError(f"moments_from_counts takes (channels, 256) integer counts, got {counts.dtype}, {tuple(counts.shape)}")
+    total = float(counts[0].sum())   # every channel counts every pixel once
+    if total < 1:
+        raise ValueError("moments_from_counts needs at least one pixel")
+    counts = counts.double()   # (C, 256)
     values = torch.arange(256, dtype=torch.uint8).float().div(255).double().to(counts.device)   # to_tensor's float32 values
-    total = float(flat.shape[0])
     mean = (counts * values).sum(dim=1) / total
     var = (counts * (values.unsqueeze(0) - mean.unsqueeze(1)) ** 2).sum(dim=1) / total
     return mean, var.sqrt()
+
+
+def _source_device(device, tensor: Tensor) -> torch.device:
+    """Where a byte-resident source lives: ``device``, else the tensor's GPU, else the current one.  No GPU: RuntimeError."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("dctn_amd: a DeviceBatches source lives on an MI355X device, but no GPU is visible. "
+                           "There is deliberately no CPU implementation of this path.")
+    if device is not None:
+        return torch.device(device)
+    return tensor.device if tensor.is_cuda else torch.device("cuda", torch.cuda.current_device())
+
+
+def byte_histogram(images_u8: Tensor, device=None) -> Tensor:
+    """(channels, 256) int64 on the device: how often each byte value occurs in each channel (the last dimension, at most
+    4) of ``images_u8`` (..., channels) uint8 - one launch over the bytes (`dctn_byte_histogram`), exact.  CPU bytes are
+    moved to the device first; bytes already there are read in place."""
+    if images_u8.dtype != torch.uint8 or images_u8.ndim < 2:
+        raise TypeError(f"byte_histogram takes (..., channels) uint8 bytes, got {images_u8.dtype}, {tuple(images_u8.shape)}")
+    C = images_u8.shape[-1]
+    if not 1 <= C <= MAX_WIDTH:
+        raise NotImplementedError(f"one launch counts 1 .. {MAX_WIDTH} channels, got {C}")
+    if images_u8.numel() < 1:
+        raise ValueError("byte_histogram needs at least one pixel")
+    dev = _source_device(device, images_u8)
+    src = images_u8.to(dev).contiguous()
+    counts = torch.empty((C, 256), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().dctn_byte_histogram(src.data_ptr(), src.numel() // C, C, counts.data_ptr(), L.stream_ptr(dev)),
+                "byte histogram")
+    return counts
+
+
+def colour_moments(images_u8: Tensor, device=None) -> Tuple[Tensor, Tensor]:
+    """`channel_moments` of bytes that live on the device, without the 4-byte copy of every channel that ``bincount`` needs:
+    the histogram kernel, a copy of channels x 256 integers to the host, `moments_from_counts` there.  Returns CPU float64
+    tensors that equal ``channel_moments(images_u8.cpu())`` bit for bit - integer counts have no summation order - and so
+    are the same on every rank."""
+    return moments_from_counts(byte_histogram(images_u8, device).cpu())
+
+
+def _check_autoscale(kernel_size, samples, H: int, Wd: int) -> None:
+    """The errors of ``autoscale_kernel_size`` / ``autoscale_samples``, without a device."""
+    if isinstance(samples, bool) or not isinstance(samples, int) or samples < 1:
+        raise ValueError(f"autoscale_samples is a positive integer, got {samples!r}")
+    if kernel_size is None:
+        return
+    if isinstance(kernel_size, bool) or not isinstance(kernel_size, int) or not 1 <= kernel_size <= min(H, Wd):
+        raise ValueError(f"autoscale_kernel_size is an integer in [1, {min(H, Wd)}] for {H} x {Wd} images, got {kernel_size!r}")
 
 
 class DeviceBatches:
@@ -280,6 +346,9 @@ class DeviceBatches:
     float32 ops once per intensity (`feature_table`), then cast.  `from_colour` takes raw (n, height, width, channels)
     colour bytes and one 256-row table per channel (`colour_table`); `from_features` takes a tensor that is already expanded.
     CPU inputs are moved to the device once, here; without a GPU the constructor raises.
+    ``autoscale_kernel_size=K`` (instead of a ``scale``) is the reference's ``get_data_loaders(..., autoscale_kernel_size)``:
+    the scale is `calc_scaling_factor_from_bytes` of the first ``autoscale_samples`` images, computed from the bytes on the
+    device, the same float on every rank; ``src.scale`` holds it.
 
     ``draw_into(x, y, indices)`` enqueues one launch into caller-owned buffers and never reads the device: it can be
     captured, and the replays draw the following batches (``GraphedTrainStep(batch_source=...)`` does so).  ``draw()``
@@ -312,7 +381,8 @@ class DeviceBatches:
     def __init__(self, images_u8: Tensor, labels: Tensor, batch_size: int, *, dtype: torch.dtype, seed: int,
                  scale: float = 1.0, phi: Sequence[Callable[[Tensor], Tensor]] = φ_cos_sin_squared_1,
                  shuffle: bool = True, drop_last: bool = True, rank: Optional[int] = None,
-                 world: Optional[int] = None, device=None, augment: Optional[Augment] = None):
+                 world: Optional[int] = None, device=None, augment: Optional[Augment] = None,
+                 autoscale_kernel_size: Optional[int] = None, autoscale_samples: int = 10880):
         if images_u8.dtype != torch.uint8 or images_u8.ndim != 3:
             raise TypeError("DeviceBatches takes (samples, height, width) uint8 intensities; float-valued sources go "
                             f"through DeviceBatches.from_features (got {images_u8.dtype}, {tuple(images_u8.shape)})")
@@ -320,11 +390,18 @@ class DeviceBatches:
             raise NotImplementedError(f"the table of one launch has 1 .. {MAX_WIDTH} columns, phi has {len(phi)}")
         L.dtype_code(torch.empty(0, dtype=dtype))
         n, H, W = images_u8.shape
+        if autoscale_kernel_size is not None and scale != 1.0:
+            raise ValueError("autoscale_kernel_size computes the scale: give one of the two, not both")
+        _check_autoscale(autoscale_kernel_size, autoscale_samples, H, W)
         self._plan(n, labels, batch_size, seed, shuffle, drop_last, rank, world)
         self._plan_augment(augment, H, W, 1)
         dev = self._device(device, images_u8)
         self.kind, self.dtype = L.BATCH_SRC_U8_TABLE, dtype
         self.src = images_u8.to(dev).contiguous()
+        if autoscale_kernel_size is not None:   # get_data_loaders(..., autoscale_kernel_size): the factor of phi's float32 values
+            scale = calc_scaling_factor_from_bytes(self.src, feature_table(phi, 1.0, torch.float32).t().contiguous(),
+                                                   autoscale_kernel_size, samples=autoscale_samples, device=dev)
+        self.scale = float(scale)
         self.table = feature_table(phi, scale, dtype).to(dev)
         self.row_len, self.width = H * W, len(phi)
         self.x_shape = lambda count: (1, count, H, W, len(phi))
@@ -356,30 +433,61 @@ class DeviceBatches:
         return self
 
     @classmethod
-    def from_colour(cls, images_u8: Tensor, labels: Tensor, batch_size: int, *, dtype: torch.dtype, seed: int, nu,
+    def from_colour(cls, images_u8: Tensor, labels: Tensor, batch_size: int, *, dtype: torch.dtype, seed: int, nu=None,
                     mean: Optional[Tensor] = None, std: Optional[Tensor] = None,
                     constant_channel: Optional[float] = None, shuffle: bool = True, drop_last: bool = True,
                     rank: Optional[int] = None, world: Optional[int] = None, device=None,
-                    augment: Optional[Augment] = None) -> "DeviceBatches":
+                    augment: Optional[Augment] = None, center_and_normalize: bool = False,
+                    autoscale_kernel_size: Optional[int] = None, autoscale_samples: int = 10880,
+                    nu_constant: float = 1.0) -> "DeviceBatches":
         """A source over raw colour images: ``images_u8`` (n, height, width, channels) uint8 with the channels interleaved
         (what ``torchvision.datasets.CIFAR10.data`` holds; for YCbCr the caller converts the bytes on the host first),
         channels <= 4.  ``x`` comes out as (1, Bl, height, width, Wout), Wout = channels (+ 1 with ``constant_channel``):
         the reference's colour pipeline (dataset_loading.py:331-389 - ``to_tensor``, the per-channel ``mean`` / ``std``,
         the constant channel, the per-channel ``nu``) evaluated once per byte value and channel (`colour_table`), then
         cast.  `channel_moments` gives ``mean`` and ``std`` of a training split from its bytes.  The data set stays on the
-        device as its bytes: 45 000 x 32 x 32 x 3 is 138 MB, against 737 MB expanded to float32 with a constant channel."""
+        device as its bytes: 45 000 x 32 x 32 x 3 is 138 MB, against 737 MB expanded to float32 with a constant channel.
+
+        The loader's two remaining arguments work from the bytes as well, in the reference's order (:349-375).
+        ``center_and_normalize=True`` (instead of ``mean`` / ``std``) takes the moments of THESE bytes (`colour_moments`: the
+        histogram kernel).  ``autoscale_kernel_size=K`` (instead of ``nu``: exactly one of the two) then builds the nu = 1
+        table with the constant channel, takes `calc_scaling_factor_from_bytes` of the first ``autoscale_samples`` images
+        and puts that factor on EVERY column, the constant one included (:372).  Both are exact or fixed-order sums, so
+        every rank that holds the same bytes builds the same table bits.  The source carries ``mean``, ``std`` (CPU float64,
+        or None), ``nu`` and ``colour_pipeline`` - a dict of ``nu``, ``mean``, ``std``, ``constant_channel`` and
+        ``nu_constant`` - so that the validation and test sources are ``from_colour(val_bytes, ..., **train.colour_pipeline)``:
+        the reference applies the training split's numbers to all three splits."""
         self = cls.__new__(cls)
         if images_u8.dtype != torch.uint8 or images_u8.ndim != 4:
             raise TypeError("from_colour takes (samples, height, width, channels) uint8 bytes; float-valued sources go "
                             f"through DeviceBatches.from_features (got {images_u8.dtype}, {tuple(images_u8.shape)})")
         n, H, W, C = images_u8.shape
-        table = colour_table(C, nu=nu, mean=mean, std=std, constant_channel=constant_channel, dtype=dtype)
+        if (nu is None) == (autoscale_kernel_size is None):
+            raise ValueError("give exactly one of nu and autoscale_kernel_size")
+        if center_and_normalize and (mean is not None or std is not None):
+            raise ValueError("center_and_normalize=True takes the moments of these bytes: it excludes mean and std")
+        if autoscale_kernel_size is not None and nu_constant != 1.0:
+            raise ValueError("autoscale_kernel_size puts its factor on every column: it excludes nu_constant")
+        _check_autoscale(autoscale_kernel_size, autoscale_samples, H, W)
+        pipeline = dict(mean=mean, std=std, constant_channel=constant_channel)
+        # the table's own errors (channels, width, dtype, the lengths of nu, mean and std) before a device is needed
+        table = colour_table(C, nu=1.0 if nu is None else nu, dtype=dtype, nu_constant=nu_constant, **pipeline)
         Wout = table.shape[0]
         self._plan(n, labels, batch_size, seed, shuffle, drop_last, rank, world)
         self._plan_augment(augment, H, W, C)
         dev = self._device(device, images_u8)
         self.kind, self.dtype = L.BATCH_SRC_COLOUR, dtype
         self.src = images_u8.to(dev).contiguous()
+        if center_and_normalize:
+            pipeline["mean"], pipeline["std"] = colour_moments(self.src, dev)
+        if autoscale_kernel_size is not None:
+            unit = colour_table(C, nu=1.0, dtype=torch.float32, **pipeline)
+            nu = nu_constant = calc_scaling_factor_from_bytes(self.src, unit, autoscale_kernel_size,
+                                                              samples=autoscale_samples, device=dev)
+        if center_and_normalize or autoscale_kernel_size is not None:
+            table = colour_table(C, nu=nu, dtype=dtype, nu_constant=nu_constant, **pipeline)
+        self.mean, self.std, self.nu = pipeline["mean"], pipeline["std"], nu
+        self.colour_pipeline = dict(pipeline, nu=nu, nu_constant=nu_constant)
         self.table = table.to(dev)
         self.row_len, self.width = H * W, Wout
         self.x_shape = lambda count: (1, count, H, W, Wout)
@@ -422,12 +530,7 @@ class DeviceBatches:
 
     @staticmethod
     def _device(device, tensor: Tensor) -> torch.device:
-        if not torch.cuda.is_available():
-            raise RuntimeError("dctn_amd: a DeviceBatches source lives on an MI355X device, but no GPU is visible. "
-                               "There is deliberately no CPU implementation of this path.")
-        if device is not None:
-            return torch.device(device)
-        return tensor.device if tensor.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        return _source_device(device, tensor)
 
     def _finish(self, labels: Tensor, dev: torch.device) -> None:
         self.device = dev

@@ -364,6 +364,32 @@ int dctn_window_stats(const void* x, const int64_t x_strides[5], void* sums,
 int dctn_phi_window_stats(const void* images, void* sums, int B, int H, int W, int K, void* stream);
 int dctn_phi_expand(const void* images, void* x, int64_t n_pixels, float scale, int dtype, void* stream);
 
+/* Statistics of a byte-resident data set, from the bytes (version 517; dctn_amd/csrc/byte_stats.hip): what the reference's
+ * colour loader computes from the EXPANDED training tensor (dctn/dataset_loading.py:351-352 and calc_scaling_factor, :79-94)
+ * for the sources that keep the data set on the device as uint8.  Nothing of the data set's size is expanded.
+ *   dctn_byte_histogram : src (n_pixels, channels) interleaved uint8, channels 1 .. 4, ANY byte alignment;
+ *       counts int64 [channels][256] (8-byte aligned), OVERWRITTEN: counts[c][v] = the pixels whose channel c holds v.
+ *       Workgroups count in 32-bit LDS counters - the plan bounds a workgroup's share to 2^31 + 6 pixels, so none wraps -
+ *       and add them with 64-bit integer atomics: the result is exact and the same in any order.
+ *   dctn_byte_window_stats : the two sums of dctn_window_stats (C = 1) for the tensor that a 256-row table per channel
+ *       expands the bytes to, without it.  src (n, H, W, channels) interleaved uint8, any alignment; tu double
+ *       [channels][256][2]: for byte value v in channel c the sum t and the sum of squares u of the features that byte
+ *       produces; t0, u0: the same of the columns no byte feeds (a constant channel).  A pixel's pair is
+ *       t = t0 + sum_c tu[c][byte_c].t (channels ascending), u likewise; a window's two terms are the products of t and of
+ *       u over its K x K pixels; sums (two float64, OVERWRITTEN) = {sum_w prod t, sum_w prod u}.
+ *       One workgroup per image; each STORES its pair of partial sums into workspace[image], and the workgroup that draws
+ *       the last ticket adds the n pairs in one fixed order (no workgroup waits, no float atomic): two launches on the same
+ *       input leave the SAME BITS, whatever the number of CUs.
+ *       workspace: dctn_byte_window_stats_workspace_bytes of n bytes exactly, 8-byte aligned, any previous content.
+ *       DCTN_ERR_UNSUPPORTED, before any launch, when the table plus the image's pairs (16 (256 channels + H W) bytes and
+ *       80 more) exceed what a workgroup of this device may claim (15/16 of dctn_device_limits' LDS), or a float64 or
+ *       int64 buffer is off its 8-byte alignment.  Checks in the library's order: NULL, shape (n_pixels, n < 1, channels
+ *       outside 1 .. 4, K < 1, H or W < K), unsupported; no argument carries a dtype. */
+int dctn_byte_histogram(const void* src, int64_t n_pixels, int channels, void* counts, void* stream);
+size_t dctn_byte_window_stats_workspace_bytes(int64_t n);
+int dctn_byte_window_stats(const void* src, int64_t n, int H, int W, int channels, const void* tu, double t0, double u0,
+                           int K, void* workspace, void* sums, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Tail of a training iteration (reference: dctn/training.py:77-84 with
  * F.cross_entropy, the L2 regularisers of dctn/eps_plus_linear.py:149-159 and torch.optim.SGD).
