@@ -306,6 +306,60 @@ class _ManyConvSBSFunction(torch.autograd.Function):
         return _wanted(ctx, d_x, d_cores)
 
 
+class _ManyConvSBSStackedFunction(torch.autograd.Function):
+    """`_ManyConvSBSFunction` with the strings' outputs in ONE buffer (n_strings, B, H', W', out): the library gets the
+    pointers of its slices, so the next layer reads the stacked tensor as it is, with no copy in between, and the backward
+    takes the slices of the one incoming gradient.  The same library calls, hence the same bits.  Only for layers
+    `_ManyConvSBSFunction.supported` takes and whose strings have one output shape."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, specs, *cores: Tensor):
+        dev = L.require_device(x, *cores)
+        C, B, H, W, q = x.shape
+        plans = [_plan(sp) for sp in specs]
+        ns, n = len(plans), plans[0].n
+        assert all(C == p.C and q == p.q for p in plans)
+        cores_c = [c.contiguous() for c in cores]
+        for core, shape in zip(cores_c, [t for p in plans for t in p.shape_tuples]):
+            assert tuple(core.shape) == shape
+            if core.dtype != x.dtype:
+                raise TypeError(f"ConvSBS: core is {core.dtype} but input is {x.dtype}")
+        outs_arr, bonds_arr, ph_arr, pw_arr = _many_arrays(plans)
+        p0 = plans[0]
+        out = torch.empty((ns, B, H - p0.max_h, W - p0.max_w, p0.out_total), dtype=x.dtype, device=dev)
+        L.check(
+            L.lib().dctn_convsbs_many_fwd(x.data_ptr(), L.strides5(x), L.ptr_array(cores_c), L.ptr_array(list(out.unbind(0))), ns,
+                                          n, outs_arr, bonds_arr, ph_arr, pw_arr, C, B, H, W, q, L.F32, L.stream_ptr(dev)),
+            "ManyConvSBS forward",
+        )
+        ctx.save_for_backward(x, *cores_c)
+        ctx.meta = (plans, C, B, H, W, q)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out: Tensor):
+        plans, C, B, H, W, q = ctx.meta
+        x, *cores_c = ctx.saved_tensors
+        dev = x.device
+        ns, n = len(plans), plans[0].n
+        need_dx = ctx.needs_input_grad[0]
+        need_dcores = any(ctx.needs_input_grad[2:])
+        gs = list(d_out.contiguous().unbind(0))
+        d_x = torch.empty((C, B, H, W, q), dtype=x.dtype, device=dev) if need_dx else None
+        d_cores = [v for k in range(0, ns * n, n) for v in _core_grad_views(cores_c[k : k + n])] if need_dcores else None
+        outs_arr, bonds_arr, ph_arr, pw_arr = _many_arrays(plans)
+        nbytes = L.lib().dctn_convsbs_many_workspace_bytes(ns, n, outs_arr, bonds_arr, C, B, H, W, q, ph_arr, pw_arr, L.F32)
+        ws = L.workspace(nbytes, dev)
+        L.check(
+            L.lib().dctn_convsbs_many_bwd(
+                x.data_ptr(), L.strides5(x), L.ptr_array(cores_c), L.ptr_array(gs), None if d_x is None else d_x.data_ptr(),
+                None if d_cores is None else L.ptr_array(d_cores), ns, n, outs_arr, bonds_arr, ph_arr, pw_arr, C, B, H, W, q,
+                ws.data_ptr(), ws.numel(), L.F32, L.stream_ptr(dev)),
+            "ManyConvSBS backward",
+        )
+        return _wanted(ctx, d_x, d_cores)
+
+
 def _many_arrays(plans):
     """(out sizes, bond sizes, pos_h, pos_w) of several strings, string-major, as C int arrays."""
     cat = lambda name: L.int_array([v for p in plans for v in getattr(p, name)])
@@ -487,3 +541,16 @@ class ManyConvSBS(nn.Module):
         if _ManyConvSBSFunction.supported(x, specs):   # the strings of the layer in one launch each way
             return _ManyConvSBSFunction.apply(x, specs, *(c for string in self.strings for c in string.cores))
         return tuple(string(x) for string in self.strings)
+
+    def forward_stacked(self, channels: Union[Tensor, Tuple[Tensor, ...]], /) -> Tensor:
+        """The outputs of `forward` as one tensor (n_strings, batch, height', width', out) - what the next layer stacks its
+        input channels into anyway.  A layer that runs its strings in one launch writes them into one buffer (no copy);
+        every other layer returns ``torch.stack(self.forward(x))``.  The same bits as `forward` either way."""
+        x = channels if isinstance(channels, Tensor) else torch.stack(tuple(channels))
+        _, staged = L.placement(x, *self.parameters())
+        specs = tuple(string.spec for string in self.strings)
+        if not staged and _ManyConvSBSFunction.supported(x, specs):
+            extents = {(sp.max_height_pos, sp.max_width_pos, sp.out_total_quantum_dim_size) for sp in specs}
+            if len(extents) == 1:
+                return _ManyConvSBSStackedFunction.apply(x, specs, *(c for string in self.strings for c in string.cores))
+        return torch.stack(self.forward(x))

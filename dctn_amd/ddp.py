@@ -363,6 +363,19 @@ def all_reduce_scalar_sums(*values: Tensor) -> List[Tensor]:
 
 
 @torch.no_grad()
+def all_reduce_moment_rows(rows, device=None) -> List[tuple]:
+    """Rows of float64 sums - ``(n, sum, sum of squares, ...)`` per tensor, as `tensor_stats.OutputStats` leaves them for this
+    rank's shard - summed over the ranks in ONE all-reduce: every rank gets the rows of the union of the shards, the same
+    bits everywhere.  Without a process group (or with one rank) the rows come back as they are."""
+    rows = [tuple(float(v) for v in row) for row in rows]
+    if not dist.is_initialized() or dist.get_world_size() == 1:
+        return rows
+    packed = torch.tensor(rows, dtype=torch.float64, device=device)
+    dist.all_reduce(packed, op=dist.ReduceOp.SUM)
+    return [tuple(row) for row in packed.cpu().tolist()]
+
+
+@torch.no_grad()
 def global_biased_std_from_sums(count: int, sums: Tensor) -> Tensor:
     """The same statistic from ``(count, [sum, sum of squares])`` of this rank's shard (what `dctn_eps_fwd_stats`
     leaves): one all-reduce of three float64 numbers."""

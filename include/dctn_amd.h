@@ -1136,6 +1136,51 @@ int dctn_state_scatter(const void* arena, void* const* dsts, const int64_t* byte
                        void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The tail of the ConvSBS classifier and the statistics of its strings' outputs (version 518; dctn_amd/csrc/sbs_tail.hip;
+ * host side: dctn_amd/mnist_model.py, dctn_amd/tensor_stats.py).  Dtypes: DCTN_F32 / DCTN_F64 only.  None of the three
+ * reports to dctn_last_kernel.  Return codes, decided on the host before any launch, in the project's order:
+ * DCTN_ERR_NULL, DCTN_ERR_BAD_SHAPE, DCTN_ERR_BAD_DTYPE, DCTN_ERR_UNSUPPORTED (then DCTN_ERR_WORKSPACE where there is one).
+ *
+ * dctn_position_mean_fwd : the reference's einops.reduce(result, "b h w l -> b l", "mean") (mnist.py:263).  y: (B, P, L)
+ *   contiguous, the final string's (B, H', W', L); out: (B, L), OVERWRITTEN.  out[b, l] = the sum over p in FLOAT64, divided by
+ *   P in float64, rounded once to `dtype`.  B >= 1 (and < 2^31), P >= 1: DCTN_ERR_BAD_SHAPE otherwise; 1 <= L <= 64:
+ *   DCTN_ERR_UNSUPPORTED otherwise.  One workgroup per sample with R L threads, R = 256 / L: thread t owns label t % L and
+ *   the positions t / L, t / L + R, ...; the R partial sums of a label are added in that order.  Grid and summation order are
+ *   a function of (P, L) alone, never of B or of the device: a sample's row has the same bits in whatever batch it sits.
+ * dctn_position_mean_bwd : dy[b, p, l] = dlogits[b, l] / P, divided in float64 and rounded once; dy (B, P, L) is
+ *   OVERWRITTEN.  The same limits and codes.
+ *
+ * dctn_tensor_stats : the moments of up to 8 tensors in ONE launch.  tensors / counts: HOST arrays of n_tensors device
+ *   pointers (contiguous values of `dtype`, aligned to their element size; a 16-byte aligned pointer is read four elements
+ *   per access - the record does not depend on which form ran) and element counts.  1 <= n_tensors <= 8 and every count
+ *   >= 1: DCTN_ERR_BAD_SHAPE otherwise.  records: device, 8-byte aligned, n_tensors records of
+ *   dctn_tensor_stats_record_bytes() = 64 bytes, laid out as
+ *        0  int64    n          all elements
+ *        8  double   sum        } over the FINITE elements only, in float64 (a float32 value and its square are exact
+ *       16  double   sum_sq     } in a double)
+ *       24  double   sum_abs    }
+ *       32  float    min_abs    +Inf if the tensor has no finite element
+ *       36  float    max_abs    0 if it has none
+ *       40  uint32   nonfinite  NaN and +-Inf elements
+ *       44  uint32   seq        advanced by one by every launch
+ *       48  uint32   ticket     0 between launches
+ *       52  uint32   reserved[3]
+ *   The records must be ZERO before the first launch and are the caller's to read after any launch; every launch
+ *   overwrites all fields but `reserved`.  workspace: device, 8-byte aligned, dctn_tensor_stats_workspace_bytes(n_tensors)
+ *   bytes (too small: DCTN_ERR_WORKSPACE); it need not be initialised and nothing of it is kept between launches.
+ *   Tensor i is read by min(256, ceil(count / 4096)) workgroups of 1024 threads; each stores its partial sums into its
+ *   own slots of the workspace and draws the tensor's ticket; the workgroup that draws the last one adds the slots in
+ *   index order, writes the record and puts the ticket back to 0.  No workgroup waits for another, and the record's bits
+ *   are a function of the tensor's values alone.  Capturable: the launch reads no host state but its arguments.
+ * ------------------------------------------------------------------------------------------ */
+int dctn_position_mean_fwd(const void* y, void* out, int64_t B, int64_t P, int L, int dtype, void* stream);
+int dctn_position_mean_bwd(const void* dlogits, void* dy, int64_t B, int64_t P, int L, int dtype, void* stream);
+size_t dctn_tensor_stats_record_bytes(void);
+size_t dctn_tensor_stats_workspace_bytes(int n_tensors);
+int dctn_tensor_stats(const void* const* tensors, const int64_t* counts, int n_tensors, void* records, void* workspace,
+                      size_t workspace_bytes, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Tensor-network inner product of two stacks of EPS cores - replaces the contractions of
  * dctn/epses_composition.py:21-58 `inner_product` (Gram of the first pair of cores over their input legs:
  * dctn/eps.py:106-112 `contract_on_input_dims`; that matrix absorbed into every input leg of the next core:
