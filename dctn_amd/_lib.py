@@ -200,6 +200,9 @@ SIGNATURES = {
     "dctn_tensor_stats_record_bytes": (c_size, []),
     "dctn_tensor_stats_workspace_bytes": (c_size, [c_int]),
     "dctn_tensor_stats": (c_int, [_PtrP, _I64P, c_int, c_void, c_void, c_size, c_int, c_void]),
+    "dctn_tensor_hist_block_bytes": (c_size, [c_int]),
+    "dctn_tensor_hist": (c_int, [_PtrP, _I64P, c_int, c_void, c_int, c_void, c_int, c_int, c_void]),
+    "dctn_tensor_hist_reset": (c_int, [c_void, c_int, c_int, c_void]),
     "dctn_mode_product": (c_int, [c_void, c_void, c_void, c_i64, c_int, c_int, c_i64, c_int, c_void]),
     "dctn_fiber_gram_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_i64, c_int]),
     "dctn_fiber_gram": (c_int, [c_void, c_void, c_void, c_void, c_size, c_i64, c_int, c_int, c_i64, c_int, c_void]),

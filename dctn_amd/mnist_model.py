@@ -8,6 +8,8 @@ same ``forward`` and ``scale_layers_using_batch``.  What differs is how the tail
   - ``model.output_stats = OutputStats(dev, model.string_names())`` makes every training forward end with one launch that
     leaves mean / std / |y| range / non-finite count of every string's output on the device - the reference's forward
     hooks (mnist.py:537-553), which no captured step can run.  Eval forwards record nothing;
+  - ``model.output_histograms = OutputHistograms(dev, model.string_names(), period=20)`` adds one more launch over the
+    same outputs: the reference's `log_dumb_histogram` over TensorBoard's buckets, accumulated on the device;
   - `scale_layers_using_batch` reads the std of a layer's strings from one such launch and one host read per layer, and
     with a process group scales by the std of the UNION of the ranks' shards, so that replicas stay replicas.
 `forward` also takes the quantum batch (1, B, H, W, 2) that a ``DeviceBatches(phi=quantum_phi(...), scale=multiplier)``
@@ -27,6 +29,7 @@ from . import ddp
 from .conv_sbs import Initialization, ManyConvSBS
 from .conv_sbs_spec import SBSSpecCore
 from .pos2d import Pos2D
+from .tensor_hist import OutputHistograms
 from .tensor_stats import OutputStats, std_from_moments
 
 logger = logging.getLogger(__name__)
@@ -161,6 +164,7 @@ class DCTNMnistModel(nn.Module):
         )
         self.after_batch_to_quantum_callback = after_batch_to_quantum_callback
         self.output_stats: Optional[OutputStats] = None   # opt-in: OutputStats(device, model.string_names())
+        self.output_histograms: Optional[OutputHistograms] = None   # opt-in: OutputHistograms(device, model.string_names())
 
     def string_names(self) -> List[str]:
         """One name per string, in the order a forward records them: ``conv_sbses.{layer}.strings.{string}``."""
@@ -186,15 +190,19 @@ class DCTNMnistModel(nn.Module):
 
     def forward(self, x: Tensor) -> Tensor:
         intermediate = self._quantum(x)
-        record = self.training and self.output_stats is not None
+        stats = self.output_stats if self.training else None
+        hists = self.output_histograms if self.training else None
+        record = stats is not None or hists is not None
         outputs: List[Tensor] = []
         for conv_sbs in self.conv_sbses:
             intermediate = self._layer(conv_sbs, intermediate)
             if record:
                 outputs.extend(intermediate.unbind(0))
         assert intermediate.shape[0] == 1
-        if record:
-            self.output_stats.record(outputs)   # ONE launch over every string's output (two beyond eight strings)
+        if stats is not None:
+            stats.record(outputs)   # ONE launch over every string's output (two beyond eight strings)
+        if hists is not None:
+            hists.record(outputs)   # and one more over the same list
         return position_mean(intermediate[0])
 
     def scale_layers_using_batch(self, x: Tensor, reduce: Optional[Callable] = None) -> Tensor:

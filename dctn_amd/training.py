@@ -2015,6 +2015,17 @@ def make_trace_logger(trace: "StepTrace", every: int, sink: Callable[..., None])
     return _TraceLogger(trace, every, sink)
 
 
+def make_histogram_logger(hists, every: int, sink: Callable[..., None]) -> Callable[[StX, StIt], None]:
+    """Hook for ``train_graphed(after_launch=[...])``: every ``every`` launches it reads ``hists`` (a
+    `tensor_hist.OutputHistograms`: the one synchronisation), calls ``sink(name, summary, num_iters_done)`` per name and
+    resets the blocks.  ``summary`` holds the arguments of ``SummaryWriter.add_histogram_raw``: ``min``, ``max``, ``num``,
+    ``bucket_limits`` and ``bucket_counts`` are exact, ``sum`` and ``sum_squares`` approximations from the buckets' centres
+    (`tensor_hist.histogram_summary`)."""
+    from .tensor_hist import HistogramLogger
+
+    return HistogramLogger(hists, every, sink)
+
+
 def every_n_iters_intervals(*intervals):
     """Decorator factory: ``intervals`` are ``(length, period)`` pairs laid end to end from iteration 0; the
     hook runs when ``num_iters_done`` is a multiple of the period of the interval it falls in.  The last

@@ -1181,6 +1181,55 @@ int dctn_tensor_stats(const void* const* tensors, const int64_t* counts, int n_t
                       size_t workspace_bytes, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Histograms of up to 8 tensors in ONE launch over a table of bin edges (version 519; dctn_amd/csrc/tensor_hist.hip;
+ * host side: dctn_amd/tensor_hist.py) - the reference's log_dumb_histogram (mnist.py:537-553) over TensorBoard's bucket
+ * set, or any other table.  Dtypes: DCTN_F32 / DCTN_F64, one per call.  None of the three reports to dctn_last_kernel.
+ *
+ * dctn_tensor_hist : tensors / counts: HOST arrays of n_tensors device pointers (contiguous values of `dtype`, aligned
+ *   to their element size; a 16-byte aligned pointer is read four elements per access - the block does not depend on
+ *   which form ran) and element counts.  edges: DEVICE, 8-byte aligned, n_edges float64 values, STRICTLY INCREASING and
+ *   finite (the caller's duty: the library cannot read them).  blocks: DEVICE, 8-byte aligned, n_tensors blocks of
+ *   dctn_tensor_hist_block_bytes(n_edges) = 80 + 8 (n_edges - 1) bytes each, one after the other, laid out as
+ *        0  uint64   total      every element seen
+ *        8  uint64   below      finite and < edges[0]
+ *       16  uint64   above      finite and > edges[n_edges - 1]
+ *       24  uint64   nan
+ *       32  uint64   pos_inf
+ *       40  uint64   neg_inf
+ *       48  uint64   max_key    key(largest finite value); 0: no finite value yet
+ *       56  uint64   min_key_c  ~key(smallest finite value); 0: no finite value yet
+ *       64  uint32   calls      launches so far, recorded or not
+ *       68  uint32   recorded   launches that counted
+ *       72  uint32   ticket     0 between launches
+ *       76  uint32   reserved
+ *       80  uint64   counts[n_edges - 1]
+ *   key(v), for the float64 bits b of v: ~b if the sign bit is set, b | 2^63 otherwise - unsigned order is value order,
+ *   and no finite value has key 0 or ~0.  A block must be ZERO before its first launch: all zero is a valid empty block.
+ *   Semantics, those of numpy.histogram(v.astype(float64), bins=edges): a finite v counts in bin i when
+ *   edges[i] <= v < edges[i + 1]; the last bin is closed on the right; a float32 value is widened exactly and compared
+ *   in float64; -0.0 is 0.0 (in min / max too).  The bin is found by a binary search of comparisons against the table.
+ *   A launch ADDS to what the block holds, if it is recorded: it is iff calls % period == 0 for the `calls` it finds; a
+ *   launch that is not reads no element.  Either way it leaves calls + 1 and ticket 0.  Everything accumulated is an
+ *   integer sum or a max: the block's bits are a function of the values of the recorded launches alone.  Tensor i is
+ *   read by min(256, ceil(count / 4096)) workgroups of 1024 threads; no workgroup waits for another.  Capturable: the
+ *   launch reads no host state but its arguments; the blocks it reads and writes are device state, so a replay goes on
+ *   where the last launch stopped.  The tensors and the table are only read; nothing outside the blocks is written; no
+ *   workspace.
+ *   Return codes, decided on the host before any launch, in the project's order: DCTN_ERR_NULL (an array, an entry,
+ *   edges, blocks); DCTN_ERR_BAD_SHAPE (n_tensors outside 1..8, a count < 1, n_edges outside 2..2048, period < 1);
+ *   DCTN_ERR_BAD_DTYPE (bf16 or anything else); DCTN_ERR_UNSUPPORTED (a count above 2^39; edges or blocks not 8-byte
+ *   aligned).
+ * dctn_tensor_hist_reset : zeroes counts, counters, keys and `recorded` of n_tensors blocks and KEEPS `calls`, so the
+ *   period's phase survives a read.  One small launch on `stream`, between launches of dctn_tensor_hist; not meant to be
+ *   captured.  DCTN_ERR_NULL; DCTN_ERR_BAD_SHAPE (n_tensors < 1, n_edges outside 2..2048); DCTN_ERR_UNSUPPORTED
+ *   (n_tensors > 65535, alignment).
+ * ------------------------------------------------------------------------------------------ */
+size_t dctn_tensor_hist_block_bytes(int n_edges);   /* 0 for n_edges < 2 */
+int dctn_tensor_hist(const void* const* tensors, const int64_t* counts, int n_tensors, const void* edges, int n_edges,
+                     void* blocks, int period, int dtype, void* stream);
+int dctn_tensor_hist_reset(void* blocks, int n_tensors, int n_edges, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Tensor-network inner product of two stacks of EPS cores - replaces the contractions of
  * dctn/epses_composition.py:21-58 `inner_product` (Gram of the first pair of cores over their input legs:
  * dctn/eps.py:106-112 `contract_on_input_dims`; that matrix absorbed into every input leg of the next core:
