@@ -73,6 +73,15 @@ class BatchCall(ctypes.Structure):
 
 _BatchCallP = ctypes.POINTER(BatchCall)
 
+
+class TTString(ctypes.Structure):
+    """dctn_tt_string_t: one ConvSBS string as dctn_tt_stats takes it; the bonds are cyclic (bond_sizes[0] == 1: open)."""
+    _fields_ = [("n_cores", c_int), ("C", c_int), ("q", c_int), ("reserved", c_int), ("out_sizes", c_int * 16),
+                ("bond_sizes", c_int * 16)]
+
+
+_TTStringP = ctypes.POINTER(TTString)
+
 # name -> (restype, argtypes); mirrors include/dctn_amd.h one to one
 SIGNATURES = {
     "dctn_version": (c_int, []),
@@ -203,6 +212,9 @@ SIGNATURES = {
     "dctn_tensor_hist_block_bytes": (c_size, [c_int]),
     "dctn_tensor_hist": (c_int, [_PtrP, _I64P, c_int, c_void, c_int, c_void, c_int, c_int, c_void]),
     "dctn_tensor_hist_reset": (c_int, [c_void, c_int, c_int, c_void]),
+    "dctn_tt_stats_block_bytes": (c_size, [c_int, c_int]),
+    "dctn_tt_stats_workspace_bytes": (c_size, [_TTStringP, c_int]),
+    "dctn_tt_stats": (c_int, [_PtrP, _TTStringP, c_int, c_void, c_int, c_int, c_void, c_size, c_int, c_void]),
     "dctn_mode_product": (c_int, [c_void, c_void, c_void, c_i64, c_int, c_int, c_i64, c_int, c_void]),
     "dctn_fiber_gram_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_i64, c_int]),
     "dctn_fiber_gram": (c_int, [c_void, c_void, c_void, c_void, c_size, c_i64, c_int, c_int, c_i64, c_int, c_void]),

@@ -10,6 +10,9 @@ same ``forward`` and ``scale_layers_using_batch``.  What differs is how the tail
     hooks (mnist.py:537-553), which no captured step can run.  Eval forwards record nothing;
   - ``model.output_histograms = OutputHistograms(dev, model.string_names(), period=20)`` adds one more launch over the
     same outputs: the reference's `log_dumb_histogram` over TensorBoard's buckets, accumulated on the device;
+  - ``model.tt_stats = TTStats.for_model(model, period=20)`` makes every training forward BEGIN with one launch that
+    leaves the sum and squared norm of the tensor every string represents on the device, from the cores as the iteration
+    finds them: the reference's ``mean_of_tt_tensor`` / ``std_of_tt_tensor`` (conv_sbs_statistics_logging.py);
   - `scale_layers_using_batch` reads the std of a layer's strings from one such launch and one host read per layer, and
     with a process group scales by the std of the UNION of the ranks' shards, so that replicas stay replicas.
 `forward` also takes the quantum batch (1, B, H, W, 2) that a ``DeviceBatches(phi=quantum_phi(...), scale=multiplier)``
@@ -31,6 +34,7 @@ from .conv_sbs_spec import SBSSpecCore
 from .pos2d import Pos2D
 from .tensor_hist import OutputHistograms
 from .tensor_stats import OutputStats, std_from_moments
+from .tt_stats import TTStats
 
 logger = logging.getLogger(__name__)
 
@@ -165,6 +169,7 @@ class DCTNMnistModel(nn.Module):
         self.after_batch_to_quantum_callback = after_batch_to_quantum_callback
         self.output_stats: Optional[OutputStats] = None   # opt-in: OutputStats(device, model.string_names())
         self.output_histograms: Optional[OutputHistograms] = None   # opt-in: OutputHistograms(device, model.string_names())
+        self.tt_stats: Optional[TTStats] = None   # opt-in: TTStats.for_model(model, period), built after the optimizer
 
     def string_names(self) -> List[str]:
         """One name per string, in the order a forward records them: ``conv_sbses.{layer}.strings.{string}``."""
@@ -194,6 +199,8 @@ class DCTNMnistModel(nn.Module):
         hists = self.output_histograms if self.training else None
         record = stats is not None or hists is not None
         outputs: List[Tensor] = []
+        if self.training and self.tt_stats is not None:
+            self.tt_stats.record()   # ONE launch over every string's cores, as the iteration finds them
         for conv_sbs in self.conv_sbses:
             intermediate = self._layer(conv_sbs, intermediate)
             if record:

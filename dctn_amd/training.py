@@ -2026,6 +2026,17 @@ def make_histogram_logger(hists, every: int, sink: Callable[..., None]) -> Calla
     return HistogramLogger(hists, every, sink)
 
 
+def make_tt_stats_logger(tt, every: int, sink: Callable[..., None], first_iter: int = 0) -> Callable[[StX, StIt], None]:
+    """Hook for ``train_graphed(after_launch=[...])``: every ``every`` launches it reads ``tt`` (a `tt_stats.TTStats`: the
+    one synchronisation) and, for every row not yet read, calls ``sink("mean_of_tt_tensor/" + name, mean, first_iter + call)``
+    and ``sink("std_of_tt_tensor/" + name, std, first_iter + call)`` per string - the reference's two tags
+    (conv_sbs_statistics_logging.py) in ``add_scalar``'s argument order.  ``flush()`` reads and reports at once.  Give the
+    ring ``capacity >= every * iters_per_launch / period`` rows and nothing is lost."""
+    from .tt_stats import TTStatsLogger
+
+    return TTStatsLogger(tt, every, sink, first_iter)
+
+
 def every_n_iters_intervals(*intervals):
     """Decorator factory: ``intervals`` are ``(length, period)`` pairs laid end to end from iteration 0; the
     hook runs when ``num_iters_done`` is a multiple of the period of the interval it falls in.  The last

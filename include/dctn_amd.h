@@ -1230,6 +1230,63 @@ int dctn_tensor_hist(const void* const* tensors, const int64_t* counts, int n_te
 int dctn_tensor_hist_reset(void* blocks, int n_tensors, int n_edges, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Sum and squared Frobenius norm of the tensor each of up to 16 ConvSBS strings REPRESENTS, in ONE launch, from the
+ * cores alone (version 520; dctn_amd/csrc/tt_stats.hip; host side: dctn_amd/tt_stats.py) - what the reference logs per
+ * string every 20 iterations as mean_of_tt_tensor / std_of_tt_tensor (dctn/conv_sbs_statistics_logging.py, from
+ * ConvSBS.mean() and ConvSBS.var() ** 0.5).  Dtypes: DCTN_F32 / DCTN_F64, one per call; all arithmetic is float64 (a
+ * float32 element is widened exactly).  None of the three reports to dctn_last_kernel.
+ *
+ * dctn_tt_string_t : one string.  Core c is (out_sizes[c], l_c, r_c, q, ..., q) contiguous, q repeated C times, with
+ *   l_c = bond_sizes[c] and r_c = bond_sizes[(c + 1) % n_cores]: the bonds are taken cyclically, so bond_sizes[0] == 1 is an
+ *   open chain and anything larger a ring.  P = q^C; the slices A_c[o, p] are l_c x r_c.  `reserved` is ignored.
+ * dctn_tt_stats : cores: HOST array of the strings' device pointers, string-major (the n_cores of string 0, then those
+ *   of string 1, ...), each aligned to its element size.  strings: HOST array of n_strings descriptors.  Per string
+ *        sum     = tr(S_0 S_1 ... S_{N-1}),                              S_c    = sum_{o,p} A_c[o, p]
+ *        sq_norm = sum_{i,j < l_0} (F_{N-1} o ... o F_0)(e_i e_j^T)[i, j],   F_c(V) = sum_{o,p} A_c[o, p]^T V A_c[o, p]
+ *   the sum of all elements of the represented tensor and its squared Frobenius norm.  Limits: 1 <= n_cores <= 16,
+ *   every bond <= 32 (non-uniform bonds included), P <= 256, any out size >= 1 as long as a core has fewer than 2^31
+ *   elements.  block: DEVICE, 8-byte aligned, dctn_tt_stats_block_bytes(n_strings, capacity) =
+ *   32 + capacity (16 + 16 n_strings) bytes, laid out as
+ *        0  uint32   calls        launches so far, recorded or not
+ *        4  uint32   recorded     launches that wrote a row
+ *        8  uint32   ticket       0 between launches
+ *       12  uint32   reserved[5]
+ *       32  rows[capacity], each
+ *             0  uint32   call      the `calls` value the row was taken at
+ *             4  uint32   seq       the `recorded` value it got, written last
+ *             8  uint64   reserved
+ *            16  { double sum, double sq_norm } [n_strings]
+ *   The block must be ZERO before the first launch.  A launch is RECORDED iff calls % period == 0 for the `calls` it
+ *   finds; a recorded launch writes row recorded % capacity (a ring: the oldest row is overwritten); a launch that is not
+ *   recorded reads no core and writes nothing but the header.  Either way it leaves calls + 1 and ticket 0.
+ *   workspace: DEVICE, 8-byte aligned, dctn_tt_stats_workspace_bytes(strings, n_strings) bytes = 16 per workgroup; it need
+ *   not be initialised and nothing of it is kept between launches.  A string owns bond_sizes[0] workgroups of 256
+ *   threads (an open chain: one); each stores its two partial values into its own slot and draws the ticket; the
+ *   workgroup that draws the launch's last one adds every string's slots in index order, writes the row and advances the
+ *   header.  No workgroup waits for another.  Grid and every summation order are functions of the string's own shape: a
+ *   string's 16 bytes do not depend on how many strings the launch holds, on its place among them, on the device or on
+ *   what the workspace held.  Capturable: the launch reads no host state but its arguments (the descriptors and pointers
+ *   travel in the kernel's argument); the block is device state, so a replay goes on where the last launch stopped.  The
+ *   cores are only read; nothing outside the block and the workspace is written.
+ *   Return codes, decided on the host before any launch, in the project's order: DCTN_ERR_NULL (cores, strings, block, or
+ *   an entry of cores); DCTN_ERR_BAD_SHAPE (n_strings outside 1..16; n_cores, C, q, an out size or a bond < 1;
+ *   n_cores > 16; capacity < 1; period < 1); DCTN_ERR_BAD_DTYPE (bf16 or anything else); DCTN_ERR_UNSUPPORTED (a bond
+ *   above 32, P above 256, a core of 2^31 elements or more; a misaligned core, block or workspace); DCTN_ERR_WORKSPACE
+ *   (workspace NULL or too small).
+ * dctn_tt_stats_block_bytes : 0 for n_strings outside 1..16 or capacity < 1.
+ * dctn_tt_stats_workspace_bytes : 0 for NULL, n_strings outside 1..16 or a string dctn_tt_stats would refuse.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct dctn_tt_string_t {
+  int n_cores, C, q, reserved;
+  int out_sizes[16];
+  int bond_sizes[16];
+} dctn_tt_string_t;
+size_t dctn_tt_stats_block_bytes(int n_strings, int capacity);
+size_t dctn_tt_stats_workspace_bytes(const dctn_tt_string_t* strings, int n_strings);
+int dctn_tt_stats(const void* const* cores, const dctn_tt_string_t* strings, int n_strings, void* block, int capacity, int period,
+                  void* workspace, size_t workspace_bytes, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Tensor-network inner product of two stacks of EPS cores - replaces the contractions of
  * dctn/epses_composition.py:21-58 `inner_product` (Gram of the first pair of cores over their input legs:
  * dctn/eps.py:106-112 `contract_on_input_dims`; that matrix absorbed into every input leg of the next core:
