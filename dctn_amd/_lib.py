@@ -215,6 +215,9 @@ SIGNATURES = {
     "dctn_tt_stats_block_bytes": (c_size, [c_int, c_int]),
     "dctn_tt_stats_workspace_bytes": (c_size, [_TTStringP, c_int]),
     "dctn_tt_stats": (c_int, [_PtrP, _TTStringP, c_int, c_void, c_int, c_int, c_void, c_size, c_int, c_void]),
+    "dctn_param_stats_block_bytes": (c_size, [c_int, c_int]),
+    "dctn_param_stats_workspace_bytes": (c_size, [_I64P, c_int]),
+    "dctn_param_stats": (c_int, [c_void, c_void, c_void, _I64P, c_int, c_void, c_int, c_int, c_void, c_size, c_int, c_void]),
     "dctn_mode_product": (c_int, [c_void, c_void, c_void, c_i64, c_int, c_int, c_i64, c_int, c_void]),
     "dctn_fiber_gram_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_i64, c_int]),
     "dctn_fiber_gram": (c_int, [c_void, c_void, c_void, c_void, c_size, c_i64, c_int, c_int, c_i64, c_int, c_void]),

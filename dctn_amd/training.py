@@ -1296,7 +1296,19 @@ class WeightEMA(_WordTable):
         self.warmup = bool(int(words[1]) & self._WARMUP)
 
 
-class _FlatOptimizer:
+class _TakesParamStats(type):
+    """The constructor call of the flat optimizers.  ``param_stats=`` is the one option all three take in the same place
+    and the same way, so it is taken HERE, keyword-only by construction, and bound once the subclass's ``__init__`` has
+    allocated every buffer (the master copy among them); the ``__init__`` lists themselves stay what callers who pass
+    positionally rely on."""
+
+    def __call__(cls, *args, param_stats=None, **kw):
+        optimizer = super().__call__(*args, **kw)
+        optimizer._bind_param_stats(param_stats)
+        return optimizer
+
+
+class _FlatOptimizer(metaclass=_TakesParamStats):
     """What FlatSGD, FlatAdam and FlatRMSprop share: the parameters moved into ONE flat buffer (their ``.data`` become views of it,
     in the order regularised + others), the gradients read in place when they already sit back to back in that
     order (the fused EPS + head backward allocates them so) and gathered otherwise, and the regulariser's value left
@@ -1376,6 +1388,26 @@ class _FlatOptimizer:
         self.ema = ema
         if ema is not None:
             ema._bind(self)
+        self.param_stats = None   # set by the constructor call (`_TakesParamStats`)
+
+    def _bind_param_stats(self, param_stats) -> None:
+        """``param_stats``: a `param_stats.ParamStats` whose record every ``step()`` ends with, or None.  It gets the
+        segments' sizes here: one per parameter, in flat order."""
+        if param_stats is not None:
+            from .param_stats import ParamStats
+
+            if not isinstance(param_stats, ParamStats):
+                raise TypeError(f"param_stats must be a ParamStats, got {type(param_stats).__name__}")
+            if len(self.params) > ParamGroups.MAX_SEGMENTS:
+                raise NotImplementedError(f"param_stats: at most {ParamGroups.MAX_SEGMENTS} parameters (one segment each), "
+                                          f"got {len(self.params)}")
+            if len(param_stats.names) != len(self.params):
+                raise ValueError(f"the monitor holds {len(param_stats.names)} names, the optimizer {len(self.params)} "
+                                 "parameters: one name per parameter, in flat order (regularised + others)")
+            if param_stats.device != self.flat.device:
+                raise ValueError(f"the monitor's block is on {param_stats.device}, the parameters on {self.flat.device}")
+            param_stats.bind([p.numel() for p in self.params])
+        self.param_stats = param_stats
 
     def _finish_init(self, lr: float, what: str) -> None:
         """A subclass's constructor ends here, its hyper-parameters set and its buffers allocated."""
@@ -1547,9 +1579,10 @@ class _FlatOptimizer:
         on = [name for name, p in ptr.items() if p is not None]
         self._what = what + (f" ({', '.join(on)})" if on else "")
 
-    def _begin_step(self) -> None:
+    def _begin_step(self) -> Tensor:
         """What changes from one step to the next goes into the descriptor - where the gradients lie, and ``n_reg`` and
-        ``l2``, plain attributes a caller may have assigned - and the guard's check is launched in front of the step."""
+        ``l2``, plain attributes a caller may have assigned - and the guard's check is launched in front of the step.
+        Returns the gradients' buffer for `_end_step`."""
         if self.ema is not None:
             self.ema._refuse_applied(f"{type(self).__name__}.step()")
         g = self._grads()
@@ -1557,6 +1590,14 @@ class _FlatOptimizer:
         d.grads, d.n_reg, d.l2 = g.data_ptr(), self.n_reg, self.l2
         if self.guard is not None:
             self.guard.check(g, self.guard_loss() if callable(self.guard_loss) else self.guard_loss)
+        return g
+
+    def _end_step(self, g: Tensor) -> None:
+        """Behind the step launch: the monitor's record, when there is one, of the weights the step just wrote (the master
+        copy where there is one) and of the gradients it read - as they stand in the buffer, before the guard's
+        coefficient.  A step the guard skipped is recorded too: its weights are simply unchanged."""
+        if self.param_stats is not None:
+            self.param_stats.record(self.flat, self.master, g)
 
     def _put_step_block(self, steps: int) -> None:
         """Writes the 16-byte step block: ``steps`` taken, the rate of the last of them."""
@@ -1589,13 +1630,18 @@ class _FlatOptimizer:
                 regions += part.run_regions()
         if self._state is not None:
             regions.append(("state", self._state))
-        return regions + [("sq_sum", self.sq_sum)]
+        regions.append(("sq_sum", self.sq_sum))
+        if self.param_stats is not None:   # behind everything a run without a monitor writes
+            regions += self.param_stats.run_regions()
+        return regions
 
     def run_host(self) -> Dict[str, Any]:
         host = dict(kind=type(self).__name__, lr=self._lr)
         for k in self._hyper():
             v = getattr(self, k)
             host[k] = list(v) if isinstance(v, tuple) else v
+        if self.param_stats is not None:
+            host["param_stats"] = self.param_stats.run_host()
         return host
 
     def run_check(self, host: Dict[str, Any]) -> None:
@@ -1610,6 +1656,9 @@ class _FlatOptimizer:
         for part in (self.ema, self.schedule, self.groups):
             if part is not None:
                 part.run_restored(None, {name: blocks[name] for name, _ in part.run_regions()})
+        if self.param_stats is not None:
+            self.param_stats.run_restored(host.get("param_stats"), {name: blocks[name] for name, _ in
+                                                                    self.param_stats.run_regions()})
 
 
 class FlatSGD(_FlatOptimizer):
@@ -1667,6 +1716,9 @@ class FlatSGD(_FlatOptimizer):
     its default, and a `ParamGroup` may name its own.  ``state_dict()`` and ``run_host()`` carry it under
     ``"weight_decay"``.  ``None`` (the default): the optimizer has no weight decay, refuses a table that names one, and
     ``step()`` makes the calls it always made.
+
+    ``param_stats`` (a `param_stats.ParamStats`): `FlatAdam`'s option - every ``step()`` ends with the monitor's record of
+    the weights it wrote and the gradients it read.  Without it ``step()`` makes the calls it always made.
     """
 
     def __init__(self, regularised, others=(), lr: float = 1e-3, momentum: float = 0.0, l2: float = 0.0,
@@ -1691,7 +1743,7 @@ class FlatSGD(_FlatOptimizer):
 
     @torch.no_grad()
     def step(self) -> None:
-        self._begin_step()
+        g = self._begin_step()
         # Without a schedule or a group table the launch takes the rate and `first` from the host.  `first` is the host's
         # count of launches, and under a guard the host does not know whether the guard let a launch through.  A skipped
         # step 0 leaves the momentum buffer at its zeros, and the next launch, with first = 0, forms momentum * 0 + g = g:
@@ -1708,6 +1760,7 @@ class FlatSGD(_FlatOptimizer):
                                                    self.momentum, 1 if self._steps == 0 else 0,
                                                    L.stream_ptr(self.flat.device)), self._what)
         self._steps += 1
+        self._end_step(g)
 
     def _with_own_decay(self, values: Dict[str, Any]) -> Dict[str, Any]:
         """(a state written without the ``weight_decay`` option keeps this optimizer's value)"""
@@ -1785,6 +1838,14 @@ class FlatAdam(_FlatOptimizer):
     the guard skipped and a frozen segment leave their averages alone; every other buffer holds the bits it would hold
     without the average.  ``state_dict()`` holds the average under ``"ema"``; a state without one resets it from the
     parameters.  Without ``ema`` ``step()`` makes the calls it always made.
+
+    ``param_stats`` (keyword only, taken by the constructor call of all three flat optimizers and bound behind
+    ``__init__``; a `param_stats.ParamStats` with one name per parameter, in flat order): every ``step()`` ends with one
+    more launch, `dctn_param_stats`, behind the step: sum, sum of squares, largest magnitude and non-finite count of every
+    parameter as the step left it - the master copy where there is one - and of its gradient as it stands in the buffer
+    the step read, before the guard's coefficient.  A step the guard skipped is recorded too.  A captured ``step()``
+    carries the record, so each of the K iterations of one launch leaves its row.  No other buffer changes a bit.
+    Without ``param_stats`` ``step()`` makes the calls it always made.
     """
 
     def __init__(self, regularised, others=(), lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
@@ -1807,7 +1868,7 @@ class FlatAdam(_FlatOptimizer):
 
     @torch.no_grad()
     def step(self) -> None:
-        self._begin_step()
+        g = self._begin_step()
         # (with a group table every segment's weight decay is in the table, and the launch ignores this one)
         if self._ema_ref is None:
             L.check(L.lib().dctn_adam_flat_step(self._desc_ref, self.m.data_ptr(), self.v.data_ptr(), self.betas[0],
@@ -1817,6 +1878,7 @@ class FlatAdam(_FlatOptimizer):
             L.check(L.lib().dctn_adam_flat_step_ema(self._desc_ref, self._ema_ref, self.m.data_ptr(), self.v.data_ptr(),
                                                     self.betas[0], self.betas[1], self.eps, self.weight_decay,
                                                     L.stream_ptr(self.flat.device)), self._what)
+        self._end_step(g)
 
 
 class FlatRMSprop(_FlatOptimizer):
@@ -1829,7 +1891,7 @@ class FlatRMSprop(_FlatOptimizer):
 
     The step count and the learning rate live in `FlatAdam`'s 16-byte DEVICE block, with its behaviour: the launch
     advances the count, a captured ``step()`` follows ``opt.lr = x`` assigned between replays, ``opt.t`` reads the device.
-    ``master_weights``, ``guard`` / ``guard_loss``, ``schedule``, ``groups`` and ``ema`` are `FlatAdam`'s options with its
+    ``master_weights``, ``guard`` / ``guard_loss``, ``schedule``, ``groups``, ``ema`` and ``param_stats`` are `FlatAdam`'s options with its
     semantics (a segment of a group table has no bias correction to keep: it steps with ``rate * lr_scale`` and its own
     weight decay, and its count only advances).  ``state_dict()`` / ``load_state_dict()`` carry t, lr, the buffers, the
     hyper-parameters, the master copy and the average: a run resumed from them continues bit-identically.
@@ -1857,12 +1919,13 @@ class FlatRMSprop(_FlatOptimizer):
 
     @torch.no_grad()
     def step(self) -> None:
-        self._begin_step()
+        g = self._begin_step()
         # (with a group table every segment's weight decay is in the table, and the launch ignores this one)
         L.check(L.lib().dctn_rmsprop_flat_step(self._desc_ref, self._ema_ref, self.square_avg.data_ptr(),
                                                None if self.buf is None else self.buf.data_ptr(), self.alpha, self.eps,
                                                self.weight_decay, self.momentum, L.stream_ptr(self.flat.device)),
                 self._what)
+        self._end_step(g)
 
     def _same_momentum(self, saved, complaint: str) -> None:
         if (float(saved) > 0.0) != (self.buf is not None):
@@ -2035,6 +2098,21 @@ def make_tt_stats_logger(tt, every: int, sink: Callable[..., None], first_iter: 
     from .tt_stats import TTStatsLogger
 
     return TTStatsLogger(tt, every, sink, first_iter)
+
+
+def make_param_stats_logger(ps, every: int, sink: Callable[..., None], first_iter: int = 0, weight_tag: str = "weights_norm",
+                            grad_tag: str = "grads_norm") -> Callable[[StX, StIt], None]:
+    """Hook for ``train_graphed(after_launch=[...])``: every ``every`` launches it reads ``ps`` (a `param_stats.ParamStats`
+    held by the optimizer: the one synchronisation) and, for every row not yet read and every parameter, calls
+    ``sink(f"{weight_tag}/{name.replace('.', '/')}", norm of the parameter, first_iter + call)`` and
+    ``sink(f"{grad_tag}/{name.replace('.', '/')}", norm of its gradient, first_iter + call)``, in ``add_scalar``'s argument
+    order.  ``flush()`` reads and reports at once.  The default tags are meant to be what ignite's ``WeightsScalarHandler``
+    and ``GradsScalarHandler`` write for ``reduction=torch.norm`` (the reference's add_weights_and_grads_logging,
+    mnist.py:535); neither ignite nor the reference's ``libcrap`` was at hand to confirm the spelling, which is why both are
+    arguments.  Give the ring ``capacity >= every * iters_per_launch / period`` rows and nothing is lost."""
+    from .param_stats import ParamStatsLogger
+
+    return ParamStatsLogger(ps, every, sink, first_iter, weight_tag, grad_tag)
 
 
 def every_n_iters_intervals(*intervals):

@@ -1287,6 +1287,64 @@ int dctn_tt_stats(const void* const* cores, const dctn_tt_string_t* strings, int
                   void* workspace, size_t workspace_bytes, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Sum, sum of squares, largest magnitude and non-finite count of every parameter and of its gradient, for up to 64
+ * parameters in ONE launch over the two flat buffers of a flat optimizer (version 521; dctn_amd/csrc/param_stats.hip;
+ * host side: dctn_amd/param_stats.py) - what the reference logs per parameter and iteration through
+ * add_weights_and_grads_logging (mnist.py:535: a norm of each parameter and of its gradient) and log_parameters_stats
+ * (dctn/training.py:247: mean and std).  Dtypes: DCTN_F32 / DCTN_F64 / DCTN_BF16, one per call; all arithmetic is float64
+ * (a bfloat16 or float32 element and its square are exact there).  None of the three reports to dctn_last_kernel.
+ *
+ * dctn_param_stats : params: DEVICE, n values of `dtype`.  master_or_null: DEVICE, n float32 values (DCTN_BF16 only);
+ *   when given, the WEIGHT statistics are taken from it and params is not read.  grads: DEVICE, n values of `dtype`.
+ *   ends: HOST array of n_segments exclusive segment ends, strictly increasing, ends[n_segments - 1] = n: segment s is the
+ *   elements ends[s - 1] .. ends[s] - 1 of every buffer (ends[-1] = 0).  1 <= n_segments <= 64, a segment has fewer than
+ *   2^31 elements.  block: DEVICE, 8-byte aligned, dctn_param_stats_block_bytes(n_segments, capacity) =
+ *   32 + capacity (16 + 64 n_segments) bytes, laid out as
+ *        0  uint32   calls        launches so far, recorded or not
+ *        4  uint32   recorded     launches that wrote a row
+ *        8  uint32   ticket       0 between launches
+ *       12  uint32   reserved[5]
+ *       32  rows[capacity], each
+ *             0  uint32   call      the `calls` value the row was taken at
+ *             4  uint32   seq       the `recorded` value it got, written last
+ *             8  uint64   reserved
+ *            16  { double w_sum, w_sum_sq, w_max_abs; uint64 w_nonfinite;
+ *                  double g_sum, g_sum_sq, g_max_abs; uint64 g_nonfinite } [n_segments]
+ *   sum and sum_sq run over the FINITE elements only; max_abs is their largest magnitude, 0 when the segment has no
+ *   finite element (-0.0 counts as 0); nonfinite counts NaN and +-Inf.
+ *   The block must be ZERO before the first launch.  A launch is RECORDED iff calls % period == 0 for the `calls` it
+ *   finds; a recorded launch writes row recorded % capacity (a ring: the oldest row is overwritten); a launch that is not
+ *   recorded reads no element and writes nothing but the header.  Either way it leaves calls + 1 and ticket 0.
+ *   workspace: DEVICE, 8-byte aligned, dctn_param_stats_workspace_bytes(ends, n_segments) bytes = 64 per workgroup; it
+ *   need not be initialised and nothing of it is kept between launches.
+ *   The plan: a segment of c elements owns min(64, ceil(c / 8192)) workgroups of 256 threads.  The segment is cut into
+ *   groups of four consecutive elements counted from the SEGMENT's first element; thread j of the segment's 256 W threads
+ *   (workgroup-major) owns the groups j, j + 256 W, ... and adds their elements in index order.  A whole group is loaded in
+ *   one access per buffer when its address allows (16 bytes of float32, 8 of bfloat16, two 16-byte accesses of float64)
+ *   and element by element otherwise.  A workgroup reads its part of both buffers in one pass, reduces in a fixed tree
+ *   (lanes by shuffles at distances 32 .. 1, the four waves through LDS in index order), stores its eight partial values
+ *   into its own 64-byte slot and draws the ticket; the workgroup that draws the launch's last one adds every segment's
+ *   slots in index order, writes the row and advances the header.  No workgroup waits for another.
+ *   A segment's 64 bytes are a function of its own values alone: they do not depend on its offset in the flat buffer (and
+ *   so the alignment of its first element, or whether a group was loaded in one access), on the other segments of the
+ *   launch or its place among them, on the device's CU count or on what the workspace held.  Capturable: the launch reads
+ *   no host state but its arguments (the ends travel in the kernel's argument); the block is device state, so a replay
+ *   goes on where the last launch stopped.  The three buffers are only read; nothing outside the block and the workspace
+ *   is written.
+ *   Return codes, decided on the host before any launch, in the project's order: DCTN_ERR_NULL (params, grads, ends or
+ *   block); DCTN_ERR_BAD_SHAPE (n_segments < 1; ends not strictly increasing or the first < 1; capacity < 1; period < 1);
+ *   DCTN_ERR_BAD_DTYPE (anything but the three); DCTN_ERR_UNSUPPORTED (n_segments > 64; a segment of 2^31 elements or
+ *   more; params, grads or the master copy not aligned to its element size; block or workspace not 8-byte aligned; a
+ *   master copy with a dtype other than DCTN_BF16); DCTN_ERR_WORKSPACE (workspace NULL or too small).
+ * dctn_param_stats_block_bytes : 0 for n_segments outside 1..64 or capacity < 1.
+ * dctn_param_stats_workspace_bytes : 0 for NULL, n_segments outside 1..64 or ends dctn_param_stats would refuse.
+ * ------------------------------------------------------------------------------------------ */
+size_t dctn_param_stats_block_bytes(int n_segments, int capacity);
+size_t dctn_param_stats_workspace_bytes(const int64_t* ends, int n_segments);
+int dctn_param_stats(const void* params, const void* master_or_null, const void* grads, const int64_t* ends, int n_segments,
+                     void* block, int capacity, int period, void* workspace, size_t workspace_bytes, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Tensor-network inner product of two stacks of EPS cores - replaces the contractions of
  * dctn/epses_composition.py:21-58 `inner_product` (Gram of the first pair of cores over their input legs:
  * dctn/eps.py:106-112 `contract_on_input_dims`; that matrix absorbed into every input leg of the next core:
