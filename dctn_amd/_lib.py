@@ -82,6 +82,17 @@ class TTString(ctypes.Structure):
 
 _TTStringP = ctypes.POINTER(TTString)
 
+
+class BatchMonitorCall(ctypes.Structure):
+    """dctn_batch_monitor_t: every buffer, shape and option of one batch-monitor launch; ``indices`` may be None."""
+    _fields_ = [("x", c_void), ("logits", c_void), ("y", c_void), ("indices", c_void), ("edges", c_void), ("block", c_void),
+                ("workspace", c_void), ("workspace_bytes", c_size), ("B", c_i64), ("C", c_int), ("H", c_int), ("W", c_int),
+                ("Q", c_int), ("K", c_int), ("L", c_int), ("n_edges", c_int), ("period", c_int), ("capacity", c_int),
+                ("x_dtype", c_int), ("logits_dtype", c_int), ("reserved", c_int)]
+
+
+_BatchMonitorP = ctypes.POINTER(BatchMonitorCall)
+
 # name -> (restype, argtypes); mirrors include/dctn_amd.h one to one
 SIGNATURES = {
     "dctn_version": (c_int, []),
@@ -218,6 +229,9 @@ SIGNATURES = {
     "dctn_param_stats_block_bytes": (c_size, [c_int, c_int]),
     "dctn_param_stats_workspace_bytes": (c_size, [_I64P, c_int]),
     "dctn_param_stats": (c_int, [c_void, c_void, c_void, _I64P, c_int, c_void, c_int, c_int, c_void, c_size, c_int, c_void]),
+    "dctn_batch_monitor_block_bytes": (c_size, [c_i64, c_int, c_int]),
+    "dctn_batch_monitor_workspace_bytes": (c_size, [c_i64]),
+    "dctn_batch_monitor": (c_int, [_BatchMonitorP, c_void]),
     "dctn_mode_product": (c_int, [c_void, c_void, c_void, c_i64, c_int, c_int, c_i64, c_int, c_void]),
     "dctn_fiber_gram_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_i64, c_int]),
     "dctn_fiber_gram": (c_int, [c_void, c_void, c_void, c_void, c_size, c_i64, c_int, c_int, c_i64, c_int, c_void]),

@@ -212,7 +212,7 @@ static bool eps_head_next(const EpsP& p, int rc) {
 
 extern "C" {
 
-int dctn_version(void) { return 521; }   // callers only check that a library answers (>= 100)
+int dctn_version(void) { return 522; }   // callers only check that a library answers (>= 100)
 
 const char* dctn_last_kernel(void) { return g_last_kernel.load(std::memory_order_relaxed); }
 

@@ -41,9 +41,14 @@ def train_step(
     reg_fn: Optional[Callable[[torch.nn.Module], Tensor]] = None,
     reg_coeff: float = 0.0,
     reducer: Optional[ddp.FlatGradAllReducer] = None,
+    monitor=None,
+    indices: Optional[Tensor] = None,
 ) -> Dict[str, Tensor]:
     """``x``: this rank's shard (channels, batch, height, width, features); ``y``: its labels.
-    Returns the detached ``output``, ``loss`` and ``reg_term`` of this rank."""
+    Returns the detached ``output``, ``loss`` and ``reg_term`` of this rank.  ``monitor`` (a `batch_monitor.BatchMonitor`):
+    the iteration ends with its record of ``x``, the output, ``y`` and ``indices`` (the batch's sample numbers, or None) -
+    this rank's shard in a data-parallel run."""
+    _refuse_image_batch(monitor, x)
     model.train()
     output = model(x)
     loss = loss_fn(output if getattr(loss_fn, "accepts_low_precision", False) else output.float(), y)
@@ -57,7 +62,17 @@ def train_step(
     if reducer is not None:
         reducer()
     optimizer.step()
+    if monitor is not None:
+        monitor.record(x, output.detach(), y, indices)
     return {"output": output.detach(), "loss": loss.detach(), "reg_term": reg_term.detach()}
+
+
+def _refuse_image_batch(monitor, x: Tensor) -> None:
+    """A batch monitor reads the quantum form of the batch; the image form of `DCTNMnistModel.forward` is refused before
+    anything runs."""
+    if monitor is not None and x.ndim == 4:
+        raise ValueError(f"the batch monitor reads the QUANTUM form of the batch, (C, B, H, W, Q) as a DeviceBatches draws "
+                         f"it; the step was given a {tuple(x.shape)} image batch")
 
 
 class GraphedTrainStep:
@@ -114,13 +129,22 @@ class GraphedTrainStep:
     order BETWEEN launches: they take effect at a launch boundary, for all K iterations of the next launch.  Once the
     guard halts inside a launch, the rest of that launch runs forward and backward and applies nothing, as replays do.
     With the defaults (K = 1, no trace) the captured graph is exactly what it was without these arguments.
+
+    ``monitor`` (a `batch_monitor.BatchMonitor`): every iteration - the warm-up ones too - ends with ``monitor.record(...)``
+    beside the trace record: ONE more launch that, every ``period``-th time, writes the input statistics of the static
+    batch buffer, the logits' min / max / mean / std, the histogram of their softmax and every sample's probability of
+    its true class, prediction, label and (with a ``batch_source``) sample number into a ring of rows on the device.  With
+    ``iters_per_launch=K`` every recorded inner iteration keeps its row.  The monitor reads the (C, B, H, W, Q) batch a
+    `DeviceBatches` draws: a 4-d image batch is refused (ValueError).  In a data-parallel run each rank records its own
+    shard.  Without ``monitor`` the graph holds no node for it.
     """
 
     def __init__(self, model: torch.nn.Module, example_x: Optional[Tensor], example_y: Optional[Tensor],
                  loss_fn: Callable[[Tensor, Tensor], Tensor], optimizer: torch.optim.Optimizer,
                  reg_fn: Optional[Callable[[torch.nn.Module], Tensor]] = None, reg_coeff: float = 0.0,
                  reducer: Optional[ddp.FlatGradAllReducer] = None, warmup: int = 3,
-                 graph_allreduce: Optional[bool] = None, *, iters_per_launch: int = 1, trace=None, batch_source=None):
+                 graph_allreduce: Optional[bool] = None, *, iters_per_launch: int = 1, trace=None, monitor=None,
+                 batch_source=None):
         self.model, self.optimizer, self.reducer = model, optimizer, reducer
         self.batch_source = batch_source
         self._ema = getattr(optimizer, "ema", None)   # a WeightEMA: no replay while it is applied
@@ -140,6 +164,8 @@ class GraphedTrainStep:
             self.x, self.y = example_x.clone(), example_y.clone()
         else:
             self.x, self.y, self.indices = batch_source.empty_batch()
+        self.monitor = monitor
+        _refuse_image_batch(monitor, self.x)
         dev = self.x.device
         reduces = reducer is not None and (reducer.world > 1 or not reducer.skip_single_rank)
         if reduces and graph_allreduce is None:
@@ -173,10 +199,12 @@ class GraphedTrainStep:
             total.backward(unit_seed(dev, total.dtype))
             return out, loss, reg
 
-        def record(out, loss, reg):   # the iteration's last launch; nothing at all without a trace
+        def record(out, loss, reg):   # the iteration's last launches; nothing at all without a trace or a monitor
             if trace is not None:
                 trace.record(out, self.y, loss, reg=None if reg is no_reg else reg,
                              guard=getattr(optimizer, "guard", None), optimizer=optimizer, batch_source=batch_source)
+            if monitor is not None:
+                monitor.record(self.x, out.detach(), self.y, self.indices if batch_source is not None else None)
 
         def iterations():   # K whole iterations back to back on the one capture stream: a single chain, no forks
             last = None
@@ -2113,6 +2141,23 @@ def make_param_stats_logger(ps, every: int, sink: Callable[..., None], first_ite
     from .param_stats import ParamStatsLogger
 
     return ParamStatsLogger(ps, every, sink, first_iter, weight_tag, grad_tag)
+
+
+def make_batch_monitor_logger(mon, every: int, scalar_sink: Callable[..., None], histogram_sink=None, sample_sink=None,
+                              first_iter: int = 0) -> Callable[[StX, StIt], None]:
+    """Hook for ``train_graphed(after_launch=[...])``: every ``every`` launches it reads ``mon`` (the step's
+    `batch_monitor.BatchMonitor`: the one synchronisation) and reports every row not yet read with
+    ``iteration = first_iter + call``: ``scalar_sink(tag, value, iteration)`` for ``train_input/dumb_mean``,
+    ``train_input/dumb_std``, ``train_input_intermediate_output_std_of_coordinates_of_windows/`` and
+    ``train_outputs_of_the_whole_model_intermediate_output_dumb_{min,max,mean,std}/`` (the reference's tags,
+    mnist.py:298-311 and :555-591; ``add_scalar``'s argument order), ``histogram_sink(tag, summary, iteration)`` for
+    ``train_outputs_of_the_whole_model_intermediate_output_logits_as_probabilities/`` with the arguments of
+    ``add_histogram_raw`` (`batch_monitor.histogram_summary`), and ``sample_sink(iteration, index, label, pred, p_true)``
+    with the four per-sample arrays (new_runner.py:512-531).  ``flush()`` reads and reports at once.  Give the ring
+    ``capacity >= every * iters_per_launch / period`` rows and nothing is lost."""
+    from .batch_monitor import BatchMonitorLogger
+
+    return BatchMonitorLogger(mon, every, scalar_sink, histogram_sink, sample_sink, first_iter)
 
 
 def every_n_iters_intervals(*intervals):

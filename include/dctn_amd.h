@@ -1345,6 +1345,84 @@ int dctn_param_stats(const void* params, const void* master_or_null, const void*
                      void* block, int capacity, int period, void* workspace, size_t workspace_bytes, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The batch monitor (version 522; dctn_amd/csrc/batch_monitor.hip; host side: dctn_amd/batch_monitor.py): what the
+ * reference's hooks read off the BATCH, in ONE launch - the input statistics (mnist.py:298-311, :571-591: mean and std of
+ * the quantum batch, std_of_coordinates_of_windows of its K x K windows as rank-one tensors), the whole model's output
+ * (mnist.py:555-569: signed min, max, mean, std of the logits, the histogram of softmax(logits, dim=1)) and the per-sample
+ * confidence (new_runner.py:512-531: the probability each sample gives its true class, beside the sample indices).  All
+ * arithmetic is float64.  None of the three reports to dctn_last_kernel.
+ *
+ * dctn_batch_monitor_t: on the HOST, read during the call only.  Every pointer in it is a DEVICE pointer; the five inputs
+ * are only read:
+ *   x        contiguous (C, B, H, W, Q) values of x_dtype
+ *   logits   contiguous (B, L) values of logits_dtype (chosen independently of x_dtype)
+ *   y        B int64 labels
+ *   indices  B int64 sample numbers, or NULL
+ *   edges    n_edges float64 values, strictly increasing (the caller's duty, as for dctn_tensor_hist), 2 <= n_edges <= 2048
+ *   block    8-byte aligned, dctn_batch_monitor_block_bytes(B, n_edges, capacity) bytes; all-zero is a valid empty block
+ *   workspace, workspace_bytes   8-byte aligned, EXACTLY dctn_batch_monitor_workspace_bytes(B) = 40 B bytes; it may hold
+ *            anything before the launch and nothing of it is kept
+ *   K        the window size; 0 turns the window sums off.  period >= 1, capacity >= 1, 1 <= L <= 1024, B >= 1,
+ *            B * L < 2^32, B <= 2^31 - 2.  DCTN_F32 / DCTN_F64 / DCTN_BF16 for either dtype.
+ * The block, with R = 112 + 8 ceil((n_edges - 1) / 2) + 24 B the bytes of a row:
+ *        0  uint32   calls        launches so far, recorded or not
+ *        4  uint32   recorded     launches that wrote a row
+ *        8  uint32   ticket       0 between launches
+ *       12  uint32   reserved[5]
+ *       32  rows[capacity], R bytes each
+ *             0  uint32   call          the `calls` value the row was taken at
+ *             4  uint32   seq           the `recorded` value it got, written last
+ *             8  uint32   rows          samples with 0 <= y < L
+ *            12  uint32   correct       those of `rows` whose prediction equals y
+ *            16  uint32   bad_rows      samples whose logits hold a non-finite value
+ *            20  uint32   z_nonfinite   non-finite logits
+ *            24  uint64   x_nonfinite   non-finite elements of x
+ *            32  double   x_sum, x_sum_sq          over the FINITE elements of x
+ *            48  double   win_sum, win_sq          win_sum = sum over b and the (H-K+1)(W-K+1) windows of the product over
+ *                                                  (dh, dw, c) of sum_q x[c, b, h+dh, w+dw, q]; win_sq the same with x^2.
+ *                                                  Non-finite values are NOT filtered out of these two: one NaN or Inf in a
+ *                                                  sample makes them non-finite.  Both 0 when K == 0.
+ *            64  double   z_sum, z_sum_sq, z_min, z_max   over the FINITE logits; +inf / -inf when there is none
+ *            96  uint32   below, above, nan, reserved     probabilities outside the table; nan: L for every bad row
+ *           112  uint32   counts[n_edges - 1]             then 4 zero bytes when n_edges - 1 is odd
+ *                int64    label[B]      y as given
+ *                int64    index[B]      indices as given, -1 where indices is NULL
+ *                float    p_true[B]     NaN when y is outside [0, L) or the row is bad
+ *                int32    pred[B]       the argmax, the lowest index among equal maxima; -1 for a bad row
+ *   The softmax, for a row without a non-finite logit, in float64: m = max_j z_j, e_j = exp(z_j - m), S = sum_j e_j in
+ *   increasing j, p_j = e_j / S.  Every p_j is binned as numpy.histogram bins it (bin i: edges[i] <= p < edges[i + 1], the
+ *   last bin closed on the right); p_true is p_y rounded to float32.  A bad row adds L to `nan` and nothing to `counts`.
+ *   A launch is RECORDED iff calls % period == 0 for the `calls` it finds; a recorded launch writes row recorded % capacity
+ *   completely (a ring) with seq = recorded and call = calls, then leaves recorded + 1; a launch that is not recorded reads
+ *   no element and writes nothing but the header.  Either way it leaves calls + 1 and ticket 0.
+ *   The plan: B + 1 workgroups of 256 threads, a function of B alone.  Workgroup b < B reads sample b of x once, stages its
+ *   (sum_q x, sum_q x^2) pairs in LDS (K > 0), forms every window product from them, reduces in a fixed tree (lanes by
+ *   shuffles at distances 32 .. 1, the four waves in index order) and stores five values into its 40-byte slot; workgroup B
+ *   takes the logits, one thread per row, adds the rows' values in row order and writes its piece of the row directly; the
+ *   workgroup that draws the launch's last ticket adds the slots in sample order.  No workgroup waits for another.  The
+ *   same values leave the same row bytes (apart from call / seq) on every launch, device and CU count.  Capturable: the
+ *   launch reads no host state but its arguments.  Nothing outside the block and the workspace is written.
+ *   Return codes, decided on the host before any launch, in the project's order: DCTN_ERR_NULL (the struct, x, logits, y,
+ *   edges, block or workspace); DCTN_ERR_BAD_SHAPE (B, C, H, W or Q < 1; K < 0, K > H or K > W; L outside 1..1024;
+ *   n_edges outside 2..2048; period or capacity < 1); DCTN_ERR_BAD_DTYPE (either dtype not one of the three);
+ *   DCTN_ERR_UNSUPPORTED (B * L >= 2^32 or B > 2^31 - 2; x or logits not aligned to its element, y, indices, edges, block
+ *   or workspace not 8-byte aligned; workspace_bytes not exactly the size above; the LDS of a workgroup - 10 416 bytes plus
+ *   the larger of 16 C H W (K > 0) and 4 (n_edges + 2) rounded up to 16 - above 15/16 of what dctn_device_limits reports).
+ * dctn_batch_monitor_block_bytes : 32 + capacity R; 0 for B outside 1..2^31 - 2, n_edges outside 2..2048 or capacity < 1.
+ * dctn_batch_monitor_workspace_bytes : 40 B; 0 for B outside 1..2^31 - 2.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  const void *x, *logits, *y, *indices, *edges;
+  void *block, *workspace;
+  size_t workspace_bytes;
+  int64_t B;
+  int C, H, W, Q, K, L, n_edges, period, capacity, x_dtype, logits_dtype, reserved;
+} dctn_batch_monitor_t;
+size_t dctn_batch_monitor_block_bytes(int64_t B, int n_edges, int capacity);
+size_t dctn_batch_monitor_workspace_bytes(int64_t B);
+int dctn_batch_monitor(const dctn_batch_monitor_t* monitor, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Tensor-network inner product of two stacks of EPS cores - replaces the contractions of
  * dctn/epses_composition.py:21-58 `inner_product` (Gram of the first pair of cores over their input legs:
  * dctn/eps.py:106-112 `contract_on_input_dims`; that matrix absorbed into every input leg of the next core:
